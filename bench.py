@@ -7,6 +7,7 @@ solve + per-vertex evaluation with the reference's epilogue.  The model is
 rebuilt every step, as the reference does every cook.
 
     python bench.py --gpus 1 --steps 200 --warmup 20
+    python bench.py --gpus 1 --steps 200 --warmup 20 --dump-outputs DIR   # + the last timed step's outputs as DIR/*.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -23,10 +24,6 @@ import tempfile
 import time
 
 import numpy as np
-
-# Independent frames run on separate HIP streams; the runtime maps streams onto this many
-# hardware queues (default 4, which lets only ~2 streams overlap).  Must be set before HIP starts.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
@@ -110,7 +107,37 @@ def parse_args():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-pairs", type=float, default=3.0e8,
                     help="bound on (vertex, centre) pairs in the CPU baseline sample")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed for its last step (deformed positions and "
+                         "fall-off of that frame) as DIR/<name>.npy; rank 0 only.  Inputs are synthetic and fixed, so two builds "
+                         "run with the same arguments can be compared output for output")
     return ap.parse_args()
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_SEED = 20240607
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES):
+    """Write each array of `arrays` (name -> host array) as out_dir/<name>.npy, float32 kept, any other dtype as float64.
+    Arrays share their leading (vertex) axis; if together they exceed `budget`, the same fixed, seeded, sorted sample of rows
+    is written for every array (`row_index.npy`, float64, names the rows).  Returns {name: shape written}."""
+    arrays = {k: (np.asarray(v) if np.asarray(v).dtype == np.float32 else np.asarray(v, dtype=np.float64)) for k, v in arrays.items()}
+    n = {a.shape[0] for a in arrays.values()}
+    if len(n) != 1:
+        raise ValueError(f"dump_outputs: arrays disagree on their leading axis: { {k: a.shape for k, a in arrays.items()} }")
+    n = n.pop()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > budget:
+        per_row = sum(a.nbytes // max(n, 1) for a in arrays.values()) + 8          # + the index row
+        keep = max(1, min(n, budget // per_row))
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=keep, replace=False))
+        arrays = {k: np.ascontiguousarray(a[rows]) for k, a in arrays.items()}
+        arrays["row_index"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+    return {k: list(a.shape) for k, a in arrays.items()}
 
 
 def cpu_baseline(cfg_name, P, rest, deform, max_pairs):
@@ -191,7 +218,7 @@ def run_split_mesh(args, torch, dist, capi, synth, rank, world, local_rank, dev,
         batch.set_eval_cus(args.eval_cus)
         batch.build_async(stream.cuda_stream); batch.build_result()
         nbytes = engines[0].model_bytes()
-        lanes.append({"stream": stream, "engines": engines, "batch": batch,
+        lanes.append({"stream": stream, "engines": engines, "batches": {B: batch},
                       "blob": torch.zeros((B, nbytes), dtype=torch.uint8, device=dev),
                       "blob_host": torch.zeros((B, nbytes), dtype=torch.uint8).pin_memory() if rehearse else None,
                       "out": [torch.empty_like(d_P) for _ in range(B)],
@@ -204,18 +231,22 @@ def run_split_mesh(args, torch, dist, capi, synth, rank, world, local_rank, dev,
             dist.barrier()
             torch.cuda.synchronize()
 
-    def one_mode(redundant):
+    def one_mode(redundant, dump=False):
         ev = [[torch.cuda.Event(enable_timing=True) for _ in range(4)] for _ in range(n_groups)]
 
-        def group(g, first, e=None):
-            """Frames first .. first + B - 1 (always a full group: the last one may cook spare frames)."""
+        def group(g, first, e=None, count=B):
+            """Frames first .. first + count - 1 (count <= B: the timed run's last group holds what is left of --steps)."""
             ln = lanes[g % n_lanes]
-            stream, engines, batch, blob = ln["stream"], ln["engines"], ln["batch"], ln["blob"]
-            frames = [(first + k) % N_FRAMES for k in range(B)]
+            if count not in ln["batches"]:
+                ln["batches"][count] = capi.Batch(ln["engines"][:count])
+                ln["batches"][count].set_eval_cus(args.eval_cus)
+            stream, engines, batch, blob = ln["stream"], ln["engines"][:count], ln["batches"][count], ln["blob"]
+            outs, falls = ln["out"][:count], ln["fall"][:count]
+            frames = [(first + k) % N_FRAMES for k in range(count)]
             with torch.cuda.stream(stream):
                 if e: e[0].record(stream)
                 if rank == 0 or redundant:
-                    batch.set_points_dev([d_rest.data_ptr()] * B, [d_deltas.data_ptr() + f * delta_stride for f in frames], n_ctrl)
+                    batch.set_points_dev([d_rest.data_ptr()] * count, [d_deltas.data_ptr() + f * delta_stride for f in frames], n_ctrl)
                     batch.build_async(stream.cuda_stream)
                     if world > 1 and not redundant:
                         for k, eng in enumerate(engines):
@@ -237,11 +268,11 @@ def run_split_mesh(args, torch, dist, capi, synth, rank, world, local_rank, dev,
                 if n_mine > 0 and args.eval_launch == "shared" and B > 1:
                     # the frames of a group share the mesh and the rest rig (imported models carry the rig's identity):
                     # phi once per (vertex, centre) for all of them, on this rank's vertex range
-                    batch.deform_shared_dev(n_mine, d_P.data_ptr(), [o.data_ptr() for o in ln["out"]],
-                                            d_falloff=[f.data_ptr() for f in ln["fall"]], stream_ptr=stream.cuda_stream)
+                    batch.deform_shared_dev(n_mine, d_P.data_ptr(), [o.data_ptr() for o in outs],
+                                            d_falloff=[f.data_ptr() for f in falls], stream_ptr=stream.cuda_stream)
                 elif n_mine > 0:
-                    batch.deform_dev(n_mine, [d_P.data_ptr()] * B, [o.data_ptr() for o in ln["out"]],
-                                     d_falloff=[f.data_ptr() for f in ln["fall"]], stream_ptr=stream.cuda_stream)
+                    batch.deform_dev(n_mine, [d_P.data_ptr()] * count, [o.data_ptr() for o in outs],
+                                     d_falloff=[f.data_ptr() for f in falls], stream_ptr=stream.cuda_stream)
                 if e: e[3].record(stream)
 
         if redundant and rank != 0:
@@ -250,12 +281,23 @@ def run_split_mesh(args, torch, dist, capi, synth, rank, world, local_rank, dev,
                     eng.set_points_dev(d_rest.data_ptr(), d_deltas.data_ptr(), n_ctrl)
         for g in range((args.warmup + B - 1) // B + n_lanes):
             group(g, g * B)
+        if args.steps % B:                         # the ragged last group has its own batch object (primed twice: a batch
+            for _ in range(2):                     # alternates between two packed sets, each allocated on first use)
+                group(n_groups - 1, (n_groups - 1) * B, count=args.steps % B)
         sync_all()
         t0 = time.perf_counter()
         for g in range(n_groups):
-            group(g, g * B, ev[g])
+            group(g, g * B, ev[g], count=min(B, args.steps - g * B))
         sync_all()
         elapsed = time.perf_counter() - t0
+        if dump and rank == 0 and args.steps > 0 and n_mine > 0:
+            # the timed run's last step on this rank's vertex range [lo, hi) (the other mode reuses these buffers)
+            s_last = args.steps - 1
+            ln_last, k_last = lanes[(s_last // B) % n_lanes], s_last % B
+            shapes = dump_outputs(args.dump_outputs, {"deformed_P": ln_last["out"][k_last].cpu().numpy(),
+                                                      "falloff": ln_last["fall"][k_last][:n_mine].cpu().numpy()})
+            print(f"[dump-outputs] step {s_last} (delta phase {s_last % N_FRAMES}), vertices {lo}..{hi} -> {args.dump_outputs}: {shapes}",
+                  file=sys.stderr, flush=True)
         t = torch.tensor([elapsed], device="cpu" if rehearse else dev, dtype=torch.float64)
         if world > 1:
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -265,10 +307,10 @@ def run_split_mesh(args, torch, dist, capi, synth, rank, world, local_rank, dev,
                 "eval_ms": float(np.mean([e[2].elapsed_time(e[3]) for e in ev]))}
 
     order = ["broadcast", "redundant"] if args.c5_solve == "broadcast" else ["redundant", "broadcast"]
-    res = {m: one_mode(m == "redundant") for m in order}
+    res = {m: one_mode(m == "redundant", dump=bool(args.dump_outputs) and m == order[0]) for m in order}
     main_r, alt_r = res[order[0]], res[order[1]]
     redundant = order[0] == "redundant"
-    frames_done = n_groups * B                    # >= args.steps; the surplus is work done, not credited
+    frames_done = args.steps                      # the last group holds what is left of --steps
     if rank == 0:
         flops = (FLOPS_PER_PAIR * n_ctrl + FLOPS_PER_VERTEX_AFFINE) * n_mine * B
         tf = flops / (main_r["eval_ms"] * 1e-3) / 1e12
@@ -301,7 +343,8 @@ def run_split_mesh(args, torch, dist, capi, synth, rank, world, local_rank, dev,
         }), flush=True)
     torch.cuda.synchronize()
     for ln in lanes:
-        ln["batch"].close()
+        for batch in ln["batches"].values():
+            batch.close()
         for e in ln["engines"]:
             e.set_stream(None)
             e.close()
@@ -782,6 +825,14 @@ def main():
     sync_all()
     elapsed = time.perf_counter() - t0
     gc.enable()
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        # the timed run's last step: frame k of its last group, on that group's lane (the passes below reuse these buffers)
+        s_last = args.steps - 1
+        ln_last, k_last = lanes[(s_last // B) % n_lanes], s_last % B
+        shapes = dump_outputs(args.dump_outputs, {"deformed_P": ln_last["out"][k_last].cpu().numpy(),
+                                                  "falloff": ln_last["fall"][k_last].cpu().numpy()})
+        print(f"[dump-outputs] step {s_last} (delta phase {(s_last * world + rank) % N_FRAMES}) -> {args.dump_outputs}: {shapes}",
+              file=sys.stderr, flush=True)
     build_events = events
     if c_groups and args.steps <= B:
         # the one group again, untimed, with an event on either side of its builds: `phases_ms.build_batch` (the timed group
