@@ -349,8 +349,7 @@ __global__ __launch_bounds__(TMAX) void k_lu_panel(const BatchSlot *tab, int lda
                                                    int k0, int step)
 {
     double *A = tab[blockIdx.z].A;
-    // one move list per elimination step: with look-ahead the next panel writes its list while
-    // the rest of this step's trailing update still reads the current one
+    // one move list per elimination step
     int *ipiv = tab[blockIdx.z].ipiv, *moves = tab[blockIdx.z].moves + (size_t)step * kMovesStride;
     DevModel *model = tab[blockIdx.z].model;
     constexpr int R = 32 / NB;          // rows per lane: R * NB = 32 doubles in registers
@@ -912,21 +911,9 @@ int panel_width(int npad, int k0)
     return nrem <= 1024 ? 32 : (nrem <= 2048 ? 16 : (nrem <= 4096 ? 8 : 4));
 }
 
-struct LuStreams {
-    hipStream_t main, aux;      // aux == nullptr: no look-ahead, everything on main
-    hipEvent_t ev_panel[2], ev_rest[2];
-    bool rest_pending = false;  // a part-B update has been enqueued on aux and not yet waited for
-    int last_rest = 0;
-};
-
-// One elimination step.  Without look-ahead (the default, see make_lookahead in fd_capi.hip):
-// panel, then the whole trailing update, on one stream.  With it the update is split: part A = the column blocks the NEXT panel will read,
-// on the main stream right after the panel; part B = everything to the right of them, on the
-// aux stream.  The next panel therefore overlaps part B, and the critical path per step is
-// max(panel, part B) + part A instead of panel + full update.  Part A of step k+1 lies inside
-// part B of step k, hence the wait on ev_rest before it.
+// One elimination step: panel, then the whole trailing update, on one stream.
 template <int NB>
-void lu_step(const BuildBuffers &b, int k0, int step, LuStreams &st)
+void lu_step(const BuildBuffers &b, int k0, int step, hipStream_t stream)
 {
     constexpr int R = 32 / NB;
     const int nrem = b.npad - k0;
@@ -934,43 +921,20 @@ void lu_step(const BuildBuffers &b, int k0, int step, LuStreams &st)
     int threads = round_up((nrem + R - 1) / R, 64);
     if (threads < 64) threads = 64;
     if (b.nopivot && NB == 32 && threads <= 512)
-        hipLaunchKernelGGL((k_lu_panel_np<512>), dim3(1, 1, nb), dim3(threads), 0, st.main, b.d_slots, b.lda, b.npad, b.n, k0, step);
+        hipLaunchKernelGGL((k_lu_panel_np<512>), dim3(1, 1, nb), dim3(threads), 0, stream, b.d_slots, b.lda, b.npad, b.n, k0, step);
     else if (b.nopivot && NB == 32)
-        hipLaunchKernelGGL((k_lu_panel_np<1024>), dim3(1, 1, nb), dim3(threads), 0, st.main, b.d_slots, b.lda, b.npad, b.n, k0, step);
+        hipLaunchKernelGGL((k_lu_panel_np<1024>), dim3(1, 1, nb), dim3(threads), 0, stream, b.d_slots, b.lda, b.npad, b.n, k0, step);
     else if (threads <= 512)
-        hipLaunchKernelGGL((k_lu_panel<NB, 512>), dim3(1, 1, nb), dim3(threads), 0, st.main, b.d_slots, b.lda,
+        hipLaunchKernelGGL((k_lu_panel<NB, 512>), dim3(1, 1, nb), dim3(threads), 0, stream, b.d_slots, b.lda,
                            b.npad, b.n, k0, step);
     else
-        hipLaunchKernelGGL((k_lu_panel<NB, 1024>), dim3(1, 1, nb), dim3(threads), 0, st.main, b.d_slots, b.lda,
+        hipLaunchKernelGGL((k_lu_panel<NB, 1024>), dim3(1, 1, nb), dim3(threads), 0, stream, b.d_slots, b.lda,
                            b.npad, b.n, k0, step);
     // the last block may run into the 16 zero columns allocated past ncols
     const int ncb = (b.ncols - (k0 + NB) + kColBlock - 1) / kColBlock;
     if (ncb <= 0) return;
-    if (!st.aux) {
-        hipLaunchKernelGGL((k_lu_trail<NB>), dim3(ncb, 1, nb), dim3(256), 0, st.main, b.d_slots, b.lda, b.npad, k0,
-                           step, 0, 1);
-        return;
-    }
-    const int next_k0 = k0 + NB;
-    int na = next_k0 < b.npad ? (panel_width(b.npad, next_k0) + kColBlock - 1) / kColBlock : 0;
-    if (na > ncb) na = ncb;
-    const int par = step & 1;
-    if (ncb > na) {
-        (void)hipEventRecord(st.ev_panel[par], st.main);
-        (void)hipStreamWaitEvent(st.aux, st.ev_panel[par], 0);
-    }
-    if (na > 0) {
-        if (st.rest_pending) { (void)hipStreamWaitEvent(st.main, st.ev_rest[st.last_rest], 0); st.rest_pending = false; }
-        hipLaunchKernelGGL((k_lu_trail<NB>), dim3(na, 1, nb), dim3(256), 0, st.main, b.d_slots, b.lda, b.npad, k0,
-                           step, 0, 1);
-    }
-    if (ncb > na) {
-        hipLaunchKernelGGL((k_lu_trail<NB>), dim3(ncb - na, 1, nb), dim3(256), 0, st.aux, b.d_slots, b.lda, b.npad, k0,
-                           step, na, 1);
-        (void)hipEventRecord(st.ev_rest[par], st.aux);
-        st.rest_pending = true;
-        st.last_rest = par;
-    }
+    hipLaunchKernelGGL((k_lu_trail<NB>), dim3(ncb, 1, nb), dim3(256), 0, stream, b.d_slots, b.lda, b.npad, k0,
+                       step, 0, 1);
 }
 
 // Consecutive panels can share ONE deep trailing update: np panels of width w, then a single
@@ -1076,8 +1040,7 @@ hipError_t launch_assemble_block(const BuildBuffers &b, hipStream_t stream, int 
 {
     const unsigned nb = (unsigned)b.nbatch;
     // kernels without per-column radii give a block that is symmetric bit for bit: half of it is computed
-    static const bool no_sym = tuning_env("FD_ASSEMBLE_FULL") != nullptr;
-    const int sym = (!no_sym && b.kind != FD_KERNEL_GAUSSIAN && b.kind != FD_KERNEL_GAUSSIAN_QNN && b.kind != FD_KERNEL_GAUSSIAN_ML) ? 1 : 0;
+    const int sym = (b.kind != FD_KERNEL_GAUSSIAN && b.kind != FD_KERNEL_GAUSSIAN_QNN && b.kind != FD_KERNEL_GAUSSIAN_ML) ? 1 : 0;
     if (npad_a <= 512) {
         const unsigned g = (unsigned)(npad_a + 31) / 32;
         hipLaunchKernelGGL((k_assemble<2>), dim3(g, g, nb), dim3(256), 0, stream, b.d_slots, b.M, b.M, npad_a,
@@ -1131,13 +1094,9 @@ hipError_t launch_qnn_radii(const BuildBuffers &b, hipStream_t stream)
 // its back-substitution into X; b.n real unknowns, the rest identity padding
 hipError_t launch_lu_factor_solve(const BuildBuffers &b, hipStream_t stream)
 {
-    LuStreams st{};
-    st.main = stream;
-    st.aux = b.aux_stream;
-    for (int q = 0; q < 2; ++q) { st.ev_panel[q] = b.aux_events[q]; st.ev_rest[q] = b.aux_events[2 + q]; }
     int k0 = 0, step = 0;
     while (k0 < b.npad) {
-        const int np = st.aux ? 1 : group_at(b.npad, k0, b.group_panels != 0);
+        const int np = group_at(b.npad, k0, b.group_panels != 0);
         if (np > 1) {
             const int wg = panel_width(b.npad, k0);
             if (wg == 16) lu_group_step<16>(b, k0, step, np, stream);
@@ -1147,15 +1106,13 @@ hipError_t launch_lu_factor_solve(const BuildBuffers &b, hipStream_t stream)
             continue;
         }
         const int w = panel_width(b.npad, k0);
-        if (w == 32) lu_step<32>(b, k0, step, st);
-        else if (w == 16) lu_step<16>(b, k0, step, st);
-        else if (w == 8) lu_step<8>(b, k0, step, st);
-        else lu_step<4>(b, k0, step, st);
+        if (w == 32) lu_step<32>(b, k0, step, stream);
+        else if (w == 16) lu_step<16>(b, k0, step, stream);
+        else if (w == 8) lu_step<8>(b, k0, step, stream);
+        else lu_step<4>(b, k0, step, stream);
         k0 += w;
         ++step;
     }
-    // rejoin: whatever part-B update is still running on the aux stream
-    if (st.rest_pending) (void)hipStreamWaitEvent(st.main, st.ev_rest[st.last_rest], 0);
     launch_backsub(b, stream, b.npad);
     return hipGetLastError();
 }

@@ -1759,10 +1759,8 @@ hipError_t launch_build_reg(const BuildBuffers &b, hipStream_t stream, const Poi
     static const bool stamps_late = stamps_env && atoi(tuning_env("FD_REG_STAMPS")) == 2;      // 2: no read-back per launch (the pipeline stays a pipeline); the last launch's stamps at exit
     const bool want_stamps = stamps_env && hipStreamIsCapturing(stream, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone;
     if (want_stamps && !d_stamps) { (void)hipMalloc((void **)&d_stamps, 96 * sizeof(unsigned long long)); (void)hipMemset(d_stamps, 0, 96 * sizeof(unsigned long long)); }
-    // The front end over all CUs (k_reg_front1 / k_reg_front2), then the factorisation in one workgroup per model.  (Tuning builds:
-    // FD_REG_SPLIT=0 keeps the whole build in the one workgroup, round 3's form.)
-    static const bool split_env = [] { const char *e = tuning_env("FD_REG_SPLIT"); return e == nullptr || atoi(e) != 0; }();
-    const bool split = split_env && b.reg_front != 0 && reg_front_doubles(b.M) <= ns_doubles(b.M);
+    // The front end over all CUs (k_reg_front1 / k_reg_front2), then the factorisation in one workgroup per model.
+    const bool split = b.reg_front != 0 && reg_front_doubles(b.M) <= ns_doubles(b.M);
     if (split) {
         const int nbk = (b.M + 15) / 16, ntiles = nbk * (nbk + 1) / 2;
         // tiles per wave: the fewest that keep a launch's workgroups within the CUs (batches: a workgroup alone on its CU runs its

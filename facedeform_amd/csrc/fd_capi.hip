@@ -95,10 +95,6 @@ struct fd_ctx {
     float *m_out = nullptr, *m_fall = nullptr;      // result staging for pageable outputs
 
     hipEvent_t ev0 = nullptr, ev_mid = nullptr, ev1 = nullptr;
-    // LU look-ahead (fd_build.hip lu_step): a second stream and four events, only with
-    // FD_LOOKAHEAD set (see make_lookahead)
-    hipStream_t lu_stream = nullptr;
-    hipEvent_t lu_events[4] = {nullptr, nullptr, nullptr, nullptr};
 
     // The build is ~25 dependent launches whose arguments depend only on the configuration
     // and on buffer addresses: captured once into a hipGraph, replayed on every later build.
@@ -121,8 +117,6 @@ struct fd_batch {
     PointSrc src{};
     bool have_src = false;
     hipEvent_t ev0 = nullptr, ev_mid = nullptr, ev1 = nullptr;
-    hipStream_t lu_stream = nullptr;
-    hipEvent_t lu_events[4] = {nullptr, nullptr, nullptr, nullptr};
     hipGraphExec_t exec = nullptr;
     bool use_graph = true;
     struct Key { int M, kind, term, nparams; double params[4]; } key{};
@@ -279,27 +273,6 @@ static int ensure_solver_capacity(fd_ctx *ctx, int npad)
     return FD_OK;
 }
 
-// Second stream + events of the LU look-ahead (fd_build.hip lu_step); false leaves the build on
-// one stream.  OFF unless FD_LOOKAHEAD is set: measured on MI355X / ROCm 7.2 it loses -- C2 build
-// 0.444 vs 0.401 ms, C3 7.65 vs 6.63 ms -- because every cross-queue event wait costs more than
-// the overlap of a ~25 us panel with a ~30 us update buys.
-static bool make_lookahead(hipStream_t *stream, hipEvent_t events[4])
-{
-    static const bool on = tuning_env("FD_LOOKAHEAD") != nullptr;
-    if (!on) return false;
-    if (*stream) return true;
-    if (hipStreamCreateWithFlags(stream, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); *stream = nullptr; return false; }
-    for (int q = 0; q < 4; ++q)
-        if (hipEventCreateWithFlags(&events[q], hipEventDisableTiming) != hipSuccess) {
-            (void)hipGetLastError();
-            for (int r = 0; r < q; ++r) { (void)hipEventDestroy(events[r]); events[r] = nullptr; }
-            (void)hipStreamDestroy(*stream);
-            *stream = nullptr;
-            return false;
-        }
-    return true;
-}
-
 static int sync_slot(fd_ctx *ctx)
 {
     BatchSlot t{};
@@ -419,7 +392,6 @@ fd_ctx *fd_create(const fd_config *cfg)
         return nullptr;
     }
     ctx->tev0 = ctx->ev0; ctx->tev_mid = ctx->ev_mid; ctx->tev1 = ctx->ev1;
-    ctx->use_graph = tuning_env("FD_NO_GRAPH") == nullptr;
     return ctx;
 }
 
@@ -442,8 +414,6 @@ void fd_destroy(fd_ctx *ctx)
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev_mid) (void)hipEventDestroy(ctx->ev_mid);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
-    for (hipEvent_t e : ctx->lu_events) if (e) (void)hipEventDestroy(e);
-    if (ctx->lu_stream) (void)hipStreamDestroy(ctx->lu_stream);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
 }
@@ -594,11 +564,10 @@ static double ctx_lambda(const fd_ctx *ctx)
     return ctx->nparams > idx ? ctx->params[idx] : 0.0;
 }
 
-// FD_SOLVER=lu keeps every system on the pivoted LU (A/B measurements, tests of that path)
+// FD_SOLVER_LU keeps every system on the pivoted LU
 static bool use_spd(const fd_ctx *ctx)
 {
-    static const char *env = tuning_env("FD_SOLVER");
-    if ((env && strcmp(env, "lu") == 0) || ctx->solver == FD_SOLVER_LU || ctx->prefer_lu) return false;
+    if (ctx->solver == FD_SOLVER_LU || ctx->prefer_lu) return false;
     if (ctx->kind == FD_KERNEL_GAUSSIAN_ML) return false;          // its own pipeline (launch_build_ml)
     return spd_applicable(ctx->kind, ctx->term, ctx_lambda(ctx), ctx->M);
 }
@@ -607,18 +576,15 @@ static bool use_spd(const fd_ctx *ctx)
 // a build of this rig has asked for the pivoted LU (prefer_lu), nor under FD_SOLVER_LU.
 static bool use_nopivot(const fd_ctx *ctx)
 {
-    static const char *env = tuning_env("FD_SOLVER");
-    if ((env && strcmp(env, "lu") == 0) || ctx->solver == FD_SOLVER_LU || ctx->prefer_lu) return false;
+    if (ctx->solver == FD_SOLVER_LU || ctx->prefer_lu) return false;
     return ctx->kind == FD_KERNEL_GAUSSIAN_QNN && round_up(ctx->M, 32) <= 1024;
 }
 
 // The register-resident one-launch build (fd_build_reg.hip): what FD_SOLVER_AUTO takes on the definite path up to 256
-// control points; FD_SOLVER_CHAIN keeps the launch chain, FD_SOLVER_ONE_WORKGROUP the round-2 one-workgroup build
-// (FD_REG_BUILD=0 in the environment: never, for A/B measurements).
+// control points; FD_SOLVER_CHAIN keeps the launch chain, FD_SOLVER_ONE_WORKGROUP the round-2 one-workgroup build.
 static bool use_reg(const fd_ctx *ctx)
 {
-    static const bool off = [] { const char *e = tuning_env("FD_REG_BUILD"); return e && atoi(e) == 0; }();
-    if (off || !(ctx->solver == FD_SOLVER_AUTO || ctx->solver == FD_SOLVER_REGISTER)) return false;
+    if (!(ctx->solver == FD_SOLVER_AUTO || ctx->solver == FD_SOLVER_REGISTER)) return false;
     return reg_applicable(ctx->kind, ctx->term, ctx_lambda(ctx), ctx->M);
 }
 
@@ -646,8 +612,6 @@ static void fill_build_buffers(const fd_ctx *ctx, BuildBuffers &b)
     b.reg = (b.spd && use_reg(ctx)) ? 1 : 0;
     b.reg_front = 1;
     b.nopivot = use_nopivot(ctx) ? 1 : 0;
-    b.aux_stream = nullptr;
-    for (hipEvent_t &e : b.aux_events) e = nullptr;
 }
 
 int fd_build_async(fd_ctx *ctx)
@@ -733,10 +697,6 @@ int fd_build_async(fd_ctx *ctx)
             return FD_OK;
         }
         return post_status(ctx, st);
-    }
-    if (make_lookahead(&ctx->lu_stream, ctx->lu_events)) {
-        b.aux_stream = ctx->lu_stream;
-        for (int q = 0; q < 4; ++q) b.aux_events[q] = ctx->lu_events[q];
     }
     if (grew) {
         // the 16 overrun columns past the RHS block must read as zero forever
@@ -972,11 +932,10 @@ int fd_deform(fd_ctx *ctx, int64_t N, const float *P_in, float *P_out, const flo
     // and writes them in place over the host link -- reads and writes travel in both directions
     // at once and nothing is staged.  Measured at C2: 0.44 ms against 0.62 ms for upload +
     // evaluate + download (chunking those copies over two streams did not overlap them at all).
-    static const bool no_zero_copy = tuning_env("FD_NO_ZEROCOPY") != nullptr;
     const bool all_pinned = host_is_pinned(P_in) && host_is_pinned(P_out) && (!dist2 || host_is_pinned(dist2)) &&
                             (!falloff_out || host_is_pinned(falloff_out)) &&
                             (!tu || (host_is_pinned(tu) && host_is_pinned(tv) && host_is_pinned(nrm)));
-    if (all_pinned && !no_zero_copy) {
+    if (all_pinned) {
         bool ok = true;
         auto dp = [&ok](const void *h) -> void * {
             void *d = nullptr;
@@ -1207,8 +1166,7 @@ int fd_deform_mesh(fd_ctx *ctx, float *P_out, float *falloff_out, float radius2,
                 *nr = ctx->mesh_has_frames ? ctx->m_nrm : nullptr;
     // page-locked outputs: the kernel reads the mesh from HBM and writes the results straight
     // into the caller's arrays -- the only traffic on the host link is the result itself
-    static const bool no_zero_copy = tuning_env("FD_NO_ZEROCOPY") != nullptr;
-    if (!no_zero_copy && host_is_pinned(P_out) && (!falloff_out || host_is_pinned(falloff_out))) {
+    if (host_is_pinned(P_out) && (!falloff_out || host_is_pinned(falloff_out))) {
         void *zo = nullptr, *zf = nullptr;
         bool ok = hipHostGetDevicePointer(&zo, P_out, 0) == hipSuccess;
         if (ok && falloff_out) ok = hipHostGetDevicePointer(&zf, falloff_out, 0) == hipSuccess;
@@ -1446,7 +1404,6 @@ fd_batch *fd_batch_create(fd_ctx *const *ctxs, int n)
         fd_batch_destroy(b);
         return nullptr;
     }
-    b->use_graph = tuning_env("FD_NO_GRAPH") == nullptr;
     return b;
 }
 
@@ -1465,8 +1422,6 @@ void fd_batch_destroy(fd_batch *b)
     }
     if (b->status_ev) (void)hipEventDestroy(b->status_ev);
     if (b->exec) (void)hipGraphExecDestroy(b->exec);
-    for (hipEvent_t e : b->lu_events) if (e) (void)hipEventDestroy(e);
-    if (b->lu_stream) (void)hipStreamDestroy(b->lu_stream);
     if (b->d_slots) (void)hipFree(b->d_slots);
     for (auto &st : b->sets) {
         if (st.d_wtiles) (void)hipFree(st.d_wtiles);
@@ -1581,12 +1536,7 @@ int fd_batch_build_async(fd_batch *b, void *hip_stream)
     // a caller that leaves CUs to the builds (fd_batch_set_eval_cus below the device's count) runs them BESIDE evaluation launches:
     // one workgroup per model then stays on those CUs; the front end's short wide launches would queue for CUs the evaluation holds
     bb.reg_front = (b->eval_cus <= 0 || b->eval_cus >= (int)device_cus()) ? 1 : 0;
-    static const bool no_groups = tuning_env("FD_NO_PANEL_PAIRS") != nullptr;
-    bb.group_panels = (b->n >= 4 && !no_groups && !tuning_env("FD_LOOKAHEAD")) ? 1 : 0;
-    if (make_lookahead(&b->lu_stream, b->lu_events)) {
-        bb.aux_stream = b->lu_stream;
-        for (int q = 0; q < 4; ++q) bb.aux_events[q] = b->lu_events[q];
-    }
+    bb.group_panels = b->n >= 4 ? 1 : 0;
 
     fd_batch::Key key{};
     key.M = c0->M; key.kind = c0->kind; key.term = c0->term | (bb.spd << 9) | (bb.small << 10) | (bb.reg << 11) | (bb.nopivot << 12); key.nparams = c0->nparams;

@@ -804,8 +804,7 @@ hipError_t launch_kind(const DeformArgs &a, const EvalParams &p, hipStream_t str
     // thin-plate with at least four centre tiles: d2 on the matrix pipe (variant 200) is the
     // faster kernel (C2 68 vs 80 us, C3 429 vs 540 us); below that its per-group set-up shows
     if (a.variant <= 0 && KIND == FD_KERNEL_THIN_PLATE && a.tiles != nullptr && a.Mpad >= 64) {
-        static const bool bf16_tiles = tuning_env("FD_MFMA_BF16") != nullptr;
-        variant = (a.tiles16 != nullptr && !bf16_tiles) ? 202 : 200;
+        variant = a.tiles16 != nullptr ? 202 : 200;
     }
     if (variant == 202 && a.tiles16 == nullptr) variant = 200;
     if (variant == 200 || variant == 202) {
@@ -815,11 +814,7 @@ hipError_t launch_kind(const DeformArgs &a, const EvalParams &p, hipStream_t str
             const int64_t ngroups = (a.N + per - 1) / per;
             // at most ~8 workgroups per CU in the grid; beyond that a workgroup walks several
             // vertex groups and stages a resident model only once
-            static const int64_t max_grid = [] {
-                const char *e = tuning_env("FD_MFMA_GRID");
-                const long v = e ? atol(e) : 0;
-                return (int64_t)(v > 0 ? v : 2048);
-            }();
+            constexpr int64_t max_grid = 2048;
             const int64_t rounds = (ngroups + max_grid - 1) / max_grid;
             const unsigned grid = (unsigned)((ngroups + rounds - 1) / rounds);
             const int ntiles = a.Mpad / 16;
@@ -842,8 +837,7 @@ hipError_t launch_kind(const DeformArgs &a, const EvalParams &p, hipStream_t str
             const int64_t per = (int64_t)kBlock * 4;
             const unsigned grid = (unsigned)((a.N + per - 1) / per);
             const unsigned ncu = device_cus(), share = (grid + ncu - 1) / ncu;
-            const bool bal = tuning_env("FD_NO_BALANCE") == nullptr;
-            const size_t dyn = (bal && share >= 3 && share <= 8) ? (((160u * 1024u) / share) & ~1023u) : 0;
+            const size_t dyn = (share >= 3 && share <= 8) ? (((160u * 1024u) / share) & ~1023u) : 0;
             if (a.layers % 8 == 0)
                 hipLaunchKernelGGL((k_deform32<KIND, 4, false, f32x2, 8>), dim3(grid), dim3(kBlock), dyn, stream, p);
             else if (a.layers % 4 == 0)
@@ -858,7 +852,6 @@ hipError_t launch_kind(const DeformArgs &a, const EvalParams &p, hipStream_t str
     // Even placement: with every workgroup resident at once the dispatcher may stack 5 on one
     // CU and 3 on another, and the kernel then lasts as long as the fullest CU.  Reserving
     // 160 KiB / ceil(grid / 256) of LDS per workgroup caps every CU at the even share.
-    const bool balance = tuning_env("FD_NO_BALANCE") == nullptr;
     const unsigned ncu = device_cus();
 #define FD_LAUNCH(VV, LDS, LT)                                                                      \
     do {                                                                                             \
@@ -866,7 +859,7 @@ hipError_t launch_kind(const DeformArgs &a, const EvalParams &p, hipStream_t str
         const unsigned grid = (unsigned)((a.N + per - 1) / per);                                     \
         size_t dyn = (LDS) ? lds_bytes : 0;                                                          \
         const unsigned share = (grid + ncu - 1) / ncu;                                               \
-        if (!(LDS) && balance && share >= 3 && share <= 8) dyn = ((160u * 1024u) / share) & ~1023u;  \
+        if (!(LDS) && share >= 3 && share <= 8) dyn = ((160u * 1024u) / share) & ~1023u;  \
         hipLaunchKernelGGL((k_deform32<KIND, VV, LDS, LT>), dim3(grid), dim3(kBlock), dyn, stream, p); \
         return hipGetLastError();                                                                    \
     } while (0)
@@ -939,8 +932,7 @@ hipError_t launch_deform_batch(const DeformArgs *a, int n, hipStream_t stream)
         same = a[i].precision == FD_EVAL_FP32 && a[i].variant <= 0 && a[i].N == a[0].N && a[i].N > 0 &&
                a[i].Mpad == a[0].Mpad && a[i].kind == a[0].kind &&
                !(a[i].layers >= 2 && a[i].layers % 2 == 0);     // shared-distance multilayer kernel: single launches (same bits as fd_deform)
-    static const bool bf16_tiles = tuning_env("FD_MFMA_BF16") != nullptr;
-    bool mfma = same && a[0].kind == FD_KERNEL_THIN_PLATE && a[0].Mpad >= 64 && !bf16_tiles;
+    bool mfma = same && a[0].kind == FD_KERNEL_THIN_PLATE && a[0].Mpad >= 64;
     for (int i = 0; i < n && mfma; ++i) mfma = a[i].tiles16 != nullptr;
     const bool valu = same && !mfma && !(a[0].kind == FD_KERNEL_THIN_PLATE && a[0].Mpad >= 64);
     if (!mfma && !valu) {

@@ -89,11 +89,9 @@ struct SharedParams {
     const float *norm;            // normalisation of the shared rest rig (DevModel::norm32), the pack kernel's copy
     const uint4 *wtiles;          // [nkb][nT][2 (hi, lo)][64 lanes] x 16 B, then the polynomial tiles [nT][64 lanes] x 16 B
     const SharedFrame *frames;    // [nT * 4]
-    int dbg;                      // FD_SHARED_DBG (diagnostics, tests/tools/shared_eval_timing.py): 1 = no stores, 2 = no K loop
     int fast;                     // no dist2, no tangent frames, every frame slot in use and built, fd_falloff wanted everywhere:
                                   // full vertex groups take the branch-free epilogue (below)
     int delta;                    // FD_OUTPUT_DISPLACEMENT: write d f instead of P + d f (general epilogue only: the host clears `fast`)
-    int stagger;                  // waves 4..7 start this many x 8192 cycles late (resident model only)
     unsigned long long *stamps;   // diagnostics (FD_SHARED_STAMPS): shader-clock shares of the phases, per wave of workgroup 0
 };
 
@@ -361,12 +359,7 @@ void k_deform32_tps_shared(const SharedParams p, int ngroups)
         // logarithm phase together and their matrix phase together, and each phase then has one
         // pipe idle.  A start-up delay for the second half puts one wave's vector work beside
         // the other's matrix work (no barrier follows while the model is resident).
-        if (wave >= 4) {
-            __builtin_amdgcn_s_sleep(12);
-            for (int q = 0; q < (p.stagger & 0xff); ++q) __builtin_amdgcn_s_sleep(127);
-        }
-        // experiment: workgroups start in four phases ((stagger >> 8) x 8128 cycles apart)
-        for (int q = 0; q < (p.stagger >> 8) * (int)(blockIdx.x & 3); ++q) __builtin_amdgcn_s_sleep(127);
+        if (wave >= 4) __builtin_amdgcn_s_sleep(12);
     } else {
         __syncthreads();
     }
@@ -546,7 +539,7 @@ void k_deform32_tps_shared(const SharedParams p, int ngroups)
         for (int kb0 = 0; kb0 < p.nkb; kb0 += p.kchunk) {
             const int nk = p.nkb - kb0 < p.kchunk ? p.nkb - kb0 : p.kchunk;
             if (!resident) stage(kb0, nk);
-            if ((!FAST && !wave_work) || (p.dbg & 2)) continue;
+            if (!FAST && !wave_work) continue;
             // Software pipeline over the K blocks: while the matrix pipe contracts block kb with the weights, the
             // vector unit forms phi of block kb + 1 (two d2 instructions per vertex tile, 8 logarithms, 8 multiplies
             // and the fp16 split per lane).  Inside one wave the two would otherwise run back to back -- the
@@ -569,32 +562,6 @@ void k_deform32_tps_shared(const SharedParams p, int ngroups)
                     }
                 }
             };
-#ifdef FD_KLOOP_UNROLL2
-            // Two operand buffers in turn: the loop is unrolled by two so that neither is ever copied; a full scheduling
-            // barrier between the halves keeps the second half's operand loads out of the first (unfenced: 109 spills)
-            u32x4 bhA[TV], blA[TV], bhB[TV], blB[TV];
-            phi_block(0, bhA, blA);
-            int kb = 0;
-            for (; kb + 2 < nk; kb += 2) {
-                phi_block(kb + 1, bhB, blB);
-                contract(kb, bhA, blA);
-                interleave();
-                __builtin_amdgcn_sched_barrier(0);
-                phi_block(kb + 2, bhA, blA);
-                contract(kb + 1, bhB, blB);
-                interleave();
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            if (kb + 1 < nk) {
-                phi_block(kb + 1, bhB, blB);
-                contract(kb, bhA, blA);
-                interleave();
-                __builtin_amdgcn_sched_barrier(0);
-                contract(kb + 1, bhB, blB);
-            } else {
-                contract(kb, bhA, blA);
-            }
-#else
             u32x4 bh[TV], bl[TV];
             phi_block(0, bh, bl);
             for (int kb = 0; kb + 1 < nk; ++kb) {
@@ -602,12 +569,11 @@ void k_deform32_tps_shared(const SharedParams p, int ngroups)
                 phi_block(kb + 1, nbh, nbl);
                 contract(kb, bh, bl);
                 interleave();
-                // (32 register copies per block; FD_KLOOP_UNROLL2 is the variant without them)
+                // (32 register copies per block)
 #pragma unroll
                 for (int t = 0; t < TV; ++t) { bh[t] = nbh[t]; bl[t] = nbl[t]; }
             }
             contract(nk - 1, bh, bl);
-#endif
         }
 
         FD_SSTAMP(1)
@@ -750,7 +716,6 @@ void k_deform32_tps_shared(const SharedParams p, int ngroups)
                     const int T = fs / 4, k = fs % 4;
                     disp[0] = acc[T][k][0] * inv; disp[1] = acc[T][k][1] * inv; disp[2] = acc[T][k][2] * inv;
                 }
-                if (p.dbg & 1) continue;         // diagnostics: everything but the stores
                 if (p.tu) {
                     const float da1 = disp[0] * a1[0] + disp[1] * a1[1] + disp[2] * a1[2];
                     const float da2 = disp[0] * a2[0] + disp[1] * a2[1] + disp[2] * a2[2];
@@ -795,7 +760,6 @@ void k_deform32_tps_shared(const SharedParams p, int ngroups)
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr bool shared_wide(int nF, int kind) { (void)kind; return nF > 16; }      // thin-plate and the Gaussian kinds alike
 constexpr int kWideSlots = 32;                      // frame records
-constexpr int kWideDefaultVar = 49;      // skewed K loop, units from the counter, non-temporal stores and loads: the fastest inside bench.py
 // Rows of the output tiles are packed densely: row 3 f + c of the stack of 32-row tiles is component c of frame slot f, so
 // 17..20 frames are TWO tiles (60 rows of 64) where one tile per component would be three (r2: 96 rows whatever the frame
 // count) -- a third fewer matrix instructions for the driver's 20-frame launch.  After the epilogue's lane-half swap a lane
@@ -929,24 +893,14 @@ __global__ __launch_bounds__(256) void k_pack_shared_wide(const SharedSlots slot
     }
 }
 
-#ifndef FD_WIDE_VPM
-#define FD_WIDE_VPM 3            // vector instructions placed after each matrix instruction of the K loop
-#endif
-#ifndef FD_W1_VPM
-#define FD_W1_VPM 3              // the same for the one-tile kernel (k_deform32_shared_w1)
-#endif
+constexpr int kWideVpm = 3;      // vector instructions placed after each matrix instruction of the K loop
+constexpr int kW1Vpm = 3;        // the same for the one-tile kernel (k_deform32_shared_w1)
 
-// VAR (build variants kept for A/B runs inside one process: FD_SHARED_WIDE_VAR, tests/tools/wide_variants_timing.py):
-//   bit 0  the K loop skewed by half a block, operands written straight into dead registers (clear: phi of block k + 1 under
-//          the whole contraction of block k, 32 register copies per block)
-//   bit 1  fixed shares of the units per wave (clear: the counter in LDS)
-//   bit 2  LDS reads of the weights one (component, K step) pair ahead of their use (skewed loop only)
-//   bit 3  the last, partial round dealt out as whole groups (clear: as single units)
-//   bit 4  the straight-line epilogue's stores with the non-temporal hint
-//   bit 5  the positions read with the non-temporal hint
-// Instantiated: 49 only (r2 kept eight for A/B runs; the others lost and are gone from the library).
+// The K loop is skewed by half a block, operands written straight into dead registers; a wave takes its units from the
+// counter in LDS; the last, partial round is dealt out as single units; the straight-line epilogue's stores and the
+// position loads carry the non-temporal hint.
 // NT row tiles of 32 (2 or 3), NSLOT frame slots (20: NT = 2; 24, 28, 32: NT = 3) -- see wide_slots / wide_tiles.
-template <int VAR, bool GAUSS, int NT, int NSLOT>
+template <bool GAUSS, int NT, int NSLOT>
 __global__ __launch_bounds__(64 * kWideWaves) __attribute__((amdgpu_waves_per_eu(kWideWaves / 4, kWideWaves / 4)))
 void k_deform32_tps_shared_wide(const SharedParams p, int ngroups)
 {
@@ -955,10 +909,6 @@ void k_deform32_tps_shared_wide(const SharedParams p, int ngroups)
     constexpr int WAVES = kWideWaves, THREADS = 64 * WAVES;
     static_assert(NSLOT % 4 == 0 && NSLOT <= kWideSlots && 3 * NSLOT <= 32 * NT, "frame slots in fours, three rows each");
     constexpr int kWideW16 = wide_w16(NT);
-    constexpr bool SKEWED = (VAR & 1) != 0;
-    static_assert(!GAUSS || SKEWED, "the Gaussian kinds take the skewed loop only");
-    constexpr bool AHEAD = (VAR & 4) != 0;
-    constexpr bool NONTEMPORAL = (VAR & 16) != 0;
     constexpr int TV = 2;                        // vertex tiles (of 32) per wave
     constexpr int kSlots = kWideSlots;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1025,11 +975,7 @@ void k_deform32_tps_shared_wide(const SharedParams p, int ngroups)
     }
     if (resident) {
         stage(0, p.nkb);
-        if (wave >= 4) {                         // the second wave of each SIMD starts out of phase (as above)
-            __builtin_amdgcn_s_sleep(12);
-            for (int q = 0; q < (p.stagger & 0xff); ++q) __builtin_amdgcn_s_sleep(127);
-        }
-        if ((p.dbg & 4) && wave >= 4) return;      // diagnostics: one wave per SIMD (no barrier follows while the model is resident)
+        if (wave >= 4) __builtin_amdgcn_s_sleep(12);      // the second wave of each SIMD starts out of phase (as above)
     } else {
         __syncthreads();
     }
@@ -1045,17 +991,15 @@ void k_deform32_tps_shared_wide(const SharedParams p, int ngroups)
     // counter in LDS instead of always the one with its own number: the two waves of a SIMD do not run at the same pace
     // (the second starts later and yields more often), and with fixed shares the first four waves of a workgroup
     // finished a group's time before the others, who then ran their last group with the matrix pipe half empty.
-    constexpr bool DYNAMIC = (VAR & 2) == 0;
-    const bool dynamic = DYNAMIC && resident;
+    const bool dynamic = resident;
     // The groups that do not fill a last round (ngroups % gridDim of them) are dealt out as single units, workgroup by
-    // workgroup (VAR bit 3 clear): every workgroup then ends with one or two lone units at a lone wave's pace (0.6 of a
+    // workgroup: every workgroup then ends with one or two lone units at a lone wave's pace (0.6 of a
     // round) instead of a few workgroups running a whole extra round beside idle CUs (at 192 CUs: 34 of them).
-    constexpr bool POOL = (VAR & 8) == 0;
     // (A device-wide draw of the groups -- a workgroup fetching its next group from a global counter three rounds ahead, published to
     // its waves through a ring in LDS -- was built in round 3 and measured slower, 245 against 170 us per launch: the ring's LDS
     // word sits between the epilogue's stores and any small wait there waits for the stores in flight.  Removed in round 4;
     // DESIGN.md 4.1c keeps the account.)
-    const int whole_rounds = (dynamic && POOL) ? ngroups / (int)gridDim.x : (ngroups + (int)gridDim.x - 1) / (int)gridDim.x;
+    const int whole_rounds = dynamic ? ngroups / (int)gridDim.x : (ngroups + (int)gridDim.x - 1) / (int)gridDim.x;
     const int64_t pool0 = (int64_t)whole_rounds * (int64_t)gridDim.x * WAVES, total_units = (int64_t)ngroups * WAVES;
     auto unit_global = [&](int u) -> int64_t {          // the 64-vertex unit behind local ticket u (>= total_units: none)
         if (u < WAVES * whole_rounds) return ((int64_t)blockIdx.x + (int64_t)(u / WAVES) * (int64_t)gridDim.x) * WAVES + (u % WAVES);
@@ -1079,12 +1023,9 @@ void k_deform32_tps_shared_wide(const SharedParams p, int ngroups)
         for (int t = 0; t < TV; ++t) {
             const int64_t vi = vb + 32 * t + j;
             const int64_t vc = vi < p.N ? vi : p.N - 1;
-            if constexpr ((VAR & 32) != 0) {        // read once per launch: streamed past L2 like the outputs
-                r.p[t][0] = __builtin_nontemporal_load(&p.P_in[3 * vc]); r.p[t][1] = __builtin_nontemporal_load(&p.P_in[3 * vc + 1]);
-                r.p[t][2] = __builtin_nontemporal_load(&p.P_in[3 * vc + 2]);
-            } else {
-                r.p[t][0] = p.P_in[3 * vc]; r.p[t][1] = p.P_in[3 * vc + 1]; r.p[t][2] = p.P_in[3 * vc + 2];
-            }
+            // read once per launch: streamed past L2 like the outputs
+            r.p[t][0] = __builtin_nontemporal_load(&p.P_in[3 * vc]); r.p[t][1] = __builtin_nontemporal_load(&p.P_in[3 * vc + 1]);
+            r.p[t][2] = __builtin_nontemporal_load(&p.P_in[3 * vc + 2]);
             if constexpr (FAST) r.d2[t] = 0.f; else r.d2[t] = p.dist2 ? p.dist2[vc] : 0.f;
         }
         return r;
@@ -1145,69 +1086,10 @@ void k_deform32_tps_shared_wide(const SharedParams p, int ngroups)
         }
         FD_SSTAMP(0)
 
-        // phi of K block kb for the two vertex tiles: 16 values per lane and tile, as fp16 pieces (8 + 8 registers)
-        auto phi_block = [&](int kb, u32x8 (&xh)[TV], u32x8 (&xl)[TV]) {
-            const f16x4 aop0 = __builtin_bit_cast(f16x4, s_ct[(size_t)kb * 128 + lane]);
-            const f16x4 aop1 = __builtin_bit_cast(f16x4, s_ct[(size_t)kb * 128 + 64 + lane]);
-#pragma unroll
-            for (int t = 0; t < TV; ++t) {
-                f32x16 d = __builtin_amdgcn_mfma_f32_32x32x8f16(aop0, bop0[t], zero16, 0, 0, 0);
-                d = __builtin_amdgcn_mfma_f32_32x32x8f16(aop1, bop1[t], d, 0, 0, 0);
-#pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    unsigned hh, ll;
-                    split_pair_f16(d2_log_d2(d[2 * q]), d2_log_d2(d[2 * q + 1]), hh, ll);
-                    xh[t][q] = hh; xl[t][q] = ll;
-                }
-            }
-        };
-        // acc += W(kb) x phi(kb): per component and K step the three split products of both vertex tiles
-        auto contract = [&](int kb, const u32x8 (&xh)[TV], const u32x8 (&xl)[TV]) {
-            const uint4 *wk = s_w + (size_t)kb * kWideW16 + lane;
-#pragma unroll
-            for (int c = 0; c < NT; ++c) {
-#pragma unroll
-                for (int s = 0; s < 2; ++s) {
-                    const f16x8 ah = __builtin_bit_cast(f16x8, wk[((c * 2 + s) * 2) * 64]), al = __builtin_bit_cast(f16x8, wk[((c * 2 + s) * 2 + 1) * 64]);
-                    f16x8 vh[TV], vl[TV];
-#pragma unroll
-                    for (int t = 0; t < TV; ++t) {
-                        vh[t] = __builtin_bit_cast(f16x8, (u32x4){xh[t][4 * s], xh[t][4 * s + 1], xh[t][4 * s + 2], xh[t][4 * s + 3]});
-                        vl[t] = __builtin_bit_cast(f16x8, (u32x4){xl[t][4 * s], xl[t][4 * s + 1], xl[t][4 * s + 2], xl[t][4 * s + 3]});
-                    }
-#pragma unroll
-                    for (int t = 0; t < TV; ++t) acc[c][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, vh[t], acc[c][t], 0, 0, 0);
-#pragma unroll
-                    for (int t = 0; t < TV; ++t) acc[c][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, vh[t], acc[c][t], 0, 0, 0);
-#pragma unroll
-                    for (int t = 0; t < TV; ++t) acc[c][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, vl[t], acc[c][t], 0, 0, 0);
-                }
-            }
-        };
         for (int kb0 = 0; kb0 < p.nkb; kb0 += p.kchunk) {
             const int nk = p.nkb - kb0 < p.kchunk ? p.nkb - kb0 : p.kchunk;
             if (!resident) stage(kb0, nk);
-            if ((!FAST && !wave_work) || (p.dbg & 2)) continue;
-            // software pipeline as above: phi of block kb + 1 under the matrix instructions of block kb
-            // issue order of one pipelined block: the four d2 instructions of block kb + 1 first, two of block kb's
-            // contraction to cover their latency, then one logarithm and FD_WIDE_VPM vector instructions under each
-            // matrix instruction; the weights of a (component, K step) pair are read from LDS one pair ahead
-            auto interleave = [&]() {
-                __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);          // d2 operands, weights of the first pair
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x002, FD_WIDE_VPM, 0);
-                }
-#pragma unroll
-                for (int q = 0; q < 36; ++q) {
-                    if (q % 6 == 0 && q < 30) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    if (q >= 2 && q < 34) __builtin_amdgcn_sched_group_barrier(0x400, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x002, FD_WIDE_VPM, 0);
-                }
-            };
-          if constexpr (SKEWED) {
+            if (!FAST && !wave_work) continue;
             // Pipeline skewed by HALF a block, no operand copies: the d2 of block kb + 1 is issued in the middle of
             // block kb; its K step 0 operands are formed under block kb's K step 1 instructions (whose own step 0
             // operands are dead by then) and its K step 1 operands under the first half of block kb + 1.
@@ -1285,35 +1167,9 @@ void k_deform32_tps_shared_wide(const SharedParams p, int ngroups)
                 if constexpr (GAUSS) continue;       // the Gaussian block is left to the scheduler's own order
                 // issue order: 18 matrix instructions of K step 0 with the 16 logarithms of this block's step 1 operands,
                 // the four d2 instructions, 18 of K step 1 with the next block's 16 (two instructions after the d2)
-              if constexpr (AHEAD) {
-                // LDS reads one (component, K step) pair AHEAD of their use: the pair after next is requested behind the
-                // first matrix instruction of the current one (as written above, each pair's first instruction waited
-                // out the LDS latency of its own operands: six exposed round trips per block)
-                __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-#pragma unroll
-                for (int q = 0; q < 18; ++q) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    if (q % 6 == 0 && q < 12) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-                    if (q == 12) __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);      // d2 operands, first pair of K step 1
-                    if (q < 16) __builtin_amdgcn_sched_group_barrier(0x400, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x002, FD_WIDE_VPM, 0);
-                }
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);
-                }
-#pragma unroll
-                for (int q = 0; q < 18; ++q) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    if (q % 6 == 0 && q < 12) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-                    if (q >= 2) __builtin_amdgcn_sched_group_barrier(0x400, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x002, FD_WIDE_VPM, 0);
-                }
-              } else {
                 // NM matrix instructions per K step; the 16 logarithms of a half block go under them one at a time (three
                 // row tiles: 18 instructions) or two at a time at first (two row tiles: 12)
-                constexpr int NM = 6 * NT, VPM = NT == 3 ? FD_WIDE_VPM : FD_WIDE_VPM + 2;
+                constexpr int NM = 6 * NT, VPM = NT == 3 ? kWideVpm : kWideVpm + 2;
                 __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
 #pragma unroll
                 for (int q = 0; q < NM; ++q) {
@@ -1337,24 +1193,10 @@ void k_deform32_tps_shared_wide(const SharedParams p, int ngroups)
                     else if (q >= 2) __builtin_amdgcn_sched_group_barrier(0x400, 1, 0);
                     __builtin_amdgcn_sched_group_barrier(0x002, VPM, 0);
                 }
-              }
             }
             phi_half(nk - 1, 1, b1h, b1l);
             contract_half(nk - 1, 0, b0h, b0l);
             contract_half(nk - 1, 1, b1h, b1l);
-          } else {
-            u32x8 bh[TV], bl[TV];
-            phi_block(0, bh, bl);
-            for (int kb = 0; kb + 1 < nk; ++kb) {
-                u32x8 nbh[TV], nbl[TV];
-                phi_block(kb + 1, nbh, nbl);
-                contract(kb, bh, bl);
-                interleave();
-#pragma unroll
-                for (int t = 0; t < TV; ++t) { bh[t] = nbh[t]; bl[t] = nbl[t]; }
-            }
-            contract(nk - 1, bh, bl);
-          }
         }
 
         FD_SSTAMP(1)
@@ -1399,15 +1241,9 @@ void k_deform32_tps_shared_wide(const SharedParams p, int ngroups)
                 const uint64_t pout = ((uint64_t)(unsigned)__builtin_amdgcn_readlane((int)tab[(8 * fs + 5) / 64], (8 * fs + 5) % 64) << 32) |
                                       (unsigned)__builtin_amdgcn_readlane((int)tab[(8 * fs + 4) / 64], (8 * fs + 4) % 64);
                 const float d0 = row_of(fs, 0), d1 = row_of(fs, 1), d2c = row_of(fs, 2);
-                if constexpr (NONTEMPORAL) {
-                    if (fs % 4 == 0) __builtin_nontemporal_store(ones, (f32x4_a16 FD_GLOBAL *)(s_ftab[(fs / 4) * 64 + lane] + fbase));
-                    store_pos3_nt((Pos3 FD_GLOBAL *)((char FD_GLOBAL *)pout + voff), __builtin_fmaf(d0, inv, pos[0]), __builtin_fmaf(d1, inv, pos[1]),
-                                  __builtin_fmaf(d2c, inv, pos[2]));
-                } else {
-                    if (fs % 4 == 0) *(f32x4 FD_GLOBAL *)(s_ftab[(fs / 4) * 64 + lane] + fbase) = ones;
-                    store_pos3((Pos3 FD_GLOBAL *)((char FD_GLOBAL *)pout + voff), __builtin_fmaf(d0, inv, pos[0]), __builtin_fmaf(d1, inv, pos[1]),
-                               __builtin_fmaf(d2c, inv, pos[2]));
-                }
+                if (fs % 4 == 0) __builtin_nontemporal_store(ones, (f32x4_a16 FD_GLOBAL *)(s_ftab[(fs / 4) * 64 + lane] + fbase));
+                store_pos3_nt((Pos3 FD_GLOBAL *)((char FD_GLOBAL *)pout + voff), __builtin_fmaf(d0, inv, pos[0]), __builtin_fmaf(d1, inv, pos[1]),
+                              __builtin_fmaf(d2c, inv, pos[2]));
             }
             settle(nxt);
             FD_SSTAMP(3)
@@ -1470,7 +1306,6 @@ void k_deform32_tps_shared_wide(const SharedParams p, int ngroups)
                 continue;
             }
             float disp[3] = {row_of(fs, 0) * inv, row_of(fs, 1) * inv, row_of(fs, 2) * inv};       // 2^-k is exact
-            if (p.dbg & 1) continue;
             if (p.tu) {
                 const float da1 = disp[0] * a1[0] + disp[1] * a1[1] + disp[2] * a1[2];
                 const float da2 = disp[0] * a2[0] + disp[1] * a2[1] + disp[2] * a2[2];
@@ -1540,18 +1375,18 @@ void k_deform32_tps_shared_wide(const SharedParams p, int ngroups)
 // the K-slot <-> centre map and the polynomial tile are round 3's.  The K loop is plain double buffering, unrolled by two so
 // that no operand is copied: phi of block k + 1 (16 logarithms, 16 multiplies, the fp16 split) goes under the 18 matrix
 // instructions of block k.
-constexpr int kW1Waves = 12;                      // three per SIMD (tuning builds also instantiate 8: two per SIMD)
+constexpr int kW1Waves = 12;                      // three per SIMD
 constexpr int kW1Unit = 32;                       // vertices per wave and unit
 constexpr size_t w1_fixed_lds(int nt) { return sizeof(SharedFrame) * (size_t)kWideSlots + 32 * 16 + (size_t)nt * 64 * 16 + 256 * sizeof(uint64_t) + 16; }
 
 // The whole model must be resident in LDS (p.nkb <= p.kchunk: M = 256 at 32 frames): no staging and no barrier inside the unit
 // loop.  Models that are staged in chunks keep the two-tile kernel: its 512-vertex groups re-stage the model a quarter less often
 // (C3, M = 2048: 1.04 against 1.15 ms per 32 frames; C5's ranges, M = 512: 0.40 against 0.44 ms, same process).
-template <bool GAUSS, int NT, int NSLOT, int WAVES>
-__global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(WAVES / 4, WAVES / 4)))
+template <bool GAUSS, int NT, int NSLOT>
+__global__ __launch_bounds__(64 * kW1Waves) __attribute__((amdgpu_waves_per_eu(kW1Waves / 4, kW1Waves / 4)))
 void k_deform32_shared_w1(const SharedParams p, int ngroups)
 {
-    constexpr int THREADS = 64 * WAVES;
+    constexpr int WAVES = kW1Waves, THREADS = 64 * WAVES;
     constexpr int NLF = NSLOT / 2;                 // local frames per lane half
     constexpr int NFQ = (NSLOT + 7) / 8;           // fd_falloff stores per unit (eight frames each)
     static_assert(NSLOT % 4 == 0 && NSLOT <= kWideSlots && 3 * NLF <= 16 * NT, "frame slots in fours, three rows each, half of them per lane half");
@@ -1656,8 +1491,7 @@ void k_deform32_shared_w1(const SharedParams p, int ngroups)
     UnitRaw nxt;
     int uc = 0;                                   // units this wave has done
 #ifdef FD_TUNING
-    // diagnostics of tuning builds (-DFD_TUNING): shader-clock shares of a unit's phases per wave of workgroup 0, p.dbg bit 0 = no
-    // stores, bit 1 = no K loop
+    // diagnostics of tuning builds (-DFD_TUNING): shader-clock shares of a unit's phases per wave of workgroup 0
     const bool stamp = p.stamps != nullptr && blockIdx.x == 0;
     const unsigned long long st_t0 = p.stamps ? __builtin_amdgcn_s_memtime() : 0, st_r0 = p.stamps ? __builtin_amdgcn_s_memrealtime() : 0;
     unsigned long long st_prev = st_t0, st_acc[4] = {0, 0, 0, 0};
@@ -1795,14 +1629,10 @@ void k_deform32_shared_w1(const SharedParams p, int ngroups)
                 if (q % 3 == 0) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
                 if (q == 1) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
                 if (q == QD) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x002, NT == 3 ? FD_W1_VPM : FD_W1_VPM + 1, 0);
+                __builtin_amdgcn_sched_group_barrier(0x002, NT == 3 ? kW1Vpm : kW1Vpm + 1, 0);
             }
         };
-#ifdef FD_TUNING
-        const bool k_loop = (FAST || wave_work) && !(p.dbg & 2);
-#else
         const bool k_loop = FAST || wave_work;
-#endif
         if (k_loop) {
             const int nk = p.nkb;
             u32x8 ah_, al_, bh_, bl_;
@@ -1848,9 +1678,6 @@ void k_deform32_shared_w1(const SharedParams p, int ngroups)
                 const uint4 e = ent[lf];
                 const uint64_t dst = (((uint64_t)e.y << 32) | (uint64_t)e.x) + voff;
                 const float inv = __uint_as_float(e.z);
-#ifdef FD_TUNING
-                if (p.dbg & 1) { asm volatile("" :: "v"(accf(3 * lf)), "v"(accf(3 * lf + 1)), "v"(accf(3 * lf + 2)), "v"(dst), "v"(inv)); continue; }
-#endif
                 if (lf % 4 == 0) __builtin_nontemporal_store(ones, (f32x4_a16 FD_GLOBAL *)(fptr[lf / 4] + fbase));
                 store_pos3_nt((Pos3 FD_GLOBAL *)dst, __builtin_fmaf(accf(3 * lf), inv, pos[0]), __builtin_fmaf(accf(3 * lf + 1), inv, pos[1]),
                               __builtin_fmaf(accf(3 * lf + 2), inv, pos[2]));
@@ -1996,20 +1823,9 @@ hipError_t launch_deform_shared(const SharedDeformArgs &a, hipStream_t stream)
         out.P_out[f] = a.P_out[q]; out.falloff_out[f] = a.falloff_out ? a.falloff_out[q] : nullptr;
     }
     slots.M = a.M; slots.nreal = a.nF; slots.mismatch = a.mismatch;
-    // 17..32 frames: one vertex tile per wave, three waves per SIMD (k_deform32_shared_w1); FD_SHARED_W1=0: round 3's two-tile kernel
-#ifdef FD_TUNING
-    // (tuning builds read the switch on every launch: tests/tools/shared_ab_timing.py alternates the two kernels inside one process)
-    const bool w1sel = [] { const char *e = tuning_env("FD_SHARED_W1"); return e ? atoi(e) != 0 : true; }();
-#else
-    constexpr bool w1sel = true;
-#endif
-    // ... where the whole model is resident in LDS (M = 256 at 32 frames, 384 at 20); models staged in chunks keep the two-tile kernel
-    const bool w1 = wide && w1sel && (kSharedLdsBudget - w1_fixed_lds(wNT)) / ((size_t)1024 + (size_t)wide_w16(wNT) * 16) >= (size_t)nkb;
-#ifdef FD_TUNING
-    const int w1waves = [] { const char *e = tuning_env("FD_W1_WAVES"); return e && atoi(e) == 8 ? 8 : kW1Waves; }();
-#else
-    constexpr int w1waves = kW1Waves;
-#endif
+    // 17..32 frames: one vertex tile per wave, three waves per SIMD (k_deform32_shared_w1) where the whole model is resident in
+    // LDS (M = 256 at 32 frames, 384 at 20); models staged in chunks keep the two-tile kernel
+    const bool w1 = wide && (kSharedLdsBudget - w1_fixed_lds(wNT)) / ((size_t)1024 + (size_t)wide_w16(wNT) * 16) >= (size_t)nkb;
     if (a.mode != 2) {
         if (wide)
             hipLaunchKernelGGL(k_pack_shared_wide, dim3(nkb, wNT), dim3(256), 0, stream, slots, out, a.nF, wslot, a.Mpad, (uint4 *)a.wtiles,
@@ -2037,36 +1853,24 @@ hipError_t launch_deform_shared(const SharedDeformArgs &a, hipStream_t stream)
         p.norm = reinterpret_cast<const float *>(copy + (size_t)2 * nkb * (sizeof(MfmaTileH) / 16));
     }
     p.wtiles = (const uint4 *)a.wtiles; p.frames = (const SharedFrame *)a.frames;
-#ifdef FD_TUNING
-    { const char *e = tuning_env("FD_SHARED_DBG"); p.dbg = e ? atoi(e) : 0; }
-#else
-    { static const char *e = tuning_env("FD_SHARED_DBG"); p.dbg = e ? atoi(e) : 0; }
-#endif
     {
-        static const bool no_fast = tuning_env("FD_SHARED_NO_FAST") != nullptr;       // A/B: general epilogue everywhere
         // no gate, no fall-off input, no tangent frames, fd_falloff wanted for every frame: the straight-line epilogue.
         // Any frame count: the slots a launch runs beyond nF repeat the last frame (above).
         // (repeated slots cost stores: worth it up to a quarter of the frames -- 17..32 frames always qualify)
-        bool fast = !no_fast && !a.delta_out && (p.dbg & 1) == 0 && a.dist2 == nullptr && a.tu == nullptr && a.radius2 > 0.f && a.falloff_out != nullptr &&
+        bool fast = !a.delta_out && a.dist2 == nullptr && a.tu == nullptr && a.radius2 > 0.f && a.falloff_out != nullptr &&
                     a.N < ((int64_t)1 << 28) && 4 * (nslot - a.nF) <= a.nF;
         // (the straight-line epilogues store fd_falloff 8 and 16 bytes at a time: 16-byte aligned arrays, or the general path)
         for (int f = 0; fast && f < a.nF; ++f) fast = a.falloff_out[f] != nullptr && a.P_out[f] != nullptr && ((uintptr_t)a.falloff_out[f] & 15) == 0;
         p.fast = fast ? 1 : 0;
     }
 #ifdef FD_TUNING
-    { const char *e = tuning_env("FD_SHARED_STAGGER"); p.stagger = e ? atoi(e) : 0; }
-#else
-    { static const char *e = tuning_env("FD_SHARED_STAGGER"); p.stagger = e ? atoi(e) : 0; }
-#endif
-#if defined(FD_SHARED_STAMPS_BUILD) || defined(FD_TUNING)
-    // diagnostics, compiled in only for profiling builds (-DFD_SHARED_STAMPS_BUILD / -DFD_TUNING): in-kernel clock stamps, printed per launch
+    // diagnostics, compiled in only for tuning builds (-DFD_TUNING): in-kernel clock stamps, printed per launch
     static unsigned long long *d_stamps = nullptr;
     static const bool want_stamps = tuning_env("FD_SHARED_STAMPS") != nullptr;
     constexpr size_t kStampWords = 64 + (size_t)kMaxCUs * 8 * 2;
     if (want_stamps && !d_stamps) (void)hipMalloc((void **)&d_stamps, kStampWords * sizeof(unsigned long long));
     if (want_stamps && d_stamps) (void)hipMemsetAsync(d_stamps, 0, kStampWords * sizeof(unsigned long long), stream);
     p.stamps = want_stamps ? d_stamps : nullptr;
-    { static const bool e = tuning_env("FD_SHARED_STAMPS_GENERAL") != nullptr; if (want_stamps && e) p.fast = 0; }
 #else
     p.stamps = nullptr;
 #endif
@@ -2079,7 +1883,7 @@ hipError_t launch_deform_shared(const SharedDeformArgs &a, hipStream_t stream)
     if (kchunk > nkb) kchunk = nkb;
     p.kchunk = kchunk;
     const size_t lds = fixed + per_kb * (size_t)kchunk;
-    const int64_t per = w1 ? kW1Unit * w1waves : wide ? 64 * kWideWaves : kSharedThreads / 64 * 64;          // vertices per workgroup and group
+    const int64_t per = w1 ? kW1Unit * kW1Waves : wide ? 64 * kWideWaves : kSharedThreads / 64 * 64;          // vertices per workgroup and group
     const int64_t ngroups = (a.N + per - 1) / per;
     // One persistent workgroup per CU (150 KiB of LDS, two 240-register waves per SIMD: nothing else fits beside it).
     // a.max_wgs < 256 (fd_batch_set_eval_cus) leaves the other CUs to whatever runs on other streams -- the builds of the
@@ -2099,24 +1903,19 @@ hipError_t launch_deform_shared(const SharedDeformArgs &a, hipStream_t stream)
 #define FD_WIDE_CASE(GSS, NTW, NSL)                                                                                  \
     {                                                                                                                \
         static LdsAttrOnce once;                                                                                     \
-        hipError_t e = once.ensure((const void *)k_deform32_tps_shared_wide<kWideDefaultVar, GSS, NTW, NSL>, 160 * 1024); \
+        hipError_t e = once.ensure((const void *)k_deform32_tps_shared_wide<GSS, NTW, NSL>, 160 * 1024); \
         if (e != hipSuccess) return e;                                                                               \
-        hipLaunchKernelGGL((k_deform32_tps_shared_wide<kWideDefaultVar, GSS, NTW, NSL>), dim3(grid), dim3(64 * kWideWaves), lds, stream, p, (int)ngroups); \
+        hipLaunchKernelGGL((k_deform32_tps_shared_wide<GSS, NTW, NSL>), dim3(grid), dim3(64 * kWideWaves), lds, stream, p, (int)ngroups); \
     }
 #define FD_WIDE_KIND(NTW, NSL) { if (gauss) FD_WIDE_CASE(true, NTW, NSL) else FD_WIDE_CASE(false, NTW, NSL) }
-#define FD_W1_CASE(GSS, NTW, NSL, WVS)                                                                               \
+#define FD_W1_CASE(GSS, NTW, NSL)                                                                                    \
     {                                                                                                                \
         static LdsAttrOnce once;                                                                                     \
-        hipError_t e = once.ensure((const void *)k_deform32_shared_w1<GSS, NTW, NSL, WVS>, 160 * 1024);              \
+        hipError_t e = once.ensure((const void *)k_deform32_shared_w1<GSS, NTW, NSL>, 160 * 1024);                   \
         if (e != hipSuccess) return e;                                                                               \
-        hipLaunchKernelGGL((k_deform32_shared_w1<GSS, NTW, NSL, WVS>), dim3(grid), dim3(64 * WVS), lds, stream, p, (int)ngroups); \
+        hipLaunchKernelGGL((k_deform32_shared_w1<GSS, NTW, NSL>), dim3(grid), dim3(64 * kW1Waves), lds, stream, p, (int)ngroups); \
     }
-#ifdef FD_TUNING
-#define FD_W1_WV(GSS, NTW, NSL) { if (w1waves == 8) FD_W1_CASE(GSS, NTW, NSL, 8) else FD_W1_CASE(GSS, NTW, NSL, kW1Waves) }
-#else
-#define FD_W1_WV(GSS, NTW, NSL) FD_W1_CASE(GSS, NTW, NSL, kW1Waves)
-#endif
-#define FD_W1_KIND(NTW, NSL) { if (gauss) FD_W1_WV(true, NTW, NSL) else FD_W1_WV(false, NTW, NSL) }
+#define FD_W1_KIND(NTW, NSL) { if (gauss) FD_W1_CASE(true, NTW, NSL) else FD_W1_CASE(false, NTW, NSL) }
     if (w1) {
         if (wslot == 20) FD_W1_KIND(2, 20)
         else if (wslot == 24) FD_W1_KIND(3, 24)
@@ -2143,9 +1942,8 @@ hipError_t launch_deform_shared(const SharedDeformArgs &a, hipStream_t stream)
 #undef FD_WIDE_CASE
 #undef FD_WIDE_KIND
 #undef FD_W1_CASE
-#undef FD_W1_WV
 #undef FD_W1_KIND
-#if defined(FD_SHARED_STAMPS_BUILD) || defined(FD_TUNING)
+#ifdef FD_TUNING
     if (want_stamps && d_stamps) {
         static unsigned long long h[kStampWords];
         (void)hipStreamSynchronize(stream);         // (a non-blocking stream: the copy below does not wait for it by itself)

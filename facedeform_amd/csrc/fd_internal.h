@@ -178,10 +178,6 @@ struct BuildBuffers {
     // Multilayer Gaussian model (FD_KERNEL_GAUSSIAN_ML, fd_nullspace.hip launch_build_ml): number of
     // layers, 0 for every other kind.  `kind` is then FD_KERNEL_GAUSSIAN (what the assembly evaluates).
     int ml_layers;
-    // LU look-ahead: second stream + {panel done, rest done} x 2 events; aux_stream == nullptr
-    // runs every step on the one stream
-    hipStream_t aux_stream;
-    hipEvent_t aux_events[4];
 };
 
 hipError_t launch_prepare(const BuildBuffers &b, hipStream_t stream, const PointSrc *src);

@@ -34,8 +34,7 @@
 //                     at rank 128, with the steps in between keeping one column pair current.
 //                     The right-hand sides ride along as three extra rows, so the forward solve
 //                     costs nothing; L^T is mirrored into the upper triangle as it is produced.
-//                     (k_chol_first / k_chol_solve / k_chol_trail: the unfused pieces, used by
-//                     fd_set_deltas and by FD_CHOL_UNFUSED.)
+//                     (k_chol_solve / k_chol_trail: the unfused pieces, used by fd_set_deltas.)
 //   k_backsub_inv     L^T y = z with the inverted diagonal blocks (a by-product of an otherwise
 //                     idle wave of the right-hand-side workgroup), then -- one-range systems --
 //                     a from R and w = Q [y; 0] into X in the layout k_pack expects
@@ -569,15 +568,6 @@ __device__ __forceinline__ void factor_block(const BatchSlot &s, int M, int lda,
     if (threadIdx.x < 64) factor_wave(as_global(s.model), n1, kb, sC, sInv, sCol, true);
     __syncthreads();
     block_store(s, M, lda, kb, sC, sInv, true);
-}
-
-// the first diagonal block has no trailing update before it
-__global__ __launch_bounds__(256) FD_FIT_BESIDE_EVAL void k_chol_first(const BatchSlot *tab, int M, int lda, int n1)
-{
-    __shared__ __attribute__((aligned(16))) double sC[kNB][kLdsRow];
-    __shared__ double sInv[kNB];
-    __builtin_amdgcn_s_setprio(3);
-    factor_block(tab[blockIdx.z], M, lda, n1, 0, -1, sC, sC, sInv);
 }
 
 // ---- Cholesky: rows below the diagonal block ---------------------------------------------------
@@ -1151,7 +1141,7 @@ __global__ __launch_bounds__(256) FD_FIT_BESIDE_EVAL void k_chol_step(const Batc
     for (int cc = 0; cc < kNB; ++cc) up[cc] = x[cc];
 }
 
-// ---- the whole build of a small system in ONE launch of ONE workgroup (FD_SOLVER_ONE_WORKGROUP; FD_SMALL_BUILD=1) ----
+// ---- the whole build of a small system in ONE launch of ONE workgroup (FD_SOLVER_ONE_WORKGROUP) ----
 // Slower than the chain for a lone build, the better citizen for batches solved beside a running evaluation: see
 // launch_build_spd for the measurements.
 // A lone order-256 system is 5.6 MFLOP of fp64 work that the chain above spreads over 18 dependent
@@ -1486,9 +1476,7 @@ __global__ void k_qnn_finish(const BatchSlot *tab, int M, int T, int npad, int f
 void launch_factor(const BuildBuffers &b, hipStream_t stream, int npc, int n1, int rhs_only)
 {
     const unsigned nb = (unsigned)b.nbatch;
-    static const bool unfused = tuning_env("FD_CHOL_UNFUSED") != nullptr;      // A/B: two launches per step
-    if (!rhs_only && unfused) hipLaunchKernelGGL(k_chol_first, dim3(1, 1, nb), dim3(256), 0, stream, b.d_slots, b.M, b.lda, n1);
-    if (!rhs_only && !unfused) {
+    if (!rhs_only) {
         // block 0: the step kernel with no panel before it (factorise, solve the rows below, nothing else)
         const int npanel = (npc - kNB + kStepSlab - 1) / kStepSlab + 1;
         hipLaunchKernelGGL(k_chol_step, dim3(npanel, 1, nb), dim3(256), kStepPanelLds, stream, b.d_slots, b.M, b.lda, b.npad,
@@ -1496,14 +1484,14 @@ void launch_factor(const BuildBuffers &b, hipStream_t stream, int npc, int n1, i
     }
     for (int k0 = 0; k0 < npc; k0 += kNB) {
         const int below = npc - k0 - kNB;
-        if (rhs_only || unfused) {
+        if (rhs_only) {
             const int nslab = rhs_only ? 0 : (below + kSlab - 1) / kSlab;
             hipLaunchKernelGGL(k_chol_solve, dim3(nslab + 1, 1, nb), dim3(256), 0, stream, b.d_slots, b.M, b.lda, b.npad, npc,
                                k0, nslab, rhs_only ? 0 : 1);
         }
         if (below <= 0) break;
         const int ncb = below / 16;
-        if (rhs_only || unfused) {
+        if (rhs_only) {
             // enough workgroups to cover the device while the trailing matrix is large
             int nchunk = rhs_only ? 1 : (ncb + 15) / 16;
             nchunk = nchunk < 1 ? 1 : (nchunk > 8 ? 8 : nchunk);
@@ -1576,7 +1564,7 @@ hipError_t launch_build_spd(const BuildBuffers &b, hipStream_t stream, hipEvent_
     const unsigned nb = (unsigned)b.nbatch;
     const int M = b.M, T = b.T;
     const int n1 = M - T, npc = round_up(n1, kNB), npa = round_up(M, 32);
-    // fd_config.solver = FD_SOLVER_ONE_WORKGROUP (or FD_SMALL_BUILD=1 for every context): the one-workgroup build
+    // fd_config.solver = FD_SOLVER_ONE_WORKGROUP: the one-workgroup build
     // (k_build_small) up to order 512.  Not what AUTO takes -- measured
     // on MI355X it LOSES to the chain: 0.37 vs 0.25 ms at M = 256, 1.19 vs 0.43 ms at M = 512, and no gain
     // for batches of 32 either (profiles/r02_build_small.txt).  With the matrix in L2 every phase is a
@@ -1585,8 +1573,7 @@ hipError_t launch_build_spd(const BuildBuffers &b, hipStream_t stream, hipEvent_
     // 32 frames on most of the device while the next 32 models are solved it is the other way round: 32 workgroups
     // on 32 CUs for 0.65 ms disturb the evaluation less than 18 launches with grids all over the device (bench.py:
     // 120-122k against 112k Mverts/s).
-    static const bool use_small = [] { const char *e = tuning_env("FD_SMALL_BUILD"); return e && atoi(e) == 1; }();
-    if (npc <= kSmallMaxNpc && (use_small || b.small)) {
+    if (npc <= kSmallMaxNpc && b.small) {
         // one workgroup per model does everything after the assembly
         hipError_t e0 = launch_assemble_block(b, stream, npa);
         if (e0 != hipSuccess) return e0;
