@@ -1,5 +1,6 @@
 // fd_capi.hip -- the C ABI of include/facedeform_hip.h over the HIP kernels.
 // No CPU fallback anywhere: without a gfx950 device fd_create fails loudly.
+#include <atomic>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -9,6 +10,13 @@
 #include "fd_internal.h"
 
 using namespace fd;
+
+// what a captured build graph was made for (ensure_graph): another key captures again
+struct GraphKey {
+    int M, kind, term, nparams;       // term | the solver path's flags << 8
+    double params[4];
+    const void *A, *rest, *rec32;     // a single context's buffers (null for a batch: its graph reads the slot table)
+};
 
 struct fd_batch;
 struct fd_ctx {
@@ -100,11 +108,7 @@ struct fd_ctx {
     // and on buffer addresses: captured once into a hipGraph, replayed on every later build.
     hipGraphExec_t build_exec = nullptr;
     bool use_graph = true;
-    struct GraphKey {
-        int M, kind, term, nparams;
-        double params[4];
-        const void *A, *rest, *rec32;
-    } graph_key{}, resolve_key{};
+    GraphKey graph_key{}, resolve_key{};
     char err[512] = {0};
 };
 
@@ -119,7 +123,7 @@ struct fd_batch {
     hipEvent_t ev0 = nullptr, ev_mid = nullptr, ev1 = nullptr;
     hipGraphExec_t exec = nullptr;
     bool use_graph = true;
-    struct Key { int M, kind, term, nparams; double params[4]; } key{};
+    GraphKey key{};
     // a stream that already waits for the current build (set by the first evaluation that
     // needed it): the other contexts' evaluations on that stream need no wait of their own
     hipStream_t waited_stream = nullptr;
@@ -220,7 +224,6 @@ static int dev_alloc(fd_ctx *ctx, T **p, size_t count)
 }
 
 static int order_of(const fd_ctx *ctx) { return ctx->M + term_cols(ctx->term); }
-static bool use_spd(const fd_ctx *ctx);
 static int ml_layers(const fd_ctx *ctx) { return ctx->kind == FD_KERNEL_GAUSSIAN_ML ? (int)ctx->params[1] : 0; }
 // Gaussian records of the solved model, and the kernel the evaluation sees
 static int model_centres(const fd_ctx *ctx) { return ctx->kind == FD_KERNEL_GAUSSIAN_ML ? ctx->M * ml_layers(ctx) : ctx->M; }
@@ -309,8 +312,7 @@ static int order_after_batch(fd_ctx *ctx, hipStream_t s)
     return FD_OK;
 }
 
-// the model's status into page-locked host memory (one thread; the build's last kernel wrote it)
-__global__ void k_post_status(const DevModel *model, int *host_word) { *host_word = model->terminationtype; }
+// the models' statuses into page-locked host memory (one thread each; the build's last kernel wrote them)
 struct StatusTable { const DevModel *model[kMaxBatch]; int *host_word[kMaxBatch]; };
 __global__ void k_post_status_batch(const StatusTable t, int n)
 {
@@ -318,15 +320,97 @@ __global__ void k_post_status_batch(const StatusTable t, int n)
     if (i < n) *t.host_word[i] = t.model[i]->terminationtype;
 }
 
-static int post_status(fd_ctx *ctx, hipStream_t s)
+// Arms the asynchronous status (fd_ctx::h_status) of a build of ctxs[0..n) just enqueued on `s`.  The register-resident build
+// (`reg`) posts every status word itself when each has a device address: `done`, the event behind the build, says they are in.
+// Otherwise one kernel posts them all and `status_ev` is recorded behind it (one event for all: a record on every context's own
+// event object would cost a stream operation each).  A context without the device address arms nothing.
+static void arm_status(fd_ctx *const *ctxs, int n, hipStream_t s, bool reg, hipEvent_t done, hipEvent_t status_ev)
 {
-    int *dword = ctx->d_status_alias;
-    if (!dword) return FD_OK;
-    hipLaunchKernelGGL(k_post_status, dim3(1), dim3(1), 0, s, ctx->d_model, dword);
-    if (hipGetLastError() != hipSuccess || hipEventRecord(ctx->status_ev, s) != hipSuccess) { (void)hipGetLastError(); return FD_OK; }
-    ctx->status_poll = ctx->status_ev;
-    ctx->status_inflight = true;
-    return FD_OK;
+    bool posted_in_kernel = reg;
+    for (int i = 0; i < n; ++i) posted_in_kernel = posted_in_kernel && ctxs[i]->h_slot.host_status != nullptr;
+    hipEvent_t poll = done;
+    if (!posted_in_kernel) {
+        StatusTable t{};
+        for (int i = 0; i < n; ++i) {
+            if (!ctxs[i]->d_status_alias) return;
+            t.model[i] = ctxs[i]->d_model;
+            t.host_word[i] = ctxs[i]->d_status_alias;
+        }
+        hipLaunchKernelGGL(k_post_status_batch, dim3(1), dim3(kMaxBatch), 0, s, t, n);
+        if (hipGetLastError() != hipSuccess || hipEventRecord(status_ev, s) != hipSuccess) { (void)hipGetLastError(); return; }
+        poll = status_ev;
+    }
+    for (int i = 0; i < n; ++i) { ctxs[i]->status_poll = poll; ctxs[i]->status_inflight = true; }
+}
+
+// A build of c's model has been enqueued on `s`: later calls on other streams wait for `done` (recorded on `s`, by `batch` for a
+// batched build), the report times the build by t0 / t_mid / t1, and its status is not read back yet.  `path`: the solver path of
+// a full build, which leaves a factorisation fd_set_deltas can reuse (not the multilayer model's); null for a re-solve through the
+// factorisation left before, whose path stays.  `rig_build_id` (fd_ctx) is a batch's alone.
+static void note_build_enqueued(fd_ctx *c, hipEvent_t done, hipStream_t s, fd_batch *batch, hipEvent_t t0, hipEvent_t t_mid,
+                                hipEvent_t t1, const BuildBuffers *path, uint64_t rig_build_id)
+{
+    c->wait_event = done; c->wait_stream = s; c->wait_batch = batch;
+    c->tev0 = t0; c->tev_mid = t_mid; c->tev1 = t1;
+    if (path) {
+        c->have_factor = path->ml_layers == 0;
+        c->factor_grouped = path->group_panels != 0;
+        c->last_spd = path->spd != 0;
+        c->last_reg = path->spd != 0 && path->reg != 0;
+        c->last_nopivot = path->nopivot != 0;
+        c->deltas_only = false;
+    }
+    if (batch) c->rig_build_id = rig_build_id;
+    c->build_pending = true;
+    ++c->model_gen;
+    c->built = false;
+    c->have_report = false;
+    c->sticky_rc = FD_OK;
+}
+
+// The graph for `key` in *exec, captured from what `launch()` enqueues on `s` unless *exec was made for this key already.  On
+// failure *exec is null: the caller launches directly.
+template <typename Launch>
+static hipError_t ensure_graph(hipStream_t s, hipGraphExec_t *exec, GraphKey *exec_key, const GraphKey &key, Launch launch)
+{
+    if (*exec && memcmp(&key, exec_key, sizeof(key)) == 0) return hipSuccess;
+    if (*exec) { (void)hipGraphExecDestroy(*exec); *exec = nullptr; }
+    hipGraph_t graph = nullptr;
+    hipError_t e = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
+    if (e == hipSuccess) {
+        const hipError_t e1 = launch();
+        e = hipStreamEndCapture(s, &graph);
+        if (e == hipSuccess && e1 != hipSuccess) e = e1;
+    }
+    if (e == hipSuccess && graph) e = hipGraphInstantiate(exec, graph, nullptr, nullptr, 0);
+    if (graph) (void)hipGraphDestroy(graph);
+    if (e != hipSuccess) { (void)hipGetLastError(); *exec = nullptr; }
+    else *exec_key = key;
+    return e;
+}
+
+// the key of a graph that builds c's model along the solver path `flags`; a single context's graph reads its own buffers
+static GraphKey graph_key(const fd_ctx *c, int flags, bool single)
+{
+    GraphKey k{};
+    k.M = c->M; k.kind = c->kind; k.term = c->term | flags; k.nparams = c->nparams;
+    memcpy(k.params, c->params, sizeof(k.params));
+    if (single) { k.A = c->d_A; k.rest = c->d_rest; k.rec32 = c->d_rec32; }
+    return k;
+}
+
+// same M, kernel, parameters and term: one launch chain builds their models, one shared-rig evaluation reads them
+static bool same_model(const fd_ctx *a, const fd_ctx *b)
+{
+    return a->M == b->M && a->kind == b->kind && a->term == b->term && a->nparams == b->nparams &&
+           memcmp(a->params, b->params, sizeof(a->params)) == 0;
+}
+
+// tangent frames: all three arrays or none
+static bool frames_ok(const void *tu, const void *tv, const void *nrm)
+{
+    const int n = (tu != nullptr) + (tv != nullptr) + (nrm != nullptr);
+    return n == 0 || n == 3;
 }
 
 static int poll_status(fd_ctx *ctx);
@@ -607,11 +691,23 @@ static void fill_build_buffers(const fd_ctx *ctx, BuildBuffers &b)
     b.d_slots = ctx->d_slot;
     b.nbatch = 1;
     b.group_panels = 0;
-    b.spd = use_spd(ctx) ? 1 : 0;
-    b.small = ctx->solver == FD_SOLVER_ONE_WORKGROUP ? 1 : 0;
-    b.reg = (b.spd && use_reg(ctx)) ? 1 : 0;
+    b.spd = b.small = b.reg = b.nopivot = 0;     // the solver path: choose_build
     b.reg_front = 1;
-    b.nopivot = use_nopivot(ctx) ? 1 : 0;
+}
+
+// The solver path of a build of ctxs[0..n) (n = 1: a single build), whose models are context 0's: every path is everybody's
+// choice or nobody's -- one context that fell back to the LU takes the batch with it.
+static void choose_build(fd_ctx *const *ctxs, int n, BuildBuffers &b)
+{
+    fill_build_buffers(ctxs[0], b);
+    b.spd = b.small = b.reg = b.nopivot = 1;
+    for (int i = 0; i < n; ++i) {
+        if (!use_spd(ctxs[i])) b.spd = 0;
+        if (ctxs[i]->solver != FD_SOLVER_ONE_WORKGROUP) b.small = 0;
+        if (!use_reg(ctxs[i])) b.reg = 0;
+        if (!use_nopivot(ctxs[i])) b.nopivot = 0;
+    }
+    if (!b.spd) b.reg = 0;      // the register-resident build is a form of the definite path
 }
 
 int fd_build_async(fd_ctx *ctx)
@@ -627,132 +723,59 @@ int fd_build_async(fd_ctx *ctx)
     if ((rc = ensure_records_capacity(ctx, model_centres(ctx)))) return rc;
     if ((rc = sync_slot(ctx))) return rc;
     BuildBuffers b;
-    fill_build_buffers(ctx, b);
+    choose_build(&ctx, 1, b);
     if (b.reg) FD_HIP(ctx, reg_build_init());
     if (ctx->deltas_only && ctx->have_factor && ctx->last_reg) {
         // the register-resident build keeps no factorisation (it is faster than the stored-factor path was): new deltas
         // are a new build from the context's own copy of the points -- bit-identical to fd_set_points + fd_build by construction
         ctx->deltas_only = false;
     }
-    if (ctx->deltas_only && ctx->have_factor) {
+    hipStream_t st = cur_stream(ctx);
+    const bool resolve = ctx->deltas_only && ctx->have_factor;
+    if (resolve) {
         // fd_set_deltas: right-hand sides only, through the factorisation of the last full build
         b.group_panels = ctx->factor_grouped ? 1 : 0;
         b.spd = ctx->last_spd ? 1 : 0;                // the path that left the factorisation (a batch may have overruled this context's own choice)
-        hipStream_t st = cur_stream(ctx);
-        fd_ctx::GraphKey rkey{};
-        rkey.M = ctx->M; rkey.kind = ctx->kind; rkey.term = ctx->term | (b.group_panels << 8) | (b.spd << 9); rkey.nparams = ctx->nparams;
-        memcpy(rkey.params, ctx->params, sizeof(rkey.params));
-        rkey.A = ctx->d_A; rkey.rest = ctx->d_rest; rkey.rec32 = ctx->d_rec32;
-        if (ctx->use_graph && (!ctx->resolve_exec || memcmp(&rkey, &ctx->resolve_key, sizeof(rkey)) != 0)) {
-            if (ctx->resolve_exec) { (void)hipGraphExecDestroy(ctx->resolve_exec); ctx->resolve_exec = nullptr; }
-            hipGraph_t graph = nullptr;
-            hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
-            if (e == hipSuccess) {
-                hipError_t e1 = launch_resolve(b, st, nullptr);
-                e = hipStreamEndCapture(st, &graph);
-                if (e == hipSuccess && e1 != hipSuccess) e = e1;
-            }
-            if (e == hipSuccess && graph) e = hipGraphInstantiate(&ctx->resolve_exec, graph, nullptr, nullptr, 0);
-            if (graph) (void)hipGraphDestroy(graph);
-            if (e != hipSuccess) { (void)hipGetLastError(); ctx->resolve_exec = nullptr; }
-            else ctx->resolve_key = rkey;
-        }
+        const GraphKey key = graph_key(ctx, (b.group_panels << 8) | (b.spd << 9), true);
+        if (ctx->use_graph) (void)ensure_graph(st, &ctx->resolve_exec, &ctx->resolve_key, key, [&] { return launch_resolve(b, st, nullptr); });
         FD_HIP(ctx, hipEventRecord(ctx->ev0, st));
         FD_HIP(ctx, hipEventRecord(ctx->ev_mid, st));
         if (ctx->use_graph && ctx->resolve_exec) FD_HIP(ctx, hipGraphLaunch(ctx->resolve_exec, st));
         else FD_HIP(ctx, launch_resolve(b, st, nullptr));
-        FD_HIP(ctx, hipEventRecord(ctx->ev1, st));
-        // a later evaluation on ANOTHER stream (fd_deform_dev_stream, fd_batch_deform*) is ordered behind this build
-        ctx->wait_event = ctx->ev1; ctx->wait_stream = st; ctx->wait_batch = nullptr;
-        ctx->tev0 = ctx->ev0; ctx->tev_mid = ctx->ev_mid; ctx->tev1 = ctx->ev1;
-        ctx->last_spd = b.spd != 0;
-        ctx->build_pending = true;
-        ++ctx->model_gen;
-        ctx->built = false;
-        ctx->have_report = false;
-        ctx->sticky_rc = FD_OK;
-        return post_status(ctx, st);
-    }
-    if (b.reg) {
+    } else if (b.reg) {
         // the register-resident build is ONE launch, control table included: nothing to capture, nothing to prepare
-        hipStream_t st = cur_stream(ctx);
+        // (it keeps no factorisation, yet fd_set_deltas is allowed: it builds again, see above)
         FD_HIP(ctx, hipEventRecord(ctx->ev0, st));
         FD_HIP(ctx, launch_build_reg(b, st, nullptr, ctx->ev_mid));
-        FD_HIP(ctx, hipEventRecord(ctx->ev1, st));
-        ctx->wait_event = ctx->ev1; ctx->wait_stream = st; ctx->wait_batch = nullptr;
-        ctx->tev0 = ctx->ev0; ctx->tev_mid = ctx->ev_mid; ctx->tev1 = ctx->ev1;
-        ctx->have_factor = true;          // (fd_set_deltas is allowed: it builds again, see above)
-        ctx->last_spd = true; ctx->last_reg = true; ctx->last_nopivot = false;
-        ctx->factor_grouped = false;
-        ctx->deltas_only = false;
-        ctx->build_pending = true;
-        ++ctx->model_gen;
-        ctx->built = false;
-        ctx->have_report = false;
-        ctx->sticky_rc = FD_OK;
-        if (ctx->h_slot.host_status) {
-            // the build's own last thread has posted the status word: the event behind the build is the one to poll
-            ctx->status_poll = ctx->ev1;
-            ctx->status_inflight = true;
-            return FD_OK;
-        }
-        return post_status(ctx, st);
-    }
-    if (grew) {
-        // the 16 overrun columns past the RHS block must read as zero forever
-        const size_t cols = (size_t)ctx->cap_npad + kRhsCols + 16;
-        FD_HIP(ctx, hipMemsetAsync(ctx->d_A, 0, sizeof(double) * (size_t)ctx->cap_npad * cols, cur_stream(ctx)));
-    }
-    fd_ctx::GraphKey key{};
-    key.M = ctx->M; key.kind = ctx->kind; key.term = ctx->term | (b.spd << 9) | (b.reg << 11) | (b.nopivot << 12); key.nparams = ctx->nparams;
-    memcpy(key.params, ctx->params, sizeof(key.params));
-    key.A = ctx->d_A; key.rest = ctx->d_rest; key.rec32 = ctx->d_rec32;
-    if (ctx->use_graph && (!ctx->build_exec || memcmp(&key, &ctx->graph_key, sizeof(key)) != 0)) {
-        if (ctx->build_exec) { (void)hipGraphExecDestroy(ctx->build_exec); ctx->build_exec = nullptr; }
-        hipGraph_t graph = nullptr;
-        hipError_t e = hipStreamBeginCapture(cur_stream(ctx), hipStreamCaptureModeThreadLocal);
-        if (e == hipSuccess) {
-            hipError_t e1 = launch_prepare(b, cur_stream(ctx), nullptr);
-            hipError_t e2 = launch_build(b, cur_stream(ctx), nullptr);
-            e = hipStreamEndCapture(cur_stream(ctx), &graph);
-            if (e == hipSuccess && (e1 != hipSuccess || e2 != hipSuccess)) e = e1 != hipSuccess ? e1 : e2;
-        }
-        if (e == hipSuccess && graph) e = hipGraphInstantiate(&ctx->build_exec, graph, nullptr, nullptr, 0);
-        if (graph) (void)hipGraphDestroy(graph);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            ctx->build_exec = nullptr;
-            ctx->use_graph = false;      // this runtime cannot capture the sequence: launch directly
-        } else {
-            ctx->graph_key = key;
-        }
-    }
-    FD_HIP(ctx, hipEventRecord(ctx->ev0, cur_stream(ctx)));
-    if (ctx->use_graph && ctx->build_exec) {
-        FD_HIP(ctx, hipEventRecord(ctx->ev_mid, cur_stream(ctx)));   // phases are not split inside a graph
-        FD_HIP(ctx, hipGraphLaunch(ctx->build_exec, cur_stream(ctx)));
     } else {
-        FD_HIP(ctx, launch_prepare(b, cur_stream(ctx), nullptr));
-        FD_HIP(ctx, launch_build(b, cur_stream(ctx), ctx->ev_mid));
+        if (grew) {
+            // the 16 overrun columns past the RHS block must read as zero forever
+            const size_t cols = (size_t)ctx->cap_npad + kRhsCols + 16;
+            FD_HIP(ctx, hipMemsetAsync(ctx->d_A, 0, sizeof(double) * (size_t)ctx->cap_npad * cols, st));
+        }
+        const GraphKey key = graph_key(ctx, (b.spd << 9) | (b.reg << 11) | (b.nopivot << 12), true);
+        if (ctx->use_graph && ensure_graph(st, &ctx->build_exec, &ctx->graph_key, key, [&] {
+                const hipError_t e1 = launch_prepare(b, st, nullptr);
+                const hipError_t e2 = launch_build(b, st, nullptr);
+                return e1 != hipSuccess ? e1 : e2;
+            }) != hipSuccess)
+            ctx->use_graph = false;      // this runtime cannot capture the sequence: launch directly
+        FD_HIP(ctx, hipEventRecord(ctx->ev0, st));
+        if (ctx->use_graph && ctx->build_exec) {
+            FD_HIP(ctx, hipEventRecord(ctx->ev_mid, st));   // phases are not split inside a graph
+            FD_HIP(ctx, hipGraphLaunch(ctx->build_exec, st));
+        } else {
+            FD_HIP(ctx, launch_prepare(b, st, nullptr));
+            FD_HIP(ctx, launch_build(b, st, ctx->ev_mid));
+        }
     }
-    FD_HIP(ctx, hipEventRecord(ctx->ev1, cur_stream(ctx)));
+    FD_HIP(ctx, hipEventRecord(ctx->ev1, st));
     // A later evaluation on ANOTHER stream is ordered behind this build (order_after_batch): a single build as much as
     // a batched one, and in particular the LU rebuild that poll_status enqueues here when the Cholesky lost definiteness --
     // the evaluation that triggered the repair may launch on a stream that knows nothing of this one.
-    ctx->wait_event = ctx->ev1; ctx->wait_stream = cur_stream(ctx); ctx->wait_batch = nullptr;
-    ctx->tev0 = ctx->ev0; ctx->tev_mid = ctx->ev_mid; ctx->tev1 = ctx->ev1;
-    ctx->have_factor = b.ml_layers == 0;     // the multilayer model keeps no single factorisation to reuse
-    ctx->last_spd = b.spd != 0;
-    ctx->last_reg = b.spd != 0 && b.reg != 0;
-    ctx->last_nopivot = b.nopivot != 0;
-    ctx->factor_grouped = false;
-    ctx->deltas_only = false;
-    ctx->build_pending = true;
-    ++ctx->model_gen;
-    ctx->built = false;
-    ctx->have_report = false;
-    ctx->sticky_rc = FD_OK;
-    return post_status(ctx, cur_stream(ctx));
+    note_build_enqueued(ctx, ctx->ev1, st, nullptr, ctx->ev0, ctx->ev_mid, ctx->ev1, resolve ? nullptr : &b, 0);
+    arm_status(&ctx, 1, st, !resolve && b.reg, ctx->ev1, ctx->status_ev);
+    return FD_OK;
 }
 
 int fd_build_result(fd_ctx *ctx, fd_report *report)
@@ -874,6 +897,25 @@ static int poll_status(fd_ctx *ctx)
     return ctx->sticky_rc;
 }
 
+// the evaluation of c's model over N vertices
+static DeformArgs deform_args(const fd_ctx *c, int64_t N, const float *P_in, float *P_out, const float *dist2, float *falloff_out,
+                              const float *tu, const float *tv, const float *nrm, float radius2, float falloffrate)
+{
+    DeformArgs a;
+    a.N = N;
+    a.P_in = P_in; a.P_out = P_out;
+    a.dist2 = dist2; a.falloff_out = falloff_out;
+    a.tu = tu; a.tv = tv; a.nrm = nrm;
+    a.radius2 = radius2; a.falloffrate = falloffrate;
+    a.M = model_centres(c); a.Mpad = round_up(a.M, kRecPad); a.kind = eval_kind(c); a.layers = record_layers(c);
+    a.rec32 = c->d_rec32; a.rec64 = c->d_rec64; a.tiles = c->d_tiles; a.tiles16 = c->d_tiles16;
+    a.model = c->d_model;
+    a.precision = c->eval_precision;
+    a.variant = c->eval_variant;
+    a.delta_out = c->output == FD_OUTPUT_DISPLACEMENT;
+    return a;
+}
+
 extern "C" {
 
 int fd_deform_dev(fd_ctx *ctx, int64_t N, const float *d_P_in, float *d_P_out, const float *d_dist2,
@@ -892,25 +934,13 @@ int fd_deform_dev_stream(fd_ctx *ctx, void *hip_stream, int64_t N, const float *
     if (!ctx) return FD_E_INVALID;
     hipStream_t launch_stream = hip_stream ? (hipStream_t)hip_stream : cur_stream(ctx);
     if (N < 0 || (N > 0 && (!d_P_in || !d_P_out))) { set_err(ctx, "fd_deform: bad N / P pointers"); return FD_E_INVALID; }
-    const int ntan = (d_tu != nullptr) + (d_tv != nullptr) + (d_nrm != nullptr);
-    if (ntan != 0 && ntan != 3) { set_err(ctx, "fd_deform: tu, tv, nrm must be all set or all NULL"); return FD_E_INVALID; }
+    if (!frames_ok(d_tu, d_tv, d_nrm)) { set_err(ctx, "fd_deform: tu, tv, nrm must be all set or all NULL"); return FD_E_INVALID; }
     if (!ctx->built && !ctx->build_pending) { set_err(ctx, "fd_deform: no successfully built model"); return FD_E_NOT_BUILT; }
     if (N == 0) return FD_OK;
     int rc = use_device(ctx);
     if (rc) return rc;
     if ((rc = poll_status(ctx))) return rc;           // a failed asynchronous build: repaired here, or reported
-    DeformArgs a;
-    a.N = N;
-    a.P_in = d_P_in; a.P_out = d_P_out;
-    a.dist2 = d_dist2; a.falloff_out = d_falloff_out;
-    a.tu = d_tu; a.tv = d_tv; a.nrm = d_nrm;
-    a.radius2 = radius2; a.falloffrate = falloffrate;
-    a.M = model_centres(ctx); a.Mpad = round_up(a.M, kRecPad); a.kind = eval_kind(ctx); a.layers = record_layers(ctx);
-    a.rec32 = ctx->d_rec32; a.rec64 = ctx->d_rec64; a.tiles = ctx->d_tiles; a.tiles16 = ctx->d_tiles16;
-    a.model = ctx->d_model;
-    a.precision = ctx->eval_precision;
-    a.variant = ctx->eval_variant;
-    a.delta_out = ctx->output == FD_OUTPUT_DISPLACEMENT;
+    const DeformArgs a = deform_args(ctx, N, d_P_in, d_P_out, d_dist2, d_falloff_out, d_tu, d_tv, d_nrm, radius2, falloffrate);
     if ((rc = order_after_batch(ctx, launch_stream))) return rc;
     FD_HIP(ctx, launch_deform(a, launch_stream));
     return FD_OK;
@@ -922,8 +952,7 @@ int fd_deform(fd_ctx *ctx, int64_t N, const float *P_in, float *P_out, const flo
 {
     if (!ctx) return FD_E_INVALID;
     if (N < 0 || (N > 0 && (!P_in || !P_out))) { set_err(ctx, "fd_deform: bad N / P pointers"); return FD_E_INVALID; }
-    const int ntan = (tu != nullptr) + (tv != nullptr) + (nrm != nullptr);
-    if (ntan != 0 && ntan != 3) { set_err(ctx, "fd_deform: tu, tv, nrm must be all set or all NULL"); return FD_E_INVALID; }
+    if (!frames_ok(tu, tv, nrm)) { set_err(ctx, "fd_deform: tu, tv, nrm must be all set or all NULL"); return FD_E_INVALID; }
     if (!ctx->built && !ctx->build_pending) { set_err(ctx, "fd_deform: no successfully built model"); return FD_E_NOT_BUILT; }
     if (N == 0) return FD_OK;
     int rc = use_device(ctx);
@@ -1112,8 +1141,7 @@ int fd_mesh_set(fd_ctx *ctx, int64_t N, const float *P, const float *dist2, cons
 {
     if (!ctx) return FD_E_INVALID;
     if (N <= 0 || !P) { set_err(ctx, "fd_mesh_set: need N > 0 and P"); return FD_E_INVALID; }
-    const int ntan = (tu != nullptr) + (tv != nullptr) + (nrm != nullptr);
-    if (ntan != 0 && ntan != 3) { set_err(ctx, "fd_mesh_set: tu, tv, nrm must be all set or all NULL"); return FD_E_INVALID; }
+    if (!frames_ok(tu, tv, nrm)) { set_err(ctx, "fd_mesh_set: tu, tv, nrm must be all set or all NULL"); return FD_E_INVALID; }
     int rc = use_device(ctx);
     if (rc) return rc;
     ctx->mesh_N = 0;
@@ -1490,8 +1518,7 @@ int fd_batch_build_async(fd_batch *b, void *hip_stream)
         fd_ctx *c = b->ctxs[i];
         if (!c->points_set) { batch_err(b, "fd_batch_build: context %d has no control points", i); return FD_E_INVALID; }
         c->imported_layers = 0;
-        if (c->M != c0->M || c->kind != c0->kind || c->term != c0->term || c->nparams != c0->nparams ||
-            memcmp(c->params, c0->params, sizeof(c->params)) != 0) {
+        if (!same_model(c, c0)) {
             batch_err(b, "fd_batch_build: context %d differs from context 0 in M, kernel, parameters or term", i);
             return FD_E_INVALID;
         }
@@ -1520,41 +1547,19 @@ int fd_batch_build_async(fd_batch *b, void *hip_stream)
         if (e != hipSuccess) { batch_err(b, "slot table upload failed: %s", hipGetErrorString(e)); return FD_E_DEVICE; }
     }
     BuildBuffers bb;
-    fill_build_buffers(c0, bb);
+    choose_build(b->ctxs, b->n, bb);
     bb.d_slots = b->d_slots;
     bb.nbatch = b->n;
-    for (int i = 0; i < b->n; ++i)
-        if (!use_spd(b->ctxs[i])) bb.spd = 0;        // one context that fell back to the LU takes the batch with it
-    for (int i = 0; i < b->n; ++i)
-        if (b->ctxs[i]->solver != FD_SOLVER_ONE_WORKGROUP) bb.small = 0;      // ... and the one-workgroup build is everybody's choice or nobody's
-    for (int i = 0; i < b->n; ++i)
-        if (!use_reg(b->ctxs[i])) bb.reg = 0;                                  // ... and so is the register-resident one
-    if (!bb.spd) bb.reg = 0;
-    for (int i = 0; i < b->n; ++i)
-        if (!use_nopivot(b->ctxs[i])) bb.nopivot = 0;
     if (bb.reg && reg_build_init() != hipSuccess) { (void)hipGetLastError(); bb.reg = 0; }
     // a caller that leaves CUs to the builds (fd_batch_set_eval_cus below the device's count) runs them BESIDE evaluation launches:
     // one workgroup per model then stays on those CUs; the front end's short wide launches would queue for CUs the evaluation holds
     bb.reg_front = (b->eval_cus <= 0 || b->eval_cus >= (int)device_cus()) ? 1 : 0;
     bb.group_panels = b->n >= 4 ? 1 : 0;
 
-    fd_batch::Key key{};
-    key.M = c0->M; key.kind = c0->kind; key.term = c0->term | (bb.spd << 9) | (bb.small << 10) | (bb.reg << 11) | (bb.nopivot << 12); key.nparams = c0->nparams;
-    memcpy(key.params, c0->params, sizeof(key.params));
-    if (!bb.reg && b->use_graph && (!b->exec || memcmp(&key, &b->key, sizeof(key)) != 0)) {
-        if (b->exec) { (void)hipGraphExecDestroy(b->exec); b->exec = nullptr; }
-        hipGraph_t graph = nullptr;
-        hipError_t e = hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal);
-        if (e == hipSuccess) {
-            hipError_t e2 = launch_build(bb, stream, nullptr);
-            e = hipStreamEndCapture(stream, &graph);
-            if (e == hipSuccess && e2 != hipSuccess) e = e2;
-        }
-        if (e == hipSuccess && graph) e = hipGraphInstantiate(&b->exec, graph, nullptr, nullptr, 0);
-        if (graph) (void)hipGraphDestroy(graph);
-        if (e != hipSuccess) { (void)hipGetLastError(); b->exec = nullptr; b->use_graph = false; }
-        else b->key = key;
-    }
+    const GraphKey key = graph_key(c0, (bb.spd << 9) | (bb.small << 10) | (bb.reg << 11) | (bb.nopivot << 12), false);
+    if (!bb.reg && b->use_graph &&
+        ensure_graph(stream, &b->exec, &b->key, key, [&] { return launch_build(bb, stream, nullptr); }) != hipSuccess)
+        b->use_graph = false;
 #define FD_BHIP(call)                                                                         \
     do {                                                                                      \
         hipError_t e_ = (call);                                                               \
@@ -1595,48 +1600,12 @@ int fd_batch_build_async(fd_batch *b, void *hip_stream)
     if (!b->lean) FD_BHIP(hipEventRecord(b->ev1, stream));      // (lean: fd_batch_cook_group records it behind the evaluation)
     b->waited_stream = nullptr;
 #undef FD_BHIP
-    static uint64_t build_ids = 0;
+    static std::atomic<uint64_t> build_ids{0};
     const uint64_t this_build = same_rest_launch ? ++build_ids : 0;
-    for (int i = 0; i < b->n; ++i) {
-        fd_ctx *c = b->ctxs[i];
-        c->rig_build_id = this_build;
-        c->wait_event = b->ev1; c->wait_stream = stream; c->wait_batch = b;
-        c->tev0 = b->lean ? nullptr : b->ev0; c->tev_mid = b->lean ? nullptr : (bb.reg ? b->ev0 : b->ev_mid); c->tev1 = b->lean ? nullptr : b->ev1;
-        c->have_factor = bb.ml_layers == 0;   // a batched build leaves a factorisation fd_set_deltas can reuse (not the multilayer model)
-        c->factor_grouped = bb.group_panels != 0;
-        c->last_spd = bb.spd != 0;
-        c->last_reg = bb.spd != 0 && bb.reg != 0;
-        c->last_nopivot = bb.nopivot != 0;
-        c->deltas_only = false;
-        c->build_pending = true;
-        ++c->model_gen;
-        c->built = false;
-        c->have_report = false;
-        c->sticky_rc = FD_OK;
-    }
-    // the statuses of all contexts: one launch, one event (recorded on every context's own event
-    // object would cost a stream operation each)
-    bool posted_in_kernel = bb.reg != 0;
-    for (int i = 0; i < b->n; ++i) posted_in_kernel = posted_in_kernel && b->ctxs[i]->h_slot.host_status != nullptr;
-    if (posted_in_kernel) {
-        // (the register-resident build posts every context's status word itself: no status kernel behind it)
-        for (int i = 0; i < b->n; ++i) { b->ctxs[i]->status_poll = b->ev1; b->ctxs[i]->status_inflight = true; }
-    } else {
-        StatusTable st{};
-        bool ok = true;
-        for (int i = 0; i < b->n && ok; ++i) {
-            st.model[i] = b->ctxs[i]->d_model;
-            int *dword = b->ctxs[i]->d_status_alias;
-            ok = dword != nullptr;
-            st.host_word[i] = dword;
-        }
-        if (ok) {
-            hipLaunchKernelGGL(k_post_status_batch, dim3(1), dim3(kMaxBatch), 0, stream, st, b->n);
-            ok = hipGetLastError() == hipSuccess && hipEventRecord(b->status_ev, stream) == hipSuccess;
-            for (int i = 0; i < b->n && ok; ++i) { b->ctxs[i]->status_poll = b->status_ev; b->ctxs[i]->status_inflight = true; }
-        }
-        if (!ok) (void)hipGetLastError();
-    }
+    // (lean: the reports carry no phase times; the register-resident build has no phases to split)
+    hipEvent_t t0 = b->lean ? nullptr : b->ev0, t_mid = b->lean ? nullptr : (bb.reg ? b->ev0 : b->ev_mid), t1 = b->lean ? nullptr : b->ev1;
+    for (int i = 0; i < b->n; ++i) note_build_enqueued(b->ctxs[i], b->ev1, stream, b, t0, t_mid, t1, &bb, this_build);
+    arm_status(b->ctxs, b->n, stream, bb.reg != 0, b->ev1, b->status_ev);
     return FD_OK;
 }
 
@@ -1691,8 +1660,7 @@ int fd_batch_deform_dev(fd_batch *b, void *hip_stream, int64_t N, const float *c
 {
     if (!b || !d_P_in || !d_P_out) return FD_E_INVALID;
     if (N < 0) { batch_err(b, "fd_batch_deform_dev: N < 0"); return FD_E_INVALID; }
-    const int ntab = (d_tu != nullptr) + (d_tv != nullptr) + (d_nrm != nullptr);
-    if (ntab != 0 && ntab != 3) { batch_err(b, "fd_batch_deform_dev: tu, tv, nrm tables must be all set or all NULL"); return FD_E_INVALID; }
+    if (!frames_ok(d_tu, d_tv, d_nrm)) { batch_err(b, "fd_batch_deform_dev: tu, tv, nrm tables must be all set or all NULL"); return FD_E_INVALID; }
     if (N == 0) return FD_OK;
     fd_ctx *c0 = b->ctxs[0];
     int rc = use_device(c0);
@@ -1704,20 +1672,9 @@ int fd_batch_deform_dev(fd_batch *b, void *hip_stream, int64_t N, const float *c
         if (!d_P_in[i] || !d_P_out[i]) { batch_err(b, "fd_batch_deform_dev: NULL vertex array for context %d", i); return FD_E_INVALID; }
         if (!c->built && !c->build_pending) { batch_err(b, "fd_batch_deform_dev: context %d has no built model", i); return FD_E_NOT_BUILT; }
         const float *tu = d_tu ? d_tu[i] : nullptr, *tv = d_tv ? d_tv[i] : nullptr, *nr = d_nrm ? d_nrm[i] : nullptr;
-        const int ntan = (tu != nullptr) + (tv != nullptr) + (nr != nullptr);
-        if (ntan != 0 && ntan != 3) { batch_err(b, "fd_batch_deform_dev: context %d: tu, tv, nrm must be all set or all NULL", i); return FD_E_INVALID; }
-        DeformArgs &a = args[i];
-        a.N = N;
-        a.P_in = d_P_in[i]; a.P_out = d_P_out[i];
-        a.dist2 = d_dist2 ? d_dist2[i] : nullptr; a.falloff_out = d_falloff_out ? d_falloff_out[i] : nullptr;
-        a.tu = tu; a.tv = tv; a.nrm = nr;
-        a.radius2 = radius2; a.falloffrate = falloffrate;
-        a.M = model_centres(c); a.Mpad = round_up(a.M, kRecPad); a.kind = eval_kind(c); a.layers = record_layers(c);
-        a.rec32 = c->d_rec32; a.rec64 = c->d_rec64; a.tiles = c->d_tiles; a.tiles16 = c->d_tiles16;
-        a.model = c->d_model;
-        a.precision = c->eval_precision;
-        a.variant = c->eval_variant;
-        a.delta_out = c0->output == FD_OUTPUT_DISPLACEMENT;
+        if (!frames_ok(tu, tv, nr)) { batch_err(b, "fd_batch_deform_dev: context %d: tu, tv, nrm must be all set or all NULL", i); return FD_E_INVALID; }
+        args[i] = deform_args(c, N, d_P_in[i], d_P_out[i], d_dist2 ? d_dist2[i] : nullptr, d_falloff_out ? d_falloff_out[i] : nullptr,
+                              tu, tv, nr, radius2, falloffrate);
         if (c->output != c0->output) { batch_err(b, "fd_batch_deform_dev: context %d has another fd_set_output setting than context 0", i); return FD_E_INVALID; }
     }
     // statuses first: a model the poll had to rebuild (on its context's stream) is then ordered like any other build
@@ -1744,8 +1701,7 @@ static int shared_applies(fd_batch *b, const char *who, float *const *d_P_out, i
         if (!d_P_out[i]) { batch_err(b, "%s: NULL output array for context %d", who, i); return FD_E_INVALID; }
         if (!c->built && !c->build_pending) { batch_err(b, "%s: context %d has no built model", who, i); return FD_E_NOT_BUILT; }
         // one rest rig: every context read its rest points in place from the SAME device array
-        if (!c->rest_src || c->rest_src != c0->rest_src || c->M != c0->M || c->kind != c0->kind ||
-            c->term != c0->term || c->nparams != c0->nparams || memcmp(c->params, c0->params, sizeof(c->params)) != 0) {
+        if (!c->rest_src || c->rest_src != c0->rest_src || !same_model(c, c0)) {
             batch_err(b, "%s: the contexts must share one rest rig (fd_batch_set_points_dev with the "
                          "same rest array for all), kernel and term; context %d does not", who, i);
             return FD_E_INVALID;
@@ -1846,8 +1802,7 @@ int fd_batch_deform_shared_dev(fd_batch *b, void *hip_stream, int64_t N, const f
 {
     if (!b || !d_P_out) return FD_E_INVALID;
     if (N < 0 || (N > 0 && !d_P_in)) { batch_err(b, "fd_batch_deform_shared_dev: bad N / P_in"); return FD_E_INVALID; }
-    const int ntan = (d_tu != nullptr) + (d_tv != nullptr) + (d_nrm != nullptr);
-    if (ntan != 0 && ntan != 3) { batch_err(b, "fd_batch_deform_shared_dev: tu, tv, nrm must be all set or all NULL"); return FD_E_INVALID; }
+    if (!frames_ok(d_tu, d_tv, d_nrm)) { batch_err(b, "fd_batch_deform_shared_dev: tu, tv, nrm must be all set or all NULL"); return FD_E_INVALID; }
     if (N == 0) return FD_OK;
     fd_ctx *c0 = b->ctxs[0];
     int rc = use_device(c0);
