@@ -41,6 +41,12 @@ class FdReport(C.Structure):
                 ("delta_min", C.c_double), ("delta_max", C.c_double), ("extent", C.c_double)]
 
 
+class FdVectors(C.Structure):
+    """fd_vectors: the vectors fd_deform_vectors* carry through the deformation (N x 3 each) and its Jacobian (N x 9)."""
+    _fields_ = [("struct_size", C.c_int), ("N", C.c_void_p), ("N_out", C.c_void_p), ("tu", C.c_void_p), ("tu_out", C.c_void_p),
+                ("tv", C.c_void_p), ("tv_out", C.c_void_p), ("jacobian", C.c_void_p)]
+
+
 class FdsopGeo(C.Structure):
     _fields_ = [("npoints", C.c_int64), ("P", _f32p), ("tangentu", _f32p), ("tangentv", _f32p),
                 ("N", _f32p), ("dist2", _f32p), ("rest_npoints", C.c_int64),
@@ -58,7 +64,7 @@ class FdsopGeo(C.Structure):
 EXPORTS = [
     "fd_create", "fd_destroy", "fd_last_error", "fd_abi_version", "fd_set_stream", "fd_set_eval_precision", "fd_set_output", "fd_fp32_holds", "fd_set_points",
     "fd_set_points_dev", "fd_set_deltas", "fd_set_deltas_dev", "fd_set_kernel", "fd_set_term", "fd_build", "fd_build_async",
-    "fd_build_result", "fd_deform", "fd_deform_dev", "fd_deform_dev_stream", "fd_get_weights", "fd_model_centres", "fd_model_bytes",
+    "fd_build_result", "fd_deform", "fd_deform_dev", "fd_deform_dev_stream", "fd_deform_vectors", "fd_deform_vectors_dev", "fd_get_weights", "fd_model_centres", "fd_model_bytes",
     "fd_export_model", "fd_import_model", "fd_synchronize", "fd_host_alloc", "fd_host_free",
     "fd_mesh_set", "fd_mesh_size", "fd_deform_mesh", "fd_mesh_capture", "fd_mesh_get_dist2",
     "fd_capture_dist2", "fd_capture_dist2_dev", "fd_capture_islands", "fd_capture_islands_dev",
@@ -121,6 +127,10 @@ def load() -> C.CDLL:
     L.fd_deform_dev.restype = i32
     L.fd_deform_dev_stream.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float]
     L.fd_deform_dev_stream.restype = i32
+    L.fd_deform_vectors.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, C.POINTER(FdVectors)]
+    L.fd_deform_vectors.restype = i32
+    L.fd_deform_vectors_dev.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, C.POINTER(FdVectors)]
+    L.fd_deform_vectors_dev.restype = i32
     L.fd_get_weights.argtypes = [vp, _f64p, _f64p]; L.fd_get_weights.restype = i32
     L.fd_model_centres.argtypes = [vp]; L.fd_model_centres.restype = i32
     L.fd_model_bytes.argtypes = [vp]; L.fd_model_bytes.restype = sz
@@ -390,6 +400,38 @@ class Engine:
                                                 vp(d_dist2 or None), vp(d_falloff or None), vp(d_tu or None),
                                                 vp(d_tv or None), vp(d_nrm or None), float(radius2),
                                                 float(falloffrate)))
+
+    def deform_vectors(self, P, dist2=None, tangents=None, N=None, tu=None, tv=None, want_jacobian=False,
+                       radius2=1.0, falloffrate=1.0):
+        """fd_deform_vectors: the deformation plus what it does to vectors.  tangents = (tu, tv, nrm) are the projection
+        frames; N is transported as a normal, tu / tv as tangents.  Returns (P_out, falloff, N_out, tu_out, tv_out,
+        jacobian), None for what was not asked for; jacobian is N x 3 x 3 (row-major A per vertex)."""
+        P = np.ascontiguousarray(P, np.float32).reshape(-1, 3)
+        n = P.shape[0]
+        out = P.copy()
+        d2 = None if dist2 is None else np.ascontiguousarray(dist2, np.float32)
+        fall = np.zeros(n, np.float32)
+        fu = fv = fn = None
+        if tangents is not None:
+            fu, fv, fn = (np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in tangents)
+        ins = [None if a is None else np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in (N, tu, tv)]
+        outs = [None if a is None else np.empty_like(a) for a in ins]
+        jac = np.empty((n, 3, 3), np.float32) if want_jacobian else None
+        vec = FdVectors(C.sizeof(FdVectors), *(x for a, o in zip(ins, outs) for x in (_np_ptr(a), _np_ptr(o))), _np_ptr(jac))
+        self._check(self.L.fd_deform_vectors(self.ctx, n, _np_ptr(out), _np_ptr(out), _np_ptr(d2), _np_ptr(fall), _np_ptr(fu),
+                                             _np_ptr(fv), _np_ptr(fn), float(radius2), float(falloffrate), C.byref(vec)))
+        return (out, fall, *outs, jac)
+
+    def deform_vectors_dev(self, N: int, d_P_in: int, d_P_out: int, d_dist2: int = 0, d_falloff: int = 0, d_tu: int = 0,
+                           d_tv: int = 0, d_nrm: int = 0, d_N: int = 0, d_N_out: int = 0, d_vtu: int = 0, d_vtu_out: int = 0,
+                           d_vtv: int = 0, d_vtv_out: int = 0, d_jacobian: int = 0, radius2=1.0, falloffrate=1.0):
+        """fd_deform_vectors_dev: device pointers (ints), asynchronous on the context's stream.  d_tu / d_tv / d_nrm are the
+        projection frames, d_N / d_vtu / d_vtv the transported vectors with their outputs."""
+        vp = C.c_void_p
+        vec = FdVectors(C.sizeof(FdVectors), *(vp(a or None) for a in (d_N, d_N_out, d_vtu, d_vtu_out, d_vtv, d_vtv_out, d_jacobian)))
+        self._check(self.L.fd_deform_vectors_dev(self.ctx, N, vp(d_P_in), vp(d_P_out), vp(d_dist2 or None), vp(d_falloff or None),
+                                                 vp(d_tu or None), vp(d_tv or None), vp(d_nrm or None), float(radius2),
+                                                 float(falloffrate), C.byref(vec)))
 
     def get_weights(self):
         n = int(self.L.fd_model_centres(self.ctx))     # M, or M * layers for the multilayer model

@@ -95,6 +95,9 @@ struct fd_ctx {
     int64_t cap_N = 0;
     float *d_P = nullptr, *d_dist2 = nullptr, *d_fall = nullptr;
     float *d_tu = nullptr, *d_tv = nullptr, *d_nrm = nullptr;
+    // fd_deform_vectors: staging of the transported vectors + Jacobian (N x 18), and P_in set aside when it is overwritten
+    int64_t cap_vec = 0, cap_vecP = 0;
+    float *d_vec = nullptr, *d_vecP = nullptr;
     // fd_mesh_set: the mesh arrays that stay the same from cook to cook live in their own
     // device buffers (the staging above is evaluated in place, so it cannot serve as a cache)
     int64_t mesh_N = 0, mesh_cap = 0;
@@ -414,6 +417,8 @@ static bool frames_ok(const void *tu, const void *tv, const void *nrm)
 }
 
 static int poll_status(fd_ctx *ctx);
+static int deform_host(fd_ctx *ctx, int64_t N, const float *P_in, float *P_out, const float *dist2, float *falloff_out,
+                       const float *tu, const float *tv, const float *nrm, float radius2, float falloffrate, const fd_vectors *vec);
 
 extern "C" {
 
@@ -486,7 +491,7 @@ void fd_destroy(fd_ctx *ctx)
     if (ctx->stream_ || ctx->own_stream) (void)hipStreamSynchronize(cur_stream(ctx));
     void *bufs[] = {ctx->d_rest, ctx->d_delta, ctx->d_centres, ctx->d_radii, ctx->d_W, ctx->d_A,
                     ctx->d_X, ctx->d_ipiv, ctx->d_moves, ctx->d_rec32, ctx->d_rec64, ctx->d_tiles, ctx->d_tiles16, ctx->d_ns, ctx->d_model, ctx->d_slot,
-                    ctx->d_P, ctx->d_dist2, ctx->d_fall, ctx->d_tu, ctx->d_tv, ctx->d_nrm,
+                    ctx->d_P, ctx->d_dist2, ctx->d_fall, ctx->d_tu, ctx->d_tv, ctx->d_nrm, ctx->d_vec, ctx->d_vecP,
                     ctx->m_P, ctx->m_dist2, ctx->m_tu, ctx->m_tv, ctx->m_nrm, ctx->m_out, ctx->m_fall};
     for (void *p : bufs) if (p) (void)hipFree(p);
     if (ctx->h_model) (void)hipHostFree(ctx->h_model);
@@ -916,6 +921,68 @@ static DeformArgs deform_args(const fd_ctx *c, int64_t N, const float *P_in, flo
     return a;
 }
 
+// fd_deform_vectors*: a struct of at least this ABI's size, each transported vector with its output
+static bool vectors_ok(fd_ctx *ctx, const fd_vectors *vec)
+{
+    if (!vec) return true;
+    if (vec->struct_size < (int)sizeof(fd_vectors)) {
+        set_err(ctx, "fd_deform_vectors: vec->struct_size is %d, must be sizeof(fd_vectors) = %d", vec->struct_size,
+                (int)sizeof(fd_vectors));
+        return false;
+    }
+    if ((!vec->N != !vec->N_out) || (!vec->tu != !vec->tu_out) || (!vec->tv != !vec->tv_out)) {
+        set_err(ctx, "fd_deform_vectors: every vector needs its input and its output (both or neither)");
+        return false;
+    }
+    return true;
+}
+static bool vectors_wanted(const fd_vectors *vec) { return vec && (vec->N || vec->tu || vec->tv || vec->jacobian); }
+
+// fd_deform_dev_stream / fd_deform_vectors_dev / the staged host calls: vec == nullptr is the deformation alone
+static int deform_dev_common(fd_ctx *ctx, void *hip_stream, int64_t N, const float *d_P_in, float *d_P_out,
+                             const float *d_dist2, float *d_falloff_out, const float *d_tu, const float *d_tv,
+                             const float *d_nrm, float radius2, float falloffrate, const fd_vectors *vec)
+{
+    hipStream_t launch_stream = hip_stream ? (hipStream_t)hip_stream : cur_stream(ctx);
+    if (N < 0 || (N > 0 && (!d_P_in || !d_P_out))) { set_err(ctx, "fd_deform: bad N / P pointers"); return FD_E_INVALID; }
+    if (!frames_ok(d_tu, d_tv, d_nrm)) { set_err(ctx, "fd_deform: tu, tv, nrm must be all set or all NULL"); return FD_E_INVALID; }
+    if (!ctx->built && !ctx->build_pending) { set_err(ctx, "fd_deform: no successfully built model"); return FD_E_NOT_BUILT; }
+    if (N == 0) return FD_OK;
+    int rc = use_device(ctx);
+    if (rc) return rc;
+    if ((rc = poll_status(ctx))) return rc;           // a failed asynchronous build: repaired here, or reported
+    const DeformArgs a = deform_args(ctx, N, d_P_in, d_P_out, d_dist2, d_falloff_out, d_tu, d_tv, d_nrm, radius2, falloffrate);
+    if ((rc = order_after_batch(ctx, launch_stream))) return rc;
+    if (!vec) {
+        FD_HIP(ctx, launch_deform(a, launch_stream));
+        return FD_OK;
+    }
+    // The vectors' launch reads P_in and the frames, the deformation's writes P_out: the vectors go first, so that
+    // P_out may alias P_in.  A transported vector written over a projection frame (N_out == nrm: the SOP's in-place N)
+    // must wait for the deformation instead, which then may not overwrite P_in: P_in is copied aside for that case.
+    const VectorArgs v{vec->N, vec->tu, vec->tv, vec->N_out, vec->tu_out, vec->tv_out, vec->jacobian};
+    const float *const outs[3] = {v.N_out, v.tu_out, v.tv_out};
+    bool clash = false;
+    for (const float *o : outs) clash |= o && (o == d_tu || o == d_tv || o == d_nrm || o == d_dist2);
+    if (!clash) {
+        FD_HIP(ctx, launch_vectors(a, v, launch_stream));
+        FD_HIP(ctx, launch_deform(a, launch_stream));
+        return FD_OK;
+    }
+    DeformArgs av = a;
+    if (d_P_out == d_P_in) {
+        if (N > ctx->cap_vecP) {
+            if ((rc = dev_alloc(ctx, &ctx->d_vecP, (size_t)N * 3))) return rc;
+            ctx->cap_vecP = N;
+        }
+        FD_HIP(ctx, hipMemcpyAsync(ctx->d_vecP, d_P_in, sizeof(float) * 3 * (size_t)N, hipMemcpyDeviceToDevice, launch_stream));
+        av.P_in = ctx->d_vecP;
+    }
+    FD_HIP(ctx, launch_deform(a, launch_stream));
+    FD_HIP(ctx, launch_vectors(av, v, launch_stream));
+    return FD_OK;
+}
+
 extern "C" {
 
 int fd_deform_dev(fd_ctx *ctx, int64_t N, const float *d_P_in, float *d_P_out, const float *d_dist2,
@@ -932,18 +999,18 @@ int fd_deform_dev_stream(fd_ctx *ctx, void *hip_stream, int64_t N, const float *
                          const float *d_tv, const float *d_nrm, float radius2, float falloffrate)
 {
     if (!ctx) return FD_E_INVALID;
-    hipStream_t launch_stream = hip_stream ? (hipStream_t)hip_stream : cur_stream(ctx);
-    if (N < 0 || (N > 0 && (!d_P_in || !d_P_out))) { set_err(ctx, "fd_deform: bad N / P pointers"); return FD_E_INVALID; }
-    if (!frames_ok(d_tu, d_tv, d_nrm)) { set_err(ctx, "fd_deform: tu, tv, nrm must be all set or all NULL"); return FD_E_INVALID; }
-    if (!ctx->built && !ctx->build_pending) { set_err(ctx, "fd_deform: no successfully built model"); return FD_E_NOT_BUILT; }
-    if (N == 0) return FD_OK;
-    int rc = use_device(ctx);
-    if (rc) return rc;
-    if ((rc = poll_status(ctx))) return rc;           // a failed asynchronous build: repaired here, or reported
-    const DeformArgs a = deform_args(ctx, N, d_P_in, d_P_out, d_dist2, d_falloff_out, d_tu, d_tv, d_nrm, radius2, falloffrate);
-    if ((rc = order_after_batch(ctx, launch_stream))) return rc;
-    FD_HIP(ctx, launch_deform(a, launch_stream));
-    return FD_OK;
+    return deform_dev_common(ctx, hip_stream, N, d_P_in, d_P_out, d_dist2, d_falloff_out, d_tu, d_tv, d_nrm, radius2,
+                             falloffrate, nullptr);
+}
+
+int fd_deform_vectors_dev(fd_ctx *ctx, int64_t N, const float *d_P_in, float *d_P_out, const float *d_dist2,
+                          float *d_falloff_out, const float *d_tu, const float *d_tv, const float *d_nrm,
+                          float radius2, float falloffrate, const fd_vectors *vec)
+{
+    if (!ctx) return FD_E_INVALID;
+    if (!vectors_ok(ctx, vec)) return FD_E_INVALID;
+    return deform_dev_common(ctx, nullptr, N, d_P_in, d_P_out, d_dist2, d_falloff_out, d_tu, d_tv, d_nrm, radius2,
+                             falloffrate, vectors_wanted(vec) ? vec : nullptr);
 }
 
 int fd_deform(fd_ctx *ctx, int64_t N, const float *P_in, float *P_out, const float *dist2,
@@ -951,6 +1018,26 @@ int fd_deform(fd_ctx *ctx, int64_t N, const float *P_in, float *P_out, const flo
               float falloffrate)
 {
     if (!ctx) return FD_E_INVALID;
+    return deform_host(ctx, N, P_in, P_out, dist2, falloff_out, tu, tv, nrm, radius2, falloffrate, nullptr);
+}
+
+int fd_deform_vectors(fd_ctx *ctx, int64_t N, const float *P_in, float *P_out, const float *dist2,
+                      float *falloff_out, const float *tu, const float *tv, const float *nrm,
+                      float radius2, float falloffrate, const fd_vectors *vec)
+{
+    if (!ctx) return FD_E_INVALID;
+    if (!vectors_ok(ctx, vec)) return FD_E_INVALID;
+    return deform_host(ctx, N, P_in, P_out, dist2, falloff_out, tu, tv, nrm, radius2, falloffrate,
+                       vectors_wanted(vec) ? vec : nullptr);
+}
+
+}  // extern "C"
+
+// fd_deform / fd_deform_vectors on host arrays: staged through the context's device buffers, or -- page-locked arrays and
+// no vectors -- read and written in place
+static int deform_host(fd_ctx *ctx, int64_t N, const float *P_in, float *P_out, const float *dist2, float *falloff_out,
+                       const float *tu, const float *tv, const float *nrm, float radius2, float falloffrate, const fd_vectors *vec)
+{
     if (N < 0 || (N > 0 && (!P_in || !P_out))) { set_err(ctx, "fd_deform: bad N / P pointers"); return FD_E_INVALID; }
     if (!frames_ok(tu, tv, nrm)) { set_err(ctx, "fd_deform: tu, tv, nrm must be all set or all NULL"); return FD_E_INVALID; }
     if (!ctx->built && !ctx->build_pending) { set_err(ctx, "fd_deform: no successfully built model"); return FD_E_NOT_BUILT; }
@@ -961,7 +1048,7 @@ int fd_deform(fd_ctx *ctx, int64_t N, const float *P_in, float *P_out, const flo
     // and writes them in place over the host link -- reads and writes travel in both directions
     // at once and nothing is staged.  Measured at C2: 0.44 ms against 0.62 ms for upload +
     // evaluate + download (chunking those copies over two streams did not overlap them at all).
-    const bool all_pinned = host_is_pinned(P_in) && host_is_pinned(P_out) && (!dist2 || host_is_pinned(dist2)) &&
+    const bool all_pinned = !vec && host_is_pinned(P_in) && host_is_pinned(P_out) && (!dist2 || host_is_pinned(dist2)) &&
                             (!falloff_out || host_is_pinned(falloff_out)) &&
                             (!tu || (host_is_pinned(tu) && host_is_pinned(tv) && host_is_pinned(nrm)));
     if (all_pinned) {
@@ -1011,15 +1098,40 @@ int fd_deform(fd_ctx *ctx, int64_t N, const float *P_in, float *P_out, const flo
         FD_HIP(ctx, hipMemcpyAsync(ctx->d_tv, tv, b3, hipMemcpyHostToDevice, s));
         FD_HIP(ctx, hipMemcpyAsync(ctx->d_nrm, nrm, b3, hipMemcpyHostToDevice, s));
     }
-    rc = fd_deform_dev(ctx, N, ctx->d_P, ctx->d_P, dist2 ? ctx->d_dist2 : nullptr,
-                       falloff_out ? ctx->d_fall : nullptr, tu ? ctx->d_tu : nullptr,
-                       tu ? ctx->d_tv : nullptr, tu ? ctx->d_nrm : nullptr, radius2, falloffrate);
+    // the vectors: each staged in its own device array and transported in place there
+    fd_vectors dv{};
+    if (vec) {
+        if (N > ctx->cap_vec) {
+            if ((rc = dev_alloc(ctx, &ctx->d_vec, (size_t)N * 18))) return rc;
+            ctx->cap_vec = N;
+        }
+        float *const slot[4] = {ctx->d_vec, ctx->d_vec + 3 * N, ctx->d_vec + 6 * N, ctx->d_vec + 9 * N};
+        const float *const in[3] = {vec->N, vec->tu, vec->tv};
+        for (int k = 0; k < 3; ++k)
+            if (in[k]) FD_HIP(ctx, hipMemcpyAsync(slot[k], in[k], b3, hipMemcpyHostToDevice, s));
+        dv.struct_size = (int)sizeof(fd_vectors);
+        if (vec->N) { dv.N = slot[0]; dv.N_out = slot[0]; }
+        if (vec->tu) { dv.tu = slot[1]; dv.tu_out = slot[1]; }
+        if (vec->tv) { dv.tv = slot[2]; dv.tv_out = slot[2]; }
+        if (vec->jacobian) dv.jacobian = slot[3];
+    }
+    rc = deform_dev_common(ctx, nullptr, N, ctx->d_P, ctx->d_P, dist2 ? ctx->d_dist2 : nullptr,
+                           falloff_out ? ctx->d_fall : nullptr, tu ? ctx->d_tu : nullptr,
+                           tu ? ctx->d_tv : nullptr, tu ? ctx->d_nrm : nullptr, radius2, falloffrate, vec ? &dv : nullptr);
     if (rc) return rc;
     FD_HIP(ctx, hipMemcpyAsync(P_out, ctx->d_P, b3, hipMemcpyDeviceToHost, s));
     if (falloff_out) FD_HIP(ctx, hipMemcpyAsync(falloff_out, ctx->d_fall, b1, hipMemcpyDeviceToHost, s));
+    if (vec) {
+        if (vec->N) FD_HIP(ctx, hipMemcpyAsync(vec->N_out, dv.N_out, b3, hipMemcpyDeviceToHost, s));
+        if (vec->tu) FD_HIP(ctx, hipMemcpyAsync(vec->tu_out, dv.tu_out, b3, hipMemcpyDeviceToHost, s));
+        if (vec->tv) FD_HIP(ctx, hipMemcpyAsync(vec->tv_out, dv.tv_out, b3, hipMemcpyDeviceToHost, s));
+        if (vec->jacobian) FD_HIP(ctx, hipMemcpyAsync(vec->jacobian, dv.jacobian, 3 * b3, hipMemcpyDeviceToHost, s));
+    }
     FD_HIP(ctx, hipStreamSynchronize(s));
     return FD_OK;
 }
+
+extern "C" {
 
 // ---- dist2 producer (next row N2; kernel in fd_capture.hip) -----------------------------------
 int fd_capture_dist2_dev(fd_ctx *ctx, int64_t N, const float *d_P, const unsigned char *d_mask, int T,

@@ -237,6 +237,14 @@ struct DeformArgs {
     int delta_out;         // FD_OUTPUT_DISPLACEMENT: P_out receives the displacement (the addend of :438), not P + displacement
 };
 hipError_t launch_deform(const DeformArgs &a, hipStream_t stream);
+// the deformation's Jacobian and the vectors it carries (fd_vectors.hip, fd_deform_vectors*): reads P_in, dist2, the
+// projection frames and the model of `a`; writes neither P_out nor falloff_out.  Each output may alias its own input.
+struct VectorArgs {
+    const float *N, *tu, *tv;
+    float *N_out, *tu_out, *tv_out;
+    float *jacobian;      // N x 9, row-major A
+};
+hipError_t launch_vectors(const DeformArgs &a, const VectorArgs &v, hipStream_t stream);
 hipError_t launch_deform_batch(const DeformArgs *a, int n, hipStream_t stream);
 // frames that share the mesh and the rest rig (fd_eval.hip, k_deform32_tps_shared): phi once per
 // (vertex, centre), the 3 F-wide weight contraction on the matrix pipe

@@ -95,6 +95,30 @@ struct PackGlobal {
     __device__ __forceinline__ int dup_flag() const { return model->dup_flag; }
 };
 
+// ---- derivative constants of the records as packed (fd_vectors.hip) ---------------------
+// With phi' the function the evaluation applies to a record (phi32 / phi64 in fd_eval.hip) and w* the weight as packed
+// below, the Jacobian's RBF part is  J = grad_scale * sum_j w*_j g_j(d2) (x - c_j)  with
+//   fp64 records (raw coordinates; w64 = 0.5 w for thin-plate, -w for biharmonic):
+//     thin-plate  g = ln d2 + 1          scale 2       (d/dx d2 ln d2 = 2 (x - c)(ln d2 + 1))
+//     Gaussian    g = phi' * s64         scale 2       (s64 = -1/R^2)
+//     biharmonic  g = 1 / r              scale 1       (0 at r = 0)
+//     cubic       g = r                  scale 3
+//   fp32 records (normalised x' = (x - x0) inv_s, w32 as folded below): the same with x' and c', times the chain-rule
+//   factor inv_s, and for thin-plate g = log2 d2' + log2(e) (the 0.5 ln2 s^2 of w32 and the log2 combine to the raw
+//   w s (x' - c')(ln d2' + 1); the missing 2 s ln s w (x' - c') is the derivative of poly32's kappa terms, 2 q x' - 2 kappa m1).
+//   Gaussian: the exp2 argument s32 = -log2(e) s^2 / R^2 brings a factor ln 2.
+// The polynomial part is d/dx of affine64 (fp64) and inv_s (L' + 2 q x') of poly32 (fp32).
+constexpr float kTpsGradLog2e = 1.4426950408889634f;
+__host__ __device__ constexpr double grad_scale64(int kind)
+{
+    return kind == FD_KERNEL_BIHARMONIC ? 1.0 : (kind == FD_KERNEL_CUBIC ? 3.0 : 2.0);
+}
+__host__ __device__ constexpr float grad_scale32(int kind)
+{
+    return kind == FD_KERNEL_GAUSSIAN || kind == FD_KERNEL_GAUSSIAN_QNN ? (float)(2.0 * 0.6931471805599453)
+                                                                        : (float)grad_scale64(kind);
+}
+
 // (256 threads; a kernel of its own in fd_build.hip, the last phase of the one-launch build in fd_nullspace.hip)
 template <class Src>
 __device__ __forceinline__ void pack_body_from(const Src &in, const BatchSlot &slot, int npad, int M, int Mpad, int T, int kind, int from_w, int layers)

@@ -256,6 +256,55 @@ int fd_deform_dev_stream(fd_ctx *ctx, void *hip_stream, int64_t N, const float *
                          const float *d_dist2, float *d_falloff_out, const float *d_tu,
                          const float *d_tv, const float *d_nrm, float radius2, float falloffrate);
 
+/* ---- normals, tangents and the Jacobian of the deformation -------------------
+ * At a vertex x that the gate lets through (!(dist2 > radius2), :408), the evaluation writes
+ * P' = x + f . Pi . d(x):
+ *   d   is the RBF field, including its polynomial term;
+ *   Pi  = a1 a1^T + a2 a2^T is the tangent projection of project_to_tangents, built from the same
+ *       normalised u, v, n.  It is the identity when no frames are given;
+ *   f   is the fall-off.
+ * dist2 and the frames are per-point attributes, so f and Pi are constant under the derivative.
+ * The local Jacobian is therefore
+ *   A = I + f . Pi . J(x),   J = dd/dx = sum_j w_j grad phi_j(x - c_j) + L
+ * (L: the 3x3 linear-term block; 0 for CONST/ZERO terms).  The outputs follow from A:
+ *   jacobian            A, row-major, 9 floats per vertex;
+ *   tangentu, tangentv  t' = A t, not renormalised, so stretch shows;
+ *   N                   n' = cof(A) n, rescaled to |n|.  cof(A) = det(A) A^-T, written with cofactors
+ *                       and no division: exactly the normal of the deformed tangent plane,
+ *                       cof(A)(u x v) = (A u) x (A v), and defined when A is singular.  If n = 0 or
+ *                       cof(A) n = 0, n is written unchanged.
+ * Gated vertices and a model that is not built (terminationtype != 1, fd_deform's pass-through):
+ * every output is the input bit for bit, and A = I exactly.  A vertex with f = 0 also gets A = I exactly.
+ * grad phi per kind, in the raw form of the table above (r = |x - c|):
+ *   thin-plate   (x - c)(2 ln r + 1), 0 at r = 0;
+ *   Gaussian, QNN and multilayer   -2 (x - c) / R_j^2 . phi, one record per layer for the multilayer model;
+ *   cubic        3 r (x - c);
+ *   biharmonic   -(x - c) / r, taken as 0 at r = 0: the cone -r has no gradient at its tip.
+ * A is evaluated in the context's precision (fd_set_eval_precision) and stored as fp32.
+ *
+ * fd_vectors: what to transport.  N, tu, tv are N x 3 fp32, each with its *_out (both or neither);
+ * an output may alias its own input.  jacobian: N x 9, or NULL.  The projection frames (tu, tv, nrm
+ * of the call) are separate arguments: a caller may transport N without projecting, and may pass
+ * the same arrays to both. */
+typedef struct fd_vectors {
+    int struct_size;                 /* = sizeof(fd_vectors); smaller is FD_E_INVALID          */
+    const float *N;  float *N_out;   /* transported as normals (n' = cof(A) n, |n'| = |n|)     */
+    const float *tu; float *tu_out;  /* transported as tangents (t' = A t)                     */
+    const float *tv; float *tv_out;
+    float *jacobian;                 /* N x 9 row-major A, or NULL                             */
+} fd_vectors;
+
+/* fd_deform plus the outputs of `vec`.  P_out and falloff_out are bit-identical to fd_deform's for the
+ * same arguments, precision and fd_set_output setting; vec == NULL, or every pointer in it NULL, is
+ * fd_deform.  Same error codes, build-status poll and repair as fd_deform.  Host arrays, synchronous. */
+int fd_deform_vectors(fd_ctx *ctx, int64_t N, const float *P_in, float *P_out, const float *dist2,
+                      float *falloff_out, const float *tu, const float *tv, const float *nrm,
+                      float radius2, float falloffrate, const fd_vectors *vec);
+/* Same, device pointers (those in `vec` too), asynchronous on the context's stream, like fd_deform_dev. */
+int fd_deform_vectors_dev(fd_ctx *ctx, int64_t N, const float *d_P_in, float *d_P_out, const float *d_dist2,
+                          float *d_falloff_out, const float *d_tu, const float *d_tv, const float *d_nrm,
+                          float radius2, float falloffrate, const fd_vectors *vec);
+
 /* ---- device-resident mesh (next row N3, engine side) --------------------------
  * In an animated shot the mesh on input 0 -- P, the capture's dist2, the tangent
  * frames -- is the same from cook to cook (Houdini tells by the attributes' data
