@@ -47,6 +47,14 @@ class FdVectors(C.Structure):
                 ("tv", C.c_void_p), ("tv_out", C.c_void_p), ("jacobian", C.c_void_p)]
 
 
+class FdBatchVectors(C.Structure):
+    """fd_batch_vectors: ONE input array per vector (the shared mesh's, N x 3) with a table of one output pointer per
+    context, and a table of Jacobian outputs (N x 9 each) or NULL."""
+    _fields_ = [("struct_size", C.c_int), ("N", C.c_void_p), ("N_out", C.POINTER(C.c_void_p)), ("tu", C.c_void_p),
+                ("tu_out", C.POINTER(C.c_void_p)), ("tv", C.c_void_p), ("tv_out", C.POINTER(C.c_void_p)),
+                ("jacobian", C.POINTER(C.c_void_p))]
+
+
 class FdsopGeo(C.Structure):
     _fields_ = [("npoints", C.c_int64), ("P", _f32p), ("tangentu", _f32p), ("tangentv", _f32p),
                 ("N", _f32p), ("dist2", _f32p), ("rest_npoints", C.c_int64),
@@ -74,7 +82,7 @@ EXPORTS = [
     "fd_morph_get_qr",
     "fd_batch_create", "fd_batch_destroy", "fd_batch_size", "fd_batch_last_error", "fd_batch_wait_consumed", "fd_batch_prepare_shared", "fd_batch_set_eval_cus", "fd_batch_cook_group", "fd_shared_kernel_name", "fd_batch_set_shared_factor", "fd_batch_last_build_shared_factor",
     "fd_batch_set_points_dev", "fd_batch_build_async", "fd_batch_build_result", "fd_batch_deform_dev",
-    "fd_batch_deform_shared_dev",
+    "fd_batch_deform_shared_dev", "fd_batch_deform_vectors_shared_dev", "fd_shared_vectors_kernel_name",
     "fdsop_create", "fdsop_destroy", "fdsop_set_float", "fdsop_set_int", "fdsop_set_string",
     "fdsop_get_float", "fdsop_get_int", "fdsop_parm_count", "fdsop_parm_token", "fdsop_cook",
     "fdsop_messages", "fdsop_effective_float", "fdsop_engine",
@@ -182,6 +190,9 @@ def load() -> C.CDLL:
     L.fd_batch_deform_dev.restype = i32
     L.fd_batch_deform_shared_dev.argtypes = [vp, vp, i64, vp, pv, vp, pv, vp, vp, vp, C.c_float, C.c_float]
     L.fd_batch_deform_shared_dev.restype = i32
+    L.fd_batch_deform_vectors_shared_dev.argtypes = [vp, vp, i64, vp, pv, vp, pv, vp, vp, vp, C.c_float, C.c_float, C.POINTER(FdBatchVectors)]
+    L.fd_batch_deform_vectors_shared_dev.restype = i32
+    L.fd_shared_vectors_kernel_name.argtypes = [i32, i32, i32]; L.fd_shared_vectors_kernel_name.restype = C.c_char_p
     L.fdsop_create.argtypes = [C.POINTER(FdConfig)]; L.fdsop_create.restype = vp
     L.fdsop_destroy.argtypes = [vp]; L.fdsop_destroy.restype = None
     L.fdsop_set_float.argtypes = [vp, C.c_char_p, i32, C.c_double]; L.fdsop_set_float.restype = i32
@@ -574,6 +585,32 @@ class Batch:
                                                       falls, vp(tu or None), vp(tv or None), vp(nr or None),
                                                       float(radius2), float(falloffrate)))
 
+    def deform_vectors_shared_dev(self, N: int, d_P_in: int, d_P_out, d_dist2: int = 0, d_falloff=None, d_tangents=None,
+                                  d_N: int = 0, d_N_out=None, d_vtu: int = 0, d_vtu_out=None, d_vtv: int = 0, d_vtv_out=None,
+                                  d_jacobian=None, radius2=1.0, falloffrate=1.0, stream_ptr: int | None = None):
+        """fd_batch_deform_vectors_shared_dev: deform_shared_dev plus, per context, the Jacobian and the vectors it carries.
+        d_N / d_vtu / d_vtv are ONE device array each (the shared mesh's); d_N_out / d_vtu_out / d_vtv_out / d_jacobian
+        are lists of one output pointer per context (or None)."""
+        n = len(self.engines)
+        vp = C.c_void_p
+        if len(d_P_out) != n or (d_falloff is not None and len(d_falloff) != n):
+            raise ValueError("one output pointer per context")
+
+        def tab(t):
+            if t is None:
+                return None
+            if len(t) != n:
+                raise ValueError("one output pointer per context")
+            return (vp * n)(*[p or None for p in t])
+        outs = (vp * n)(*d_P_out)
+        falls = None if d_falloff is None else (vp * n)(*[p or None for p in d_falloff])
+        tu, tv, nr = d_tangents if d_tangents is not None else (0, 0, 0)
+        vec = FdBatchVectors(C.sizeof(FdBatchVectors), vp(d_N or None), tab(d_N_out), vp(d_vtu or None), tab(d_vtu_out),
+                             vp(d_vtv or None), tab(d_vtv_out), tab(d_jacobian))
+        self._check(self.L.fd_batch_deform_vectors_shared_dev(self.h, vp(stream_ptr or 0), N, vp(d_P_in), outs, vp(d_dist2 or None),
+                                                              falls, vp(tu or None), vp(tv or None), vp(nr or None),
+                                                              float(radius2), float(falloffrate), C.byref(vec)))
+
     def prepare_shared(self, d_P_out, d_falloff=None, stream_ptr=None):
         """fd_batch_prepare_shared: pack the current models for a shared-rig evaluation into the batch's scratch on
         `stream_ptr` (typically the build stream); deform_shared_dev with the same outputs then only evaluates."""
@@ -730,3 +767,7 @@ class Morph:
         self._check(self.L.fd_morph_get_qr(self.h, QR.ctypes.data_as(_f64p), tau.ctypes.data_as(_f64p)))
         return QR, tau[: self.S]
 
+
+def fd_shared_vectors_kernel_name(M: int, frames: int, kind: int) -> str:
+    """The kernel fd_batch_deform_vectors_shared_dev's vector launch takes ("" where it runs the per-context launches)."""
+    return load().fd_shared_vectors_kernel_name(int(M), int(frames), int(kind)).decode()

@@ -1990,6 +1990,97 @@ int fd_batch_deform_shared_dev(fd_batch *b, void *hip_stream, int64_t N, const f
     return FD_OK;
 }
 
+// fd_batch_deform_vectors_shared_dev: the position launch as fd_batch_deform_shared_dev runs it, then the vector launch
+// (fd_vectors_shared.hip) on the same scratch set; where the shared launch does not apply, fd_deform_vectors_dev's work per context
+int fd_batch_deform_vectors_shared_dev(fd_batch *b, void *hip_stream, int64_t N, const float *d_P_in, float *const *d_P_out,
+                                       const float *d_dist2, float *const *d_falloff_out, const float *d_tu, const float *d_tv,
+                                       const float *d_nrm, float radius2, float falloffrate, const fd_batch_vectors *vec)
+{
+    if (!b || !d_P_out) return FD_E_INVALID;
+    const char *who = "fd_batch_deform_vectors_shared_dev";
+    if (vec && vec->struct_size < (int)sizeof(fd_batch_vectors)) {
+        batch_err(b, "%s: vec->struct_size is %d, must be sizeof(fd_batch_vectors) = %d", who, vec->struct_size, (int)sizeof(fd_batch_vectors));
+        return FD_E_INVALID;
+    }
+    const bool want = vec && (vec->N || vec->N_out || vec->tu || vec->tu_out || vec->tv || vec->tv_out || vec->jacobian);
+    if (!want)
+        return fd_batch_deform_shared_dev(b, hip_stream, N, d_P_in, d_P_out, d_dist2, d_falloff_out, d_tu, d_tv, d_nrm, radius2, falloffrate);
+    if ((!vec->N != !vec->N_out) || (!vec->tu != !vec->tu_out) || (!vec->tv != !vec->tv_out)) {
+        batch_err(b, "%s: every vector needs its input and its output table (both or neither)", who);
+        return FD_E_INVALID;
+    }
+    if (N < 0 || (N > 0 && !d_P_in)) { batch_err(b, "%s: bad N / P_in", who); return FD_E_INVALID; }
+    if (!frames_ok(d_tu, d_tv, d_nrm)) { batch_err(b, "%s: tu, tv, nrm must be all set or all NULL", who); return FD_E_INVALID; }
+    // tables of n non-NULL entries, none of which is a shared input
+    const void *ins[8] = {d_P_in, d_dist2, d_tu, d_tv, d_nrm, vec->N, vec->tu, vec->tv};
+    float *const *tabs[6] = {d_P_out, d_falloff_out, vec->N_out, vec->tu_out, vec->tv_out, vec->jacobian};
+    for (int t = 0; t < 6; ++t) {
+        if (!tabs[t]) continue;
+        for (int i = 0; i < b->n; ++i) {
+            const void *o = tabs[t][i];
+            if (!o) { batch_err(b, "%s: output table %d has a NULL entry for context %d", who, t, i); return FD_E_INVALID; }
+            for (const void *in : ins)
+                if (in && o == in) { batch_err(b, "%s: an output of context %d is a shared input array", who, i); return FD_E_INVALID; }
+        }
+    }
+    if (N == 0) return FD_OK;
+    fd_ctx *c0 = b->ctxs[0];
+    int rc = use_device(c0);
+    if (rc) { batch_err(b, "%s", c0->err); return rc; }
+    hipStream_t stream = hip_stream ? (hipStream_t)hip_stream : cur_stream(c0);
+    int ek = 0;
+    const int applies = shared_applies(b, who, d_P_out, &ek);
+    if (applies < 0) return applies;
+    if (applies == 0) {
+        // any other kernel / precision / size: what fd_deform_vectors_dev runs, per context, on the shared arrays
+        for (int i = 0; i < b->n; ++i) {
+            fd_ctx *c = b->ctxs[i];
+            const fd_vectors v{(int)sizeof(fd_vectors), vec->N, vec->N ? vec->N_out[i] : nullptr, vec->tu, vec->tu ? vec->tu_out[i] : nullptr,
+                               vec->tv, vec->tv ? vec->tv_out[i] : nullptr, vec->jacobian ? vec->jacobian[i] : nullptr};
+            rc = deform_dev_common(c, stream, N, d_P_in, d_P_out[i], d_dist2, d_falloff_out ? d_falloff_out[i] : nullptr, d_tu, d_tv, d_nrm,
+                                   radius2, falloffrate, &v);
+            if (rc) { batch_err(b, "context %d: %s", i, c->err); return rc; }
+        }
+        // these launches read the models to their end: fd_batch_wait_consumed waits for all of them
+        if (make_event(&b->fallback_ev)) {
+            if (hipEventRecord(b->fallback_ev, stream) != hipSuccess) { (void)hipGetLastError(); return FD_E_DEVICE; }
+            b->packed_valid = false;
+            b->consumed_override = nullptr;
+        }
+        return FD_OK;
+    }
+    if ((rc = fd_batch_deform_shared_dev(b, hip_stream, N, d_P_in, d_P_out, d_dist2, d_falloff_out, d_tu, d_tv, d_nrm, radius2, falloffrate)))
+        return rc;
+    fd_batch::SharedSet &st = b->sets[b->cur_set];
+    SharedVectorArgs a{};
+    a.N = N; a.P_in = d_P_in; a.dist2 = d_dist2; a.tu = d_tu; a.tv = d_tv; a.nrm = d_nrm;
+    a.radius2 = radius2; a.falloffrate = falloffrate;
+    a.Mpad = round_up(c0->M, kRecPad); a.nF = b->n; a.kind = ek;
+    a.vN = vec->N; a.vtu = vec->tu; a.vtv = vec->tv;
+    for (int i = 0; i < b->n; ++i) {
+        a.N_out[i] = vec->N ? vec->N_out[i] : nullptr;
+        a.tu_out[i] = vec->tu ? vec->tu_out[i] : nullptr;
+        a.tv_out[i] = vec->tv ? vec->tv_out[i] : nullptr;
+        a.jacobian[i] = vec->jacobian ? vec->jacobian[i] : nullptr;
+    }
+    a.wtiles = st.d_wtiles; a.frames = st.d_frames;
+    a.max_wgs = b->eval_cus;
+    hipError_t e = launch_vectors_shared(a, stream);
+    if (e != hipSuccess) { batch_err(b, "launch_vectors_shared failed: %s", hipGetErrorString(e)); return FD_E_DEVICE; }
+    // the next pack into this set waits for the vector launch too (the position launch's event is behind it in stream order)
+    if (st.eval_pending && st.eval_done == st.eval_ev && st.eval_ev && hipEventRecord(st.eval_ev, stream) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(stream);
+    }
+    return FD_OK;
+}
+
+const char *fd_shared_vectors_kernel_name(int M, int frames, int kind)
+{
+    const char *pos = fd_shared_kernel_name(M, frames, kind);
+    return pos[0] ? shared_vectors_kernel_name(round_up(M, kRecPad), frames, kind) : "";
+}
+
 int fd_batch_wait_consumed(fd_batch *b, void *hip_stream)
 {
     if (!b) return FD_E_INVALID;

@@ -1,4 +1,4 @@
-// fd_eval_common.h -- device helpers the evaluation translation units share (fd_eval.hip, fd_eval_shared.hip).
+// fd_eval_common.h -- helpers the evaluation translation units share (fd_eval.hip, fd_eval_shared.hip, fd_vectors_shared.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -32,6 +32,24 @@ __device__ __forceinline__ float d2_log_d2(float d)
 {
     return fd_fmul_legacy(d, __builtin_amdgcn_logf(__builtin_fabsf(d)));
 }
+
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a per-DEVICE property of a kernel: one process may hold contexts on
+// several GPUs (fd_config.device), so "done" is remembered per (kernel, device), not per process.  (Host code: the shared-rig
+// launches, fd_eval_shared.hip and fd_vectors_shared.hip.)
+constexpr int kMaxDevices = 64;
+struct LdsAttrOnce {
+    bool done[kMaxDevices] = {};
+    hipError_t ensure(const void *fn, int bytes)
+    {
+        int dev = 0;
+        hipError_t e = hipGetDevice(&dev);
+        if (e != hipSuccess) return e;
+        if (dev >= 0 && dev < kMaxDevices && done[dev]) return hipSuccess;
+        e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        if (e == hipSuccess && dev >= 0 && dev < kMaxDevices) done[dev] = true;
+        return e;
+    }
+};
 
 }  // namespace
 }  // namespace fd

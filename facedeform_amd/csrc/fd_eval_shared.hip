@@ -1783,23 +1783,6 @@ void k_deform32_shared_w1(const SharedParams p, int ngroups)
 }
 }  // namespace
 
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a per-DEVICE property of a kernel: one process may hold contexts on
-// several GPUs (fd_config.device), so "done" is remembered per (kernel, device), not per process.
-constexpr int kMaxDevices = 64;
-struct LdsAttrOnce {
-    bool done[kMaxDevices] = {};
-    hipError_t ensure(const void *fn, int bytes)
-    {
-        int dev = 0;
-        hipError_t e = hipGetDevice(&dev);
-        if (e != hipSuccess) return e;
-        if (dev >= 0 && dev < kMaxDevices && done[dev]) return hipSuccess;
-        e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-        if (e == hipSuccess && dev >= 0 && dev < kMaxDevices) done[dev] = true;
-        return e;
-    }
-};
-
 // Frames of one mesh and one rest rig (SharedDeformArgs): pack the weight tiles, then one launch.
 hipError_t launch_deform_shared(const SharedDeformArgs &a, hipStream_t stream)
 {
@@ -1989,6 +1972,29 @@ const char *shared_kernel_name(int Mpad, int nF, int kind)
     const int nkb = (Mpad / 16 + 1) / 2, wNT = wide_tiles(wide_slots(nF));
     const bool w1 = (kSharedLdsBudget - w1_fixed_lds(wNT)) / ((size_t)1024 + (size_t)wide_w16(wNT) * 16) >= (size_t)nkb;
     return w1 ? "k_deform32_shared_w1" : "k_deform32_tps_shared_wide";
+}
+// where launch_deform_shared's pack kernel leaves what the shared-rig vector launch (fd_vectors_shared.hip) reads
+SharedPacking shared_packing(int Mpad, int nF)
+{
+    SharedPacking q{};
+    const int nkb = (Mpad / 16 + 1) / 2;
+    if (!shared_wide(nF, 0)) {
+        const int nT = shared_tiles(nF);
+        q.layout = shared_dense(nF) ? 1 : 0;
+        q.ntiles = nT;
+        q.poly_at = (size_t)nkb * nT * 128;
+        q.copy_at = q.poly_at + (size_t)nT * 64;
+        q.norm_at = q.copy_at + (size_t)2 * nkb * (sizeof(MfmaTileH) / 16);
+    } else {
+        const int wNT = wide_tiles(wide_slots(nF));
+        const bool w1 = (kSharedLdsBudget - w1_fixed_lds(wNT)) / ((size_t)1024 + (size_t)wide_w16(wNT) * 16) >= (size_t)nkb;
+        q.layout = w1 ? 3 : 2;
+        q.ntiles = wNT;
+        q.poly_at = (size_t)nkb * wide_w16(wNT);
+        q.copy_at = q.poly_at + (size_t)wNT * 64;
+        q.norm_at = q.copy_at + (size_t)nkb * 64;
+    }
+    return q;
 }
 size_t shared_frame_bytes(int nF)
 {

@@ -278,6 +278,28 @@ hipError_t launch_deform_shared(const SharedDeformArgs &a, hipStream_t stream);
 size_t shared_wtile_bytes(int Mpad, int nF);
 size_t shared_frame_bytes(int nF);
 const char *shared_kernel_name(int Mpad, int nF, int kind);
+// What the pack kernel of launch_deform_shared left in the scratch, for the shared-rig vector launch: the weight tiles' row
+// layout (0: 16-row padded, 1: 16-row dense, 2: 32-row rows 3 f + c, 3: 32-row per lane half -- fd_eval_shared.hip), their
+// row tiles, and the 16-byte word offsets of the polynomial tiles, the rest rig's centre copy and its normalisation.
+struct SharedPacking {
+    int layout, ntiles;
+    size_t poly_at, copy_at, norm_at;
+};
+SharedPacking shared_packing(int Mpad, int nF);
+// The Jacobian and the vectors it carries for every frame of a shared-rig evaluation (fd_vectors_shared.hip): reads the
+// scratch set launch_deform_shared packed (wtiles, frames), the mesh and the vectors; nothing of the contexts.
+struct SharedVectorArgs {
+    int64_t N;
+    const float *P_in, *dist2, *tu, *tv, *nrm;
+    float radius2, falloffrate;
+    int Mpad, nF, kind;
+    const float *vN, *vtu, *vtv;
+    float *N_out[kMaxBatch], *tu_out[kMaxBatch], *tv_out[kMaxBatch], *jacobian[kMaxBatch];
+    const void *wtiles, *frames;
+    int max_wgs;
+};
+hipError_t launch_vectors_shared(const SharedVectorArgs &a, hipStream_t stream);
+const char *shared_vectors_kernel_name(int Mpad, int nF, int kind);
 // island mask (fd_capture.hip): nearest mesh point per rig point + max_edges breadth-first rings
 hipError_t launch_capture_islands(const float *d_P, int64_t N, const int64_t *d_offsets, const int *d_neighbours,
                                   const float *d_rig, int M, int max_edges, unsigned char *d_mask, hipStream_t stream);

@@ -11,6 +11,7 @@
 // Built with -ffp-contract=off like fd_eval.hip: every fused multiply-add is written out.
 #include "fd_eval_common.h"
 #include "fd_pack.h"
+#include "fd_transport.h"
 
 namespace fd {
 
@@ -37,6 +38,8 @@ struct VecParams {
     const Rec32 *rec32;
     const Rec64 *rec64;
     const DevModel *model;
+    static constexpr bool kGivenAxes = false;      // (fd_transport.h: the axes are formed per vertex there)
+    static __device__ __forceinline__ void store(float *dst, float v) { *dst = v; }
 };
 
 // g of fd_pack.h's derivative table: grad phi'_j = g_j (x - c_j), the kind's scale applied once per vertex
@@ -73,97 +76,8 @@ __device__ __forceinline__ double grad64(double d2, double s)
 
 __device__ __forceinline__ f32x2 pfma(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
 
-template <typename T> __device__ __forceinline__ T vsqrt(T x);
-template <> __device__ __forceinline__ float vsqrt(float x) { return sqrtf(x); }
-template <> __device__ __forceinline__ double vsqrt(double x) { return sqrt(x); }
-
-template <typename T>
-__device__ __forceinline__ void normalize(T v[3])
-{
-    const T l2 = v[0] * v[0] + v[1] * v[1] + v[2] * v[2];
-    if (l2 > T(0)) {
-        const T inv = T(1) / vsqrt(l2);
-        v[0] *= inv; v[1] *= inv; v[2] *= inv;
-    }
-}
-
-// The transport epilogue for one live vertex: R = (J before the projection, row c = output c, column k = d/dx_k), f the
-// fall-off; T = float or double, the precision of the evaluation.  Reads the vectors, then writes (outputs may alias).
-template <typename T>
-__device__ __forceinline__ void transport(const VecParams &p, int64_t i, T R[9], float falloff)
-{
-    const T f = (T)falloff;
-    T A[9];
-    if (falloff == 0.f) {
-#pragma unroll
-        for (int q = 0; q < 9; ++q) A[q] = (q % 4 == 0) ? T(1) : T(0);
-    } else {
-        if (p.tu) {
-            // Pi = a1 a1^T + a2 a2^T, a1, a2 as project_to_tangents (reference src/SOP_FaceDeform.hpp:28-41) builds them
-            T u[3] = {(T)p.tu[3 * i], (T)p.tu[3 * i + 1], (T)p.tu[3 * i + 2]};
-            T v[3] = {(T)p.tv[3 * i], (T)p.tv[3 * i + 1], (T)p.tv[3 * i + 2]};
-            T n[3] = {(T)p.nrm[3 * i], (T)p.nrm[3 * i + 1], (T)p.nrm[3 * i + 2]};
-            normalize(u); normalize(v); normalize(n);
-            T a1[3], a2[3];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                T g[3];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) g[k] = u[k] * u[j] + v[k] * v[j] + n[k] * n[j];
-                a1[j] = u[0] * g[0] + u[1] * g[1] + u[2] * g[2];
-                a2[j] = v[0] * g[0] + v[1] * g[1] + v[2] * g[2];
-            }
-            normalize(a1); normalize(a2);
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const T p1 = a1[0] * R[k] + a1[1] * R[3 + k] + a1[2] * R[6 + k];
-                const T p2 = a2[0] * R[k] + a2[1] * R[3 + k] + a2[2] * R[6 + k];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) R[3 * c + k] = a1[c] * p1 + a2[c] * p2;
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < 9; ++q) A[q] = ((q % 4 == 0) ? T(1) : T(0)) + f * R[q];
-    }
-    if (p.vtu) {
-        const T t[3] = {(T)p.vtu[3 * i], (T)p.vtu[3 * i + 1], (T)p.vtu[3 * i + 2]};
-#pragma unroll
-        for (int c = 0; c < 3; ++c) p.otu[3 * i + c] = (float)(A[3 * c] * t[0] + A[3 * c + 1] * t[1] + A[3 * c + 2] * t[2]);
-    }
-    if (p.vtv) {
-        const T t[3] = {(T)p.vtv[3 * i], (T)p.vtv[3 * i + 1], (T)p.vtv[3 * i + 2]};
-#pragma unroll
-        for (int c = 0; c < 3; ++c) p.otv[3 * i + c] = (float)(A[3 * c] * t[0] + A[3 * c + 1] * t[1] + A[3 * c + 2] * t[2]);
-    }
-    if (p.vN) {
-        const float nf[3] = {p.vN[3 * i], p.vN[3 * i + 1], p.vN[3 * i + 2]};
-        const T n[3] = {(T)nf[0], (T)nf[1], (T)nf[2]};
-        // cof(A) n = n0 (c1 x c2) + n1 (c2 x c0) + n2 (c0 x c1), c_k = column k of A
-        T m[3];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            const int r1 = (r + 1) % 3, r2 = (r + 2) % 3;
-            const T x12 = A[3 * r1 + 1] * A[3 * r2 + 2] - A[3 * r2 + 1] * A[3 * r1 + 2];
-            const T x20 = A[3 * r1 + 2] * A[3 * r2 + 0] - A[3 * r2 + 2] * A[3 * r1 + 0];
-            const T x01 = A[3 * r1 + 0] * A[3 * r2 + 1] - A[3 * r2 + 0] * A[3 * r1 + 1];
-            m[r] = n[0] * x12 + n[1] * x20 + n[2] * x01;
-        }
-        const T nn = n[0] * n[0] + n[1] * n[1] + n[2] * n[2];
-        const T mm = m[0] * m[0] + m[1] * m[1] + m[2] * m[2];
-        float o[3] = {nf[0], nf[1], nf[2]};
-        if (nn > T(0) && mm > T(0)) {
-            const T sc = vsqrt(nn) / vsqrt(mm);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) o[c] = (float)(m[c] * sc);
-        }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) p.oN[3 * i + c] = o[c];
-    }
-    if (p.jac) {
-#pragma unroll
-        for (int q = 0; q < 9; ++q) p.jac[9 * i + q] = (float)A[q];
-    }
-}
+// the transport epilogue: fd_transport.h
+using transport::transport;
 
 // gated vertex / unbuilt model: the vectors bit for bit, A = I
 __device__ __forceinline__ void pass_through(const VecParams &p, int64_t i)

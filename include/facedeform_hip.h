@@ -429,6 +429,48 @@ int fd_batch_deform_shared_dev(fd_batch *batch, void *hip_stream, int64_t N, con
                                float *const *d_P_out, const float *d_dist2, float *const *d_falloff_out,
                                const float *d_tu, const float *d_tv, const float *d_nrm, float radius2,
                                float falloffrate);
+/* fd_batch_vectors: what fd_batch_deform_vectors_shared_dev transports for every frame of the batch.  N, tu, tv are
+ * ONE N x 3 fp32 input array each (the shared mesh's), each with a table of n output pointers (one per context);
+ * jacobian: a table of n pointers to N x 9 row-major A, or NULL.  A table is either NULL or has n non-NULL entries,
+ * and each input comes with its output table: both or neither. */
+typedef struct fd_batch_vectors {
+    int struct_size;                              /* = sizeof(fd_batch_vectors); smaller is FD_E_INVALID  */
+    const float *N;  float *const *N_out;         /* ONE input array (the shared mesh), n output pointers  */
+    const float *tu; float *const *tu_out;
+    const float *tv; float *const *tv_out;
+    float *const *jacobian;                       /* n pointers to N x 9 row-major A, or NULL              */
+} fd_batch_vectors;
+
+/* fd_batch_deform_shared_dev plus, for every frame f, the Jacobian and the vectors it carries.
+ *   Definition: exactly fd_deform_vectors' (above), per frame: A_f = I + f Pi J_f, t' = A_f t (not renormalised),
+ *     n' = cof(A_f) n rescaled to |n|.  Gated vertices, unbuilt frames and f = 0 pass every vector through bit for bit,
+ *     with A = I exactly.  Entries past N are not touched.
+ *   Positions: P_out and falloff_out are bit-identical to fd_batch_deform_shared_dev called with the same arguments:
+ *     that launch runs unchanged and a launch of its own writes the vector outputs.  vec == NULL, or every pointer in
+ *     it NULL, is exactly fd_batch_deform_shared_dev.
+ *   Aliasing: every output pointer (P_out, falloff_out and the tables of vec) must differ from every shared input
+ *     (d_P_in, d_dist2, vec->N / tu / tv, the projection frames d_tu / d_tv / d_nrm); otherwise FD_E_INVALID, before
+ *     any device work.  (One input serves F outputs: written in place, the first frame would clobber the others' input.)
+ *   Where the matrix-pipe launch applies: where fd_batch_deform_shared_dev takes its own launch (thin-plate,
+ *     FD_KERNEL_GAUSSIAN, FD_KERNEL_GAUSSIAN_QNN, fp32 evaluation, M >= 32, one rest array).  There J_f is a split-fp16
+ *     contraction of the gradient basis with the weight tiles of the position launch (its error bar is
+ *     ||dA||_F <= 2^-22 ||A||_F + 2^-21 f S').  Range: thin-plate stays finite to ~235 rig radii from every centre (the
+ *     position launch itself to ~70); the Gaussian kinds need every radius R_j above ~0.0024 rig radii (0.24 % of the
+ *     rig's extent, rounded to a power of two), below which the basis overflows fp16 and A is not finite.  Everywhere else (biharmonic, cubic, multilayer, fp64, fewer centres) the
+ *     call runs, per context, exactly what fd_deform_vectors_dev runs on the shared arrays, bit for bit.
+ *   Reads of the models: fd_batch_wait_consumed covers the vector launch as well -- it reads only the batch's scratch,
+ *     the mesh and the vectors; after it the contexts may be rebuilt while the vector launch still runs.
+ * Asynchronous on hip_stream (NULL: context 0's), like fd_batch_deform_shared_dev. */
+int fd_batch_deform_vectors_shared_dev(fd_batch *batch, void *hip_stream, int64_t N, const float *d_P_in,
+                                       float *const *d_P_out, const float *d_dist2, float *const *d_falloff_out,
+                                       const float *d_tu, const float *d_tv, const float *d_nrm,
+                                       float radius2, float falloffrate, const fd_batch_vectors *vec);
+/* The kernel the vector launch of fd_batch_deform_vectors_shared_dev takes for M centres, `frames` contexts and a
+ * kernel kind ("k_vectors32_shared_thin_plate" / "k_vectors32_shared_gaussian"), or "" where the call runs the
+ * per-context launches instead.  Like fd_shared_kernel_name it sees no context: the name holds for a batch evaluated
+ * in fp32 (fd_set_eval_precision) -- a batch set to FD_EVAL_FP64 always takes the per-context launches, whatever this
+ * returns.  For tests and profiles. */
+const char *fd_shared_vectors_kernel_name(int M, int frames, int kind);
 /* Makes hip_stream (NULL: context 0's) wait until the batch's last fd_batch_deform_shared_dev no longer reads the
  * contexts' models: that launch copies what it needs of them (weights as fp16 tiles, the rest rig's centre tiles)
  * into the batch's own scratch with a first small kernel, and the evaluation proper reads only that copy.  A pipeline
