@@ -79,7 +79,7 @@ EXPORTS = [
     "fd_morph_create", "fd_morph_destroy", "fd_morph_last_error", "fd_morph_init", "fd_morph_init_dev",
     "fd_morph_set_rest", "fd_morph_is_initialised", "fd_morph_is_computed", "fd_morph_shape_count", "fd_morph_last_init_ms",
     "fd_morph_compute_weights_dev", "fd_morph_displace_dev", "fd_morph_apply", "fd_morph_get_weights",
-    "fd_morph_get_qr",
+    "fd_morph_get_qr", "fd_morph_compute_weights_batch_dev", "fd_morph_displace_batch_dev", "fd_morph_get_weights_batch",
     "fd_batch_create", "fd_batch_destroy", "fd_batch_size", "fd_batch_last_error", "fd_batch_wait_consumed", "fd_batch_prepare_shared", "fd_batch_set_eval_cus", "fd_batch_cook_group", "fd_shared_kernel_name", "fd_batch_set_shared_factor", "fd_batch_last_build_shared_factor",
     "fd_batch_set_points_dev", "fd_batch_build_async", "fd_batch_build_result", "fd_batch_deform_dev",
     "fd_batch_deform_shared_dev", "fd_batch_deform_vectors_shared_dev", "fd_shared_vectors_kernel_name",
@@ -168,6 +168,9 @@ def load() -> C.CDLL:
     L.fd_morph_apply.argtypes = [vp, vp, vp, i32, C.c_float, _f64p]; L.fd_morph_apply.restype = i32
     L.fd_morph_get_weights.argtypes = [vp, _f64p]; L.fd_morph_get_weights.restype = i32
     L.fd_morph_get_qr.argtypes = [vp, _f64p, _f64p]; L.fd_morph_get_qr.restype = i32
+    L.fd_morph_compute_weights_batch_dev.argtypes = [vp, i32, C.POINTER(vp), vp]; L.fd_morph_compute_weights_batch_dev.restype = i32
+    L.fd_morph_displace_batch_dev.argtypes = [vp, i32, C.POINTER(vp), vp, i32, C.c_float, vp]; L.fd_morph_displace_batch_dev.restype = i32
+    L.fd_morph_get_weights_batch.argtypes = [vp, i32, _f64p]; L.fd_morph_get_weights_batch.restype = i32
     L.fd_host_alloc.argtypes = [sz]; L.fd_host_alloc.restype = vp
     L.fd_host_free.argtypes = [vp]; L.fd_host_free.restype = None
     L.fd_batch_create.argtypes = [C.POINTER(vp), i32]; L.fd_batch_create.restype = vp
@@ -760,6 +763,26 @@ class Morph:
         w = np.zeros(max(1, self.S), np.float64)
         self._check(self.L.fd_morph_get_weights(self.h, w.ctypes.data_as(_f64p)))
         return w[: self.S]
+
+    def compute_weights_batch_dev(self, d_P_list, stream_ptr: int | None = None):
+        """The weights of every frame of a shot (device pointers, N x 3 fp32 each) in one pass over the packed QR."""
+        arr = (C.c_void_p * max(1, len(d_P_list)))(*d_P_list)
+        self._check(self.L.fd_morph_compute_weights_batch_dev(self.h, len(d_P_list), arr, C.c_void_p(stream_ptr or 0)))
+        self._batch_F = len(d_P_list)
+
+    def displace_batch_dev(self, d_P_list, clamp=None, add_delta=False, falloffradius=0.0, stream_ptr: int | None = None):
+        """Every frame displaced in place with its batched weights, in one pass over the deltas."""
+        arr = (C.c_void_p * max(1, len(d_P_list)))(*d_P_list)
+        cl = None if clamp is None else np.asarray(clamp, np.float32)
+        self._check(self.L.fd_morph_displace_batch_dev(self.h, len(d_P_list), arr, _np_ptr(cl), int(bool(add_delta)),
+                                                       float(falloffradius), C.c_void_p(stream_ptr or 0)))
+
+    def weights_batch(self):
+        """(F, S) weights of the last compute_weights_batch_dev."""
+        F = getattr(self, "_batch_F", 0)
+        w = np.zeros((max(1, F), max(1, self.S)), np.float64)
+        self._check(self.L.fd_morph_get_weights_batch(self.h, F, w.ctypes.data_as(_f64p)))
+        return w.reshape(-1)[: F * self.S].reshape(F, self.S)
 
     def qr(self):
         QR = np.empty((3 * self.N, self.S), np.float64, order="F")

@@ -616,6 +616,215 @@ __global__ __launch_bounds__(kT) void k_morph_displace(const float *S32, int64_t
     P[3 * i] = rx + dx; P[3 * i + 1] = ry + dy; P[3 * i + 2] = rz + dz;
 }
 
+// ---- per group of frames (a shot) -------------------------------------------------------------
+// Neither matrix depends on the frame, so the F frames of a group share one pass over each:
+//   weights       W^T (S x F) = QR^T (S x 3N) . D (3N x F),  D[i][f] = double(float(P_f[i] - rest[i])),  fp64
+//   displacement  d_f[i] = sum_s delta[i][s] * cw[f][s],  fp32 in the one-frame kernel's operation order
+struct MorphFrames { const float *p[FD_MAX_BATCH]; };
+struct MorphFramesRW { float *p[FD_MAX_BATCH]; };
+
+typedef double double4_t __attribute__((ext_vector_type(4)));
+
+constexpr int kBK = 64;              // rows of a staged chunk (one per lane of the wave that fetches a column span)
+constexpr int kBLd = kBK + 2;        // its LDS row stride, in doubles
+constexpr int kBCols = 64;           // columns per workgroup: four 16-wide tiles
+constexpr int kBFr = FD_MAX_BATCH;   // frames: two 16-wide tiles
+constexpr int kBMaxWg = 512;         // row partitions at most (the length of the second launch's sums)
+static_assert(kBFr == 32 && kBFr <= kBLd, "two frame tiles; the tile of sums reuses the staged columns");
+
+// v_mfma_f64_16x16x4_f64 with the columns as M, the frames as N and the rows of the matrix as K: lane l gives
+// QR[k + (l >> 4)][16 t + (l & 15)] and D[k + (l >> 4)][16 u + (l & 15)] and holds the sums of column
+// 16 t + (l >> 4) + 4 r, frame 16 u + (l & 15) in element r.  Workgroup (x, y): rows [x * chunks_per_wg * kBK, ..),
+// columns [y * kBCols, ..).  A chunk is fetched one 512-byte column span per wave instruction (row = lane),
+// parked in LDS and read back in operand order; every wave multiplies its own 16 of the chunk's rows into all
+// eight tiles while the next chunk's loads are in flight.  Columns past S, frames past F and rows past 3N are
+// zero operands, never loads.  partial[(x * F + f) * ldp + column], summed by k_morph_weights_batch_reduce in a fixed
+// order: no atomics.
+__global__ __launch_bounds__(kT) void k_morph_weights_batch(const double *QR, int64_t rows, int S, int F, MorphFrames fr,
+                                                             const float *rest, int chunks_per_wg, double *partial, int ldp)
+{
+    __shared__ double sQ[kBCols * kBLd];
+    __shared__ double sD[kBFr * kBLd];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int col0 = blockIdx.y * kBCols;
+    const int ncols = S - col0 < kBCols ? S - col0 : kBCols;
+    const int nst = (ncols + 15) >> 4, nft = (F + 15) >> 4;
+    const int64_t nchunks = (rows + kBK - 1) / kBK;
+    const int64_t chunk_lo = (int64_t)blockIdx.x * chunks_per_wg;
+    const int64_t chunk_hi = chunk_lo + chunks_per_wg < nchunks ? chunk_lo + chunks_per_wg : nchunks;
+
+    double q[kBCols / 4];            // columns wave, wave + 4, ..: row lane of the chunk
+    float dl[kBFr / 4];              // frames wave, wave + 4, ..: float(P - rest) of that row (:49-51)
+    auto fetch = [&](int64_t chunk) {
+        const int64_t i = chunk * kBK + lane;
+        const bool in = i < rows;
+#pragma unroll
+        for (int j = 0; j < kBCols / 4; ++j) {
+            const int c = wave + 4 * j;
+            q[j] = in && c < ncols ? __builtin_nontemporal_load(QR + (size_t)(col0 + c) * rows + i) : 0.0;
+        }
+        const float r = in ? rest[i] : 0.f;
+#pragma unroll
+        for (int j = 0; j < kBFr / 4; ++j) {
+            const int f = wave + 4 * j;
+            dl[j] = in && f < F ? fr.p[f][i] - r : 0.f;
+        }
+    };
+
+    double4_t acc[4][2];
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int u = 0; u < 2; ++u) acc[t][u] = double4_t{0.0, 0.0, 0.0, 0.0};
+
+    fetch(chunk_lo);
+    for (int64_t chunk = chunk_lo; chunk < chunk_hi; ++chunk) {
+        __syncthreads();             // the previous chunk has been read
+#pragma unroll
+        for (int j = 0; j < kBCols / 4; ++j) sQ[(wave + 4 * j) * kBLd + lane] = q[j];
+#pragma unroll
+        for (int j = 0; j < kBFr / 4; ++j) sD[(wave + 4 * j) * kBLd + lane] = (double)dl[j];
+        __syncthreads();
+        if (chunk + 1 < chunk_hi) fetch(chunk + 1);
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+            const int k = 16 * wave + 4 * ks + (lane >> 4);
+            const double b0 = sD[(lane & 15) * kBLd + k];
+            const double b1 = nft > 1 ? sD[(16 + (lane & 15)) * kBLd + k] : 0.0;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                if (t < nst) {
+                    const double a = sQ[(16 * t + (lane & 15)) * kBLd + k];
+                    acc[t][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b0, acc[t][0], 0, 0, 0);
+                    if (nft > 1) acc[t][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b1, acc[t][1], 0, 0, 0);
+                }
+            }
+        }
+    }
+    // the four waves' sums, added in wave order into one tile [frame][column]
+    double *sOut = sQ;
+    for (int w = 0; w < 4; ++w) {
+        __syncthreads();
+        if (wave == w) {
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+#pragma unroll
+                for (int u = 0; u < 2; ++u)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        double *o = sOut + (16 * u + (lane & 15)) * kBCols + 16 * t + (lane >> 4) + 4 * r;
+                        *o = w == 0 ? acc[t][u][r] : *o + acc[t][u][r];
+                    }
+        }
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < F * kBCols; e += kT)
+        partial[((size_t)blockIdx.x * F + (e >> 6)) * ldp + col0 + (e & 63)] = sOut[e];
+}
+
+// w[f * S + column]: the row partitions' sums in four slices of consecutive partitions, then the slices in order
+__global__ __launch_bounds__(kT) void k_morph_weights_batch_reduce(const double *partial, int nwg, int S, int F, int ldp, double *w)
+{
+    __shared__ double s[kT];
+    const int f = blockIdx.y, c = blockIdx.x * kBCols + (threadIdx.x & 63), slice = threadIdx.x >> 6;
+    const int per = (nwg + 3) / 4, lo = slice * per, hi = lo + per < nwg ? lo + per : nwg;
+    const double *p = partial + (size_t)f * ldp + c;
+    const size_t stride = (size_t)F * ldp;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;       // four loads in flight per lane
+    int x = lo;
+    for (; x + 3 < hi; x += 4) {
+        a0 += p[x * stride];
+        a1 += p[(x + 1) * stride];
+        a2 += p[(x + 2) * stride];
+        a3 += p[(x + 3) * stride];
+    }
+    for (; x < hi; ++x) a0 += p[x * stride];
+    s[threadIdx.x] = (a0 + a1) + (a2 + a3);
+    __syncthreads();
+    if (threadIdx.x < 64 && c < S)
+        w[(size_t)f * S + c] = (s[threadIdx.x] + s[64 + threadIdx.x]) + (s[128 + threadIdx.x] + s[192 + threadIdx.x]);
+}
+
+// k_morph_displace for F frames at once: a lane owns a vertex, reads the three deltas of column s once and updates
+// every frame's sum with it -- the same `d = d + c * cw` per frame, columns in order, multiply and add rounded
+// separately, so frame f's result is the one-frame kernel's bit for bit.  The clamped weights of kDCols columns at
+// a time sit in LDS as [column][FT]; all lanes read the same four frames with one broadcast load.  FT: the frame
+// count rounded up (the sums are registers, 3 FT of them); frames past F carry a zero weight and are not stored.
+constexpr int kDCols = 64;
+constexpr int kDAhead = 4;           // columns whose deltas are requested ahead of the one being applied
+template <int FT>
+__global__ __launch_bounds__(kT) void k_morph_displace_batch(const float *S32, int64_t N, int S, int F, const double *w,
+                                                              float clamp_lo, float clamp_hi, int do_clamp, int add_delta,
+                                                              float falloffradius, const float *rest, MorphFramesRW fr)
+{
+    __shared__ float4 s_cw[kDCols * FT / 4];
+    const int64_t i0 = (int64_t)blockIdx.x * kT + threadIdx.x;
+    const bool live = i0 < N;
+    const int64_t i = live ? i0 : N - 1;                   // idle lanes of the last workgroup: valid loads, no stores
+    const int64_t rows = 3 * N;
+    float dx[FT], dy[FT], dz[FT];
+#pragma unroll
+    for (int f = 0; f < FT; ++f) dx[f] = dy[f] = dz[f] = 0.f;
+    for (int s0 = 0; s0 < S; s0 += kDCols) {
+        const int ns = S - s0 < kDCols ? S - s0 : kDCols;
+        __syncthreads();
+        for (int e = threadIdx.x; e < ns * FT; e += kT) {
+            const int s = e / FT, f = e % FT;
+            float v = 0.f;
+            if (f < F) {
+                const float ws = (float)(w[(size_t)f * S + s0 + s] * 3);                   // :70
+                v = do_clamp ? (ws < clamp_lo ? clamp_lo : (ws > clamp_hi ? clamp_hi : ws)) : ws;
+            }
+            reinterpret_cast<float *>(s_cw)[e] = v;
+        }
+        __syncthreads();
+        const float *col = S32 + (size_t)s0 * rows + 3 * i;
+        float c[kDAhead][3];                               // the deltas of columns s .. s + kDAhead - 1, in flight
+        auto fetch = [&](int s, float (&dst)[3]) {
+            const float *p = col + (size_t)(s < ns ? s : ns - 1) * rows;
+            dst[0] = __builtin_nontemporal_load(p);
+            dst[1] = __builtin_nontemporal_load(p + 1);
+            dst[2] = __builtin_nontemporal_load(p + 2);
+        };
+#pragma unroll
+        for (int j = 0; j < kDAhead; ++j) fetch(j, c[j]);
+#pragma unroll 1
+        for (int s = 0; s < ns; ++s) {
+            const float cx = c[0][0], cy = c[0][1], cz = c[0][2];
+#pragma unroll
+            for (int j = 0; j + 1 < kDAhead; ++j) { c[j][0] = c[j + 1][0]; c[j][1] = c[j + 1][1]; c[j][2] = c[j + 1][2]; }
+            fetch(s + kDAhead, c[kDAhead - 1]);
+#pragma unroll
+            for (int b = 0; b < FT / 4; ++b) {
+                if (4 * b < F) {
+                    const float4 cw = s_cw[s * (FT / 4) + b];
+                    const float cwv[4] = {cw.x, cw.y, cw.z, cw.w};
+#pragma unroll
+                    for (int a = 0; a < 4; ++a) {
+                        dx[4 * b + a] = dx[4 * b + a] + cx * cwv[a];
+                        dy[4 * b + a] = dy[4 * b + a] + cy * cwv[a];
+                        dz[4 * b + a] = dz[4 * b + a] + cz * cwv[a];
+                    }
+                }
+            }
+        }
+    }
+    const float rx = rest[3 * i], ry = rest[3 * i + 1], rz = rest[3 * i + 2];
+#pragma unroll
+    for (int f = 0; f < FT; ++f) {
+        if (f < F && live) {
+            float *P = fr.p[f];
+            float ax = dx[f], ay = dy[f], az = dz[f];
+            if (add_delta) {
+                ax = ax + (P[3 * i] - rx) * falloffradius;
+                ay = ay + (P[3 * i + 1] - ry) * falloffradius;
+                az = az + (P[3 * i + 2] - rz) * falloffradius;
+            }
+            P[3 * i] = rx + ax; P[3 * i + 1] = ry + ay; P[3 * i + 2] = rz + az;
+        }
+    }
+}
+
 thread_local char g_merr[512] = {0};
 
 }  // namespace
@@ -638,6 +847,10 @@ struct fd_morph {
     int64_t cap_N = 0;
     int cap_S = 0;
     size_t cap_partial = 0;
+    // a group of frames (fd_morph_*_batch*): weights F x S and the row partitions' sums, apart from d_w / computed
+    double *d_bw = nullptr, *d_bwpartial = nullptr;
+    size_t cap_bw = 0, cap_bwpartial = 0;
+    int batch_F = 0;              // frames of the last batched compute; 0: none since fd_morph_init
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     float last_init_ms = 0.f;
     char err[512] = {0};
@@ -816,7 +1029,7 @@ void fd_morph_destroy(fd_morph *m)
     (void)hipSetDevice(m->device);
     if (m->stream) (void)hipStreamSynchronize(m->stream);
     void *bufs[] = {m->d_rest_attr, m->d_rest, m->d_S32, m->d_stage, m->d_P, m->d_QR, m->d_tau, m->d_w, m->d_partial, m->d_hh, m->d_tmp,
-                    m->d_bpartial, m->d_bpartial2, m->d_Y};
+                    m->d_bpartial, m->d_bpartial2, m->d_Y, m->d_bw, m->d_bwpartial};
     for (void *p : bufs) if (p) (void)hipFree(p);
     if (m->ev0) (void)hipEventDestroy(m->ev0);
     if (m->ev1) (void)hipEventDestroy(m->ev1);
@@ -836,6 +1049,7 @@ static int morph_init_common(fd_morph *m, int64_t N, int S, const float *rest, c
     if (rc) return rc;
     m->N = N; m->S = S;
     m->initialised = false; m->computed = false;
+    m->batch_F = 0;
     m->use_rest_attr = false;
     const size_t rows = 3 * (size_t)N, bytes = rows * sizeof(float);
     const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
@@ -933,6 +1147,97 @@ int fd_morph_get_weights(fd_morph *m, double *w)
     if (!m->computed) { merr(m, "fd_morph_get_weights: weights have not been computed"); return FD_E_NOT_BUILT; }
     FDM_HIP(m, hipSetDevice(m->device));
     FDM_HIP(m, hipMemcpyAsync(w, m->d_w, sizeof(double) * (size_t)m->S, hipMemcpyDeviceToHost, m->stream));
+    FDM_HIP(m, hipStreamSynchronize(m->stream));
+    return FD_OK;
+}
+
+// argument checks of the batched calls: before any device work
+static int morph_batch_args(fd_morph *m, const char *fn, int F, const float *const *tab, bool distinct)
+{
+    if (!m) { merr(nullptr, "%s: NULL fd_morph", fn); return FD_E_INVALID; }
+    if (F < 1 || F > FD_MAX_BATCH) { merr(m, "%s: F = %d, need 1..%d frames", fn, F, FD_MAX_BATCH); return FD_E_INVALID; }
+    if (!tab) { merr(m, "%s: the table of frame pointers is NULL", fn); return FD_E_INVALID; }
+    for (int f = 0; f < F; ++f) {
+        if (!tab[f]) { merr(m, "%s: frame %d is NULL", fn, f); return FD_E_INVALID; }
+        for (int g = 0; distinct && g < f; ++g)
+            if (tab[g] == tab[f]) { merr(m, "%s: frames %d and %d are the same array", fn, g, f); return FD_E_INVALID; }
+    }
+    return FD_OK;
+}
+
+// computeWeights (dbse.cpp:39-60) for the F frames of a group: one pass over the packed QR
+int fd_morph_compute_weights_batch_dev(fd_morph *m, int F, const float *const *d_P_xyz, void *hip_stream)
+{
+    int rc = morph_batch_args(m, "fd_morph_compute_weights_batch_dev", F, d_P_xyz, false);
+    if (rc) return rc;
+    if (!m->initialised) { merr(m, "fd_morph_compute_weights_batch_dev: fd_morph_init has not succeeded"); return FD_E_NOT_BUILT; }
+    FDM_HIP(m, hipSetDevice(m->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : m->stream;
+    const int64_t rows = 3 * m->N, nchunks = (rows + kBK - 1) / kBK;
+    const int S = m->S, ngroups = (S + kBCols - 1) / kBCols, ldp = ngroups * kBCols;
+    const int cpw = (int)((nchunks + kBMaxWg - 1) / kBMaxWg), nwg = (int)((nchunks + cpw - 1) / cpw);
+    const size_t need_w = (size_t)FD_MAX_BATCH * (size_t)(S ? S : 1), need_p = (size_t)nwg * FD_MAX_BATCH * (size_t)(ldp ? ldp : 1);
+    if (need_w > m->cap_bw) {
+        m->cap_bw = 0;
+        if ((rc = mrealloc(m, &m->d_bw, need_w))) return rc;
+        m->cap_bw = need_w;
+    }
+    if (need_p > m->cap_bwpartial) {
+        m->cap_bwpartial = 0;
+        if ((rc = mrealloc(m, &m->d_bwpartial, need_p))) return rc;
+        m->cap_bwpartial = need_p;
+    }
+    if (S > 0) {
+        MorphFrames fr = {};
+        for (int f = 0; f < F; ++f) fr.p[f] = d_P_xyz[f];
+        hipLaunchKernelGGL(k_morph_weights_batch, dim3(nwg, ngroups), dim3(kT), 0, st, m->d_QR, rows, S, F, fr,
+                           m->use_rest_attr ? m->d_rest_attr : m->d_rest, cpw, m->d_bwpartial, ldp);
+        hipLaunchKernelGGL(k_morph_weights_batch_reduce, dim3(ngroups, F), dim3(kT), 0, st, m->d_bwpartial, nwg, S, F, ldp, m->d_bw);
+    }
+    FDM_HIP(m, hipGetLastError());
+    m->batch_F = F;
+    return FD_OK;
+}
+
+static int morph_batch_state(fd_morph *m, const char *fn, int F)
+{
+    if (!m->initialised || m->batch_F == 0) { merr(m, "%s: no batched weights have been computed", fn); return FD_E_NOT_BUILT; }
+    if (F != m->batch_F) { merr(m, "%s: F = %d, the batched weights hold %d frames", fn, F, m->batch_F); return FD_E_INVALID; }
+    return FD_OK;
+}
+
+// displaceVector + the loop at SOP_FaceDeform.cpp:458-473 for the F frames of a group: one pass over the deltas
+int fd_morph_displace_batch_dev(fd_morph *m, int F, float *const *d_P_xyz, const float *clamp_lo_hi, int add_delta,
+                                float falloffradius, void *hip_stream)
+{
+    int rc = morph_batch_args(m, "fd_morph_displace_batch_dev", F, d_P_xyz, true);
+    if (rc || (rc = morph_batch_state(m, "fd_morph_displace_batch_dev", F))) return rc;
+    FDM_HIP(m, hipSetDevice(m->device));
+    hipStream_t st = hip_stream ? (hipStream_t)hip_stream : m->stream;
+    MorphFramesRW fr = {};
+    for (int f = 0; f < F; ++f) fr.p[f] = d_P_xyz[f];
+    const unsigned g = (unsigned)((m->N + kT - 1) / kT);
+    const float lo = clamp_lo_hi ? clamp_lo_hi[0] : 0.f, hi = clamp_lo_hi ? clamp_lo_hi[1] : 0.f;
+    const float *rest = m->use_rest_attr ? m->d_rest_attr : m->d_rest;
+#define FD_MORPH_DISPLACE_BATCH(FT)                                                                                      \
+    hipLaunchKernelGGL(k_morph_displace_batch<FT>, dim3(g), dim3(kT), 0, st, m->d_S32, m->N, m->S, F, m->d_bw, lo, hi, \
+                       clamp_lo_hi ? 1 : 0, add_delta ? 1 : 0, falloffradius, rest, fr)
+    if (F <= 8) FD_MORPH_DISPLACE_BATCH(8);
+    else if (F <= 16) FD_MORPH_DISPLACE_BATCH(16);
+    else FD_MORPH_DISPLACE_BATCH(32);
+#undef FD_MORPH_DISPLACE_BATCH
+    FDM_HIP(m, hipGetLastError());
+    return FD_OK;
+}
+
+int fd_morph_get_weights_batch(fd_morph *m, int F, double *w)
+{
+    if (!m) { merr(nullptr, "fd_morph_get_weights_batch: NULL fd_morph"); return FD_E_INVALID; }
+    if (F < 1 || F > FD_MAX_BATCH || !w) { merr(m, "fd_morph_get_weights_batch: need F in 1..%d and an array", FD_MAX_BATCH); return FD_E_INVALID; }
+    int rc = morph_batch_state(m, "fd_morph_get_weights_batch", F);
+    if (rc) return rc;
+    FDM_HIP(m, hipSetDevice(m->device));
+    if (m->S > 0) FDM_HIP(m, hipMemcpyAsync(w, m->d_bw, sizeof(double) * (size_t)F * (size_t)m->S, hipMemcpyDeviceToHost, m->stream));
     FDM_HIP(m, hipStreamSynchronize(m->stream));
     return FD_OK;
 }

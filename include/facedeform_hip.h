@@ -613,6 +613,41 @@ int fd_morph_apply(fd_morph *m, float *P_xyz, const float *clamp_lo_hi, int add_
 int fd_morph_get_weights(fd_morph *m, double *w);
 int fd_morph_get_qr(fd_morph *m, double *qr, double *tau);   /* 3N x S column-major packed QR (tests) */
 
+/* The F = 1..FD_MAX_BATCH frames of one shot in one pass over each matrix: what
+ * a cook per frame runs F times (computeWeights, dbse.cpp:39-60; displaceVector
+ * and the loop at SOP_FaceDeform.cpp:458-473, dbse.cpp:62-77) with the packed QR
+ * and the deltas read from memory once per call instead of once per frame.
+ * d_P_xyz: a host array of F device pointers, each N x 3 fp32 -- the d_P_out
+ * table of fd_batch_deform_shared_dev / fd_batch_cook_group as it stands.
+ *   fd_morph_compute_weights_batch_dev  per frame fd_morph_compute_weights_dev's
+ *       definition: P_f - rest in fp32 (the rest of fd_morph_set_rest), widened,
+ *       multiplied with the fp64 packed QR and summed in fp64.  The summation
+ *       order differs from the one-frame call's, so the two agree to rounding,
+ *       not bit for bit; no floating-point atomics: the same inputs give the
+ *       same bits on every call.  Entries of the table may repeat.
+ *   fd_morph_displace_batch_dev  per frame fd_morph_displace_dev's arithmetic in
+ *       place on d_P_xyz[f], with frame f's batched weights: columns in order
+ *       s = 0..S-1, multiply and add rounded separately, float(3 w), the clamp,
+ *       the add_delta term and rest + d as there.  Given equal weights frame f
+ *       is bit-identical to the one-frame call.  clamp_lo_hi, add_delta and
+ *       falloffradius are node parameters: one value for all frames.  Reads
+ *       the weights in stream order.  Two equal entries (two frames writing
+ *       one array) are FD_E_INVALID.
+ *   fd_morph_get_weights_batch  F x S row-major, synchronous (the object's stream).
+ * The batched weights are a state of their own: these calls neither read nor
+ * write the one-frame weights or is_computed, the one-frame calls do not touch
+ * the batched weights, fd_morph_init* clears them.  Displacement and
+ * get_weights before a batched compute: FD_E_NOT_BUILT; with an F other than
+ * the last batched compute's: FD_E_INVALID.  Argument errors (F outside
+ * 1..FD_MAX_BATCH, a NULL table or entry, equal entries for the displacement)
+ * return FD_E_INVALID before any device work, the text in fd_morph_last_error.
+ * S = 0, any N: as the one-frame calls; entries past N are not touched.
+ * Asynchronous on hip_stream (NULL: the object's own stream). */
+int fd_morph_compute_weights_batch_dev(fd_morph *m, int F, const float *const *d_P_xyz, void *hip_stream);
+int fd_morph_displace_batch_dev(fd_morph *m, int F, float *const *d_P_xyz, const float *clamp_lo_hi, int add_delta,
+                                float falloffradius, void *hip_stream);
+int fd_morph_get_weights_batch(fd_morph *m, int F, double *w);
+
 /* ---- host-side cook: the HDK-free mirror of cookMySop ----------------------
  * fdsop_* mirrors the SOP's parm surface (src/SOP_FaceDeform.cpp:99-137) and
  * the cook sequence (:215-489) over plain arrays standing in for GU_Detail:
