@@ -83,6 +83,7 @@ EXPORTS = [
     "fd_batch_create", "fd_batch_destroy", "fd_batch_size", "fd_batch_last_error", "fd_batch_wait_consumed", "fd_batch_prepare_shared", "fd_batch_set_eval_cus", "fd_batch_cook_group", "fd_shared_kernel_name", "fd_batch_set_shared_factor", "fd_batch_last_build_shared_factor",
     "fd_batch_set_points_dev", "fd_batch_build_async", "fd_batch_build_result", "fd_batch_deform_dev",
     "fd_batch_deform_shared_dev", "fd_batch_deform_vectors_shared_dev", "fd_shared_vectors_kernel_name",
+    "fd_batch_deform_shared_fp64_dev", "fd_shared_fp64_kernel_name",
     "fdsop_create", "fdsop_destroy", "fdsop_set_float", "fdsop_set_int", "fdsop_set_string",
     "fdsop_get_float", "fdsop_get_int", "fdsop_parm_count", "fdsop_parm_token", "fdsop_cook",
     "fdsop_messages", "fdsop_effective_float", "fdsop_engine",
@@ -196,6 +197,9 @@ def load() -> C.CDLL:
     L.fd_batch_deform_vectors_shared_dev.argtypes = [vp, vp, i64, vp, pv, vp, pv, vp, vp, vp, C.c_float, C.c_float, C.POINTER(FdBatchVectors)]
     L.fd_batch_deform_vectors_shared_dev.restype = i32
     L.fd_shared_vectors_kernel_name.argtypes = [i32, i32, i32]; L.fd_shared_vectors_kernel_name.restype = C.c_char_p
+    L.fd_batch_deform_shared_fp64_dev.argtypes = [vp, vp, i64, vp, pv, vp, pv, vp, vp, vp, C.c_float, C.c_float]
+    L.fd_batch_deform_shared_fp64_dev.restype = i32
+    L.fd_shared_fp64_kernel_name.argtypes = [i32, i32, i32]; L.fd_shared_fp64_kernel_name.restype = C.c_char_p
     L.fdsop_create.argtypes = [C.POINTER(FdConfig)]; L.fdsop_create.restype = vp
     L.fdsop_destroy.argtypes = [vp]; L.fdsop_destroy.restype = None
     L.fdsop_set_float.argtypes = [vp, C.c_char_p, i32, C.c_double]; L.fdsop_set_float.restype = i32
@@ -588,6 +592,21 @@ class Batch:
                                                       falls, vp(tu or None), vp(tv or None), vp(nr or None),
                                                       float(radius2), float(falloffrate)))
 
+    def deform_shared_fp64_dev(self, N: int, d_P_in: int, d_P_out, d_dist2: int = 0, d_falloff=None, d_tangents=None,
+                               radius2=1.0, falloffrate=1.0, stream_ptr: int | None = None):
+        """fd_batch_deform_shared_fp64_dev: deform_shared_dev's arguments, every frame evaluated in fp64 by one launch
+        whatever the contexts' precision setting says."""
+        n = len(self.engines)
+        if len(d_P_out) != n or (d_falloff is not None and len(d_falloff) != n):
+            raise ValueError("one output pointer per context")
+        vp = C.c_void_p
+        outs = (vp * n)(*d_P_out)
+        falls = None if d_falloff is None else (vp * n)(*[p or None for p in d_falloff])
+        tu, tv, nr = d_tangents if d_tangents is not None else (0, 0, 0)
+        self._check(self.L.fd_batch_deform_shared_fp64_dev(self.h, vp(stream_ptr or 0), N, vp(d_P_in), outs, vp(d_dist2 or None),
+                                                           falls, vp(tu or None), vp(tv or None), vp(nr or None),
+                                                           float(radius2), float(falloffrate)))
+
     def deform_vectors_shared_dev(self, N: int, d_P_in: int, d_P_out, d_dist2: int = 0, d_falloff=None, d_tangents=None,
                                   d_N: int = 0, d_N_out=None, d_vtu: int = 0, d_vtu_out=None, d_vtv: int = 0, d_vtv_out=None,
                                   d_jacobian=None, radius2=1.0, falloffrate=1.0, stream_ptr: int | None = None):
@@ -794,3 +813,8 @@ class Morph:
 def fd_shared_vectors_kernel_name(M: int, frames: int, kind: int) -> str:
     """The kernel fd_batch_deform_vectors_shared_dev's vector launch takes ("" where it runs the per-context launches)."""
     return load().fd_shared_vectors_kernel_name(int(M), int(frames), int(kind)).decode()
+
+
+def fd_shared_fp64_kernel_name(M: int, frames: int, kind: int) -> str:
+    """The kernel fd_batch_deform_shared_fp64_dev launches ("" where it runs the per-context launches)."""
+    return load().fd_shared_fp64_kernel_name(int(M), int(frames), int(kind)).decode()

@@ -159,6 +159,13 @@ struct fd_batch {
     float *prep_fall[kMaxBatch] = {nullptr};
     bool prep_has_fall = false;
     hipEvent_t fallback_ev = nullptr;    // behind the per-frame launches when the shared launch does not apply
+    // fd_batch_deform_shared_fp64_dev: scratch of its own (the two fp32 sets, packed_valid, cur_set and prepared are not its business)
+    void *d_s64 = nullptr;
+    size_t cap_s64 = 0;
+    hipEvent_t s64_consumed_ev = nullptr; // behind the last read of the contexts' models by that call (its pack kernel, or its per-context launches)
+    bool s64_consumed = false;           // ... and recorded: fd_batch_wait_consumed waits for it too
+    hipEvent_t s64_eval_ev = nullptr;    // behind its last evaluation: the next pack kernel rewrites the scratch that one reads
+    bool s64_eval_pending = false;
     hipEvent_t group_ev = nullptr;       // fd_batch_cook_group: behind the group's builds, for the evaluation stream
     // fd_batch_cook_group with the evaluation on the build stream itself (one unpipelined group): stream order does what the
     // events between build, packing and evaluation do across streams, and every event record is a barrier packet that keeps the
@@ -1571,6 +1578,9 @@ void fd_batch_destroy(fd_batch *b)
     }
     if (b->d_fac) (void)hipFree(b->d_fac);
     if (b->fallback_ev) (void)hipEventDestroy(b->fallback_ev);
+    if (b->d_s64) (void)hipFree(b->d_s64);
+    if (b->s64_consumed_ev) (void)hipEventDestroy(b->s64_consumed_ev);
+    if (b->s64_eval_ev) (void)hipEventDestroy(b->s64_eval_ev);
     if (b->group_ev) (void)hipEventDestroy(b->group_ev);
     if (b->h_mismatch) (void)hipHostFree(b->h_mismatch);
     if (b->ev0) (void)hipEventDestroy(b->ev0);
@@ -2081,16 +2091,136 @@ const char *fd_shared_vectors_kernel_name(int M, int frames, int kind)
     return pos[0] ? shared_vectors_kernel_name(round_up(M, kRecPad), frames, kind) : "";
 }
 
-int fd_batch_wait_consumed(fd_batch *b, void *hip_stream)
+// ---- every frame in fp64 by one matrix-pipe launch (fd_eval_shared64.hip) ----
+static bool shared64_kind(int kind)
 {
-    if (!b) return FD_E_INVALID;
-    hipEvent_t ev = b->consumed_override ? b->consumed_override : (b->packed_valid ? b->sets[b->cur_set].packed_ev : b->fallback_ev);
-    if (!ev) return FD_OK;          // no shared-rig evaluation enqueued: nothing reads the models beyond stream order
+    return kind == FD_KERNEL_THIN_PLATE || kind == FD_KERNEL_GAUSSIAN || kind == FD_KERNEL_GAUSSIAN_QNN || kind == FD_KERNEL_BIHARMONIC ||
+           kind == FD_KERNEL_CUBIC;
+}
+
+int fd_batch_deform_shared_fp64_dev(fd_batch *b, void *hip_stream, int64_t N, const float *d_P_in, float *const *d_P_out,
+                                    const float *d_dist2, float *const *d_falloff_out, const float *d_tu, const float *d_tv,
+                                    const float *d_nrm, float radius2, float falloffrate)
+{
+    if (!b || !d_P_out) return FD_E_INVALID;
+    const char *who = "fd_batch_deform_shared_fp64_dev";
+    if (N < 0 || (N > 0 && !d_P_in)) { batch_err(b, "%s: bad N / P_in", who); return FD_E_INVALID; }
+    if (!frames_ok(d_tu, d_tv, d_nrm)) { batch_err(b, "%s: tu, tv, nrm must be all set or all NULL", who); return FD_E_INVALID; }
+    // aliasing, before any device work: one input serves every frame, so no output may be a shared input -- except the one
+    // frame of a batch of one written in place over the mesh, as in fd_deform_dev
+    const void *ins[5] = {d_P_in, d_dist2, d_tu, d_tv, d_nrm};
+    for (int i = 0; i < b->n; ++i) {
+        if (!d_P_out[i]) { batch_err(b, "%s: NULL output array for context %d", who, i); return FD_E_INVALID; }
+        const void *outs[2] = {d_P_out[i], d_falloff_out ? d_falloff_out[i] : nullptr};
+        for (int o = 0; o < 2; ++o)
+            for (int k = 0; k < 5; ++k) {
+                if (!outs[o] || outs[o] != ins[k]) continue;
+                if (b->n == 1 && o == 0 && k == 0) continue;
+                batch_err(b, "%s: an output of context %d is a shared input array", who, i);
+                return FD_E_INVALID;
+            }
+    }
+    if (N == 0) return FD_OK;
     fd_ctx *c0 = b->ctxs[0];
     int rc = use_device(c0);
     if (rc) { batch_err(b, "%s", c0->err); return rc; }
     hipStream_t stream = hip_stream ? (hipStream_t)hip_stream : cur_stream(c0);
-    if (hipStreamWaitEvent(stream, ev, 0) != hipSuccess) {
+    bool fast = shared64_kind(eval_kind(c0)) && c0->kind != FD_KERNEL_GAUSSIAN_ML;
+    for (int i = 0; i < b->n; ++i) {
+        fd_ctx *c = b->ctxs[i];
+        if (!c->built && !c->build_pending) { batch_err(b, "%s: context %d has no built model", who, i); return FD_E_NOT_BUILT; }
+        // one rest rig: every context read its rest points in place from the SAME device array (as fd_batch_deform_shared_dev)
+        if (!c->rest_src || c->rest_src != c0->rest_src || !same_model(c, c0)) {
+            batch_err(b, "%s: the contexts must share one rest rig (fd_batch_set_points_dev with the "
+                         "same rest array for all), kernel and term; context %d does not", who, i);
+            return FD_E_INVALID;
+        }
+        if (c->output != c0->output) { batch_err(b, "%s: context %d has another fd_set_output setting than context 0", who, i); return FD_E_INVALID; }
+        if (c->eval_variant > 0 || record_layers(c) != 0) fast = false;
+    }
+    if (!b->lean && (rc = batch_poll(b))) return rc;           // before the ordering: a repaired model's rebuild is ordered with the rest
+    for (int i = 0; i < b->n; ++i)
+        if ((rc = order_after_batch(b->ctxs[i], stream))) { batch_err(b, "context %d: %s", i, b->ctxs[i]->err); return rc; }
+    if (!make_event(&b->s64_consumed_ev)) { batch_err(b, "%s: hipEventCreate failed", who); return FD_E_DEVICE; }
+    if (!fast) {
+        // the multilayer model, an eval_variant override: per context, the launch of an FD_EVAL_FP64 context on the shared arrays
+        for (int i = 0; i < b->n; ++i) {
+            DeformArgs a = deform_args(b->ctxs[i], N, d_P_in, d_P_out[i], d_dist2, d_falloff_out ? d_falloff_out[i] : nullptr, d_tu, d_tv,
+                                       d_nrm, radius2, falloffrate);
+            a.precision = FD_EVAL_FP64;
+            hipError_t e = launch_deform(a, stream);
+            if (e != hipSuccess) { batch_err(b, "launch_deform failed: %s", hipGetErrorString(e)); return FD_E_DEVICE; }
+        }
+        // these launches read the models to their end
+        if (hipEventRecord(b->s64_consumed_ev, stream) != hipSuccess) { (void)hipGetLastError(); return FD_E_DEVICE; }
+        b->s64_consumed = true;
+        return FD_OK;
+    }
+    Shared64Args a{};
+    a.N = N; a.P_in = d_P_in; a.dist2 = d_dist2; a.tu = d_tu; a.tv = d_tv; a.nrm = d_nrm;
+    a.radius2 = radius2; a.falloffrate = falloffrate;
+    a.M = c0->M; a.Mpad = round_up(c0->M, kRecPad); a.nF = b->n; a.kind = eval_kind(c0);
+    bool one_build = c0->rig_build_id != 0;
+    for (int i = 1; i < b->n && one_build; ++i) one_build = b->ctxs[i]->rig_build_id == c0->rig_build_id;
+    for (int i = 0; i < b->n; ++i) {
+        fd_ctx *c = b->ctxs[i];
+        a.rec64[i] = c->d_rec64; a.model[i] = c->d_model; a.P_out[i] = d_P_out[i];
+        a.centres[i] = one_build ? c0->d_centres : c->d_centres;       // (one batched build read one array: equal by construction)
+    }
+    a.falloff_out = d_falloff_out;
+    a.delta_out = c0->output == FD_OUTPUT_DISPLACEMENT;
+    a.max_wgs = b->eval_cus;
+    const size_t bytes = shared64_scratch_bytes(a.Mpad, a.nF);
+    if (bytes > b->cap_s64) {
+        // (hipFree drains the device: no launch still reads the old scratch)
+        if (b->d_s64) (void)hipFree(b->d_s64);
+        b->d_s64 = nullptr; b->cap_s64 = 0; b->s64_eval_pending = false;
+        if (hipMalloc(&b->d_s64, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            batch_err(b, "%s: scratch allocation (%zu bytes) failed", who, bytes);
+            return FD_E_NOMEM;
+        }
+        b->cap_s64 = bytes;
+    }
+    // the evaluation that last read the scratch must be through with it
+    if (b->s64_eval_pending && hipStreamWaitEvent(stream, b->s64_eval_ev, 0) != hipSuccess) {
+        batch_err(b, "%s: hipStreamWaitEvent failed: %s", who, hipGetErrorString(hipGetLastError()));
+        return FD_E_DEVICE;
+    }
+    b->s64_eval_pending = false;
+    a.scratch = b->d_s64;
+    a.packed_ev = b->s64_consumed_ev;
+    if (b->h_mismatch && hipHostGetDevicePointer((void **)&a.mismatch, b->h_mismatch, 0) != hipSuccess) { (void)hipGetLastError(); a.mismatch = nullptr; }
+    hipError_t e = launch_deform_shared64(a, stream);
+    if (e != hipSuccess) { batch_err(b, "launch_deform_shared64 failed: %s", hipGetErrorString(e)); return FD_E_DEVICE; }
+    b->s64_consumed = true;
+    if (make_event(&b->s64_eval_ev) && hipEventRecord(b->s64_eval_ev, stream) == hipSuccess) {
+        b->s64_eval_pending = true;
+    } else {
+        // no event to order the next pack kernel by: be safe
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(stream);
+    }
+    return FD_OK;
+}
+
+const char *fd_shared_fp64_kernel_name(int M, int frames, int kind)
+{
+    if (M <= 0 || !shared64_kind(kind)) return "";
+    return shared64_kernel_name(round_up(M, kRecPad), frames, kind);
+}
+
+int fd_batch_wait_consumed(fd_batch *b, void *hip_stream)
+{
+    if (!b) return FD_E_INVALID;
+    hipEvent_t ev = b->consumed_override ? b->consumed_override : (b->packed_valid ? b->sets[b->cur_set].packed_ev : b->fallback_ev);
+    hipEvent_t ev64 = b->s64_consumed ? b->s64_consumed_ev : nullptr;       // fd_batch_deform_shared_fp64_dev's reads as well
+    if (!ev && !ev64) return FD_OK;          // no shared-rig evaluation enqueued: nothing reads the models beyond stream order
+    fd_ctx *c0 = b->ctxs[0];
+    int rc = use_device(c0);
+    if (rc) { batch_err(b, "%s", c0->err); return rc; }
+    hipStream_t stream = hip_stream ? (hipStream_t)hip_stream : cur_stream(c0);
+    if ((ev && hipStreamWaitEvent(stream, ev, 0) != hipSuccess) || (ev64 && hipStreamWaitEvent(stream, ev64, 0) != hipSuccess)) {
         batch_err(b, "fd_batch_wait_consumed: hipStreamWaitEvent failed: %s", hipGetErrorString(hipGetLastError()));
         return FD_E_DEVICE;
     }

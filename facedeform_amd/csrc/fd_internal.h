@@ -300,6 +300,27 @@ struct SharedVectorArgs {
 };
 hipError_t launch_vectors_shared(const SharedVectorArgs &a, hipStream_t stream);
 const char *shared_vectors_kernel_name(int Mpad, int nF, int kind);
+// Every frame of a shared-rig batch in fp64 by one matrix-pipe launch (fd_eval_shared64.hip, fd_batch_deform_shared_fp64_dev):
+// a pack kernel copies what the launch needs of the models into `scratch` (shared64_scratch_bytes; packed_ev is recorded
+// behind it, may be null), the evaluation reads only that copy.
+struct Shared64Args {
+    int64_t N;
+    const float *P_in, *dist2, *tu, *tv, *nrm;
+    float radius2, falloffrate;
+    int M, Mpad, nF, kind;                // kind: any but the multilayer model's
+    const Rec64 *rec64[kMaxBatch];
+    const DevModel *model[kMaxBatch];
+    const double *centres[kMaxBatch];     // compared with entry 0 by content unless equal to it by address; a frame that differs is passed through
+    float *P_out[kMaxBatch];
+    float *const *falloff_out;            // nF entries or nullptr
+    void *scratch;
+    hipEvent_t packed_ev;
+    int delta_out, max_wgs;
+    int *mismatch;                        // as SharedDeformArgs::mismatch
+};
+hipError_t launch_deform_shared64(const Shared64Args &a, hipStream_t stream);
+size_t shared64_scratch_bytes(int Mpad, int nF);
+const char *shared64_kernel_name(int Mpad, int nF, int kind);
 // island mask (fd_capture.hip): nearest mesh point per rig point + max_edges breadth-first rings
 hipError_t launch_capture_islands(const float *d_P, int64_t N, const int64_t *d_offsets, const int *d_neighbours,
                                   const float *d_rig, int M, int max_edges, unsigned char *d_mask, hipStream_t stream);

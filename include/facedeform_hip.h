@@ -471,6 +471,45 @@ int fd_batch_deform_vectors_shared_dev(fd_batch *batch, void *hip_stream, int64_
  * in fp32 (fd_set_eval_precision) -- a batch set to FD_EVAL_FP64 always takes the per-context launches, whatever this
  * returns.  For tests and profiles. */
 const char *fd_shared_vectors_kernel_name(int M, int frames, int kind);
+/* The frames of a shot evaluated in fp64 by ONE matrix-pipe launch: fd_batch_deform_shared_dev's arguments, gate,
+ * tangent projection, fall-off, fd_set_output handling, error codes, build-status poll, stream ordering behind the
+ * batch's builds and one-rest-rig condition (FD_E_INVALID), with
+ *   Precision: every frame is evaluated in fp64 whatever fd_set_eval_precision says on the contexts (a built model
+ *     carries its fp64 records either way); the contexts' settings are not changed by the call.
+ *   Definition: per frame, the FD_EVAL_FP64 evaluation of fd_deform_dev -- fp32 positions widened to fp64, direct
+ *     differences in raw coordinates, the kind's fp64 phi, fp64 accumulation over the centres on top of the fp64 affine
+ *     part, ONE rounding of the three sums to fp32, then the fp32 epilogue (projection, fall-off, write-back) of every
+ *     other launch.  Only the order of the fp64 summation differs from the per-frame launch: every output component is
+ *     within one fp32 ulp of fd_batch_deform_dev's on FD_EVAL_FP64 contexts, every fd_falloff value bit-identical.  phi is
+ *     formed once per (vertex, centre) for all frames and contracted with the frames' fp64 weights on
+ *     v_mfma_f64_16x16x4_f64.  No floating-point atomics: the same inputs give the same bits on every call, and a
+ *     vertex's result does not depend on its place in the launch ([0, N) in one call or in two ranges: same bits).
+ *   Pass-through: a gated vertex (d_dist2 > radius2), and every vertex of a frame whose model is not built
+ *     (terminationtype != 1), is passed through -- the position bit for bit, or 0 in FD_OUTPUT_DISPLACEMENT mode -- and
+ *     its fd_falloff entry is not written.  Entries past N are not touched.
+ *   Where the launch applies: thin-plate, FD_KERNEL_GAUSSIAN, FD_KERNEL_GAUSSIAN_QNN, biharmonic and cubic; any term;
+ *     1..FD_MAX_BATCH frames (no lower threshold); any M a model can be built for (a model that does not fit LDS is staged
+ *     in chunks of centres).  Everywhere else -- the multilayer model, an eval_variant override -- the call runs, per
+ *     context, exactly the launch fd_deform_dev_stream runs for an FD_EVAL_FP64 context on the shared arrays, bit for bit.
+ *   Aliasing: with more than one frame no output (P_out, falloff_out) may be a shared input (d_P_in, d_dist2, d_tu,
+ *     d_tv, d_nrm): FD_E_INVALID, before any device work.  With one frame P_out[0] == d_P_in is allowed, as in
+ *     fd_deform_dev; nothing else is.
+ *   Reads of the models: fd_batch_wait_consumed covers this launch as it covers fd_batch_deform_shared_dev -- a first
+ *     small kernel copies the fp64 weights (in matrix-operand order), the centre records, the affine parts, the frames'
+ *     status and the output addresses into scratch of the batch that only this call uses, and the evaluation reads that
+ *     copy alone; after fd_batch_wait_consumed the contexts may be rebuilt while the evaluation still runs.  The fp32
+ *     call's two scratch sets and fd_batch_prepare_shared are not involved.
+ *   Not covered: fd_batch_cook_group, fdsop_cook and fd_batch_deform_vectors_shared_dev do not take this launch, and
+ *     the multilayer model runs the per-context launches.
+ * Asynchronous on hip_stream (NULL: context 0's). */
+int fd_batch_deform_shared_fp64_dev(fd_batch *batch, void *hip_stream, int64_t N, const float *d_P_in,
+                                    float *const *d_P_out, const float *d_dist2, float *const *d_falloff_out,
+                                    const float *d_tu, const float *d_tv, const float *d_nrm,
+                                    float radius2, float falloffrate);
+/* The kernel fd_batch_deform_shared_fp64_dev launches for M centres, `frames` contexts and a kernel kind
+ * ("k_deform64_shared"), or "" where it runs the per-context launches (FD_KERNEL_GAUSSIAN_ML).  It sees no context: an
+ * eval_variant override takes the per-context launches whatever this returns.  For tests and profiles. */
+const char *fd_shared_fp64_kernel_name(int M, int frames, int kind);
 /* Makes hip_stream (NULL: context 0's) wait until the batch's last fd_batch_deform_shared_dev no longer reads the
  * contexts' models: that launch copies what it needs of them (weights as fp16 tiles, the rest rig's centre tiles)
  * into the batch's own scratch with a first small kernel, and the evaluation proper reads only that copy.  A pipeline
