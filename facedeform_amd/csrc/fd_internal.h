@@ -321,6 +321,22 @@ struct Shared64Args {
 hipError_t launch_deform_shared64(const Shared64Args &a, hipStream_t stream);
 size_t shared64_scratch_bytes(int Mpad, int nF);
 const char *shared64_kernel_name(int Mpad, int nF, int kind);
+// The Jacobian and the vectors it carries for every frame of that batch, in fp64 by one matrix-pipe launch
+// (fd_vectors_shared64.hip, fd_batch_deform_vectors_shared_fp64_dev): reads the scratch launch_deform_shared64's pack kernel
+// wrote for the same Mpad and nF, the mesh and the vectors; nothing of the contexts.
+struct SharedVector64Args {
+    int64_t N;
+    const float *P_in, *dist2, *tu, *tv, *nrm;
+    float radius2, falloffrate;
+    int Mpad, nF, kind;
+    const float *vN, *vtu, *vtv;
+    float *N_out[kMaxBatch], *tu_out[kMaxBatch], *tv_out[kMaxBatch], *jacobian[kMaxBatch];
+    const void *scratch;
+    int max_wgs;
+};
+hipError_t launch_vectors_shared64(const SharedVector64Args &a, hipStream_t stream);
+const char *shared_vectors64_kernel_name(int Mpad, int nF, int kind);      // "" below shared_vectors64_min_frames too
+int shared_vectors64_min_frames(int kind);                                  // fewer frames: the per-context launches are faster
 // island mask (fd_capture.hip): nearest mesh point per rig point + max_edges breadth-first rings
 hipError_t launch_capture_islands(const float *d_P, int64_t N, const int64_t *d_offsets, const int *d_neighbours,
                                   const float *d_rig, int M, int max_edges, unsigned char *d_mask, hipStream_t stream);

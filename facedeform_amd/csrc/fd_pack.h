@@ -118,6 +118,20 @@ __host__ __device__ constexpr float grad_scale32(int kind)
     return kind == FD_KERNEL_GAUSSIAN || kind == FD_KERNEL_GAUSSIAN_QNN ? (float)(2.0 * 0.6931471805599453)
                                                                         : (float)grad_scale64(kind);
 }
+// g of the derivative table in fp64, raw coordinates: grad phi_j = grad_scale64 g_j (x - c_j) (k_vectors64_<kind>, k_vectors64_shared)
+template <int KIND>
+__device__ __forceinline__ double grad64(double d2, double s)
+{
+    if constexpr (KIND == FD_KERNEL_THIN_PLATE) {
+        return d2 > 0.0 ? log(d2) + 1.0 : 0.0;        // (x - c) = 0 there
+    } else if constexpr (KIND == FD_KERNEL_GAUSSIAN || KIND == FD_KERNEL_GAUSSIAN_QNN) {
+        return exp(d2 * s) * s;
+    } else if constexpr (KIND == FD_KERNEL_BIHARMONIC) {
+        return d2 > 0.0 ? 1.0 / sqrt(d2) : 0.0;
+    } else {
+        return sqrt(d2);
+    }
+}
 
 // (256 threads; a kernel of its own in fd_build.hip, the last phase of the one-launch build in fd_nullspace.hip)
 template <class Src>

@@ -22,6 +22,7 @@ constexpr int kChunk = 64;   // centres per fp32 partial sum
 
 using packing::grad_scale32;
 using packing::grad_scale64;
+using packing::grad64;
 using packing::kTpsGradLog2e;
 
 typedef const __attribute__((address_space(4))) Rec32 *ConstRec32;
@@ -57,20 +58,6 @@ __device__ __forceinline__ f32x2 grad32(f32x2 d2, float s)
         return (f32x2){d2.x > 0.f ? __builtin_amdgcn_rsqf(d2.x) : 0.f, d2.y > 0.f ? __builtin_amdgcn_rsqf(d2.y) : 0.f};
     } else {
         return (f32x2){__builtin_amdgcn_sqrtf(d2.x), __builtin_amdgcn_sqrtf(d2.y)};
-    }
-}
-
-template <int KIND>
-__device__ __forceinline__ double grad64(double d2, double s)
-{
-    if constexpr (KIND == FD_KERNEL_THIN_PLATE) {
-        return d2 > 0.0 ? log(d2) + 1.0 : 0.0;        // (x - c) = 0 there
-    } else if constexpr (KIND == FD_KERNEL_GAUSSIAN || KIND == FD_KERNEL_GAUSSIAN_QNN) {
-        return exp(d2 * s) * s;
-    } else if constexpr (KIND == FD_KERNEL_BIHARMONIC) {
-        return d2 > 0.0 ? 1.0 / sqrt(d2) : 0.0;
-    } else {
-        return sqrt(d2);
     }
 }
 

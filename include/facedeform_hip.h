@@ -469,7 +469,7 @@ int fd_batch_deform_vectors_shared_dev(fd_batch *batch, void *hip_stream, int64_
  * kernel kind ("k_vectors32_shared_thin_plate" / "k_vectors32_shared_gaussian"), or "" where the call runs the
  * per-context launches instead.  Like fd_shared_kernel_name it sees no context: the name holds for a batch evaluated
  * in fp32 (fd_set_eval_precision) -- a batch set to FD_EVAL_FP64 always takes the per-context launches, whatever this
- * returns.  For tests and profiles. */
+ * returns (the one-launch fp64 form is fd_batch_deform_vectors_shared_fp64_dev).  For tests and profiles. */
 const char *fd_shared_vectors_kernel_name(int M, int frames, int kind);
 /* The frames of a shot evaluated in fp64 by ONE matrix-pipe launch: fd_batch_deform_shared_dev's arguments, gate,
  * tangent projection, fall-off, fd_set_output handling, error codes, build-status poll, stream ordering behind the
@@ -500,7 +500,8 @@ const char *fd_shared_vectors_kernel_name(int M, int frames, int kind);
  *     copy alone; after fd_batch_wait_consumed the contexts may be rebuilt while the evaluation still runs.  The fp32
  *     call's two scratch sets and fd_batch_prepare_shared are not involved.
  *   Not covered: fd_batch_cook_group, fdsop_cook and fd_batch_deform_vectors_shared_dev do not take this launch, and
- *     the multilayer model runs the per-context launches.
+ *     the multilayer model runs the per-context launches.  The Jacobian and the vectors of an fp64 shot have a call of
+ *     their own on top of this one: fd_batch_deform_vectors_shared_fp64_dev (below).
  * Asynchronous on hip_stream (NULL: context 0's). */
 int fd_batch_deform_shared_fp64_dev(fd_batch *batch, void *hip_stream, int64_t N, const float *d_P_in,
                                     float *const *d_P_out, const float *d_dist2, float *const *d_falloff_out,
@@ -510,6 +511,54 @@ int fd_batch_deform_shared_fp64_dev(fd_batch *batch, void *hip_stream, int64_t N
  * ("k_deform64_shared"), or "" where it runs the per-context launches (FD_KERNEL_GAUSSIAN_ML).  It sees no context: an
  * eval_variant override takes the per-context launches whatever this returns.  For tests and profiles. */
 const char *fd_shared_fp64_kernel_name(int M, int frames, int kind);
+/* fd_batch_deform_shared_fp64_dev plus, for every frame f, the Jacobian and the vectors it carries, in fp64 by ONE
+ * matrix-pipe launch of its own.
+ *   Positions: P_out and falloff_out are bit-identical to fd_batch_deform_shared_fp64_dev called with the same arguments:
+ *     that call runs unchanged first, then a launch of its own writes the vector outputs.  vec == NULL, or every pointer
+ *     in it NULL, is exactly fd_batch_deform_shared_fp64_dev.  Inherited from it: precision (fp64 whatever the contexts
+ *     say, their settings untouched), error codes, build-status poll, ordering behind the batch's builds, the
+ *     one-rest-rig condition and fd_set_output handling.
+ *   Vectors: fd_deform_vectors' definition, per frame, in fp64: A_f = I + f Pi J_f with
+ *     J_f = gs sum_j w_f[j] (x) g_j(x) (x - c_j) + L_f from fp32 positions widened to fp64 and direct differences in raw
+ *     coordinates (g and gs: the FD_EVAL_FP64 evaluation's of fd_deform_vectors_dev); t' = A_f t (not renormalised),
+ *     n' = cof(A_f) n rescaled to |n|; A is stored as fp32.  Only the order and association of the fp64 sum differ from
+ *     the per-frame fp64 launch (k_vectors64_<kind>): the basis g_j(x) (x - c_j) is formed once per (vertex, centre) for
+ *     all frames and contracted with the frames' fp64 weights on v_mfma_f64_16x16x4_f64.
+ *   Pass-through: every vector output is the input bit for bit, and A = I exactly, for gated vertices
+ *     (d_dist2 > radius2), for frames whose model is not built, and where f = 0.  Entries past N are not touched.
+ *   Aliasing: no output (P_out, falloff_out, the tables of vec) may equal any shared input (d_P_in, d_dist2, d_tu, d_tv,
+ *     d_nrm, vec->N / tu / tv): FD_E_INVALID, before any device work.  This holds for a batch of one as well -- the
+ *     position call's in-place exception does not apply, because the vector launch reads d_P_in after the position
+ *     launch has written.
+ *   Tables: as in fd_batch_deform_vectors_shared_dev -- vec->struct_size at least sizeof(fd_batch_vectors), every input
+ *     with its output table (both or neither), a table has n non-NULL entries; otherwise FD_E_INVALID.
+ *   Where the launch applies: where fd_batch_deform_shared_fp64_dev's does -- thin-plate, FD_KERNEL_GAUSSIAN,
+ *     FD_KERNEL_GAUSSIAN_QNN, biharmonic and cubic; any term; 1..FD_MAX_BATCH frames; any M (a model that does not fit
+ *     LDS is staged in chunks of centres).  The multilayer model and an eval_variant override do not take it: there the
+ *     vector outputs are, per context and bit for bit, what fd_deform_vectors_dev writes for an FD_EVAL_FP64 context on
+ *     the shared arrays.  Neither does a batch of
+ *     fewer than 2 frames (thin-plate, biharmonic) or 3 (the Gaussian kinds, cubic): measured at
+ *     1M vertices and 256 centres, one frame costs the launch 1.25 ms against 0.80 ms per context (thin-plate) and
+ *     0.83 ms against 0.34 ms (Gaussian), the launch's time stays there up to 4 frames, and it is 4.4x / 2.3x faster at
+ *     13 frames and 5.5x / 2.5x at 32.  Those batches get the per-context vector launches too, positions
+ *     unchanged.  (Biharmonic 0.84 ms against 0.46 ms per frame, cubic 0.72 ms against 0.32 ms.)
+ *   Reads of the models: the vector launch reads only the batch's fp64 scratch (as the position call packed it), the
+ *     mesh, the vectors and its own arguments: fd_batch_wait_consumed covers it, and the contexts may be rebuilt while
+ *     it runs.
+ *   Bits: no floating-point atomics; the same inputs give the same bits on every call, and a vertex's result does not
+ *     depend on its place in the launch ([0, N) in one call or in two ranges: same bits).
+ * fd_batch_deform_vectors_shared_dev is unchanged (per-context launches on fp64 contexts), and so are
+ * fd_batch_cook_group and fdsop_cook.  Asynchronous on hip_stream (NULL: context 0's). */
+int fd_batch_deform_vectors_shared_fp64_dev(fd_batch *batch, void *hip_stream, int64_t N, const float *d_P_in,
+                                            float *const *d_P_out, const float *d_dist2, float *const *d_falloff_out,
+                                            const float *d_tu, const float *d_tv, const float *d_nrm,
+                                            float radius2, float falloffrate, const fd_batch_vectors *vec);
+/* The kernel the vector launch of fd_batch_deform_vectors_shared_fp64_dev takes for M centres, `frames` contexts and a
+ * kernel kind ("k_vectors64_shared"), or "" where the call runs the per-context launches (FD_KERNEL_GAUSSIAN_ML, M <= 0,
+ * frames outside 1..FD_MAX_BATCH, and frames below the kind's threshold above: 1 for thin-plate and biharmonic, 1..2 for the
+ * Gaussian kinds and cubic).  It sees no context: an eval_variant override takes the per-context launches whatever this returns.  For
+ * tests and profiles. */
+const char *fd_shared_vectors_fp64_kernel_name(int M, int frames, int kind);
 /* Makes hip_stream (NULL: context 0's) wait until the batch's last fd_batch_deform_shared_dev no longer reads the
  * contexts' models: that launch copies what it needs of them (weights as fp16 tiles, the rest rig's centre tiles)
  * into the batch's own scratch with a first small kernel, and the evaluation proper reads only that copy.  A pipeline
