@@ -511,6 +511,47 @@ int fd_batch_deform_shared_fp64_dev(fd_batch *batch, void *hip_stream, int64_t N
  * ("k_deform64_shared"), or "" where it runs the per-context launches (FD_KERNEL_GAUSSIAN_ML).  It sees no context: an
  * eval_variant override takes the per-context launches whatever this returns.  For tests and profiles. */
 const char *fd_shared_fp64_kernel_name(int M, int frames, int kind);
+/* The frames of a shot of MULTILAYER models (FD_KERNEL_GAUSSIAN_ML) evaluated by ONE matrix-pipe launch:
+ * fd_batch_deform_shared_dev's arguments, gate, tangent projection, fall-off, fd_set_output handling, error codes,
+ * build-status poll and repair, stream ordering behind the batch's builds and one-rest-rig condition (FD_E_INVALID), with
+ *   Definition: per frame, the fp32 evaluation of the solved model's M x L Gaussian records (radii R / 2^l) on top of its
+ *     polynomial, then the fp32 epilogue of fd_deform_dev.  exp(-d2 / R_l^2) is formed once per (vertex, record) for all
+ *     frames -- d2 once per centre for the layers that sit side by side in a lane's operand, every layer with its own
+ *     multiply and its own exponential -- and contracted with the frames' weights, as two fp16 pieces each, on
+ *     v_mfma_f32_32x32x16_f16 with fp32 accumulation.  The result meets the 1e-5 parity bar against the reference like the
+ *     per-context launches do; it is not bit-identical to them (22 significant bits in the contraction against 24); every
+ *     fd_falloff value is.  No floating-point atomics: the same inputs give the same bits on every call, a vertex's
+ *     result does not depend on its place in the launch ([0, N) in one call or in two ranges: same bits), nor on
+ *     fd_batch_set_eval_cus.
+ *   Where the launch applies: every context FD_KERNEL_GAUSSIAN_ML with the same M, radius, layers, lambda and term, built
+ *     on one rest array; FD_EVAL_FP32; no eval_variant override; 1..8 layers; any M a multilayer model can be built for (the
+ *     model is staged through LDS in chunks of records); 2..FD_MAX_BATCH frames.  The lower bound of 2 frames is
+ *     provisional: the launch has not been timed on a device yet.
+ *   Everywhere else -- other kinds, fp64 contexts, eval_variant overrides, imported models, one frame, layer counts
+ *     outside 1..8 -- the call IS fd_batch_deform_shared_dev with the same arguments, bit for bit.
+ *   Pass-through: a gated vertex (d_dist2 > radius2), and every vertex of a frame whose model is not built
+ *     (terminationtype != 1), is passed through -- the position bit for bit, or 0 in FD_OUTPUT_DISPLACEMENT mode -- and
+ *     its fd_falloff entry is not written.  Entries past N are not touched.
+ *   Aliasing: no output (P_out, falloff_out) may be a shared input (d_P_in, d_dist2, d_tu, d_tv, d_nrm): FD_E_INVALID,
+ *     before any device work.  With one frame P_out[0] == d_P_in is allowed, as in fd_batch_deform_shared_fp64_dev.
+ *   Reads of the models: fd_batch_wait_consumed covers this launch -- a first small kernel copies the frames' weights
+ *     (split fp16 tiles), the M x L records {c'x, c'y, c'z, -log2(e) s^2 / R_l^2}, the polynomial tiles, the frames' status
+ *     and the output addresses into scratch of the batch that only this call uses, and the evaluation reads that copy
+ *     alone; after fd_batch_wait_consumed the contexts may be rebuilt while the evaluation still runs.  The fp32 call's
+ *     two scratch sets, fd_batch_prepare_shared and the fp64 scratch are not involved.
+ *   Not covered: fd_batch_cook_group, fdsop_cook and the four other shared calls do not take this launch (a multilayer
+ *     batch runs the per-context launches there, as before), and the Jacobian and the vectors of a multilayer shot stay
+ *     with the per-context launches.
+ * Asynchronous on hip_stream (NULL: context 0's). */
+int fd_batch_deform_shared_ml_dev(fd_batch *batch, void *hip_stream, int64_t N, const float *d_P_in,
+                                  float *const *d_P_out, const float *d_dist2, float *const *d_falloff_out,
+                                  const float *d_tu, const float *d_tv, const float *d_nrm,
+                                  float radius2, float falloffrate);
+/* The kernel fd_batch_deform_shared_ml_dev launches for M centres, `layers` layers and `frames` contexts
+ * ("k_deform32_shared_ml"), or "" where it is fd_batch_deform_shared_dev (layers outside 1..8, frames outside
+ * 2..FD_MAX_BATCH, M <= 0).  It sees no context: another kind, fp64 contexts or an eval_variant override delegate whatever
+ * this returns.  For tests and profiles. */
+const char *fd_shared_ml_kernel_name(int M, int layers, int frames);
 /* fd_batch_deform_shared_fp64_dev plus, for every frame f, the Jacobian and the vectors it carries, in fp64 by ONE
  * matrix-pipe launch of its own.
  *   Positions: P_out and falloff_out are bit-identical to fd_batch_deform_shared_fp64_dev called with the same arguments:
