@@ -85,6 +85,7 @@ EXPORTS = [
     "fd_batch_deform_shared_dev", "fd_batch_deform_vectors_shared_dev", "fd_shared_vectors_kernel_name",
     "fd_batch_deform_shared_fp64_dev", "fd_shared_fp64_kernel_name",
     "fd_batch_deform_shared_ml_dev", "fd_shared_ml_kernel_name",
+    "fd_batch_deform_shared_ml_fp64_dev", "fd_shared_ml_fp64_kernel_name",
     "fd_batch_deform_vectors_shared_fp64_dev", "fd_shared_vectors_fp64_kernel_name",
     "fdsop_create", "fdsop_destroy", "fdsop_set_float", "fdsop_set_int", "fdsop_set_string",
     "fdsop_get_float", "fdsop_get_int", "fdsop_parm_count", "fdsop_parm_token", "fdsop_cook",
@@ -205,6 +206,9 @@ def load() -> C.CDLL:
     L.fd_batch_deform_shared_ml_dev.argtypes = [vp, vp, i64, vp, pv, vp, pv, vp, vp, vp, C.c_float, C.c_float]
     L.fd_batch_deform_shared_ml_dev.restype = i32
     L.fd_shared_ml_kernel_name.argtypes = [i32, i32, i32]; L.fd_shared_ml_kernel_name.restype = C.c_char_p
+    L.fd_batch_deform_shared_ml_fp64_dev.argtypes = [vp, vp, i64, vp, pv, vp, pv, vp, vp, vp, C.c_float, C.c_float]
+    L.fd_batch_deform_shared_ml_fp64_dev.restype = i32
+    L.fd_shared_ml_fp64_kernel_name.argtypes = [i32, i32, i32]; L.fd_shared_ml_fp64_kernel_name.restype = C.c_char_p
     L.fd_batch_deform_vectors_shared_fp64_dev.argtypes = [vp, vp, i64, vp, pv, vp, pv, vp, vp, vp, C.c_float, C.c_float, C.POINTER(FdBatchVectors)]
     L.fd_batch_deform_vectors_shared_fp64_dev.restype = i32
     L.fd_shared_vectors_fp64_kernel_name.argtypes = [i32, i32, i32]; L.fd_shared_vectors_fp64_kernel_name.restype = C.c_char_p
@@ -630,6 +634,21 @@ class Batch:
                                                          falls, vp(tu or None), vp(tv or None), vp(nr or None),
                                                          float(radius2), float(falloffrate)))
 
+    def deform_shared_ml_fp64_dev(self, N: int, d_P_in: int, d_P_out, d_dist2: int = 0, d_falloff=None, d_tangents=None,
+                                  radius2=1.0, falloffrate=1.0, stream_ptr: int | None = None):
+        """fd_batch_deform_shared_ml_fp64_dev: deform_shared_fp64_dev's arguments; a shot of multilayer models is evaluated
+        in fp64 by one launch, anything else exactly as deform_shared_fp64_dev does."""
+        n = len(self.engines)
+        if len(d_P_out) != n or (d_falloff is not None and len(d_falloff) != n):
+            raise ValueError("one output pointer per context")
+        vp = C.c_void_p
+        outs = (vp * n)(*d_P_out)
+        falls = None if d_falloff is None else (vp * n)(*[p or None for p in d_falloff])
+        tu, tv, nr = d_tangents if d_tangents is not None else (0, 0, 0)
+        self._check(self.L.fd_batch_deform_shared_ml_fp64_dev(self.h, vp(stream_ptr or 0), N, vp(d_P_in), outs, vp(d_dist2 or None),
+                                                              falls, vp(tu or None), vp(tv or None), vp(nr or None),
+                                                              float(radius2), float(falloffrate)))
+
     def deform_vectors_shared_dev(self, N: int, d_P_in: int, d_P_out, d_dist2: int = 0, d_falloff=None, d_tangents=None,
                                   d_N: int = 0, d_N_out=None, d_vtu: int = 0, d_vtu_out=None, d_vtv: int = 0, d_vtv_out=None,
                                   d_jacobian=None, radius2=1.0, falloffrate=1.0, stream_ptr: int | None = None, _fp64: bool = False):
@@ -852,6 +871,11 @@ def fd_shared_vectors_fp64_kernel_name(M: int, frames: int, kind: int) -> str:
 def fd_shared_ml_kernel_name(M: int, layers: int, frames: int) -> str:
     """The kernel fd_batch_deform_shared_ml_dev launches ("" where it is fd_batch_deform_shared_dev)."""
     return load().fd_shared_ml_kernel_name(int(M), int(layers), int(frames)).decode()
+
+
+def fd_shared_ml_fp64_kernel_name(M: int, layers: int, frames: int) -> str:
+    """The kernel fd_batch_deform_shared_ml_fp64_dev launches ("" where it is fd_batch_deform_shared_fp64_dev)."""
+    return load().fd_shared_ml_fp64_kernel_name(int(M), int(layers), int(frames)).decode()
 
 
 def fd_shared_fp64_kernel_name(M: int, frames: int, kind: int) -> str:

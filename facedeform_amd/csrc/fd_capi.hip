@@ -173,6 +173,13 @@ struct fd_batch {
     bool sml_consumed = false;           // ... and recorded: fd_batch_wait_consumed waits for it too
     hipEvent_t sml_eval_ev = nullptr;    // behind its last evaluation: the next pack kernel rewrites the scratch that one reads
     bool sml_eval_pending = false;
+    // fd_batch_deform_shared_ml_fp64_dev: and once more, for the fp64 multilayer shot launch
+    void *d_sml64 = nullptr;
+    size_t cap_sml64 = 0;
+    hipEvent_t sml64_consumed_ev = nullptr; // behind its pack kernel: the last read of the contexts' models by that launch
+    bool sml64_consumed = false;           // ... and recorded: fd_batch_wait_consumed waits for it too
+    hipEvent_t sml64_eval_ev = nullptr;    // behind its last evaluation: the next pack kernel rewrites the scratch that one reads
+    bool sml64_eval_pending = false;
     hipEvent_t group_ev = nullptr;       // fd_batch_cook_group: behind the group's builds, for the evaluation stream
     // fd_batch_cook_group with the evaluation on the build stream itself (one unpipelined group): stream order does what the
     // events between build, packing and evaluation do across streams, and every event record is a barrier packet that keeps the
@@ -1591,6 +1598,9 @@ void fd_batch_destroy(fd_batch *b)
     if (b->d_sml) (void)hipFree(b->d_sml);
     if (b->sml_consumed_ev) (void)hipEventDestroy(b->sml_consumed_ev);
     if (b->sml_eval_ev) (void)hipEventDestroy(b->sml_eval_ev);
+    if (b->d_sml64) (void)hipFree(b->d_sml64);
+    if (b->sml64_consumed_ev) (void)hipEventDestroy(b->sml64_consumed_ev);
+    if (b->sml64_eval_ev) (void)hipEventDestroy(b->sml64_eval_ev);
     if (b->group_ev) (void)hipEventDestroy(b->group_ev);
     if (b->h_mismatch) (void)hipHostFree(b->h_mismatch);
     if (b->ev0) (void)hipEventDestroy(b->ev0);
@@ -2412,19 +2422,120 @@ const char *fd_shared_ml_kernel_name(int M, int layers, int frames)
     return shared_ml_kernel_name(M, layers, frames);
 }
 
+// ---- every frame of a shot of multilayer models in fp64 by one matrix-pipe launch (fd_eval_shared_ml64.hip) ----
+// where the launch applies: multilayer contexts of one model on one rest array, built here, no eval_variant, enough frames.
+// Anything else -- an unbuilt context, another rest array, mixed outputs included -- is fd_batch_deform_shared_fp64_dev's to
+// answer.
+static bool shared_ml64_fast(const fd_batch *b)
+{
+    const fd_ctx *c0 = b->ctxs[0];
+    if (c0->kind != FD_KERNEL_GAUSSIAN_ML || !shared_ml64_applies(c0->M, ml_layers(c0), b->n)) return false;
+    for (int i = 0; i < b->n; ++i) {
+        const fd_ctx *c = b->ctxs[i];
+        if (!c->built && !c->build_pending) return false;
+        if (!c->rest_src || c->rest_src != c0->rest_src || !same_model(c, c0) || c->output != c0->output) return false;
+        if (c->eval_variant > 0) return false;
+    }
+    return true;
+}
+
+int fd_batch_deform_shared_ml_fp64_dev(fd_batch *b, void *hip_stream, int64_t N, const float *d_P_in, float *const *d_P_out,
+                                       const float *d_dist2, float *const *d_falloff_out, const float *d_tu, const float *d_tv,
+                                       const float *d_nrm, float radius2, float falloffrate)
+{
+    if (!b || !d_P_out) return FD_E_INVALID;
+    const char *who = "fd_batch_deform_shared_ml_fp64_dev";
+    if (N < 0 || (N > 0 && !d_P_in)) { batch_err(b, "%s: bad N / P_in", who); return FD_E_INVALID; }
+    if (!frames_ok(d_tu, d_tv, d_nrm)) { batch_err(b, "%s: tu, tv, nrm must be all set or all NULL", who); return FD_E_INVALID; }
+    // aliasing, before any device work (as fd_batch_deform_shared_fp64_dev): one input serves every frame, so no output may be
+    // a shared input -- except the one frame of a batch of one written in place over the mesh
+    const void *ins[5] = {d_P_in, d_dist2, d_tu, d_tv, d_nrm};
+    for (int i = 0; i < b->n; ++i) {
+        if (!d_P_out[i]) { batch_err(b, "%s: NULL output array for context %d", who, i); return FD_E_INVALID; }
+        const void *outs[2] = {d_P_out[i], d_falloff_out ? d_falloff_out[i] : nullptr};
+        for (int o = 0; o < 2; ++o)
+            for (int k = 0; k < 5; ++k) {
+                if (!outs[o] || outs[o] != ins[k]) continue;
+                if (b->n == 1 && o == 0 && k == 0) continue;
+                batch_err(b, "%s: an output of context %d is a shared input array", who, i);
+                return FD_E_INVALID;
+            }
+    }
+    if (N == 0) return FD_OK;
+    if (!shared_ml64_fast(b))
+        return fd_batch_deform_shared_fp64_dev(b, hip_stream, N, d_P_in, d_P_out, d_dist2, d_falloff_out, d_tu, d_tv, d_nrm, radius2, falloffrate);
+    fd_ctx *c0 = b->ctxs[0];
+    int rc = use_device(c0);
+    if (rc) { batch_err(b, "%s", c0->err); return rc; }
+    hipStream_t stream = hip_stream ? (hipStream_t)hip_stream : cur_stream(c0);
+    if (!b->lean && (rc = batch_poll(b))) return rc;           // before the ordering: a repaired model's rebuild is ordered with the rest
+    for (int i = 0; i < b->n; ++i)
+        if ((rc = order_after_batch(b->ctxs[i], stream))) { batch_err(b, "context %d: %s", i, b->ctxs[i]->err); return rc; }
+    if (!make_event(&b->sml64_consumed_ev)) { batch_err(b, "%s: hipEventCreate failed", who); return FD_E_DEVICE; }
+    SharedMl64Args a{};
+    a.N = N; a.P_in = d_P_in; a.dist2 = d_dist2; a.tu = d_tu; a.tv = d_tv; a.nrm = d_nrm;
+    a.radius2 = radius2; a.falloffrate = falloffrate;
+    a.M = c0->M; a.layers = ml_layers(c0); a.nF = b->n;
+    bool one_build = c0->rig_build_id != 0;
+    for (int i = 1; i < b->n && one_build; ++i) one_build = b->ctxs[i]->rig_build_id == c0->rig_build_id;
+    a.check_rig = one_build ? 0 : 1;                           // (one batched build read one array: equal by construction)
+    for (int i = 0; i < b->n; ++i) { a.rec64[i] = b->ctxs[i]->d_rec64; a.model[i] = b->ctxs[i]->d_model; a.P_out[i] = d_P_out[i]; }
+    a.falloff_out = d_falloff_out;
+    a.delta_out = c0->output == FD_OUTPUT_DISPLACEMENT;
+    a.max_wgs = b->eval_cus;
+    const size_t bytes = shared_ml64_scratch_bytes(a.M, a.layers, a.nF);
+    if (bytes > b->cap_sml64) {
+        // (hipFree drains the device: no launch still reads the old scratch)
+        if (b->d_sml64) (void)hipFree(b->d_sml64);
+        b->d_sml64 = nullptr; b->cap_sml64 = 0; b->sml64_eval_pending = false;
+        if (hipMalloc(&b->d_sml64, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            batch_err(b, "%s: scratch allocation (%zu bytes) failed", who, bytes);
+            return FD_E_NOMEM;
+        }
+        b->cap_sml64 = bytes;
+    }
+    // the evaluation that last read the scratch must be through with it
+    if (b->sml64_eval_pending && hipStreamWaitEvent(stream, b->sml64_eval_ev, 0) != hipSuccess) {
+        batch_err(b, "%s: hipStreamWaitEvent failed: %s", who, hipGetErrorString(hipGetLastError()));
+        return FD_E_DEVICE;
+    }
+    b->sml64_eval_pending = false;
+    a.scratch = b->d_sml64;
+    a.packed_ev = b->sml64_consumed_ev;
+    if (b->h_mismatch && hipHostGetDevicePointer((void **)&a.mismatch, b->h_mismatch, 0) != hipSuccess) { (void)hipGetLastError(); a.mismatch = nullptr; }
+    hipError_t e = launch_deform_shared_ml64(a, stream);
+    if (e != hipSuccess) { batch_err(b, "launch_deform_shared_ml64 failed: %s", hipGetErrorString(e)); return FD_E_DEVICE; }
+    b->sml64_consumed = true;
+    if (make_event(&b->sml64_eval_ev) && hipEventRecord(b->sml64_eval_ev, stream) == hipSuccess) {
+        b->sml64_eval_pending = true;
+    } else {
+        // no event to order the next pack kernel by: be safe
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(stream);
+    }
+    return FD_OK;
+}
+
+const char *fd_shared_ml_fp64_kernel_name(int M, int layers, int frames)
+{
+    return shared_ml64_kernel_name(M, layers, frames);
+}
+
 int fd_batch_wait_consumed(fd_batch *b, void *hip_stream)
 {
     if (!b) return FD_E_INVALID;
     hipEvent_t ev = b->consumed_override ? b->consumed_override : (b->packed_valid ? b->sets[b->cur_set].packed_ev : b->fallback_ev);
     hipEvent_t ev64 = b->s64_consumed ? b->s64_consumed_ev : nullptr;       // fd_batch_deform_shared_fp64_dev's reads as well
     hipEvent_t evml = b->sml_consumed ? b->sml_consumed_ev : nullptr;       // fd_batch_deform_shared_ml_dev's
-    if (!ev && !ev64 && !evml) return FD_OK;          // no shared-rig evaluation enqueued: nothing reads the models beyond stream order
+    hipEvent_t evml64 = b->sml64_consumed ? b->sml64_consumed_ev : nullptr; // fd_batch_deform_shared_ml_fp64_dev's
+    if (!ev && !ev64 && !evml && !evml64) return FD_OK;          // no shared-rig evaluation enqueued: nothing reads the models beyond stream order
     fd_ctx *c0 = b->ctxs[0];
     int rc = use_device(c0);
     if (rc) { batch_err(b, "%s", c0->err); return rc; }
     hipStream_t stream = hip_stream ? (hipStream_t)hip_stream : cur_stream(c0);
     if ((ev && hipStreamWaitEvent(stream, ev, 0) != hipSuccess) || (ev64 && hipStreamWaitEvent(stream, ev64, 0) != hipSuccess) ||
-        (evml && hipStreamWaitEvent(stream, evml, 0) != hipSuccess)) {
+        (evml && hipStreamWaitEvent(stream, evml, 0) != hipSuccess) || (evml64 && hipStreamWaitEvent(stream, evml64, 0) != hipSuccess)) {
         batch_err(b, "fd_batch_wait_consumed: hipStreamWaitEvent failed: %s", hipGetErrorString(hipGetLastError()));
         return FD_E_DEVICE;
     }

@@ -360,6 +360,29 @@ bool shared_ml_applies(int M, int layers, int nF);      // sizes the launch take
 int shared_ml_min_frames();
 size_t shared_ml_scratch_bytes(int M, int layers, int nF);
 const char *shared_ml_kernel_name(int M, int layers, int nF);
+// Every frame of a shared-rig batch of MULTILAYER models in fp64 by one matrix-pipe launch (fd_eval_shared_ml64.hip,
+// fd_batch_deform_shared_ml_fp64_dev): a pack kernel copies what the launch needs of the models into `scratch`
+// (shared_ml64_scratch_bytes; packed_ev is recorded behind it, may be null), the evaluation reads only that copy.
+struct SharedMl64Args {
+    int64_t N;
+    const float *P_in, *dist2, *tu, *tv, *nrm;
+    float radius2, falloffrate;
+    int M, layers, nF;                    // centres, layers per centre (1..kMaxLayers), frames (shared_ml64_applies)
+    const Rec64 *rec64[kMaxBatch];        // per frame: M x layers records, centre-major (k_pack)
+    const DevModel *model[kMaxBatch];
+    float *P_out[kMaxBatch];
+    float *const *falloff_out;            // nF entries or nullptr
+    void *scratch;
+    hipEvent_t packed_ev;
+    int delta_out, max_wgs;
+    int check_rig;                        // compare every frame's records {c, s} with frame 0's; a frame that differs is passed through
+    int *mismatch;                        // as SharedDeformArgs::mismatch
+};
+hipError_t launch_deform_shared_ml64(const SharedMl64Args &a, hipStream_t stream);
+bool shared_ml64_applies(int M, int layers, int nF);    // sizes the launch takes; fewer frames than shared_ml64_min_frames: no
+int shared_ml64_min_frames();
+size_t shared_ml64_scratch_bytes(int M, int layers, int nF);
+const char *shared_ml64_kernel_name(int M, int layers, int nF);
 // island mask (fd_capture.hip): nearest mesh point per rig point + max_edges breadth-first rings
 hipError_t launch_capture_islands(const float *d_P, int64_t N, const int64_t *d_offsets, const int *d_neighbours,
                                   const float *d_rig, int M, int max_edges, unsigned char *d_mask, hipStream_t stream);

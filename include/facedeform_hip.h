@@ -500,15 +500,17 @@ const char *fd_shared_vectors_kernel_name(int M, int frames, int kind);
  *     copy alone; after fd_batch_wait_consumed the contexts may be rebuilt while the evaluation still runs.  The fp32
  *     call's two scratch sets and fd_batch_prepare_shared are not involved.
  *   Not covered: fd_batch_cook_group, fdsop_cook and fd_batch_deform_vectors_shared_dev do not take this launch, and
- *     the multilayer model runs the per-context launches.  The Jacobian and the vectors of an fp64 shot have a call of
- *     their own on top of this one: fd_batch_deform_vectors_shared_fp64_dev (below).
+ *     the multilayer model runs the per-context launches in THIS call: the one-launch fp64 form of a multilayer shot is
+ *     a call of its own, fd_batch_deform_shared_ml_fp64_dev (below).  The Jacobian and the vectors of an fp64 shot have a
+ *     call of their own on top of this one: fd_batch_deform_vectors_shared_fp64_dev (below).
  * Asynchronous on hip_stream (NULL: context 0's). */
 int fd_batch_deform_shared_fp64_dev(fd_batch *batch, void *hip_stream, int64_t N, const float *d_P_in,
                                     float *const *d_P_out, const float *d_dist2, float *const *d_falloff_out,
                                     const float *d_tu, const float *d_tv, const float *d_nrm,
                                     float radius2, float falloffrate);
 /* The kernel fd_batch_deform_shared_fp64_dev launches for M centres, `frames` contexts and a kernel kind
- * ("k_deform64_shared"), or "" where it runs the per-context launches (FD_KERNEL_GAUSSIAN_ML).  It sees no context: an
+ * ("k_deform64_shared"), or "" where it runs the per-context launches (FD_KERNEL_GAUSSIAN_ML: see
+ * fd_batch_deform_shared_ml_fp64_dev).  It sees no context: an
  * eval_variant override takes the per-context launches whatever this returns.  For tests and profiles. */
 const char *fd_shared_fp64_kernel_name(int M, int frames, int kind);
 /* The frames of a shot of MULTILAYER models (FD_KERNEL_GAUSSIAN_ML) evaluated by ONE matrix-pipe launch:
@@ -541,7 +543,7 @@ const char *fd_shared_fp64_kernel_name(int M, int frames, int kind);
  *     two scratch sets, fd_batch_prepare_shared and the fp64 scratch are not involved.
  *   Not covered: fd_batch_cook_group, fdsop_cook and the four other shared calls do not take this launch (a multilayer
  *     batch runs the per-context launches there, as before), and the Jacobian and the vectors of a multilayer shot stay
- *     with the per-context launches.
+ *     with the per-context launches.  A multilayer shot that needs fp64 has fd_batch_deform_shared_ml_fp64_dev (below).
  * Asynchronous on hip_stream (NULL: context 0's). */
 int fd_batch_deform_shared_ml_dev(fd_batch *batch, void *hip_stream, int64_t N, const float *d_P_in,
                                   float *const *d_P_out, const float *d_dist2, float *const *d_falloff_out,
@@ -552,6 +554,61 @@ int fd_batch_deform_shared_ml_dev(fd_batch *batch, void *hip_stream, int64_t N, 
  * 2..FD_MAX_BATCH, M <= 0).  It sees no context: another kind, fp64 contexts or an eval_variant override delegate whatever
  * this returns.  For tests and profiles. */
 const char *fd_shared_ml_kernel_name(int M, int layers, int frames);
+/* The frames of a shot of MULTILAYER models evaluated in FP64 by ONE matrix-pipe launch: what
+ * fd_batch_deform_shared_fp64_dev is for the one-layer kinds.  Inherited from that call: the arguments, the argument
+ * checks and their order, N == 0 answered FD_OK before any device work, gate, tangent projection, fall-off,
+ * fd_set_output handling, error codes, build-status poll and repair, stream ordering behind the batch's builds and the
+ * one-rest-rig condition (FD_E_INVALID), with
+ *   Precision: every frame is evaluated in fp64 whatever fd_set_eval_precision says on the contexts (FD_EVAL_FP32 and
+ *     FD_EVAL_FP64 contexts give the same bits); the contexts' settings are not changed by the call.
+ *   Definition: per frame, the FD_EVAL_FP64 evaluation of fd_deform_dev on the model's M x L Gaussian records (radii
+ *     R / 2^l) -- fp32 positions widened to fp64, direct differences in raw coordinates, fp64 accumulation on top of the
+ *     fp64 affine part, ONE rounding of the three sums to fp32, then the fp32 epilogue of every other launch -- with two
+ *     differences.  (1) The order of the fp64 summation: phi is formed once per (vertex, record) for all frames and
+ *     contracted with the frames' fp64 weights on v_mfma_f64_16x16x4_f64.  (2) One exponential per centre and chain, not
+ *     per record: the layers of a centre share d2 and R_l = R / 2^l, so E_0 = exp(-d2 / R_0^2) is taken with the library
+ *     exp, E_{l+1} = (E_l E_l) (E_l E_l), and AT l = 4 THE CHAIN RESTARTS with a fresh exp(-d2 / R_4^2): a chain never runs
+ *     longer than three quadruplings.
+ *   Error statement, against the per-context fp64 launches on the same batch (what fd_batch_deform_shared_fp64_dev runs
+ *     for a multilayer batch): the two fp64 sums ahead of the one rounding differ by at most (96 + M L) 2^-53 S_f, where
+ *     S_f = max_a sum_r |w_f[r][a]| (phi <= 1) -- 96 = 4^3 x 1.5 ulp covers the chain, M L the summation order -- so every
+ *     output component is within one fp32 ulp plus that bound of theirs; every fd_falloff value is bit-identical.  No
+ *     floating-point atomics: the same inputs give the same bits on every call, a vertex's result does not depend on its
+ *     place in the launch ([0, N) in one call or in two ranges: same bits), nor on fd_batch_set_eval_cus.
+ *   Where the launch applies: every context FD_KERNEL_GAUSSIAN_ML with the same M, radius, layers, lambda and term, built
+ *     on one rest array; 1..8 layers; no eval_variant override; not an imported model; any fd_set_eval_precision
+ *     setting; any M a multilayer model can be built for (the model is staged through LDS in chunks of whole centres);
+ *     1..FD_MAX_BATCH frames.  No lower threshold on the frame count: one frame already saves L - 1 or L - 2 of L
+ *     exponentials, and measured at 1M vertices and 256 centres the launch is ahead of the per-context fp64 launches from
+ *     one frame on with 4 and with 8 layers (1.1x at 1 frame, 8.8x at 32).
+ *   Everywhere else -- other kinds, eval_variant overrides, imported models, layer counts outside 1..8 -- the call IS
+ *     fd_batch_deform_shared_fp64_dev with the same arguments, bit for bit: it delegates before touching anything of
+ *     its own.
+ *   Pass-through: a gated vertex (d_dist2 > radius2), and every vertex of a frame whose model is not built
+ *     (terminationtype != 1) or whose centres differ from frame 0's (contexts of more than one build are compared on the
+ *     device; reported as by fd_batch_deform_shared_fp64_dev), is passed through -- the position bit for bit, or 0 in
+ *     FD_OUTPUT_DISPLACEMENT mode -- and its fd_falloff entry is not written.  Entries past N are not touched.
+ *   Aliasing: no output (P_out, falloff_out) may be a shared input (d_P_in, d_dist2, d_tu, d_tv, d_nrm): FD_E_INVALID,
+ *     before any device work.  With one frame P_out[0] == d_P_in is allowed, as in fd_batch_deform_shared_fp64_dev;
+ *     nothing else is.
+ *   Reads of the models: fd_batch_wait_consumed covers this launch -- a first small kernel copies the frames' fp64
+ *     weights (in matrix-operand order, layer-minor within a step of four centres), per centre {cx, cy, cz, s_0, s_4},
+ *     the affine parts, the frames' status and the output addresses into scratch of the batch that only this call uses,
+ *     and the evaluation reads that copy alone; after fd_batch_wait_consumed the contexts may be rebuilt while the
+ *     evaluation still runs.  The fp32 call's two scratch sets, fd_batch_prepare_shared, the fp64 scratch and the fp32
+ *     multilayer scratch are not involved.
+ *   Not covered: fd_batch_cook_group and fdsop_cook do not take this launch, and the Jacobian and the vectors of a
+ *     multilayer shot stay with the per-context launches (fd_batch_deform_vectors_shared_fp64_dev runs them).
+ * Asynchronous on hip_stream (NULL: context 0's). */
+int fd_batch_deform_shared_ml_fp64_dev(fd_batch *batch, void *hip_stream, int64_t N, const float *d_P_in,
+                                       float *const *d_P_out, const float *d_dist2, float *const *d_falloff_out,
+                                       const float *d_tu, const float *d_tv, const float *d_nrm,
+                                       float radius2, float falloffrate);
+/* The kernel fd_batch_deform_shared_ml_fp64_dev launches for M centres, `layers` layers and `frames` contexts
+ * ("k_deform64_shared_ml"), or "" where it is fd_batch_deform_shared_fp64_dev (layers outside 1..8, frames outside
+ * 1..FD_MAX_BATCH, M <= 0).  It sees no context: another kind, an imported model or an eval_variant override delegate
+ * whatever this returns.  For tests and profiles. */
+const char *fd_shared_ml_fp64_kernel_name(int M, int layers, int frames);
 /* fd_batch_deform_shared_fp64_dev plus, for every frame f, the Jacobian and the vectors it carries, in fp64 by ONE
  * matrix-pipe launch of its own.
  *   Positions: P_out and falloff_out are bit-identical to fd_batch_deform_shared_fp64_dev called with the same arguments:
