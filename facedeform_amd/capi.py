@@ -87,6 +87,7 @@ EXPORTS = [
     "fd_batch_deform_shared_ml_dev", "fd_shared_ml_kernel_name",
     "fd_batch_deform_shared_ml_fp64_dev", "fd_shared_ml_fp64_kernel_name",
     "fd_batch_deform_vectors_shared_fp64_dev", "fd_shared_vectors_fp64_kernel_name",
+    "fd_batch_deform_vectors_shared_ml_fp64_dev", "fd_shared_vectors_ml_fp64_kernel_name",
     "fdsop_create", "fdsop_destroy", "fdsop_set_float", "fdsop_set_int", "fdsop_set_string",
     "fdsop_get_float", "fdsop_get_int", "fdsop_parm_count", "fdsop_parm_token", "fdsop_cook",
     "fdsop_messages", "fdsop_effective_float", "fdsop_engine",
@@ -212,6 +213,9 @@ def load() -> C.CDLL:
     L.fd_batch_deform_vectors_shared_fp64_dev.argtypes = [vp, vp, i64, vp, pv, vp, pv, vp, vp, vp, C.c_float, C.c_float, C.POINTER(FdBatchVectors)]
     L.fd_batch_deform_vectors_shared_fp64_dev.restype = i32
     L.fd_shared_vectors_fp64_kernel_name.argtypes = [i32, i32, i32]; L.fd_shared_vectors_fp64_kernel_name.restype = C.c_char_p
+    L.fd_batch_deform_vectors_shared_ml_fp64_dev.argtypes = [vp, vp, i64, vp, pv, vp, pv, vp, vp, vp, C.c_float, C.c_float, C.POINTER(FdBatchVectors)]
+    L.fd_batch_deform_vectors_shared_ml_fp64_dev.restype = i32
+    L.fd_shared_vectors_ml_fp64_kernel_name.argtypes = [i32, i32, i32]; L.fd_shared_vectors_ml_fp64_kernel_name.restype = C.c_char_p
     L.fdsop_create.argtypes = [C.POINTER(FdConfig)]; L.fdsop_create.restype = vp
     L.fdsop_destroy.argtypes = [vp]; L.fdsop_destroy.restype = None
     L.fdsop_set_float.argtypes = [vp, C.c_char_p, i32, C.c_double]; L.fdsop_set_float.restype = i32
@@ -651,7 +655,7 @@ class Batch:
 
     def deform_vectors_shared_dev(self, N: int, d_P_in: int, d_P_out, d_dist2: int = 0, d_falloff=None, d_tangents=None,
                                   d_N: int = 0, d_N_out=None, d_vtu: int = 0, d_vtu_out=None, d_vtv: int = 0, d_vtv_out=None,
-                                  d_jacobian=None, radius2=1.0, falloffrate=1.0, stream_ptr: int | None = None, _fp64: bool = False):
+                                  d_jacobian=None, radius2=1.0, falloffrate=1.0, stream_ptr: int | None = None, _call: str = "fd_batch_deform_vectors_shared_dev"):
         """fd_batch_deform_vectors_shared_dev: deform_shared_dev plus, per context, the Jacobian and the vectors it carries.
         d_N / d_vtu / d_vtv are ONE device array each (the shared mesh's); d_N_out / d_vtu_out / d_vtv_out / d_jacobian
         are lists of one output pointer per context (or None)."""
@@ -671,7 +675,7 @@ class Batch:
         tu, tv, nr = d_tangents if d_tangents is not None else (0, 0, 0)
         vec = FdBatchVectors(C.sizeof(FdBatchVectors), vp(d_N or None), tab(d_N_out), vp(d_vtu or None), tab(d_vtu_out),
                              vp(d_vtv or None), tab(d_vtv_out), tab(d_jacobian))
-        call = self.L.fd_batch_deform_vectors_shared_fp64_dev if _fp64 else self.L.fd_batch_deform_vectors_shared_dev
+        call = getattr(self.L, _call)
         self._check(call(self.h, vp(stream_ptr or 0), N, vp(d_P_in), outs, vp(d_dist2 or None), falls, vp(tu or None), vp(tv or None),
                          vp(nr or None), float(radius2), float(falloffrate), C.byref(vec)))
 
@@ -679,7 +683,13 @@ class Batch:
         """fd_batch_deform_vectors_shared_fp64_dev: deform_vectors_shared_dev's arguments (same keywords), positions and
         vectors of every frame in fp64 whatever the contexts' precision setting says -- one launch for the positions, one
         for the vectors."""
-        self.deform_vectors_shared_dev(N, d_P_in, d_P_out, _fp64=True, **kw)
+        self.deform_vectors_shared_dev(N, d_P_in, d_P_out, _call="fd_batch_deform_vectors_shared_fp64_dev", **kw)
+
+    def deform_vectors_shared_ml_fp64_dev(self, N: int, d_P_in: int, d_P_out, **kw):
+        """fd_batch_deform_vectors_shared_ml_fp64_dev: deform_vectors_shared_fp64_dev's arguments (same keywords); a shot of
+        multilayer models gets its positions and its vectors in fp64 by one launch each, anything else exactly what
+        deform_vectors_shared_fp64_dev does."""
+        self.deform_vectors_shared_dev(N, d_P_in, d_P_out, _call="fd_batch_deform_vectors_shared_ml_fp64_dev", **kw)
 
     def prepare_shared(self, d_P_out, d_falloff=None, stream_ptr=None):
         """fd_batch_prepare_shared: pack the current models for a shared-rig evaluation into the batch's scratch on
@@ -866,6 +876,12 @@ def fd_shared_vectors_kernel_name(M: int, frames: int, kind: int) -> str:
 def fd_shared_vectors_fp64_kernel_name(M: int, frames: int, kind: int) -> str:
     """The kernel fd_batch_deform_vectors_shared_fp64_dev's vector launch takes ("" where it runs the per-context launches)."""
     return load().fd_shared_vectors_fp64_kernel_name(int(M), int(frames), int(kind)).decode()
+
+
+def fd_shared_vectors_ml_fp64_kernel_name(M: int, layers: int, frames: int) -> str:
+    """The kernel fd_batch_deform_vectors_shared_ml_fp64_dev's vector launch takes ("" where it runs the per-context launches
+    or is fd_batch_deform_vectors_shared_fp64_dev)."""
+    return load().fd_shared_vectors_ml_fp64_kernel_name(int(M), int(layers), int(frames)).decode()
 
 
 def fd_shared_ml_kernel_name(M: int, layers: int, frames: int) -> str:

@@ -42,6 +42,7 @@
 
 #include "fd_eval_common.h"
 #include "fd_shared64.h"
+#include "fd_shared_ml64.h"
 
 #pragma push_macro("hipLaunchKernelGGL")
 #undef hipLaunchKernelGGL
@@ -66,13 +67,7 @@ constexpr int kMl64VT = 2;                                // vertex tiles per wa
 constexpr int kMl64Group = 16 * kMl64VT * kS64Waves;      // vertices per workgroup and group
 constexpr int kMl64PackThreads = 256;
 constexpr int kMl64MinFrames = 1;                         // fewer frames: fd_batch_deform_shared_fp64_dev
-constexpr int kMl64Restart = 4;                           // layers per chain: three quadruplings at most
-constexpr int kMl64Cen = 6;                               // doubles per centre record {cx, cy, cz, s_0, s_4, 0}
-
-// scratch, in doubles behind the head (S64Head): [affine tiles NT x 64][centre records Mc4 x 6][weights nkc x L x NT x 64]
-__host__ __device__ inline size_t ml64_cen_at(int NT) { return s64_aff_at() + (size_t)NT * 64; }
-__host__ __device__ inline size_t ml64_w_at(int NT, int Mc4) { return ml64_cen_at(NT) + (size_t)Mc4 * kMl64Cen; }
-__host__ __device__ inline size_t ml64_step_w(int NT, int L) { return (size_t)L * NT * 64; }        // weights of one centre step
+// (the scratch layout -- kMl64Cen, kMl64Restart, ml64_cen_at, ml64_w_at, ml64_step_w -- is fd_shared_ml64.h's: the vector launch reads it too)
 
 struct Ml64PackArgs {
     const Rec64 *rec[kMaxBatch];          // per frame: M x L records, centre-major (k_pack)

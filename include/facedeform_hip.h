@@ -597,8 +597,9 @@ const char *fd_shared_ml_kernel_name(int M, int layers, int frames);
  *     and the evaluation reads that copy alone; after fd_batch_wait_consumed the contexts may be rebuilt while the
  *     evaluation still runs.  The fp32 call's two scratch sets, fd_batch_prepare_shared, the fp64 scratch and the fp32
  *     multilayer scratch are not involved.
- *   Not covered: fd_batch_cook_group and fdsop_cook do not take this launch, and the Jacobian and the vectors of a
- *     multilayer shot stay with the per-context launches (fd_batch_deform_vectors_shared_fp64_dev runs them).
+ *   Not covered: fd_batch_cook_group and fdsop_cook do not take this launch; the Jacobian and the vectors of a
+ *     multilayer shot in fp64 are a call of their own on top of this one: fd_batch_deform_vectors_shared_ml_fp64_dev
+ *     (below).
  * Asynchronous on hip_stream (NULL: context 0's). */
 int fd_batch_deform_shared_ml_fp64_dev(fd_batch *batch, void *hip_stream, int64_t N, const float *d_P_in,
                                        float *const *d_P_out, const float *d_dist2, float *const *d_falloff_out,
@@ -657,6 +658,77 @@ int fd_batch_deform_vectors_shared_fp64_dev(fd_batch *batch, void *hip_stream, i
  * Gaussian kinds and cubic).  It sees no context: an eval_variant override takes the per-context launches whatever this returns.  For
  * tests and profiles. */
 const char *fd_shared_vectors_fp64_kernel_name(int M, int frames, int kind);
+/* fd_batch_deform_shared_ml_fp64_dev plus, for every frame f, the Jacobian and the vectors it carries, in fp64 by ONE
+ * matrix-pipe launch of its own: to fd_batch_deform_shared_ml_fp64_dev what fd_batch_deform_vectors_shared_fp64_dev is to
+ * fd_batch_deform_shared_fp64_dev.
+ *   Positions: P_out and falloff_out are bit-identical to fd_batch_deform_shared_ml_fp64_dev called with the same arguments:
+ *     that call runs unchanged first (its pack kernel, its position launch, its mismatch report), then one launch of its
+ *     own writes the vector outputs.  vec == NULL, or every pointer in it NULL,
+ *     is exactly fd_batch_deform_shared_ml_fp64_dev.  Inherited from it: precision (fp64 whatever the contexts say, their
+ *     settings untouched), error codes, build-status poll and repair, ordering behind the batch's builds, the
+ *     one-rest-rig condition and fd_set_output handling.
+ *   Vectors: fd_deform_vectors' definition, per frame, in fp64, on the model's M x L Gaussian records (radii R / 2^l):
+ *     A_f = I + f Pi J_f with J_f = sum_c sum_l w_f[c][l] (x) 2 s_l E_l(x) (x - c) + L_f, s_l = -1 / R_l^2, from fp32
+ *     positions widened to fp64 and direct differences in raw coordinates; t' = A_f t (not renormalised),
+ *     n' = cof(A_f) n rescaled to |n|; A is stored as fp32.  Two differences from the per-context fp64 launch
+ *     (k_vectors64_gaussian on the M L records).  (1) The order and association of the fp64 sum: the basis
+ *     2 s_l E_l (x - c) is formed once per (vertex, record) for all frames and contracted with the frames' fp64 weights on
+ *     v_mfma_f64_16x16x4_f64, L_f first.  (2) One exponential per centre and chain, exactly the position launch's chain:
+ *     E_0 = exp(d2 s_0) with the library exp, E_{l+1} = (E_l E_l) (E_l E_l), s_{l+1} = 4 s_l (exact: the build forms R_l
+ *     with ldexp), and AT l = 4 THE CHAIN RESTARTS with a fresh exp(d2 s_4): a chain never runs longer than three
+ *     quadruplings, and the restart is part of the definition.  At l = 0 and l = 4 the factor E_l s_l is the per-context
+ *     launch's, bit for bit.
+ *   Error statement.  With S'_f(x) = sum_r ||w_f[r]|| |grad phi_r(x)| + ||L_f|| over the M L records: against the
+ *     per-context fp64 launches on the same batch (fd_batch_deform_vectors_shared_fp64_dev) the two fp64 values of J_f
+ *     ahead of the rounding differ in Frobenius norm by at most (104 + 2 M L) 2^-53 S'_f(x) -- 96 = 4^3 x 1.5 ulp covers
+ *     the chain, as in the position call's statement, 8 the products' associations on both sides, M L per side the
+ *     summation order -- so ||A - A_ctx||_F <= 2^-23 ||A_ctx||_F + (104 + 2 M L) 2^-53 f S'_f; for M L <= 2048 the
+ *     second term is at most 4.7e-13 f S'_f, inside the 1e-12 f S'_f of the project's fp64 bar against an independent
+ *     restatement, ||A - A_ref||_F <= 2^-22 ||A_ref||_F + 1e-12 f S'_f, which this launch is held to as well.  A chain value
+ *     in the subnormal range loses the relative bound; its absolute contribution to J_f is below 2^-1000 |s| ||w||.
+ *   Pass-through: every vector output is the input bit for bit, and A = I exactly, for gated vertices
+ *     (d_dist2 > radius2), where f = 0, and for frames whose model is not built or whose centres differ from frame 0's
+ *     (built = 0 in the scratch head, as the position call's pack kernel decided).  Entries past N are not touched.
+ *   Aliasing: no output (P_out, falloff_out, the tables of vec) may equal any shared input (d_P_in, d_dist2, d_tu, d_tv,
+ *     d_nrm, vec->N / tu / tv): FD_E_INVALID, before any device work.  This holds for a batch of one as well -- the
+ *     position call's in-place exception does not apply, because the vector launch reads d_P_in after the position
+ *     launch has written.
+ *   Tables: as in fd_batch_deform_vectors_shared_fp64_dev -- vec->struct_size at least sizeof(fd_batch_vectors), every
+ *     input with its output table (both or neither), a table has n non-NULL entries; otherwise FD_E_INVALID, before any
+ *     device work, the checks in that call's order.  N == 0 is FD_OK before any device work.
+ *   Where the launch applies: where fd_batch_deform_shared_ml_fp64_dev's own launch does (multilayer contexts of one
+ *     model built on one rest array, 1..8 layers, no eval_variant override, not an imported model, any M) and the frame
+ *     count is at or above the measured threshold: 3 frames with one layer, 2 frames with 2 to 8 layers.  Measured at 1M
+ *     vertices and 256 centres with the launch taken at every frame count (device events, the position-only call
+ *     subtracted), vectors alone, launch against per-context launches: with 4 layers 2.33 / 1.31 ms at
+ *     1 frame (0.56x), 2.34 / 2.62 ms at 2 (1.12x), 2.35 / 3.94 ms at 3, 5.40 / 15.8 ms at 12, 10.4 / 41.8 ms
+ *     at 32 (4.0x); with 8 layers 4.52 / 2.61 ms at 1 (0.58x), 4.54 / 5.21 ms at 2 (1.15x), 4.54 / 7.81 ms
+ *     at 3, 10.2 / 31.3 ms at 12, 19.3 / 82.9 ms at 32 (4.3x).  At 2 frames the ratio is 0.76x with one layer and
+ *     1.02x, 1.03x, 1.02x, 1.09x, 1.11x with 2, 3, 5, 6, 7; at 1 frame it is below one with every layer count.
+ *     A multilayer batch below the threshold keeps the positions of fd_batch_deform_shared_ml_fp64_dev and gets its
+ *     vectors from the per-context launches: per context and bit for bit what fd_deform_vectors_dev writes for an
+ *     FD_EVAL_FP64 context on the shared arrays (the batch's consumed event is re-recorded behind them: they read the
+ *     models to their end).
+ *   Everywhere else -- other kinds, eval_variant overrides, imported models, layer counts outside 1..8 -- the call
+ *     IS fd_batch_deform_vectors_shared_fp64_dev with the same arguments, bit for bit: it delegates before touching
+ *     anything of its own.
+ *   Reads of the models: the vector launch reads only the batch's multilayer-fp64 scratch (as the position call packed
+ *     it), the mesh, the vectors and its own arguments: fd_batch_wait_consumed covers it, and the contexts may be
+ *     rebuilt while it runs; the next call's pack kernel waits for it before it rewrites that scratch.
+ *   Bits: no floating-point atomics; the same inputs give the same bits on every call, a vertex's result does not
+ *     depend on its place in the launch ([0, N) in one call or in two ranges: same bits), nor on fd_batch_set_eval_cus.
+ * fd_batch_deform_vectors_shared_fp64_dev, fd_batch_deform_vectors_shared_dev, fd_batch_cook_group and fdsop_cook are unchanged.
+ * Asynchronous on hip_stream (NULL: context 0's). */
+int fd_batch_deform_vectors_shared_ml_fp64_dev(fd_batch *batch, void *hip_stream, int64_t N, const float *d_P_in,
+                                               float *const *d_P_out, const float *d_dist2, float *const *d_falloff_out,
+                                               const float *d_tu, const float *d_tv, const float *d_nrm,
+                                               float radius2, float falloffrate, const fd_batch_vectors *vec);
+/* The kernel the vector launch of fd_batch_deform_vectors_shared_ml_fp64_dev takes for M centres, `layers` layers and
+ * `frames` contexts ("k_vectors64_shared_ml"), or "" where the call runs the per-context launches or is
+ * fd_batch_deform_vectors_shared_fp64_dev (M <= 0, layers outside 1..8, frames outside 1..FD_MAX_BATCH, frames below
+ * the threshold above).  It sees no context: another kind, an imported model or an eval_variant override delegate
+ * whatever this returns.  For tests and profiles. */
+const char *fd_shared_vectors_ml_fp64_kernel_name(int M, int layers, int frames);
 /* Makes hip_stream (NULL: context 0's) wait until the batch's last fd_batch_deform_shared_dev no longer reads the
  * contexts' models: that launch copies what it needs of them (weights as fp16 tiles, the rest rig's centre tiles)
  * into the batch's own scratch with a first small kernel, and the evaluation proper reads only that copy.  A pipeline
