@@ -10,8 +10,14 @@
 // Triangles are staged through LDS in chunks as 16-float records (first vertex, two edges, their
 // three dot products, bounding sphere), so a point-triangle test is two dot products plus the
 // Voronoi-region selection (Ericson 5.1.5) in fp32 on differences from the triangle's first
-// vertex -- the error of d2 stays at a few ulps of the squared lengths involved.  A triangle
-// whose bounding sphere cannot beat the wave's current best is skipped by the whole wave.
+// vertex.  That walk divides fully cancelled numbers when the two edges are nearly parallel, so
+// make_record classifies every triangle once: one whose sin^2 of the angle at its first vertex is
+// below kIllSin2, or whose two edges there differ in length by more than 1e4 (slivers, needles,
+// collinear and degenerate triangles), keeps its three vertices in the record instead and is
+// walked in fp64 with the plane's normal for the face -- a decision per triangle, so a wave never
+// diverges over it.  |d2 - exact| <= 2e-6 (d2 + E^2), E the triangle's longest edge, for every
+// triangle.  A triangle whose bounding sphere cannot beat the wave's current best
+// is skipped by the whole wave.
 #include "fd_internal.h"
 
 namespace fd {
@@ -21,6 +27,12 @@ namespace {
 constexpr int kCapBlock = 256;
 constexpr int kTriChunk = 1024;       // 64 KiB of LDS
 constexpr int kTriRec = 16;           // floats per staged triangle
+// sin^2 of the angle at the first vertex below which a triangle takes the fp64 walk (the
+// fp32 walk's measured error per decade of sin)
+constexpr float kIllSin2 = 1e-3f;
+// ... and so does one whose edges at the first vertex differ in length by more than 1e4: the shorter one's
+// squared length is absorbed when it is subtracted from the dot products
+constexpr float kIllEdge2 = 1e-8f;
 
 __device__ __forceinline__ float dot3(const float u[3], const float v[3])
 {
@@ -28,15 +40,26 @@ __device__ __forceinline__ float dot3(const float u[3], const float v[3])
 }
 
 // record: a[3], ab[3], ac[3], ab.ab, ab.ac, ac.ac, sphere centre (as offset from a)[3], sphere radius
+// ill-conditioned triangle: a[3], b[3], c[3], -, -, -1 (ac.ac is never negative: the class mark), the same sphere
 __device__ __forceinline__ void make_record(const float *t, float *r)
 {
     const float a[3] = {t[0], t[1], t[2]};
     const float ab[3] = {t[3] - a[0], t[4] - a[1], t[5] - a[2]};
     const float ac[3] = {t[6] - a[0], t[7] - a[1], t[8] - a[2]};
+    const float n[3] = {ab[1] * ac[2] - ab[2] * ac[1], ab[2] * ac[0] - ab[0] * ac[2], ab[0] * ac[1] - ab[1] * ac[0]};
+    const float bb = dot3(ab, ab), cc = dot3(ac, ac);
+    // a zero edge, an underflow or a NaN: ill as well
+    const bool ill = !(dot3(n, n) > kIllSin2 * (bb * cc)) || !(fminf(bb, cc) > kIllEdge2 * fmaxf(bb, cc));
     r[0] = a[0]; r[1] = a[1]; r[2] = a[2];
-    r[3] = ab[0]; r[4] = ab[1]; r[5] = ab[2];
-    r[6] = ac[0]; r[7] = ac[1]; r[8] = ac[2];
-    r[9] = dot3(ab, ab); r[10] = dot3(ab, ac); r[11] = dot3(ac, ac);
+    if (ill) {
+        r[3] = t[3]; r[4] = t[4]; r[5] = t[5];
+        r[6] = t[6]; r[7] = t[7]; r[8] = t[8];
+        r[9] = 0.f; r[10] = 0.f; r[11] = -1.f;
+    } else {
+        r[3] = ab[0]; r[4] = ab[1]; r[5] = ab[2];
+        r[6] = ac[0]; r[7] = ac[1]; r[8] = ac[2];
+        r[9] = bb; r[10] = dot3(ab, ac); r[11] = cc;
+    }
     const float g[3] = {(ab[0] + ac[0]) * (1.f / 3.f), (ab[1] + ac[1]) * (1.f / 3.f), (ab[2] + ac[2]) * (1.f / 3.f)};
     const float ga[3] = {g[0], g[1], g[2]};
     const float gb[3] = {g[0] - ab[0], g[1] - ab[1], g[2] - ab[2]};
@@ -72,6 +95,55 @@ __device__ __forceinline__ float tri_dist2(const float ap[3], const float *r)
     return dot3(q, q);
 }
 
+__device__ __forceinline__ double dot3d(const double u[3], const double v[3])
+{
+    return u[0] * v[0] + u[1] * v[1] + u[2] * v[2];
+}
+
+// squared distance from p to the segment o + [0, 1] e, w = p - o
+__device__ __forceinline__ double seg_dist2d(const double w[3], const double e[3])
+{
+    const double ee = dot3d(e, e);
+    double s = 0.0;
+    if (ee > 0.0) s = fmin(fmax(dot3d(w, e) / ee, 0.0), 1.0);
+    const double q[3] = {w[0] - s * e[0], w[1] - s * e[1], w[2] - s * e[2]};
+    return dot3d(q, q);
+}
+
+// the same walk for an ill-conditioned triangle, in fp64 from its three vertices.  A zero-length edge has no
+// region of its own (its test would divide 0 by 0): the walk goes on to the remaining edge or vertex.  The
+// face is the distance to the plane, from the normal: its components are single differences of exact products
+// of fp32 differences, where the barycentric coordinates of the fp32 walk are quotients of cancelled numbers.
+__device__ __noinline__ float tri_dist2_ill(float px, float py, float pz, const float *r)
+{
+    const float p[3] = {px, py, pz};
+    double ab[3], ac[3], bc[3], ap[3], bp[3], cp[3];
+    for (int k = 0; k < 3; ++k) {
+        const double a = r[k], b = r[3 + k], c = r[6 + k], x = p[k];
+        ab[k] = b - a; ac[k] = c - a; bc[k] = c - b;
+        ap[k] = x - a; bp[k] = x - b; cp[k] = x - c;
+    }
+    const double d1 = dot3d(ab, ap), d2 = dot3d(ac, ap);
+    const double d3 = dot3d(ab, bp), d4 = dot3d(ac, bp);
+    const double d5 = dot3d(ab, cp), d6 = dot3d(ac, cp);
+    const double vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
+    double d;
+    if (d1 <= 0.0 && d2 <= 0.0) d = dot3d(ap, ap);                                                  // vertex A
+    else if (d3 >= 0.0 && d4 <= d3) d = dot3d(bp, bp);                                              // vertex B
+    else if (vc <= 0.0 && d1 >= 0.0 && d3 <= 0.0 && d1 - d3 > 0.0) d = seg_dist2d(ap, ab);          // edge AB
+    else if (d6 >= 0.0 && d5 <= d6) d = dot3d(cp, cp);                                              // vertex C
+    else if (vb <= 0.0 && d2 >= 0.0 && d6 <= 0.0 && d2 - d6 > 0.0) d = seg_dist2d(ap, ac);          // edge AC
+    else if (va <= 0.0 && (d4 - d3) >= 0.0 && (d5 - d6) >= 0.0 && (d4 - d3) + (d5 - d6) > 0.0)
+        d = seg_dist2d(bp, bc);                                                                     // edge BC
+    else {
+        const double n[3] = {ab[1] * ac[2] - ab[2] * ac[1], ab[2] * ac[0] - ab[0] * ac[2], ab[0] * ac[1] - ab[1] * ac[0]};
+        const double nn = dot3d(n, n);
+        if (nn > 0.0) { const double h = dot3d(ap, n); d = h * h / nn; }                            // face
+        else d = fmin(seg_dist2d(ap, ab), fmin(seg_dist2d(ap, ac), seg_dist2d(bp, bc)));            // three points on a line
+    }
+    return (float)d;
+}
+
 __global__ __launch_bounds__(kCapBlock) void k_capture_dist2(const float *P, int64_t N, const unsigned char *mask,
                                                               const float *tri, int T, float radius2, int dofalloff,
                                                               float *dist2)
@@ -102,7 +174,9 @@ __global__ __launch_bounds__(kCapBlock) void k_capture_dist2(const float *P, int
                 const float reach = sb + r[15];
                 const bool need = search && dot3(gp, gp) < reach * reach;
                 if (__any(need)) {
-                    const float d = tri_dist2(ap, r);
+                    // the class is the triangle's, the same in every lane: a scalar branch
+                    const bool ill = __builtin_amdgcn_readfirstlane(__float_as_int(r[11])) < 0;
+                    const float d = ill ? tri_dist2_ill(p[0], p[1], p[2], r) : tri_dist2(ap, r);
                     if (need && d < best) { best = d; sb = sqrtf(d); }
                 }
             }

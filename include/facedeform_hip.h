@@ -809,7 +809,13 @@ int fd_batch_cook_group(fd_batch *batch, void *build_stream, void *eval_stream, 
  * GU_RayIntersect::minimumPoint returns there -- when it is below radius2, else
  * -1 (:76-88); 0 when dofalloff is off (:71-75) and for points outside every
  * island (the detached attribute's default, :31).  The rig surface is T
- * triangles, 9 floats each (a, b, c).  The result is fd_deform's dist2 input;
+ * triangles, 9 floats each (a, b, c); degenerate ones (a point, a segment, three
+ * points on a line) count as the point sets they are.  Error bound, for every
+ * triangle shape and independent of where the scene lies relative to the origin:
+ * |dist2 - exact| <= 2e-6 * (exact + E^2), E the longest edge among the T
+ * triangles, for points within 10 E of the surface (the range that is tested); a
+ * point whose exact distance is within that margin of radius2 may fall on either
+ * side of the -1 decision.  The result is fd_deform's dist2 input;
  * with the _dev form it never leaves the device.  Island finding (nearest mesh
  * point of every rig point + edge rings, :101-141) needs the mesh topology and
  * stays with the caller. */

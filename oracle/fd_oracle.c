@@ -604,7 +604,9 @@ static double tri_dist2(const double p[3], const float *t)
     const double d3 = DOT(ab, bp), d4 = DOT(ac, bp);
     if (d3 >= 0.0 && d4 <= d3) { for (int k = 0; k < 3; ++k) q[k] = b[k]; goto done; }            /* vertex B */
     const double vc = d1 * d4 - d3 * d2;
-    if (vc <= 0.0 && d1 >= 0.0 && d3 <= 0.0) {                                                     /* edge AB */
+    /* a zero-length edge has no region of its own: its two (equal) vertex tests stand for it, and the
+     * walk goes on to the remaining edge or vertex -- never to 0 / 0 (which dropped the triangle) */
+    if (vc <= 0.0 && d1 >= 0.0 && d3 <= 0.0 && d1 - d3 > 0.0) {                                    /* edge AB */
         const double v = d1 / (d1 - d3);
         for (int k = 0; k < 3; ++k) q[k] = a[k] + v * ab[k];
         goto done;
@@ -613,22 +615,38 @@ static double tri_dist2(const double p[3], const float *t)
     const double d5 = DOT(ab, cp), d6 = DOT(ac, cp);
     if (d6 >= 0.0 && d5 <= d6) { for (int k = 0; k < 3; ++k) q[k] = c[k]; goto done; }            /* vertex C */
     const double vb = d5 * d2 - d1 * d6;
-    if (vb <= 0.0 && d2 >= 0.0 && d6 <= 0.0) {                                                     /* edge AC */
+    if (vb <= 0.0 && d2 >= 0.0 && d6 <= 0.0 && d2 - d6 > 0.0) {                                    /* edge AC */
         const double w = d2 / (d2 - d6);
         for (int k = 0; k < 3; ++k) q[k] = a[k] + w * ac[k];
         goto done;
     }
     const double va = d3 * d6 - d5 * d4;
-    if (va <= 0.0 && (d4 - d3) >= 0.0 && (d5 - d6) >= 0.0) {                                       /* edge BC */
+    if (va <= 0.0 && (d4 - d3) >= 0.0 && (d5 - d6) >= 0.0 && (d4 - d3) + (d5 - d6) > 0.0) {        /* edge BC */
         const double w = (d4 - d3) / ((d4 - d3) + (d5 - d6));
         for (int k = 0; k < 3; ++k) q[k] = b[k] + w * (c[k] - b[k]);
         goto done;
     }
     {
-        const double den = va + vb + vc;
-        if (den == 0.0) { for (int k = 0; k < 3; ++k) q[k] = a[k]; goto done; }                    /* degenerate */
-        const double v = vb / den, w = vc / den;                                                   /* face */
-        for (int k = 0; k < 3; ++k) q[k] = a[k] + ab[k] * v + ac[k] * w;
+        /* face: the distance to the plane, from the normal.  (Rebuilding the closest point from the barycentric
+         * coordinates vb / den, vc / den divides two fully cancelled numbers when ab is nearly parallel to ac:
+         * on a sliver of height 1e-7 of its base that misplaces the point by a hundredth of the base even in
+         * fp64.  The normal's components are single differences of exact products of fp32 differences.) */
+        const double n[3] = {ab[1] * ac[2] - ab[2] * ac[1], ab[2] * ac[0] - ab[0] * ac[2], ab[0] * ac[1] - ab[1] * ac[0]};
+        const double nn = DOT(n, n);
+        if (nn > 0.0) { const double h = DOT(ap, n); return h * h / nn; }
+        /* all three vertices on one line and yet no vertex or edge region taken: not reachable in exact
+         * arithmetic; answer with the nearest of the three segments */
+        double best = INFINITY;
+        const double *e[3][2] = {{a, b}, {b, c}, {c, a}};
+        for (int s = 0; s < 3; ++s) {
+            double d[3], w[3], r[3], t = 0.0;
+            for (int k = 0; k < 3; ++k) { d[k] = e[s][1][k] - e[s][0][k]; w[k] = p[k] - e[s][0][k]; }
+            const double dd = DOT(d, d);
+            if (dd > 0.0) { t = DOT(w, d) / dd; t = t < 0.0 ? 0.0 : (t > 1.0 ? 1.0 : t); }
+            for (int k = 0; k < 3; ++k) r[k] = w[k] - t * d[k];
+            if (DOT(r, r) < best) best = DOT(r, r);
+        }
+        return best;
     }
 done:
     {
