@@ -88,6 +88,7 @@ EXPORTS = [
     "fd_batch_deform_shared_ml_fp64_dev", "fd_shared_ml_fp64_kernel_name",
     "fd_batch_deform_vectors_shared_fp64_dev", "fd_shared_vectors_fp64_kernel_name",
     "fd_batch_deform_vectors_shared_ml_fp64_dev", "fd_shared_vectors_ml_fp64_kernel_name",
+    "fd_batch_deform_vectors_shared_ml_dev", "fd_shared_vectors_ml_kernel_name",
     "fdsop_create", "fdsop_destroy", "fdsop_set_float", "fdsop_set_int", "fdsop_set_string",
     "fdsop_get_float", "fdsop_get_int", "fdsop_parm_count", "fdsop_parm_token", "fdsop_cook",
     "fdsop_messages", "fdsop_effective_float", "fdsop_engine",
@@ -216,6 +217,9 @@ def load() -> C.CDLL:
     L.fd_batch_deform_vectors_shared_ml_fp64_dev.argtypes = [vp, vp, i64, vp, pv, vp, pv, vp, vp, vp, C.c_float, C.c_float, C.POINTER(FdBatchVectors)]
     L.fd_batch_deform_vectors_shared_ml_fp64_dev.restype = i32
     L.fd_shared_vectors_ml_fp64_kernel_name.argtypes = [i32, i32, i32]; L.fd_shared_vectors_ml_fp64_kernel_name.restype = C.c_char_p
+    L.fd_batch_deform_vectors_shared_ml_dev.argtypes = [vp, vp, i64, vp, pv, vp, pv, vp, vp, vp, C.c_float, C.c_float, C.POINTER(FdBatchVectors)]
+    L.fd_batch_deform_vectors_shared_ml_dev.restype = i32
+    L.fd_shared_vectors_ml_kernel_name.argtypes = [i32, i32, i32]; L.fd_shared_vectors_ml_kernel_name.restype = C.c_char_p
     L.fdsop_create.argtypes = [C.POINTER(FdConfig)]; L.fdsop_create.restype = vp
     L.fdsop_destroy.argtypes = [vp]; L.fdsop_destroy.restype = None
     L.fdsop_set_float.argtypes = [vp, C.c_char_p, i32, C.c_double]; L.fdsop_set_float.restype = i32
@@ -691,6 +695,12 @@ class Batch:
         deform_vectors_shared_fp64_dev does."""
         self.deform_vectors_shared_dev(N, d_P_in, d_P_out, _call="fd_batch_deform_vectors_shared_ml_fp64_dev", **kw)
 
+    def deform_vectors_shared_ml_dev(self, N: int, d_P_in: int, d_P_out, **kw):
+        """fd_batch_deform_vectors_shared_ml_dev: deform_vectors_shared_dev's arguments (same keywords); a shot of multilayer
+        models gets its positions and its vectors in fp32 by one launch each, anything else exactly what
+        deform_vectors_shared_dev does."""
+        self.deform_vectors_shared_dev(N, d_P_in, d_P_out, _call="fd_batch_deform_vectors_shared_ml_dev", **kw)
+
     def prepare_shared(self, d_P_out, d_falloff=None, stream_ptr=None):
         """fd_batch_prepare_shared: pack the current models for a shared-rig evaluation into the batch's scratch on
         `stream_ptr` (typically the build stream); deform_shared_dev with the same outputs then only evaluates."""
@@ -882,6 +892,12 @@ def fd_shared_vectors_ml_fp64_kernel_name(M: int, layers: int, frames: int) -> s
     """The kernel fd_batch_deform_vectors_shared_ml_fp64_dev's vector launch takes ("" where it runs the per-context launches
     or is fd_batch_deform_vectors_shared_fp64_dev)."""
     return load().fd_shared_vectors_ml_fp64_kernel_name(int(M), int(layers), int(frames)).decode()
+
+
+def fd_shared_vectors_ml_kernel_name(M: int, layers: int, frames: int) -> str:
+    """The kernel fd_batch_deform_vectors_shared_ml_dev's vector launch takes ("" where it runs the per-context launches or
+    is fd_batch_deform_vectors_shared_dev)."""
+    return load().fd_shared_vectors_ml_kernel_name(int(M), int(layers), int(frames)).decode()
 
 
 def fd_shared_ml_kernel_name(M: int, layers: int, frames: int) -> str:

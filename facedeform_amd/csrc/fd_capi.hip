@@ -2422,6 +2422,93 @@ const char *fd_shared_ml_kernel_name(int M, int layers, int frames)
     return shared_ml_kernel_name(M, layers, frames);
 }
 
+// fd_batch_deform_vectors_shared_ml_dev: the position call above, unchanged, then the vector launch
+// (fd_vectors_shared_ml.hip) on the scratch its pack kernel wrote; a multilayer batch of too few frames gets launch_vectors
+// per context in fp32; anything else is fd_batch_deform_vectors_shared_dev's
+int fd_batch_deform_vectors_shared_ml_dev(fd_batch *b, void *hip_stream, int64_t N, const float *d_P_in, float *const *d_P_out,
+                                          const float *d_dist2, float *const *d_falloff_out, const float *d_tu, const float *d_tv,
+                                          const float *d_nrm, float radius2, float falloffrate, const fd_batch_vectors *vec)
+{
+    if (!b || !d_P_out) return FD_E_INVALID;
+    const char *who = "fd_batch_deform_vectors_shared_ml_dev";
+    if (vec && vec->struct_size < (int)sizeof(fd_batch_vectors)) {
+        batch_err(b, "%s: vec->struct_size is %d, must be sizeof(fd_batch_vectors) = %d", who, vec->struct_size, (int)sizeof(fd_batch_vectors));
+        return FD_E_INVALID;
+    }
+    const bool want = vec && (vec->N || vec->N_out || vec->tu || vec->tu_out || vec->tv || vec->tv_out || vec->jacobian);
+    if (!want)
+        return fd_batch_deform_shared_ml_dev(b, hip_stream, N, d_P_in, d_P_out, d_dist2, d_falloff_out, d_tu, d_tv, d_nrm, radius2, falloffrate);
+    if ((!vec->N != !vec->N_out) || (!vec->tu != !vec->tu_out) || (!vec->tv != !vec->tv_out)) {
+        batch_err(b, "%s: every vector needs its input and its output table (both or neither)", who);
+        return FD_E_INVALID;
+    }
+    if (N < 0 || (N > 0 && !d_P_in)) { batch_err(b, "%s: bad N / P_in", who); return FD_E_INVALID; }
+    if (!frames_ok(d_tu, d_tv, d_nrm)) { batch_err(b, "%s: tu, tv, nrm must be all set or all NULL", who); return FD_E_INVALID; }
+    // tables of n non-NULL entries, none of which is a shared input -- a batch of one included: the vector launch reads d_P_in
+    // after the position launch has written
+    const void *ins[8] = {d_P_in, d_dist2, d_tu, d_tv, d_nrm, vec->N, vec->tu, vec->tv};
+    float *const *tabs[6] = {d_P_out, d_falloff_out, vec->N_out, vec->tu_out, vec->tv_out, vec->jacobian};
+    for (int t = 0; t < 6; ++t) {
+        if (!tabs[t]) continue;
+        for (int i = 0; i < b->n; ++i) {
+            const void *o = tabs[t][i];
+            if (!o) { batch_err(b, "%s: output table %d has a NULL entry for context %d", who, t, i); return FD_E_INVALID; }
+            for (const void *in : ins)
+                if (in && o == in) { batch_err(b, "%s: an output of context %d is a shared input array", who, i); return FD_E_INVALID; }
+        }
+    }
+    if (N == 0) return FD_OK;
+    // other kinds, fp64 contexts, an eval_variant override, an imported model, layer counts outside 1..8, fewer frames than the
+    // position launch takes: the one-layer call's, before anything of this one's is touched
+    if (!shared_ml_fast(b))
+        return fd_batch_deform_vectors_shared_dev(b, hip_stream, N, d_P_in, d_P_out, d_dist2, d_falloff_out, d_tu, d_tv, d_nrm, radius2,
+                                                  falloffrate, vec);
+    int rc = fd_batch_deform_shared_ml_dev(b, hip_stream, N, d_P_in, d_P_out, d_dist2, d_falloff_out, d_tu, d_tv, d_nrm, radius2, falloffrate);
+    if (rc) return rc;
+    fd_ctx *c0 = b->ctxs[0];
+    hipStream_t stream = hip_stream ? (hipStream_t)hip_stream : cur_stream(c0);
+    if (b->n < shared_vectors_ml_min_frames(ml_layers(c0))) {
+        // so few frames that the per-context launches are the faster way: what fd_deform_vectors_dev launches for an
+        // FD_EVAL_FP32 context on the shared arrays (the positions above are fd_batch_deform_shared_ml_dev's either way)
+        for (int i = 0; i < b->n; ++i) {
+            DeformArgs a = deform_args(b->ctxs[i], N, d_P_in, d_P_out[i], d_dist2, d_falloff_out ? d_falloff_out[i] : nullptr, d_tu, d_tv,
+                                       d_nrm, radius2, falloffrate);
+            const VectorArgs v{vec->N, vec->tu, vec->tv, vec->N ? vec->N_out[i] : nullptr, vec->tu ? vec->tu_out[i] : nullptr,
+                               vec->tv ? vec->tv_out[i] : nullptr, vec->jacobian ? vec->jacobian[i] : nullptr};
+            hipError_t e = launch_vectors(a, v, stream);
+            if (e != hipSuccess) { batch_err(b, "launch_vectors failed: %s", hipGetErrorString(e)); return FD_E_DEVICE; }
+        }
+        // these launches read the models to their end
+        if (hipEventRecord(b->sml_consumed_ev, stream) != hipSuccess) { (void)hipGetLastError(); return FD_E_DEVICE; }
+        return FD_OK;
+    }
+    SharedVectorMlArgs a{};
+    a.N = N; a.P_in = d_P_in; a.dist2 = d_dist2; a.tu = d_tu; a.tv = d_tv; a.nrm = d_nrm;
+    a.radius2 = radius2; a.falloffrate = falloffrate;
+    a.M = c0->M; a.layers = ml_layers(c0); a.nF = b->n;
+    a.vN = vec->N; a.vtu = vec->tu; a.vtv = vec->tv;
+    for (int i = 0; i < b->n; ++i) {
+        a.N_out[i] = vec->N ? vec->N_out[i] : nullptr;
+        a.tu_out[i] = vec->tu ? vec->tu_out[i] : nullptr;
+        a.tv_out[i] = vec->tv ? vec->tv_out[i] : nullptr;
+        a.jacobian[i] = vec->jacobian ? vec->jacobian[i] : nullptr;
+    }
+    a.scratch = b->d_sml;
+    a.max_wgs = b->eval_cus;
+    hipError_t e = launch_vectors_shared_ml(a, stream);
+    if (e != hipSuccess) { batch_err(b, "launch_vectors_shared_ml failed: %s", hipGetErrorString(e)); return FD_E_DEVICE; }
+    // the next pack kernel rewrites the scratch this launch reads: its event moves behind the vector launch
+    if (b->sml_eval_pending && hipEventRecord(b->sml_eval_ev, stream) == hipSuccess) return FD_OK;
+    (void)hipGetLastError();
+    (void)hipStreamSynchronize(stream);
+    return FD_OK;
+}
+
+const char *fd_shared_vectors_ml_kernel_name(int M, int layers, int frames)
+{
+    return shared_vectors_ml_kernel_name(M, layers, frames);
+}
+
 // ---- every frame of a shot of multilayer models in fp64 by one matrix-pipe launch (fd_eval_shared_ml64.hip) ----
 // where the launch applies: multilayer contexts of one model on one rest array, built here, no eval_variant, enough frames.
 // Anything else -- an unbuilt context, another rest array, mixed outputs included -- is fd_batch_deform_shared_fp64_dev's to

@@ -30,6 +30,7 @@
 
 #include "fd_eval_common.h"
 #include "fd_shared_common.h"
+#include "fd_shared_ml.h"
 
 #pragma push_macro("hipLaunchKernelGGL")
 #undef hipLaunchKernelGGL
@@ -55,20 +56,10 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int kMlWaves = 8;                       // two per SIMD, 64 vertices (two vertex tiles of 32) each per group
 constexpr int kMlThreads = 64 * kMlWaves;
 constexpr int kMlGroup = 64 * kMlWaves;           // vertices per workgroup and group
-constexpr int kMlMinFrames = 2;                   // fewer frames: the per-context launches
 
-// Rows of the stack of 32-row output tiles: row 3 f + c is component c of frame f (as the wide kernel packs them).
-constexpr int ml_tiles(int nF) { return (3 * nF + 31) / 32; }          // 1 up to 10 frames, 2 up to 21, else 3
+// (the scratch layout -- kMlNormAt, kMlPolyAt, ml_rec_at, ml_w_at, ml_w16, ml_tiles, ml_share -- and kMlMinFrames are
+// fd_shared_ml.h's: the vector launch reads the scratch too)
 constexpr int ml_tile_frames(int nt) { return 32 * nt / 3; }           // frames whose three rows fit nt tiles
-constexpr int ml_share(int L) { return L % 4 == 0 ? 4 : (L % 2 == 0 ? 2 : 1); }
-
-// scratch, in 16-byte words: [frame records 32 x 2][normalisation][polynomial tiles NT x 64][records nkb x 32]
-//                            [weight tiles nkb x NT x (K step 2 x (hi, lo) x 64 lanes)]
-constexpr size_t kMlNormAt = kMaxBatch * sizeof(SharedFrame) / 16;
-constexpr size_t kMlPolyAt = kMlNormAt + 1;
-constexpr size_t ml_rec_at(int nt) { return kMlPolyAt + (size_t)nt * 64; }
-constexpr size_t ml_w_at(int nt, int nkb) { return ml_rec_at(nt) + (size_t)nkb * 32; }
-constexpr size_t ml_w16(int nt) { return (size_t)nt * 256; }           // words of weight tiles per K block
 
 struct MlPackArgs {
     const Rec32 *rec32[kMaxBatch];

@@ -399,6 +399,22 @@ struct SharedVectorMl64Args {
 hipError_t launch_vectors_shared_ml64(const SharedVectorMl64Args &a, hipStream_t stream);
 const char *shared_vectors_ml64_kernel_name(int M, int layers, int nF);    // "" below shared_vectors_ml64_min_frames too
 int shared_vectors_ml64_min_frames(int layers);                             // fewer frames: the per-context launches are faster
+// The Jacobian and the vectors it carries for every frame of a shared-rig batch of MULTILAYER models, in fp32 by one
+// matrix-pipe launch (fd_vectors_shared_ml.hip, fd_batch_deform_vectors_shared_ml_dev): reads the scratch
+// launch_deform_shared_ml's pack kernel wrote for the same M, layers and nF, the mesh and the vectors; nothing of the contexts.
+struct SharedVectorMlArgs {
+    int64_t N;
+    const float *P_in, *dist2, *tu, *tv, *nrm;
+    float radius2, falloffrate;
+    int M, layers, nF;
+    const float *vN, *vtu, *vtv;
+    float *N_out[kMaxBatch], *tu_out[kMaxBatch], *tv_out[kMaxBatch], *jacobian[kMaxBatch];
+    const void *scratch;
+    int max_wgs;
+};
+hipError_t launch_vectors_shared_ml(const SharedVectorMlArgs &a, hipStream_t stream);
+const char *shared_vectors_ml_kernel_name(int M, int layers, int nF);      // "" below shared_vectors_ml_min_frames too
+int shared_vectors_ml_min_frames(int layers);                               // fewer frames: the per-context launches are faster
 // island mask (fd_capture.hip): nearest mesh point per rig point + max_edges breadth-first rings
 hipError_t launch_capture_islands(const float *d_P, int64_t N, const int64_t *d_offsets, const int *d_neighbours,
                                   const float *d_rig, int M, int max_edges, unsigned char *d_mask, hipStream_t stream);

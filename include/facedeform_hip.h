@@ -527,8 +527,9 @@ const char *fd_shared_fp64_kernel_name(int M, int frames, int kind);
  *     fd_batch_set_eval_cus.
  *   Where the launch applies: every context FD_KERNEL_GAUSSIAN_ML with the same M, radius, layers, lambda and term, built
  *     on one rest array; FD_EVAL_FP32; no eval_variant override; 1..8 layers; any M a multilayer model can be built for (the
- *     model is staged through LDS in chunks of records); 2..FD_MAX_BATCH frames.  The lower bound of 2 frames is
- *     provisional: the launch has not been timed on a device yet.
+ *     model is staged through LDS in chunks of records); 2..FD_MAX_BATCH frames.  Measured at 1M vertices and 256 centres
+ *     (DESIGN.md 4.1f), launch against per-context launches: with 4 layers 0.31 / 0.35 ms at 2 frames (1.14x), 0.32 / 1.32 ms
+ *     at 8, 0.57 / 5.26 ms at 32 (9.3x); with 8 layers 0.60 / 0.62 ms at 2 (1.04x), 0.99 / 10.1 ms at 32 (10.2x).
  *   Everywhere else -- other kinds, fp64 contexts, eval_variant overrides, imported models, one frame, layer counts
  *     outside 1..8 -- the call IS fd_batch_deform_shared_dev with the same arguments, bit for bit.
  *   Pass-through: a gated vertex (d_dist2 > radius2), and every vertex of a frame whose model is not built
@@ -542,8 +543,9 @@ const char *fd_shared_fp64_kernel_name(int M, int frames, int kind);
  *     alone; after fd_batch_wait_consumed the contexts may be rebuilt while the evaluation still runs.  The fp32 call's
  *     two scratch sets, fd_batch_prepare_shared and the fp64 scratch are not involved.
  *   Not covered: fd_batch_cook_group, fdsop_cook and the four other shared calls do not take this launch (a multilayer
- *     batch runs the per-context launches there, as before), and the Jacobian and the vectors of a multilayer shot stay
- *     with the per-context launches.  A multilayer shot that needs fp64 has fd_batch_deform_shared_ml_fp64_dev (below).
+ *     batch runs the per-context launches there, as before).  The Jacobian and the vectors of a multilayer shot are a
+ *     call of their own on top of this one: fd_batch_deform_vectors_shared_ml_dev (below).  A multilayer shot that needs
+ *     fp64 has fd_batch_deform_shared_ml_fp64_dev (below).
  * Asynchronous on hip_stream (NULL: context 0's). */
 int fd_batch_deform_shared_ml_dev(fd_batch *batch, void *hip_stream, int64_t N, const float *d_P_in,
                                   float *const *d_P_out, const float *d_dist2, float *const *d_falloff_out,
@@ -554,6 +556,77 @@ int fd_batch_deform_shared_ml_dev(fd_batch *batch, void *hip_stream, int64_t N, 
  * 2..FD_MAX_BATCH, M <= 0).  It sees no context: another kind, fp64 contexts or an eval_variant override delegate whatever
  * this returns.  For tests and profiles. */
 const char *fd_shared_ml_kernel_name(int M, int layers, int frames);
+/* fd_batch_deform_shared_ml_dev plus, for every frame f, the Jacobian and the vectors it carries, in fp32 by ONE
+ * matrix-pipe launch of its own: to fd_batch_deform_shared_ml_dev what fd_batch_deform_vectors_shared_ml_fp64_dev is to
+ * fd_batch_deform_shared_ml_fp64_dev, and for a multilayer shot what fd_batch_deform_vectors_shared_dev is for the
+ * one-layer kinds.
+ *   Positions: P_out and falloff_out are bit-identical to fd_batch_deform_shared_ml_dev called with the same arguments:
+ *     that call runs unchanged first (its pack kernel, its position launch, its mismatch report), then one launch of its
+ *     own writes the vector outputs.  vec == NULL, or every pointer in it NULL, is exactly fd_batch_deform_shared_ml_dev.
+ *     Inherited from it: error codes, build-status poll and repair, ordering behind the batch's builds, the one-rest-rig
+ *     condition and fd_set_output handling.
+ *   Vectors: fd_deform_vectors' definition, per frame, in fp32, on the model's M x L Gaussian records (radii R / 2^l):
+ *     A_f = I + f Pi J_f with J_f = sum_c sum_l w_f[c][l] (x) grad phi_l(x - c) + L_f(x) in the normalised coordinates of
+ *     the fp32 evaluation, direct differences; t' = A_f t (not renormalised), n' = cof(A_f) n rescaled to |n|;
+ *     A is stored as fp32.  The gradient basis 2^8 s_l E_l (x' - c') is formed once per (vertex, record) for all frames -- x' - c'
+ *     and d2 once per centre for the layers that sit side by side in a lane's operand, every layer with its own multiply
+ *     by s_l = -log2(e) / R_l'^2 and its own v_exp_f32, never E_{l+1} = E_l^4 -- and contracted with the frames' weights, as
+ *     two fp16 pieces each (hi x hi, lo x hi, hi x lo), on v_mfma_f32_16x16x32_f16 with fp32 accumulation; the weight and
+ *     polynomial tiles are the ones the position call's pack kernel wrote, their per-frame power-of-two scales undone
+ *     exactly.  Projection, fall-off, cofactors and the rescale are the one-frame launch's own code.
+ *   Error statement.  With S'_f(x) = sum_r ||w_f[r]|| |grad phi_r(x)| + ||L_f|| over the M L records: against an
+ *     independent fp64 restatement ||A - A_ref||_F <= 2^-22 ||A_ref||_F + 2^-21 f S'_f(x) -- the bar of
+ *     fd_batch_deform_vectors_shared_dev's launch, twice the one-frame fp32 launch's second term (22 significant bits in
+ *     the contraction, the dropped lo x lo product, fp32 accumulation).  It is not bit-identical to the per-context
+ *     launches.
+ *   Radius limit: the hi piece of the basis is finite in fp16 while |2^8 g (x' - c')| <= 2^8 0.52 sqrt(|s_l|) stays below
+ *     65504, that is for a FINEST-layer radius R' / 2^(L - 1) of at least 0.00245 rig radii (R' >= 0.00245 2^(L - 1):
+ *     0.0196 with 4 layers, 0.314 with 8; a rig radius is the normalisation scale of the rest rig, its extent rounded to
+ *     a power of two; fd_batch_deform_vectors_shared_dev's 0.0024, to one more digit and rounded up).  Below that
+ *     limit the basis of vertices near d = R_l' / sqrt(2) of a centre overflows to infinity and their A is not finite;
+ *     nothing is clamped and nothing is reported.  The positions have no such limit.
+ *   Pass-through: every vector output is the input bit for bit, and A = I exactly, for gated vertices
+ *     (d_dist2 > radius2), where f = 0, and for frames whose model is not built or whose centres differ from frame 0's
+ *     (built = 0 in the frame record, as the position call's pack kernel decided).  Entries past N are not touched.
+ *   Aliasing: no output (P_out, falloff_out, the tables of vec) may equal any shared input (d_P_in, d_dist2, d_tu, d_tv,
+ *     d_nrm, vec->N / tu / tv): FD_E_INVALID, before any device work.  This holds for a batch of one as well -- the
+ *     position call's in-place exception does not apply, because the vector launch reads d_P_in after the position
+ *     launch has written.
+ *   Tables: as in fd_batch_deform_vectors_shared_ml_fp64_dev -- vec->struct_size at least sizeof(fd_batch_vectors), every
+ *     input with its output table (both or neither), a table has n non-NULL entries; otherwise FD_E_INVALID, before any
+ *     device work, the checks in that call's order.  N == 0 is FD_OK before any device work.
+ *   Where the launch applies: where fd_batch_deform_shared_ml_dev's own launch does (multilayer contexts of one model
+ *     built on one rest array, FD_EVAL_FP32, 1..8 layers, no eval_variant override, not an imported model, any M,
+ *     2..FD_MAX_BATCH frames) and the frame count is at or above the measured threshold: 3 frames with one layer, 2 frames with
+ *     2 to 8 layers.  Measured at 1M vertices and 256 centres (device events, the position-only call subtracted; DESIGN.md
+ *     4.7e), vectors alone, launch against per-context launches: with 4 layers 0.82 / 0.90 ms at 2 frames (1.10x),
+ *     0.82 / 1.36 ms at 3, 1.65 / 5.91 ms at 12, 3.73 / 15.6 ms at 32 (4.2x); with 8 layers 1.61 / 1.70 ms at 2 (1.05x),
+ *     2.65 / 11.3 ms at 12, 4.60 / 30.7 ms at 32 (6.7x); at 2 frames 1.09x to 1.13x with 2, 3, 5, 6, 7 layers and a tie with
+ *     one layer (0.295 / 0.295 ms; 0.340 / 0.452 ms at 3 frames, 1.33x).
+ *     A multilayer batch below the threshold that the position launch takes keeps the positions of
+ *     fd_batch_deform_shared_ml_dev and gets its vectors from the per-context launches: per context and bit for bit what
+ *     fd_deform_vectors_dev writes for an FD_EVAL_FP32 context on the shared arrays (the batch's consumed event is
+ *     re-recorded behind them: they read the models to their end).
+ *   Everywhere else -- other kinds, fp64 contexts, eval_variant overrides, imported models, layer counts outside 1..8,
+ *     one frame -- the call IS fd_batch_deform_vectors_shared_dev with the same arguments, bit for bit: it delegates
+ *     before touching anything of its own.
+ *   Reads of the models: the vector launch reads only the batch's multilayer scratch (as the position call packed it),
+ *     the mesh, the vectors and its own arguments: fd_batch_wait_consumed covers it, and the contexts may be rebuilt
+ *     while it runs; the next call's pack kernel waits for it before it rewrites that scratch.
+ *   Bits: no floating-point atomics; the same inputs give the same bits on every call, a vertex's result does not
+ *     depend on its place in the launch ([0, N) in one call or in two ranges: same bits), nor on fd_batch_set_eval_cus.
+ * The seven other shared calls, fd_batch_cook_group and fdsop_cook are unchanged.
+ * Asynchronous on hip_stream (NULL: context 0's). */
+int fd_batch_deform_vectors_shared_ml_dev(fd_batch *batch, void *hip_stream, int64_t N, const float *d_P_in,
+                                          float *const *d_P_out, const float *d_dist2, float *const *d_falloff_out,
+                                          const float *d_tu, const float *d_tv, const float *d_nrm,
+                                          float radius2, float falloffrate, const fd_batch_vectors *vec);
+/* The kernel the vector launch of fd_batch_deform_vectors_shared_ml_dev takes for M centres, `layers` layers and
+ * `frames` contexts ("k_vectors32_shared_ml"), or "" where the call runs the per-context launches or is
+ * fd_batch_deform_vectors_shared_dev (M <= 0, layers outside 1..8, frames outside 2..FD_MAX_BATCH, frames below the
+ * threshold above).  It sees no context: another kind, fp64 contexts, an imported model or an eval_variant override
+ * delegate whatever this returns.  For tests and profiles. */
+const char *fd_shared_vectors_ml_kernel_name(int M, int layers, int frames);
 /* The frames of a shot of MULTILAYER models evaluated in FP64 by ONE matrix-pipe launch: what
  * fd_batch_deform_shared_fp64_dev is for the one-layer kinds.  Inherited from that call: the arguments, the argument
  * checks and their order, N == 0 answered FD_OK before any device work, gate, tangent projection, fall-off,

@@ -20,17 +20,17 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from facedeform_amd import capi, synth   # noqa: E402
 
 
-def timed(fn, reps, warm=3):
+def timed(fn, reps, stream, warm=3):
     for _ in range(warm):
         fn()
     torch.cuda.synchronize()
     best = []
     for _ in range(3):
         t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t0.record()
+        t0.record(stream)            # on the stream the calls are given: events on another stream bracket nothing
         for _ in range(reps):
             fn()
-        t1.record()
+        t1.record(stream)
         torch.cuda.synchronize()
         best.append(t0.elapsed_time(t1) * 1000.0 / reps)
     return sorted(best)[1]          # the median of three batches, microseconds per call
@@ -55,29 +55,33 @@ def main():
     outs = [torch.empty_like(d_P) for _ in range(Fmax)]
     falls = [torch.empty(N, device=dev) for _ in range(Fmax)]
     ptr = lambda ts: [t.data_ptr() for t in ts]
-    s = torch.cuda.current_stream().cuda_stream
+    # a stream of its own, handed to every call: torch's current stream is the null stream, whose handle 0 the library reads as
+    # "the context's own stream", and events recorded on the null stream would then time the enqueueing, not the launches
+    stream = torch.cuda.Stream(device=dev)
+    s = stream.cuda_stream
     rows = ["layers,frames,kernel,new_us,per_context_us,speedup,new_us_per_frame,per_context_us_per_frame"]
     for L in args.layers:
         engines = []
         for _ in range(Fmax):
             e = capi.Engine(device=0)
+            e.set_stream(s)
             e.set_kernel(capi.KERNEL_GAUSSIAN_ML, [1.0, L, 0.1]); e.set_term(capi.TERM_LINEAR)
             engines.append(e)
         full = capi.Batch(engines)
         full.set_points_dev([d_rest.data_ptr()] * Fmax, [d_del.data_ptr() + f * M * 12 for f in range(Fmax)], M)
-        full.build_async()
+        full.build_async(s)
         assert [r.terminationtype for r in full.build_result()] == [1] * Fmax
         for F in args.frames:
             batch = capi.Batch(engines[:F])
             name = capi.fd_shared_ml_kernel_name(M, L, F)
-            old = timed(lambda: batch.deform_shared_dev(N, d_P.data_ptr(), ptr(outs[:F]), d_falloff=ptr(falls[:F]), stream_ptr=s), args.reps)
-            new = timed(lambda: batch.deform_shared_ml_dev(N, d_P.data_ptr(), ptr(outs[:F]), d_falloff=ptr(falls[:F]), stream_ptr=s), args.reps) if name else float("nan")
+            old = timed(lambda: batch.deform_shared_dev(N, d_P.data_ptr(), ptr(outs[:F]), d_falloff=ptr(falls[:F]), stream_ptr=s), args.reps, stream)
+            new = timed(lambda: batch.deform_shared_ml_dev(N, d_P.data_ptr(), ptr(outs[:F]), d_falloff=ptr(falls[:F]), stream_ptr=s), args.reps, stream) if name else float("nan")
             rows.append(f"{L},{F},{name},{new:.1f},{old:.1f},{old / new:.2f},{new / F:.1f},{old / F:.1f}")
             print(rows[-1], flush=True)
             batch.close()
         full.close()
         for e in engines:
-            e.close()
+            e.set_stream(None); e.close()
     if args.csv:
         os.makedirs(os.path.dirname(os.path.abspath(args.csv)), exist_ok=True)
         with open(args.csv, "w") as fh:
