@@ -598,9 +598,8 @@ class Batch:
                                                tab(d_dist2), tab(d_falloff), tu, tv, nr, float(radius2),
                                                float(falloffrate)))
 
-    def deform_shared_dev(self, N: int, d_P_in: int, d_P_out, d_dist2: int = 0, d_falloff=None, d_tangents=None,
-                          radius2=1.0, falloffrate=1.0, stream_ptr: int | None = None):
-        """Frames of one mesh and one rest rig: ONE input mesh (device pointer), one output per context."""
+    def _deform_shared(self, call, N, d_P_in, d_P_out, d_dist2, d_falloff, d_tangents, radius2, falloffrate, stream_ptr):
+        """The one body of the four position shot calls: `call` is the library's function."""
         n = len(self.engines)
         if len(d_P_out) != n or (d_falloff is not None and len(d_falloff) != n):
             raise ValueError("one output pointer per context")
@@ -608,54 +607,35 @@ class Batch:
         outs = (vp * n)(*d_P_out)
         falls = None if d_falloff is None else (vp * n)(*[p or None for p in d_falloff])
         tu, tv, nr = d_tangents if d_tangents is not None else (0, 0, 0)
-        self._check(self.L.fd_batch_deform_shared_dev(self.h, vp(stream_ptr or 0), N, vp(d_P_in), outs, vp(d_dist2 or None),
-                                                      falls, vp(tu or None), vp(tv or None), vp(nr or None),
-                                                      float(radius2), float(falloffrate)))
+        self._check(call(self.h, vp(stream_ptr or 0), N, vp(d_P_in), outs, vp(d_dist2 or None), falls, vp(tu or None), vp(tv or None),
+                         vp(nr or None), float(radius2), float(falloffrate)))
+
+    def deform_shared_dev(self, N: int, d_P_in: int, d_P_out, d_dist2: int = 0, d_falloff=None, d_tangents=None,
+                          radius2=1.0, falloffrate=1.0, stream_ptr: int | None = None):
+        """Frames of one mesh and one rest rig: ONE input mesh (device pointer), one output per context."""
+        self._deform_shared(self.L.fd_batch_deform_shared_dev, N, d_P_in, d_P_out, d_dist2, d_falloff, d_tangents, radius2, falloffrate,
+                            stream_ptr)
 
     def deform_shared_fp64_dev(self, N: int, d_P_in: int, d_P_out, d_dist2: int = 0, d_falloff=None, d_tangents=None,
                                radius2=1.0, falloffrate=1.0, stream_ptr: int | None = None):
         """fd_batch_deform_shared_fp64_dev: deform_shared_dev's arguments, every frame evaluated in fp64 by one launch
         whatever the contexts' precision setting says."""
-        n = len(self.engines)
-        if len(d_P_out) != n or (d_falloff is not None and len(d_falloff) != n):
-            raise ValueError("one output pointer per context")
-        vp = C.c_void_p
-        outs = (vp * n)(*d_P_out)
-        falls = None if d_falloff is None else (vp * n)(*[p or None for p in d_falloff])
-        tu, tv, nr = d_tangents if d_tangents is not None else (0, 0, 0)
-        self._check(self.L.fd_batch_deform_shared_fp64_dev(self.h, vp(stream_ptr or 0), N, vp(d_P_in), outs, vp(d_dist2 or None),
-                                                           falls, vp(tu or None), vp(tv or None), vp(nr or None),
-                                                           float(radius2), float(falloffrate)))
+        self._deform_shared(self.L.fd_batch_deform_shared_fp64_dev, N, d_P_in, d_P_out, d_dist2, d_falloff, d_tangents, radius2,
+                            falloffrate, stream_ptr)
 
     def deform_shared_ml_dev(self, N: int, d_P_in: int, d_P_out, d_dist2: int = 0, d_falloff=None, d_tangents=None,
                              radius2=1.0, falloffrate=1.0, stream_ptr: int | None = None):
         """fd_batch_deform_shared_ml_dev: deform_shared_dev's arguments; a shot of multilayer models is evaluated by one
         launch, anything else exactly as deform_shared_dev does."""
-        n = len(self.engines)
-        if len(d_P_out) != n or (d_falloff is not None and len(d_falloff) != n):
-            raise ValueError("one output pointer per context")
-        vp = C.c_void_p
-        outs = (vp * n)(*d_P_out)
-        falls = None if d_falloff is None else (vp * n)(*[p or None for p in d_falloff])
-        tu, tv, nr = d_tangents if d_tangents is not None else (0, 0, 0)
-        self._check(self.L.fd_batch_deform_shared_ml_dev(self.h, vp(stream_ptr or 0), N, vp(d_P_in), outs, vp(d_dist2 or None),
-                                                         falls, vp(tu or None), vp(tv or None), vp(nr or None),
-                                                         float(radius2), float(falloffrate)))
+        self._deform_shared(self.L.fd_batch_deform_shared_ml_dev, N, d_P_in, d_P_out, d_dist2, d_falloff, d_tangents, radius2,
+                            falloffrate, stream_ptr)
 
     def deform_shared_ml_fp64_dev(self, N: int, d_P_in: int, d_P_out, d_dist2: int = 0, d_falloff=None, d_tangents=None,
                                   radius2=1.0, falloffrate=1.0, stream_ptr: int | None = None):
         """fd_batch_deform_shared_ml_fp64_dev: deform_shared_fp64_dev's arguments; a shot of multilayer models is evaluated
         in fp64 by one launch, anything else exactly as deform_shared_fp64_dev does."""
-        n = len(self.engines)
-        if len(d_P_out) != n or (d_falloff is not None and len(d_falloff) != n):
-            raise ValueError("one output pointer per context")
-        vp = C.c_void_p
-        outs = (vp * n)(*d_P_out)
-        falls = None if d_falloff is None else (vp * n)(*[p or None for p in d_falloff])
-        tu, tv, nr = d_tangents if d_tangents is not None else (0, 0, 0)
-        self._check(self.L.fd_batch_deform_shared_ml_fp64_dev(self.h, vp(stream_ptr or 0), N, vp(d_P_in), outs, vp(d_dist2 or None),
-                                                              falls, vp(tu or None), vp(tv or None), vp(nr or None),
-                                                              float(radius2), float(falloffrate)))
+        self._deform_shared(self.L.fd_batch_deform_shared_ml_fp64_dev, N, d_P_in, d_P_out, d_dist2, d_falloff, d_tangents, radius2,
+                            falloffrate, stream_ptr)
 
     def deform_vectors_shared_dev(self, N: int, d_P_in: int, d_P_out, d_dist2: int = 0, d_falloff=None, d_tangents=None,
                                   d_N: int = 0, d_N_out=None, d_vtu: int = 0, d_vtu_out=None, d_vtv: int = 0, d_vtv_out=None,

@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 
 #include "fd_internal.h"
@@ -115,6 +116,17 @@ struct fd_ctx {
     char err[512] = {0};
 };
 
+// Scratch of a one-launch shot call that keeps its own (fd_batch_deform_shared_fp64_dev, _ml_dev, _ml_fp64_dev; the vector call
+// that goes with each reads it too), and the two events that order the contexts' models and the scratch around its launches.
+struct ShotScratch {
+    void *d = nullptr;                   // what the call's pack kernel writes and its evaluation reads
+    size_t cap = 0;
+    hipEvent_t consumed_ev = nullptr;    // behind the last read of the contexts' models by that call (its pack kernel, or its per-context launches)
+    bool consumed = false;               // ... and recorded: fd_batch_wait_consumed waits for it too
+    hipEvent_t eval_ev = nullptr;        // behind its last evaluation: the next pack kernel rewrites the scratch that one reads
+    bool eval_pending = false;
+};
+
 struct fd_batch {
     int n = 0;
     int device = 0;
@@ -159,27 +171,11 @@ struct fd_batch {
     float *prep_fall[kMaxBatch] = {nullptr};
     bool prep_has_fall = false;
     hipEvent_t fallback_ev = nullptr;    // behind the per-frame launches when the shared launch does not apply
-    // fd_batch_deform_shared_fp64_dev: scratch of its own (the two fp32 sets, packed_valid, cur_set and prepared are not its business)
-    void *d_s64 = nullptr;
-    size_t cap_s64 = 0;
-    hipEvent_t s64_consumed_ev = nullptr; // behind the last read of the contexts' models by that call (its pack kernel, or its per-context launches)
-    bool s64_consumed = false;           // ... and recorded: fd_batch_wait_consumed waits for it too
-    hipEvent_t s64_eval_ev = nullptr;    // behind its last evaluation: the next pack kernel rewrites the scratch that one reads
-    bool s64_eval_pending = false;
-    // fd_batch_deform_shared_ml_dev: the same again, for the multilayer shot launch
-    void *d_sml = nullptr;
-    size_t cap_sml = 0;
-    hipEvent_t sml_consumed_ev = nullptr; // behind its pack kernel: the last read of the contexts' models by that launch
-    bool sml_consumed = false;           // ... and recorded: fd_batch_wait_consumed waits for it too
-    hipEvent_t sml_eval_ev = nullptr;    // behind its last evaluation: the next pack kernel rewrites the scratch that one reads
-    bool sml_eval_pending = false;
-    // fd_batch_deform_shared_ml_fp64_dev: and once more, for the fp64 multilayer shot launch
-    void *d_sml64 = nullptr;
-    size_t cap_sml64 = 0;
-    hipEvent_t sml64_consumed_ev = nullptr; // behind its pack kernel: the last read of the contexts' models by that launch
-    bool sml64_consumed = false;           // ... and recorded: fd_batch_wait_consumed waits for it too
-    hipEvent_t sml64_eval_ev = nullptr;    // behind its last evaluation: the next pack kernel rewrites the scratch that one reads
-    bool sml64_eval_pending = false;
+    // the other one-launch shot calls: a scratch of their own each (the two fp32 sets, packed_valid, cur_set and prepared are not
+    // their business)
+    ShotScratch s64;                     // fd_batch_deform_shared_fp64_dev
+    ShotScratch sml;                     // fd_batch_deform_shared_ml_dev, for the multilayer shot launch
+    ShotScratch sml64;                   // fd_batch_deform_shared_ml_fp64_dev, for the fp64 multilayer shot launch
     hipEvent_t group_ev = nullptr;       // fd_batch_cook_group: behind the group's builds, for the evaluation stream
     // fd_batch_cook_group with the evaluation on the build stream itself (one unpipelined group): stream order does what the
     // events between build, packing and evaluation do across streams, and every event record is a barrier packet that keeps the
@@ -1152,6 +1148,29 @@ static int deform_host(fd_ctx *ctx, int64_t N, const float *P_in, float *P_out, 
     return FD_OK;
 }
 
+// ---- fillers of the shot launches' argument structs (fd_batch_deform_*shared*_dev below; templates, so outside the C linkage block) ----
+// the mesh part of a launch's arguments (Shared*Args and SharedVector*Args name these fields alike)
+template <typename Args>
+static void fill_mesh(Args &a, int64_t N, const float *d_P_in, const float *d_dist2, const float *d_tu, const float *d_tv,
+                      const float *d_nrm, float radius2, float falloffrate)
+{
+    a.N = N; a.P_in = d_P_in; a.dist2 = d_dist2; a.tu = d_tu; a.tv = d_tv; a.nrm = d_nrm;
+    a.radius2 = radius2; a.falloffrate = falloffrate;
+}
+
+// the vector tables of a SharedVector*Args
+template <typename Args>
+static void fill_vector_tables(Args &a, int n, const fd_batch_vectors *vec)
+{
+    a.vN = vec->N; a.vtu = vec->tu; a.vtv = vec->tv;
+    for (int i = 0; i < n; ++i) {
+        a.N_out[i] = vec->N ? vec->N_out[i] : nullptr;
+        a.tu_out[i] = vec->tu ? vec->tu_out[i] : nullptr;
+        a.tv_out[i] = vec->tv ? vec->tv_out[i] : nullptr;
+        a.jacobian[i] = vec->jacobian ? vec->jacobian[i] : nullptr;
+    }
+}
+
 extern "C" {
 
 // ---- dist2 producer (next row N2; kernel in fd_capture.hip) -----------------------------------
@@ -1568,6 +1587,13 @@ fd_batch *fd_batch_create(fd_ctx *const *ctxs, int n)
     return b;
 }
 
+static void shot_free(ShotScratch &sc)
+{
+    if (sc.d) (void)hipFree(sc.d);
+    if (sc.consumed_ev) (void)hipEventDestroy(sc.consumed_ev);
+    if (sc.eval_ev) (void)hipEventDestroy(sc.eval_ev);
+}
+
 void fd_batch_destroy(fd_batch *b)
 {
     if (!b) return;
@@ -1592,15 +1618,7 @@ void fd_batch_destroy(fd_batch *b)
     }
     if (b->d_fac) (void)hipFree(b->d_fac);
     if (b->fallback_ev) (void)hipEventDestroy(b->fallback_ev);
-    if (b->d_s64) (void)hipFree(b->d_s64);
-    if (b->s64_consumed_ev) (void)hipEventDestroy(b->s64_consumed_ev);
-    if (b->s64_eval_ev) (void)hipEventDestroy(b->s64_eval_ev);
-    if (b->d_sml) (void)hipFree(b->d_sml);
-    if (b->sml_consumed_ev) (void)hipEventDestroy(b->sml_consumed_ev);
-    if (b->sml_eval_ev) (void)hipEventDestroy(b->sml_eval_ev);
-    if (b->d_sml64) (void)hipFree(b->d_sml64);
-    if (b->sml64_consumed_ev) (void)hipEventDestroy(b->sml64_consumed_ev);
-    if (b->sml64_eval_ev) (void)hipEventDestroy(b->sml64_eval_ev);
+    for (ShotScratch *sc : {&b->s64, &b->sml, &b->sml64}) shot_free(*sc);
     if (b->group_ev) (void)hipEventDestroy(b->group_ev);
     if (b->h_mismatch) (void)hipHostFree(b->h_mismatch);
     if (b->ev0) (void)hipEventDestroy(b->ev0);
@@ -1861,6 +1879,153 @@ static bool make_event(hipEvent_t *ev)
     return true;
 }
 
+// ---- what the eight shot calls share on the host: argument checks, the ShotScratch protocol, the per-context vector launches
+// (fill_mesh and fill_vector_tables, being templates, are in front of this linkage block) ----
+static int shot_check_mesh(fd_batch *b, const char *who, int64_t N, const float *d_P_in, const float *d_tu, const float *d_tv,
+                           const float *d_nrm)
+{
+    if (N < 0 || (N > 0 && !d_P_in)) { batch_err(b, "%s: bad N / P_in", who); return FD_E_INVALID; }
+    if (!frames_ok(d_tu, d_tv, d_nrm)) { batch_err(b, "%s: tu, tv, nrm must be all set or all NULL", who); return FD_E_INVALID; }
+    return FD_OK;
+}
+
+// aliasing of a position call, before any device work: one input serves every frame, so no output may be a shared input --
+// except the one frame of a batch of one written in place over the mesh, as in fd_deform_dev
+static int shot_check_aliasing(fd_batch *b, const char *who, const float *d_P_in, float *const *d_P_out, const float *d_dist2,
+                               float *const *d_falloff_out, const float *d_tu, const float *d_tv, const float *d_nrm)
+{
+    const void *ins[5] = {d_P_in, d_dist2, d_tu, d_tv, d_nrm};
+    for (int i = 0; i < b->n; ++i) {
+        if (!d_P_out[i]) { batch_err(b, "%s: NULL output array for context %d", who, i); return FD_E_INVALID; }
+        const void *outs[2] = {d_P_out[i], d_falloff_out ? d_falloff_out[i] : nullptr};
+        for (int o = 0; o < 2; ++o)
+            for (int k = 0; k < 5; ++k) {
+                if (!outs[o] || outs[o] != ins[k]) continue;
+                if (b->n == 1 && o == 0 && k == 0) continue;
+                batch_err(b, "%s: an output of context %d is a shared input array", who, i);
+                return FD_E_INVALID;
+            }
+    }
+    return FD_OK;
+}
+
+// The argument block of a vector call.  *want: vectors or a Jacobian are asked for; where they are not, nothing but the struct's
+// size has been looked at and the call is its position call's.
+static int shot_check_vectors(fd_batch *b, const char *who, int64_t N, const float *d_P_in, float *const *d_P_out, const float *d_dist2,
+                              float *const *d_falloff_out, const float *d_tu, const float *d_tv, const float *d_nrm,
+                              const fd_batch_vectors *vec, bool *want)
+{
+    *want = false;
+    if (vec && vec->struct_size < (int)sizeof(fd_batch_vectors)) {
+        batch_err(b, "%s: vec->struct_size is %d, must be sizeof(fd_batch_vectors) = %d", who, vec->struct_size, (int)sizeof(fd_batch_vectors));
+        return FD_E_INVALID;
+    }
+    *want = vec && (vec->N || vec->N_out || vec->tu || vec->tu_out || vec->tv || vec->tv_out || vec->jacobian);
+    if (!*want) return FD_OK;
+    if ((!vec->N != !vec->N_out) || (!vec->tu != !vec->tu_out) || (!vec->tv != !vec->tv_out)) {
+        batch_err(b, "%s: every vector needs its input and its output table (both or neither)", who);
+        return FD_E_INVALID;
+    }
+    if (int rc = shot_check_mesh(b, who, N, d_P_in, d_tu, d_tv, d_nrm)) return rc;
+    // tables of n non-NULL entries, none of which is a shared input -- a batch of one included: the vector launch reads d_P_in
+    // after the position launch has written
+    const void *ins[8] = {d_P_in, d_dist2, d_tu, d_tv, d_nrm, vec->N, vec->tu, vec->tv};
+    float *const *tabs[6] = {d_P_out, d_falloff_out, vec->N_out, vec->tu_out, vec->tv_out, vec->jacobian};
+    for (int t = 0; t < 6; ++t) {
+        if (!tabs[t]) continue;
+        for (int i = 0; i < b->n; ++i) {
+            const void *o = tabs[t][i];
+            if (!o) { batch_err(b, "%s: output table %d has a NULL entry for context %d", who, t, i); return FD_E_INVALID; }
+            for (const void *in : ins)
+                if (in && o == in) { batch_err(b, "%s: an output of context %d is a shared input array", who, i); return FD_E_INVALID; }
+        }
+    }
+    return FD_OK;
+}
+
+// before a call with a scratch of its own reads the contexts' models: their statuses, `stream` behind their builds, and the
+// event the call's reads will end at
+static int shot_begin(fd_batch *b, const char *who, ShotScratch &sc, hipStream_t stream)
+{
+    int rc;
+    if (!b->lean && (rc = batch_poll(b))) return rc;           // before the ordering: a repaired model's rebuild is ordered with the rest
+    for (int i = 0; i < b->n; ++i)
+        if ((rc = order_after_batch(b->ctxs[i], stream))) { batch_err(b, "context %d: %s", i, b->ctxs[i]->err); return rc; }
+    if (!make_event(&sc.consumed_ev)) { batch_err(b, "%s: hipEventCreate failed", who); return FD_E_DEVICE; }
+    return FD_OK;
+}
+
+// `bytes` of scratch for the pack kernel about to be enqueued on `stream`
+static int shot_reserve(fd_batch *b, const char *who, ShotScratch &sc, size_t bytes, hipStream_t stream)
+{
+    if (bytes > sc.cap) {
+        // (hipFree drains the device: no launch still reads the old scratch)
+        if (sc.d) (void)hipFree(sc.d);
+        sc.d = nullptr; sc.cap = 0; sc.eval_pending = false;
+        if (hipMalloc(&sc.d, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            batch_err(b, "%s: scratch allocation (%zu bytes) failed", who, bytes);
+            return FD_E_NOMEM;
+        }
+        sc.cap = bytes;
+    }
+    // the evaluation that last read the scratch must be through with it
+    if (sc.eval_pending && hipStreamWaitEvent(stream, sc.eval_ev, 0) != hipSuccess) {
+        batch_err(b, "%s: hipStreamWaitEvent failed: %s", who, hipGetErrorString(hipGetLastError()));
+        return FD_E_DEVICE;
+    }
+    sc.eval_pending = false;
+    return FD_OK;
+}
+
+// behind the position launch (pack kernel and evaluation; the launch itself records sc.consumed_ev behind the pack kernel)
+static void shot_evaluated(ShotScratch &sc, hipStream_t stream)
+{
+    sc.consumed = true;
+    if (make_event(&sc.eval_ev) && hipEventRecord(sc.eval_ev, stream) == hipSuccess) { sc.eval_pending = true; return; }
+    // no event to order the next pack kernel by: be safe
+    (void)hipGetLastError();
+    (void)hipStreamSynchronize(stream);
+}
+
+// behind the vector launch on the same scratch
+static void shot_vectors_evaluated(ShotScratch &sc, hipStream_t stream)
+{
+    // the next pack kernel rewrites the scratch this launch reads: its event moves behind the vector launch
+    if (sc.eval_pending && hipEventRecord(sc.eval_ev, stream) == hipSuccess) return;
+    (void)hipGetLastError();
+    (void)hipStreamSynchronize(stream);
+}
+
+// ONE batched build read every context's rest rig from one array: their centres are equal by construction
+static bool one_build(const fd_batch *b)
+{
+    const uint64_t id = b->ctxs[0]->rig_build_id;
+    if (id == 0) return false;
+    for (int i = 1; i < b->n; ++i)
+        if (b->ctxs[i]->rig_build_id != id) return false;
+    return true;
+}
+
+// per context, what fd_deform_vectors_dev launches for a context of `precision` on the shared arrays; these launches read the
+// models to their end, and `consumed_ev` is recorded behind them
+static int vectors_per_context(fd_batch *b, hipStream_t stream, int precision, hipEvent_t consumed_ev, int64_t N, const float *d_P_in,
+                               float *const *d_P_out, const float *d_dist2, float *const *d_falloff_out, const float *d_tu,
+                               const float *d_tv, const float *d_nrm, float radius2, float falloffrate, const fd_batch_vectors *vec)
+{
+    for (int i = 0; i < b->n; ++i) {
+        DeformArgs a = deform_args(b->ctxs[i], N, d_P_in, d_P_out[i], d_dist2, d_falloff_out ? d_falloff_out[i] : nullptr, d_tu, d_tv,
+                                   d_nrm, radius2, falloffrate);
+        a.precision = precision;
+        const VectorArgs v{vec->N, vec->tu, vec->tv, vec->N ? vec->N_out[i] : nullptr, vec->tu ? vec->tu_out[i] : nullptr,
+                           vec->tv ? vec->tv_out[i] : nullptr, vec->jacobian ? vec->jacobian[i] : nullptr};
+        hipError_t e = launch_vectors(a, v, stream);
+        if (e != hipSuccess) { batch_err(b, "launch_vectors failed: %s", hipGetErrorString(e)); return FD_E_DEVICE; }
+    }
+    if (hipEventRecord(consumed_ev, stream) != hipSuccess) { (void)hipGetLastError(); return FD_E_DEVICE; }
+    return FD_OK;
+}
+
 // the pack kernel of the contexts' current models into the set NOT read by the evaluation before; on `stream`
 static int shared_pack(fd_batch *b, hipStream_t stream, int ek, float *const *d_P_out, float *const *d_falloff_out)
 {
@@ -1943,11 +2108,11 @@ int fd_batch_deform_shared_dev(fd_batch *b, void *hip_stream, int64_t N, const f
                                const float *d_tv, const float *d_nrm, float radius2, float falloffrate)
 {
     if (!b || !d_P_out) return FD_E_INVALID;
-    if (N < 0 || (N > 0 && !d_P_in)) { batch_err(b, "fd_batch_deform_shared_dev: bad N / P_in"); return FD_E_INVALID; }
-    if (!frames_ok(d_tu, d_tv, d_nrm)) { batch_err(b, "fd_batch_deform_shared_dev: tu, tv, nrm must be all set or all NULL"); return FD_E_INVALID; }
+    int rc = shot_check_mesh(b, "fd_batch_deform_shared_dev", N, d_P_in, d_tu, d_tv, d_nrm);
+    if (rc) return rc;
     if (N == 0) return FD_OK;
     fd_ctx *c0 = b->ctxs[0];
-    int rc = use_device(c0);
+    rc = use_device(c0);
     if (rc) { batch_err(b, "%s", c0->err); return rc; }
     hipStream_t stream = hip_stream ? (hipStream_t)hip_stream : cur_stream(c0);
     int ek = 0;
@@ -2028,34 +2193,14 @@ int fd_batch_deform_vectors_shared_dev(fd_batch *b, void *hip_stream, int64_t N,
 {
     if (!b || !d_P_out) return FD_E_INVALID;
     const char *who = "fd_batch_deform_vectors_shared_dev";
-    if (vec && vec->struct_size < (int)sizeof(fd_batch_vectors)) {
-        batch_err(b, "%s: vec->struct_size is %d, must be sizeof(fd_batch_vectors) = %d", who, vec->struct_size, (int)sizeof(fd_batch_vectors));
-        return FD_E_INVALID;
-    }
-    const bool want = vec && (vec->N || vec->N_out || vec->tu || vec->tu_out || vec->tv || vec->tv_out || vec->jacobian);
+    bool want;
+    int rc = shot_check_vectors(b, who, N, d_P_in, d_P_out, d_dist2, d_falloff_out, d_tu, d_tv, d_nrm, vec, &want);
+    if (rc) return rc;
     if (!want)
         return fd_batch_deform_shared_dev(b, hip_stream, N, d_P_in, d_P_out, d_dist2, d_falloff_out, d_tu, d_tv, d_nrm, radius2, falloffrate);
-    if ((!vec->N != !vec->N_out) || (!vec->tu != !vec->tu_out) || (!vec->tv != !vec->tv_out)) {
-        batch_err(b, "%s: every vector needs its input and its output table (both or neither)", who);
-        return FD_E_INVALID;
-    }
-    if (N < 0 || (N > 0 && !d_P_in)) { batch_err(b, "%s: bad N / P_in", who); return FD_E_INVALID; }
-    if (!frames_ok(d_tu, d_tv, d_nrm)) { batch_err(b, "%s: tu, tv, nrm must be all set or all NULL", who); return FD_E_INVALID; }
-    // tables of n non-NULL entries, none of which is a shared input
-    const void *ins[8] = {d_P_in, d_dist2, d_tu, d_tv, d_nrm, vec->N, vec->tu, vec->tv};
-    float *const *tabs[6] = {d_P_out, d_falloff_out, vec->N_out, vec->tu_out, vec->tv_out, vec->jacobian};
-    for (int t = 0; t < 6; ++t) {
-        if (!tabs[t]) continue;
-        for (int i = 0; i < b->n; ++i) {
-            const void *o = tabs[t][i];
-            if (!o) { batch_err(b, "%s: output table %d has a NULL entry for context %d", who, t, i); return FD_E_INVALID; }
-            for (const void *in : ins)
-                if (in && o == in) { batch_err(b, "%s: an output of context %d is a shared input array", who, i); return FD_E_INVALID; }
-        }
-    }
     if (N == 0) return FD_OK;
     fd_ctx *c0 = b->ctxs[0];
-    int rc = use_device(c0);
+    rc = use_device(c0);
     if (rc) { batch_err(b, "%s", c0->err); return rc; }
     hipStream_t stream = hip_stream ? (hipStream_t)hip_stream : cur_stream(c0);
     int ek = 0;
@@ -2083,16 +2228,9 @@ int fd_batch_deform_vectors_shared_dev(fd_batch *b, void *hip_stream, int64_t N,
         return rc;
     fd_batch::SharedSet &st = b->sets[b->cur_set];
     SharedVectorArgs a{};
-    a.N = N; a.P_in = d_P_in; a.dist2 = d_dist2; a.tu = d_tu; a.tv = d_tv; a.nrm = d_nrm;
-    a.radius2 = radius2; a.falloffrate = falloffrate;
+    fill_mesh(a, N, d_P_in, d_dist2, d_tu, d_tv, d_nrm, radius2, falloffrate);
     a.Mpad = round_up(c0->M, kRecPad); a.nF = b->n; a.kind = ek;
-    a.vN = vec->N; a.vtu = vec->tu; a.vtv = vec->tv;
-    for (int i = 0; i < b->n; ++i) {
-        a.N_out[i] = vec->N ? vec->N_out[i] : nullptr;
-        a.tu_out[i] = vec->tu ? vec->tu_out[i] : nullptr;
-        a.tv_out[i] = vec->tv ? vec->tv_out[i] : nullptr;
-        a.jacobian[i] = vec->jacobian ? vec->jacobian[i] : nullptr;
-    }
+    fill_vector_tables(a, b->n, vec);
     a.wtiles = st.d_wtiles; a.frames = st.d_frames;
     a.max_wgs = b->eval_cus;
     hipError_t e = launch_vectors_shared(a, stream);
@@ -2134,25 +2272,12 @@ int fd_batch_deform_shared_fp64_dev(fd_batch *b, void *hip_stream, int64_t N, co
 {
     if (!b || !d_P_out) return FD_E_INVALID;
     const char *who = "fd_batch_deform_shared_fp64_dev";
-    if (N < 0 || (N > 0 && !d_P_in)) { batch_err(b, "%s: bad N / P_in", who); return FD_E_INVALID; }
-    if (!frames_ok(d_tu, d_tv, d_nrm)) { batch_err(b, "%s: tu, tv, nrm must be all set or all NULL", who); return FD_E_INVALID; }
-    // aliasing, before any device work: one input serves every frame, so no output may be a shared input -- except the one
-    // frame of a batch of one written in place over the mesh, as in fd_deform_dev
-    const void *ins[5] = {d_P_in, d_dist2, d_tu, d_tv, d_nrm};
-    for (int i = 0; i < b->n; ++i) {
-        if (!d_P_out[i]) { batch_err(b, "%s: NULL output array for context %d", who, i); return FD_E_INVALID; }
-        const void *outs[2] = {d_P_out[i], d_falloff_out ? d_falloff_out[i] : nullptr};
-        for (int o = 0; o < 2; ++o)
-            for (int k = 0; k < 5; ++k) {
-                if (!outs[o] || outs[o] != ins[k]) continue;
-                if (b->n == 1 && o == 0 && k == 0) continue;
-                batch_err(b, "%s: an output of context %d is a shared input array", who, i);
-                return FD_E_INVALID;
-            }
-    }
+    int rc = shot_check_mesh(b, who, N, d_P_in, d_tu, d_tv, d_nrm);
+    if (!rc) rc = shot_check_aliasing(b, who, d_P_in, d_P_out, d_dist2, d_falloff_out, d_tu, d_tv, d_nrm);
+    if (rc) return rc;
     if (N == 0) return FD_OK;
     fd_ctx *c0 = b->ctxs[0];
-    int rc = use_device(c0);
+    rc = use_device(c0);
     if (rc) { batch_err(b, "%s", c0->err); return rc; }
     hipStream_t stream = hip_stream ? (hipStream_t)hip_stream : cur_stream(c0);
     const bool fast = shared64_fast(b);
@@ -2167,10 +2292,8 @@ int fd_batch_deform_shared_fp64_dev(fd_batch *b, void *hip_stream, int64_t N, co
         }
         if (c->output != c0->output) { batch_err(b, "%s: context %d has another fd_set_output setting than context 0", who, i); return FD_E_INVALID; }
     }
-    if (!b->lean && (rc = batch_poll(b))) return rc;           // before the ordering: a repaired model's rebuild is ordered with the rest
-    for (int i = 0; i < b->n; ++i)
-        if ((rc = order_after_batch(b->ctxs[i], stream))) { batch_err(b, "context %d: %s", i, b->ctxs[i]->err); return rc; }
-    if (!make_event(&b->s64_consumed_ev)) { batch_err(b, "%s: hipEventCreate failed", who); return FD_E_DEVICE; }
+    ShotScratch &sc = b->s64;
+    if ((rc = shot_begin(b, who, sc, stream))) return rc;
     if (!fast) {
         // the multilayer model, an eval_variant override: per context, the launch of an FD_EVAL_FP64 context on the shared arrays
         for (int i = 0; i < b->n; ++i) {
@@ -2181,55 +2304,30 @@ int fd_batch_deform_shared_fp64_dev(fd_batch *b, void *hip_stream, int64_t N, co
             if (e != hipSuccess) { batch_err(b, "launch_deform failed: %s", hipGetErrorString(e)); return FD_E_DEVICE; }
         }
         // these launches read the models to their end
-        if (hipEventRecord(b->s64_consumed_ev, stream) != hipSuccess) { (void)hipGetLastError(); return FD_E_DEVICE; }
-        b->s64_consumed = true;
+        if (hipEventRecord(sc.consumed_ev, stream) != hipSuccess) { (void)hipGetLastError(); return FD_E_DEVICE; }
+        sc.consumed = true;
         return FD_OK;
     }
     Shared64Args a{};
-    a.N = N; a.P_in = d_P_in; a.dist2 = d_dist2; a.tu = d_tu; a.tv = d_tv; a.nrm = d_nrm;
-    a.radius2 = radius2; a.falloffrate = falloffrate;
+    fill_mesh(a, N, d_P_in, d_dist2, d_tu, d_tv, d_nrm, radius2, falloffrate);
     a.M = c0->M; a.Mpad = round_up(c0->M, kRecPad); a.nF = b->n; a.kind = eval_kind(c0);
-    bool one_build = c0->rig_build_id != 0;
-    for (int i = 1; i < b->n && one_build; ++i) one_build = b->ctxs[i]->rig_build_id == c0->rig_build_id;
+    const bool same_rig = one_build(b);
     for (int i = 0; i < b->n; ++i) {
         fd_ctx *c = b->ctxs[i];
         a.rec64[i] = c->d_rec64; a.model[i] = c->d_model; a.P_out[i] = d_P_out[i];
-        a.centres[i] = one_build ? c0->d_centres : c->d_centres;       // (one batched build read one array: equal by construction)
+        a.centres[i] = same_rig ? c0->d_centres : c->d_centres;       // (one batched build read one array: equal by construction)
     }
     a.falloff_out = d_falloff_out;
     a.delta_out = c0->output == FD_OUTPUT_DISPLACEMENT;
     a.max_wgs = b->eval_cus;
     const size_t bytes = shared64_scratch_bytes(a.Mpad, a.nF);
-    if (bytes > b->cap_s64) {
-        // (hipFree drains the device: no launch still reads the old scratch)
-        if (b->d_s64) (void)hipFree(b->d_s64);
-        b->d_s64 = nullptr; b->cap_s64 = 0; b->s64_eval_pending = false;
-        if (hipMalloc(&b->d_s64, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            batch_err(b, "%s: scratch allocation (%zu bytes) failed", who, bytes);
-            return FD_E_NOMEM;
-        }
-        b->cap_s64 = bytes;
-    }
-    // the evaluation that last read the scratch must be through with it
-    if (b->s64_eval_pending && hipStreamWaitEvent(stream, b->s64_eval_ev, 0) != hipSuccess) {
-        batch_err(b, "%s: hipStreamWaitEvent failed: %s", who, hipGetErrorString(hipGetLastError()));
-        return FD_E_DEVICE;
-    }
-    b->s64_eval_pending = false;
-    a.scratch = b->d_s64;
-    a.packed_ev = b->s64_consumed_ev;
+    if ((rc = shot_reserve(b, who, sc, bytes, stream))) return rc;
+    a.scratch = sc.d;
+    a.packed_ev = sc.consumed_ev;
     if (b->h_mismatch && hipHostGetDevicePointer((void **)&a.mismatch, b->h_mismatch, 0) != hipSuccess) { (void)hipGetLastError(); a.mismatch = nullptr; }
     hipError_t e = launch_deform_shared64(a, stream);
     if (e != hipSuccess) { batch_err(b, "launch_deform_shared64 failed: %s", hipGetErrorString(e)); return FD_E_DEVICE; }
-    b->s64_consumed = true;
-    if (make_event(&b->s64_eval_ev) && hipEventRecord(b->s64_eval_ev, stream) == hipSuccess) {
-        b->s64_eval_pending = true;
-    } else {
-        // no event to order the next pack kernel by: be safe
-        (void)hipGetLastError();
-        (void)hipStreamSynchronize(stream);
-    }
+    shot_evaluated(sc, stream);
     return FD_OK;
 }
 
@@ -2247,34 +2345,13 @@ int fd_batch_deform_vectors_shared_fp64_dev(fd_batch *b, void *hip_stream, int64
 {
     if (!b || !d_P_out) return FD_E_INVALID;
     const char *who = "fd_batch_deform_vectors_shared_fp64_dev";
-    if (vec && vec->struct_size < (int)sizeof(fd_batch_vectors)) {
-        batch_err(b, "%s: vec->struct_size is %d, must be sizeof(fd_batch_vectors) = %d", who, vec->struct_size, (int)sizeof(fd_batch_vectors));
-        return FD_E_INVALID;
-    }
-    const bool want = vec && (vec->N || vec->N_out || vec->tu || vec->tu_out || vec->tv || vec->tv_out || vec->jacobian);
+    bool want;
+    int rc = shot_check_vectors(b, who, N, d_P_in, d_P_out, d_dist2, d_falloff_out, d_tu, d_tv, d_nrm, vec, &want);
+    if (rc) return rc;
     if (!want)
         return fd_batch_deform_shared_fp64_dev(b, hip_stream, N, d_P_in, d_P_out, d_dist2, d_falloff_out, d_tu, d_tv, d_nrm, radius2, falloffrate);
-    if ((!vec->N != !vec->N_out) || (!vec->tu != !vec->tu_out) || (!vec->tv != !vec->tv_out)) {
-        batch_err(b, "%s: every vector needs its input and its output table (both or neither)", who);
-        return FD_E_INVALID;
-    }
-    if (N < 0 || (N > 0 && !d_P_in)) { batch_err(b, "%s: bad N / P_in", who); return FD_E_INVALID; }
-    if (!frames_ok(d_tu, d_tv, d_nrm)) { batch_err(b, "%s: tu, tv, nrm must be all set or all NULL", who); return FD_E_INVALID; }
-    // tables of n non-NULL entries, none of which is a shared input -- a batch of one included: the vector launch reads d_P_in
-    // after the position launch has written
-    const void *ins[8] = {d_P_in, d_dist2, d_tu, d_tv, d_nrm, vec->N, vec->tu, vec->tv};
-    float *const *tabs[6] = {d_P_out, d_falloff_out, vec->N_out, vec->tu_out, vec->tv_out, vec->jacobian};
-    for (int t = 0; t < 6; ++t) {
-        if (!tabs[t]) continue;
-        for (int i = 0; i < b->n; ++i) {
-            const void *o = tabs[t][i];
-            if (!o) { batch_err(b, "%s: output table %d has a NULL entry for context %d", who, t, i); return FD_E_INVALID; }
-            for (const void *in : ins)
-                if (in && o == in) { batch_err(b, "%s: an output of context %d is a shared input array", who, i); return FD_E_INVALID; }
-        }
-    }
     if (N == 0) return FD_OK;
-    int rc = fd_batch_deform_shared_fp64_dev(b, hip_stream, N, d_P_in, d_P_out, d_dist2, d_falloff_out, d_tu, d_tv, d_nrm, radius2, falloffrate);
+    rc = fd_batch_deform_shared_fp64_dev(b, hip_stream, N, d_P_in, d_P_out, d_dist2, d_falloff_out, d_tu, d_tv, d_nrm, radius2, falloffrate);
     if (rc) return rc;
     fd_ctx *c0 = b->ctxs[0];
     hipStream_t stream = hip_stream ? (hipStream_t)hip_stream : cur_stream(c0);
@@ -2282,38 +2359,18 @@ int fd_batch_deform_vectors_shared_fp64_dev(fd_batch *b, void *hip_stream, int64
         // per context, what fd_deform_vectors_dev launches for an FD_EVAL_FP64 context on the shared arrays (the multilayer model,
         // an eval_variant override -- and so few frames that these launches are the faster way: the positions above are
         // fd_batch_deform_shared_fp64_dev's either way)
-        for (int i = 0; i < b->n; ++i) {
-            DeformArgs a = deform_args(b->ctxs[i], N, d_P_in, d_P_out[i], d_dist2, d_falloff_out ? d_falloff_out[i] : nullptr, d_tu, d_tv,
-                                       d_nrm, radius2, falloffrate);
-            a.precision = FD_EVAL_FP64;
-            const VectorArgs v{vec->N, vec->tu, vec->tv, vec->N ? vec->N_out[i] : nullptr, vec->tu ? vec->tu_out[i] : nullptr,
-                               vec->tv ? vec->tv_out[i] : nullptr, vec->jacobian ? vec->jacobian[i] : nullptr};
-            hipError_t e = launch_vectors(a, v, stream);
-            if (e != hipSuccess) { batch_err(b, "launch_vectors failed: %s", hipGetErrorString(e)); return FD_E_DEVICE; }
-        }
-        // these launches read the models to their end
-        if (hipEventRecord(b->s64_consumed_ev, stream) != hipSuccess) { (void)hipGetLastError(); return FD_E_DEVICE; }
-        return FD_OK;
+        return vectors_per_context(b, stream, FD_EVAL_FP64, b->s64.consumed_ev, N, d_P_in, d_P_out, d_dist2, d_falloff_out, d_tu, d_tv, d_nrm,
+                                   radius2, falloffrate, vec);
     }
     SharedVector64Args a{};
-    a.N = N; a.P_in = d_P_in; a.dist2 = d_dist2; a.tu = d_tu; a.tv = d_tv; a.nrm = d_nrm;
-    a.radius2 = radius2; a.falloffrate = falloffrate;
+    fill_mesh(a, N, d_P_in, d_dist2, d_tu, d_tv, d_nrm, radius2, falloffrate);
     a.Mpad = round_up(c0->M, kRecPad); a.nF = b->n; a.kind = eval_kind(c0);
-    a.vN = vec->N; a.vtu = vec->tu; a.vtv = vec->tv;
-    for (int i = 0; i < b->n; ++i) {
-        a.N_out[i] = vec->N ? vec->N_out[i] : nullptr;
-        a.tu_out[i] = vec->tu ? vec->tu_out[i] : nullptr;
-        a.tv_out[i] = vec->tv ? vec->tv_out[i] : nullptr;
-        a.jacobian[i] = vec->jacobian ? vec->jacobian[i] : nullptr;
-    }
-    a.scratch = b->d_s64;
+    fill_vector_tables(a, b->n, vec);
+    a.scratch = b->s64.d;
     a.max_wgs = b->eval_cus;
     hipError_t e = launch_vectors_shared64(a, stream);
     if (e != hipSuccess) { batch_err(b, "launch_vectors_shared64 failed: %s", hipGetErrorString(e)); return FD_E_DEVICE; }
-    // the next pack kernel rewrites the scratch this launch reads: its event moves behind the vector launch
-    if (b->s64_eval_pending && hipEventRecord(b->s64_eval_ev, stream) == hipSuccess) return FD_OK;
-    (void)hipGetLastError();
-    (void)hipStreamSynchronize(stream);
+    shot_vectors_evaluated(b->s64, stream);
     return FD_OK;
 }
 
@@ -2345,75 +2402,34 @@ int fd_batch_deform_shared_ml_dev(fd_batch *b, void *hip_stream, int64_t N, cons
 {
     if (!b || !d_P_out) return FD_E_INVALID;
     const char *who = "fd_batch_deform_shared_ml_dev";
-    if (N < 0 || (N > 0 && !d_P_in)) { batch_err(b, "%s: bad N / P_in", who); return FD_E_INVALID; }
-    if (!frames_ok(d_tu, d_tv, d_nrm)) { batch_err(b, "%s: tu, tv, nrm must be all set or all NULL", who); return FD_E_INVALID; }
-    // aliasing, before any device work (as fd_batch_deform_shared_fp64_dev): one input serves every frame, so no output may be
-    // a shared input -- except the one frame of a batch of one written in place over the mesh
-    const void *ins[5] = {d_P_in, d_dist2, d_tu, d_tv, d_nrm};
-    for (int i = 0; i < b->n; ++i) {
-        if (!d_P_out[i]) { batch_err(b, "%s: NULL output array for context %d", who, i); return FD_E_INVALID; }
-        const void *outs[2] = {d_P_out[i], d_falloff_out ? d_falloff_out[i] : nullptr};
-        for (int o = 0; o < 2; ++o)
-            for (int k = 0; k < 5; ++k) {
-                if (!outs[o] || outs[o] != ins[k]) continue;
-                if (b->n == 1 && o == 0 && k == 0) continue;
-                batch_err(b, "%s: an output of context %d is a shared input array", who, i);
-                return FD_E_INVALID;
-            }
-    }
+    int rc = shot_check_mesh(b, who, N, d_P_in, d_tu, d_tv, d_nrm);
+    if (!rc) rc = shot_check_aliasing(b, who, d_P_in, d_P_out, d_dist2, d_falloff_out, d_tu, d_tv, d_nrm);
+    if (rc) return rc;
     if (N == 0) return FD_OK;
     if (!shared_ml_fast(b))
         return fd_batch_deform_shared_dev(b, hip_stream, N, d_P_in, d_P_out, d_dist2, d_falloff_out, d_tu, d_tv, d_nrm, radius2, falloffrate);
     fd_ctx *c0 = b->ctxs[0];
-    int rc = use_device(c0);
+    rc = use_device(c0);
     if (rc) { batch_err(b, "%s", c0->err); return rc; }
     hipStream_t stream = hip_stream ? (hipStream_t)hip_stream : cur_stream(c0);
-    if (!b->lean && (rc = batch_poll(b))) return rc;           // before the ordering: a repaired model's rebuild is ordered with the rest
-    for (int i = 0; i < b->n; ++i)
-        if ((rc = order_after_batch(b->ctxs[i], stream))) { batch_err(b, "context %d: %s", i, b->ctxs[i]->err); return rc; }
-    if (!make_event(&b->sml_consumed_ev)) { batch_err(b, "%s: hipEventCreate failed", who); return FD_E_DEVICE; }
+    ShotScratch &sc = b->sml;
+    if ((rc = shot_begin(b, who, sc, stream))) return rc;
     SharedMlArgs a{};
-    a.N = N; a.P_in = d_P_in; a.dist2 = d_dist2; a.tu = d_tu; a.tv = d_tv; a.nrm = d_nrm;
-    a.radius2 = radius2; a.falloffrate = falloffrate;
+    fill_mesh(a, N, d_P_in, d_dist2, d_tu, d_tv, d_nrm, radius2, falloffrate);
     a.M = c0->M; a.layers = ml_layers(c0); a.nF = b->n;
-    bool one_build = c0->rig_build_id != 0;
-    for (int i = 1; i < b->n && one_build; ++i) one_build = b->ctxs[i]->rig_build_id == c0->rig_build_id;
-    a.check_rig = one_build ? 0 : 1;                           // (one batched build read one array: equal by construction)
+    a.check_rig = one_build(b) ? 0 : 1;                        // (one batched build read one array: equal by construction)
     for (int i = 0; i < b->n; ++i) { a.rec32[i] = b->ctxs[i]->d_rec32; a.model[i] = b->ctxs[i]->d_model; a.P_out[i] = d_P_out[i]; }
     a.falloff_out = d_falloff_out;
     a.delta_out = c0->output == FD_OUTPUT_DISPLACEMENT;
     a.max_wgs = b->eval_cus;
     const size_t bytes = shared_ml_scratch_bytes(a.M, a.layers, a.nF);
-    if (bytes > b->cap_sml) {
-        // (hipFree drains the device: no launch still reads the old scratch)
-        if (b->d_sml) (void)hipFree(b->d_sml);
-        b->d_sml = nullptr; b->cap_sml = 0; b->sml_eval_pending = false;
-        if (hipMalloc(&b->d_sml, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            batch_err(b, "%s: scratch allocation (%zu bytes) failed", who, bytes);
-            return FD_E_NOMEM;
-        }
-        b->cap_sml = bytes;
-    }
-    // the evaluation that last read the scratch must be through with it
-    if (b->sml_eval_pending && hipStreamWaitEvent(stream, b->sml_eval_ev, 0) != hipSuccess) {
-        batch_err(b, "%s: hipStreamWaitEvent failed: %s", who, hipGetErrorString(hipGetLastError()));
-        return FD_E_DEVICE;
-    }
-    b->sml_eval_pending = false;
-    a.scratch = b->d_sml;
-    a.packed_ev = b->sml_consumed_ev;
+    if ((rc = shot_reserve(b, who, sc, bytes, stream))) return rc;
+    a.scratch = sc.d;
+    a.packed_ev = sc.consumed_ev;
     if (b->h_mismatch && hipHostGetDevicePointer((void **)&a.mismatch, b->h_mismatch, 0) != hipSuccess) { (void)hipGetLastError(); a.mismatch = nullptr; }
     hipError_t e = launch_deform_shared_ml(a, stream);
     if (e != hipSuccess) { batch_err(b, "launch_deform_shared_ml failed: %s", hipGetErrorString(e)); return FD_E_DEVICE; }
-    b->sml_consumed = true;
-    if (make_event(&b->sml_eval_ev) && hipEventRecord(b->sml_eval_ev, stream) == hipSuccess) {
-        b->sml_eval_pending = true;
-    } else {
-        // no event to order the next pack kernel by: be safe
-        (void)hipGetLastError();
-        (void)hipStreamSynchronize(stream);
-    }
+    shot_evaluated(sc, stream);
     return FD_OK;
 }
 
@@ -2431,76 +2447,37 @@ int fd_batch_deform_vectors_shared_ml_dev(fd_batch *b, void *hip_stream, int64_t
 {
     if (!b || !d_P_out) return FD_E_INVALID;
     const char *who = "fd_batch_deform_vectors_shared_ml_dev";
-    if (vec && vec->struct_size < (int)sizeof(fd_batch_vectors)) {
-        batch_err(b, "%s: vec->struct_size is %d, must be sizeof(fd_batch_vectors) = %d", who, vec->struct_size, (int)sizeof(fd_batch_vectors));
-        return FD_E_INVALID;
-    }
-    const bool want = vec && (vec->N || vec->N_out || vec->tu || vec->tu_out || vec->tv || vec->tv_out || vec->jacobian);
+    bool want;
+    int rc = shot_check_vectors(b, who, N, d_P_in, d_P_out, d_dist2, d_falloff_out, d_tu, d_tv, d_nrm, vec, &want);
+    if (rc) return rc;
     if (!want)
         return fd_batch_deform_shared_ml_dev(b, hip_stream, N, d_P_in, d_P_out, d_dist2, d_falloff_out, d_tu, d_tv, d_nrm, radius2, falloffrate);
-    if ((!vec->N != !vec->N_out) || (!vec->tu != !vec->tu_out) || (!vec->tv != !vec->tv_out)) {
-        batch_err(b, "%s: every vector needs its input and its output table (both or neither)", who);
-        return FD_E_INVALID;
-    }
-    if (N < 0 || (N > 0 && !d_P_in)) { batch_err(b, "%s: bad N / P_in", who); return FD_E_INVALID; }
-    if (!frames_ok(d_tu, d_tv, d_nrm)) { batch_err(b, "%s: tu, tv, nrm must be all set or all NULL", who); return FD_E_INVALID; }
-    // tables of n non-NULL entries, none of which is a shared input -- a batch of one included: the vector launch reads d_P_in
-    // after the position launch has written
-    const void *ins[8] = {d_P_in, d_dist2, d_tu, d_tv, d_nrm, vec->N, vec->tu, vec->tv};
-    float *const *tabs[6] = {d_P_out, d_falloff_out, vec->N_out, vec->tu_out, vec->tv_out, vec->jacobian};
-    for (int t = 0; t < 6; ++t) {
-        if (!tabs[t]) continue;
-        for (int i = 0; i < b->n; ++i) {
-            const void *o = tabs[t][i];
-            if (!o) { batch_err(b, "%s: output table %d has a NULL entry for context %d", who, t, i); return FD_E_INVALID; }
-            for (const void *in : ins)
-                if (in && o == in) { batch_err(b, "%s: an output of context %d is a shared input array", who, i); return FD_E_INVALID; }
-        }
-    }
     if (N == 0) return FD_OK;
     // other kinds, fp64 contexts, an eval_variant override, an imported model, layer counts outside 1..8, fewer frames than the
     // position launch takes: the one-layer call's, before anything of this one's is touched
     if (!shared_ml_fast(b))
         return fd_batch_deform_vectors_shared_dev(b, hip_stream, N, d_P_in, d_P_out, d_dist2, d_falloff_out, d_tu, d_tv, d_nrm, radius2,
                                                   falloffrate, vec);
-    int rc = fd_batch_deform_shared_ml_dev(b, hip_stream, N, d_P_in, d_P_out, d_dist2, d_falloff_out, d_tu, d_tv, d_nrm, radius2, falloffrate);
+    rc = fd_batch_deform_shared_ml_dev(b, hip_stream, N, d_P_in, d_P_out, d_dist2, d_falloff_out, d_tu, d_tv, d_nrm, radius2, falloffrate);
     if (rc) return rc;
     fd_ctx *c0 = b->ctxs[0];
     hipStream_t stream = hip_stream ? (hipStream_t)hip_stream : cur_stream(c0);
     if (b->n < shared_vectors_ml_min_frames(ml_layers(c0))) {
         // so few frames that the per-context launches are the faster way: what fd_deform_vectors_dev launches for an
-        // FD_EVAL_FP32 context on the shared arrays (the positions above are fd_batch_deform_shared_ml_dev's either way)
-        for (int i = 0; i < b->n; ++i) {
-            DeformArgs a = deform_args(b->ctxs[i], N, d_P_in, d_P_out[i], d_dist2, d_falloff_out ? d_falloff_out[i] : nullptr, d_tu, d_tv,
-                                       d_nrm, radius2, falloffrate);
-            const VectorArgs v{vec->N, vec->tu, vec->tv, vec->N ? vec->N_out[i] : nullptr, vec->tu ? vec->tu_out[i] : nullptr,
-                               vec->tv ? vec->tv_out[i] : nullptr, vec->jacobian ? vec->jacobian[i] : nullptr};
-            hipError_t e = launch_vectors(a, v, stream);
-            if (e != hipSuccess) { batch_err(b, "launch_vectors failed: %s", hipGetErrorString(e)); return FD_E_DEVICE; }
-        }
-        // these launches read the models to their end
-        if (hipEventRecord(b->sml_consumed_ev, stream) != hipSuccess) { (void)hipGetLastError(); return FD_E_DEVICE; }
-        return FD_OK;
+        // FD_EVAL_FP32 context -- which shared_ml_fast demands every context to be -- on the shared arrays (the positions above
+        // are fd_batch_deform_shared_ml_dev's either way)
+        return vectors_per_context(b, stream, FD_EVAL_FP32, b->sml.consumed_ev, N, d_P_in, d_P_out, d_dist2, d_falloff_out, d_tu, d_tv, d_nrm,
+                                   radius2, falloffrate, vec);
     }
     SharedVectorMlArgs a{};
-    a.N = N; a.P_in = d_P_in; a.dist2 = d_dist2; a.tu = d_tu; a.tv = d_tv; a.nrm = d_nrm;
-    a.radius2 = radius2; a.falloffrate = falloffrate;
+    fill_mesh(a, N, d_P_in, d_dist2, d_tu, d_tv, d_nrm, radius2, falloffrate);
     a.M = c0->M; a.layers = ml_layers(c0); a.nF = b->n;
-    a.vN = vec->N; a.vtu = vec->tu; a.vtv = vec->tv;
-    for (int i = 0; i < b->n; ++i) {
-        a.N_out[i] = vec->N ? vec->N_out[i] : nullptr;
-        a.tu_out[i] = vec->tu ? vec->tu_out[i] : nullptr;
-        a.tv_out[i] = vec->tv ? vec->tv_out[i] : nullptr;
-        a.jacobian[i] = vec->jacobian ? vec->jacobian[i] : nullptr;
-    }
-    a.scratch = b->d_sml;
+    fill_vector_tables(a, b->n, vec);
+    a.scratch = b->sml.d;
     a.max_wgs = b->eval_cus;
     hipError_t e = launch_vectors_shared_ml(a, stream);
     if (e != hipSuccess) { batch_err(b, "launch_vectors_shared_ml failed: %s", hipGetErrorString(e)); return FD_E_DEVICE; }
-    // the next pack kernel rewrites the scratch this launch reads: its event moves behind the vector launch
-    if (b->sml_eval_pending && hipEventRecord(b->sml_eval_ev, stream) == hipSuccess) return FD_OK;
-    (void)hipGetLastError();
-    (void)hipStreamSynchronize(stream);
+    shot_vectors_evaluated(b->sml, stream);
     return FD_OK;
 }
 
@@ -2532,75 +2509,34 @@ int fd_batch_deform_shared_ml_fp64_dev(fd_batch *b, void *hip_stream, int64_t N,
 {
     if (!b || !d_P_out) return FD_E_INVALID;
     const char *who = "fd_batch_deform_shared_ml_fp64_dev";
-    if (N < 0 || (N > 0 && !d_P_in)) { batch_err(b, "%s: bad N / P_in", who); return FD_E_INVALID; }
-    if (!frames_ok(d_tu, d_tv, d_nrm)) { batch_err(b, "%s: tu, tv, nrm must be all set or all NULL", who); return FD_E_INVALID; }
-    // aliasing, before any device work (as fd_batch_deform_shared_fp64_dev): one input serves every frame, so no output may be
-    // a shared input -- except the one frame of a batch of one written in place over the mesh
-    const void *ins[5] = {d_P_in, d_dist2, d_tu, d_tv, d_nrm};
-    for (int i = 0; i < b->n; ++i) {
-        if (!d_P_out[i]) { batch_err(b, "%s: NULL output array for context %d", who, i); return FD_E_INVALID; }
-        const void *outs[2] = {d_P_out[i], d_falloff_out ? d_falloff_out[i] : nullptr};
-        for (int o = 0; o < 2; ++o)
-            for (int k = 0; k < 5; ++k) {
-                if (!outs[o] || outs[o] != ins[k]) continue;
-                if (b->n == 1 && o == 0 && k == 0) continue;
-                batch_err(b, "%s: an output of context %d is a shared input array", who, i);
-                return FD_E_INVALID;
-            }
-    }
+    int rc = shot_check_mesh(b, who, N, d_P_in, d_tu, d_tv, d_nrm);
+    if (!rc) rc = shot_check_aliasing(b, who, d_P_in, d_P_out, d_dist2, d_falloff_out, d_tu, d_tv, d_nrm);
+    if (rc) return rc;
     if (N == 0) return FD_OK;
     if (!shared_ml64_fast(b))
         return fd_batch_deform_shared_fp64_dev(b, hip_stream, N, d_P_in, d_P_out, d_dist2, d_falloff_out, d_tu, d_tv, d_nrm, radius2, falloffrate);
     fd_ctx *c0 = b->ctxs[0];
-    int rc = use_device(c0);
+    rc = use_device(c0);
     if (rc) { batch_err(b, "%s", c0->err); return rc; }
     hipStream_t stream = hip_stream ? (hipStream_t)hip_stream : cur_stream(c0);
-    if (!b->lean && (rc = batch_poll(b))) return rc;           // before the ordering: a repaired model's rebuild is ordered with the rest
-    for (int i = 0; i < b->n; ++i)
-        if ((rc = order_after_batch(b->ctxs[i], stream))) { batch_err(b, "context %d: %s", i, b->ctxs[i]->err); return rc; }
-    if (!make_event(&b->sml64_consumed_ev)) { batch_err(b, "%s: hipEventCreate failed", who); return FD_E_DEVICE; }
+    ShotScratch &sc = b->sml64;
+    if ((rc = shot_begin(b, who, sc, stream))) return rc;
     SharedMl64Args a{};
-    a.N = N; a.P_in = d_P_in; a.dist2 = d_dist2; a.tu = d_tu; a.tv = d_tv; a.nrm = d_nrm;
-    a.radius2 = radius2; a.falloffrate = falloffrate;
+    fill_mesh(a, N, d_P_in, d_dist2, d_tu, d_tv, d_nrm, radius2, falloffrate);
     a.M = c0->M; a.layers = ml_layers(c0); a.nF = b->n;
-    bool one_build = c0->rig_build_id != 0;
-    for (int i = 1; i < b->n && one_build; ++i) one_build = b->ctxs[i]->rig_build_id == c0->rig_build_id;
-    a.check_rig = one_build ? 0 : 1;                           // (one batched build read one array: equal by construction)
+    a.check_rig = one_build(b) ? 0 : 1;                        // (one batched build read one array: equal by construction)
     for (int i = 0; i < b->n; ++i) { a.rec64[i] = b->ctxs[i]->d_rec64; a.model[i] = b->ctxs[i]->d_model; a.P_out[i] = d_P_out[i]; }
     a.falloff_out = d_falloff_out;
     a.delta_out = c0->output == FD_OUTPUT_DISPLACEMENT;
     a.max_wgs = b->eval_cus;
     const size_t bytes = shared_ml64_scratch_bytes(a.M, a.layers, a.nF);
-    if (bytes > b->cap_sml64) {
-        // (hipFree drains the device: no launch still reads the old scratch)
-        if (b->d_sml64) (void)hipFree(b->d_sml64);
-        b->d_sml64 = nullptr; b->cap_sml64 = 0; b->sml64_eval_pending = false;
-        if (hipMalloc(&b->d_sml64, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            batch_err(b, "%s: scratch allocation (%zu bytes) failed", who, bytes);
-            return FD_E_NOMEM;
-        }
-        b->cap_sml64 = bytes;
-    }
-    // the evaluation that last read the scratch must be through with it
-    if (b->sml64_eval_pending && hipStreamWaitEvent(stream, b->sml64_eval_ev, 0) != hipSuccess) {
-        batch_err(b, "%s: hipStreamWaitEvent failed: %s", who, hipGetErrorString(hipGetLastError()));
-        return FD_E_DEVICE;
-    }
-    b->sml64_eval_pending = false;
-    a.scratch = b->d_sml64;
-    a.packed_ev = b->sml64_consumed_ev;
+    if ((rc = shot_reserve(b, who, sc, bytes, stream))) return rc;
+    a.scratch = sc.d;
+    a.packed_ev = sc.consumed_ev;
     if (b->h_mismatch && hipHostGetDevicePointer((void **)&a.mismatch, b->h_mismatch, 0) != hipSuccess) { (void)hipGetLastError(); a.mismatch = nullptr; }
     hipError_t e = launch_deform_shared_ml64(a, stream);
     if (e != hipSuccess) { batch_err(b, "launch_deform_shared_ml64 failed: %s", hipGetErrorString(e)); return FD_E_DEVICE; }
-    b->sml64_consumed = true;
-    if (make_event(&b->sml64_eval_ev) && hipEventRecord(b->sml64_eval_ev, stream) == hipSuccess) {
-        b->sml64_eval_pending = true;
-    } else {
-        // no event to order the next pack kernel by: be safe
-        (void)hipGetLastError();
-        (void)hipStreamSynchronize(stream);
-    }
+    shot_evaluated(sc, stream);
     return FD_OK;
 }
 
@@ -2618,77 +2554,36 @@ int fd_batch_deform_vectors_shared_ml_fp64_dev(fd_batch *b, void *hip_stream, in
 {
     if (!b || !d_P_out) return FD_E_INVALID;
     const char *who = "fd_batch_deform_vectors_shared_ml_fp64_dev";
-    if (vec && vec->struct_size < (int)sizeof(fd_batch_vectors)) {
-        batch_err(b, "%s: vec->struct_size is %d, must be sizeof(fd_batch_vectors) = %d", who, vec->struct_size, (int)sizeof(fd_batch_vectors));
-        return FD_E_INVALID;
-    }
-    const bool want = vec && (vec->N || vec->N_out || vec->tu || vec->tu_out || vec->tv || vec->tv_out || vec->jacobian);
+    bool want;
+    int rc = shot_check_vectors(b, who, N, d_P_in, d_P_out, d_dist2, d_falloff_out, d_tu, d_tv, d_nrm, vec, &want);
+    if (rc) return rc;
     if (!want)
         return fd_batch_deform_shared_ml_fp64_dev(b, hip_stream, N, d_P_in, d_P_out, d_dist2, d_falloff_out, d_tu, d_tv, d_nrm, radius2, falloffrate);
-    if ((!vec->N != !vec->N_out) || (!vec->tu != !vec->tu_out) || (!vec->tv != !vec->tv_out)) {
-        batch_err(b, "%s: every vector needs its input and its output table (both or neither)", who);
-        return FD_E_INVALID;
-    }
-    if (N < 0 || (N > 0 && !d_P_in)) { batch_err(b, "%s: bad N / P_in", who); return FD_E_INVALID; }
-    if (!frames_ok(d_tu, d_tv, d_nrm)) { batch_err(b, "%s: tu, tv, nrm must be all set or all NULL", who); return FD_E_INVALID; }
-    // tables of n non-NULL entries, none of which is a shared input -- a batch of one included: the vector launch reads d_P_in
-    // after the position launch has written
-    const void *ins[8] = {d_P_in, d_dist2, d_tu, d_tv, d_nrm, vec->N, vec->tu, vec->tv};
-    float *const *tabs[6] = {d_P_out, d_falloff_out, vec->N_out, vec->tu_out, vec->tv_out, vec->jacobian};
-    for (int t = 0; t < 6; ++t) {
-        if (!tabs[t]) continue;
-        for (int i = 0; i < b->n; ++i) {
-            const void *o = tabs[t][i];
-            if (!o) { batch_err(b, "%s: output table %d has a NULL entry for context %d", who, t, i); return FD_E_INVALID; }
-            for (const void *in : ins)
-                if (in && o == in) { batch_err(b, "%s: an output of context %d is a shared input array", who, i); return FD_E_INVALID; }
-        }
-    }
     if (N == 0) return FD_OK;
     // other kinds, an eval_variant override, an imported model, layer counts outside 1..8: the one-layer call's, before
     // anything of this one's is touched
     if (!shared_ml64_fast(b))
         return fd_batch_deform_vectors_shared_fp64_dev(b, hip_stream, N, d_P_in, d_P_out, d_dist2, d_falloff_out, d_tu, d_tv, d_nrm, radius2,
                                                        falloffrate, vec);
-    int rc = fd_batch_deform_shared_ml_fp64_dev(b, hip_stream, N, d_P_in, d_P_out, d_dist2, d_falloff_out, d_tu, d_tv, d_nrm, radius2, falloffrate);
+    rc = fd_batch_deform_shared_ml_fp64_dev(b, hip_stream, N, d_P_in, d_P_out, d_dist2, d_falloff_out, d_tu, d_tv, d_nrm, radius2, falloffrate);
     if (rc) return rc;
     fd_ctx *c0 = b->ctxs[0];
     hipStream_t stream = hip_stream ? (hipStream_t)hip_stream : cur_stream(c0);
     if (b->n < shared_vectors_ml64_min_frames(ml_layers(c0))) {
         // so few frames that the per-context launches are the faster way: what fd_deform_vectors_dev launches for an
         // FD_EVAL_FP64 context on the shared arrays (the positions above are fd_batch_deform_shared_ml_fp64_dev's either way)
-        for (int i = 0; i < b->n; ++i) {
-            DeformArgs a = deform_args(b->ctxs[i], N, d_P_in, d_P_out[i], d_dist2, d_falloff_out ? d_falloff_out[i] : nullptr, d_tu, d_tv,
-                                       d_nrm, radius2, falloffrate);
-            a.precision = FD_EVAL_FP64;
-            const VectorArgs v{vec->N, vec->tu, vec->tv, vec->N ? vec->N_out[i] : nullptr, vec->tu ? vec->tu_out[i] : nullptr,
-                               vec->tv ? vec->tv_out[i] : nullptr, vec->jacobian ? vec->jacobian[i] : nullptr};
-            hipError_t e = launch_vectors(a, v, stream);
-            if (e != hipSuccess) { batch_err(b, "launch_vectors failed: %s", hipGetErrorString(e)); return FD_E_DEVICE; }
-        }
-        // these launches read the models to their end
-        if (hipEventRecord(b->sml64_consumed_ev, stream) != hipSuccess) { (void)hipGetLastError(); return FD_E_DEVICE; }
-        return FD_OK;
+        return vectors_per_context(b, stream, FD_EVAL_FP64, b->sml64.consumed_ev, N, d_P_in, d_P_out, d_dist2, d_falloff_out, d_tu, d_tv, d_nrm,
+                                   radius2, falloffrate, vec);
     }
     SharedVectorMl64Args a{};
-    a.N = N; a.P_in = d_P_in; a.dist2 = d_dist2; a.tu = d_tu; a.tv = d_tv; a.nrm = d_nrm;
-    a.radius2 = radius2; a.falloffrate = falloffrate;
+    fill_mesh(a, N, d_P_in, d_dist2, d_tu, d_tv, d_nrm, radius2, falloffrate);
     a.M = c0->M; a.layers = ml_layers(c0); a.nF = b->n;
-    a.vN = vec->N; a.vtu = vec->tu; a.vtv = vec->tv;
-    for (int i = 0; i < b->n; ++i) {
-        a.N_out[i] = vec->N ? vec->N_out[i] : nullptr;
-        a.tu_out[i] = vec->tu ? vec->tu_out[i] : nullptr;
-        a.tv_out[i] = vec->tv ? vec->tv_out[i] : nullptr;
-        a.jacobian[i] = vec->jacobian ? vec->jacobian[i] : nullptr;
-    }
-    a.scratch = b->d_sml64;
+    fill_vector_tables(a, b->n, vec);
+    a.scratch = b->sml64.d;
     a.max_wgs = b->eval_cus;
     hipError_t e = launch_vectors_shared_ml64(a, stream);
     if (e != hipSuccess) { batch_err(b, "launch_vectors_shared_ml64 failed: %s", hipGetErrorString(e)); return FD_E_DEVICE; }
-    // the next pack kernel rewrites the scratch this launch reads: its event moves behind the vector launch
-    if (b->sml64_eval_pending && hipEventRecord(b->sml64_eval_ev, stream) == hipSuccess) return FD_OK;
-    (void)hipGetLastError();
-    (void)hipStreamSynchronize(stream);
+    shot_vectors_evaluated(b->sml64, stream);
     return FD_OK;
 }
 
@@ -2701,19 +2596,21 @@ int fd_batch_wait_consumed(fd_batch *b, void *hip_stream)
 {
     if (!b) return FD_E_INVALID;
     hipEvent_t ev = b->consumed_override ? b->consumed_override : (b->packed_valid ? b->sets[b->cur_set].packed_ev : b->fallback_ev);
-    hipEvent_t ev64 = b->s64_consumed ? b->s64_consumed_ev : nullptr;       // fd_batch_deform_shared_fp64_dev's reads as well
-    hipEvent_t evml = b->sml_consumed ? b->sml_consumed_ev : nullptr;       // fd_batch_deform_shared_ml_dev's
-    hipEvent_t evml64 = b->sml64_consumed ? b->sml64_consumed_ev : nullptr; // fd_batch_deform_shared_ml_fp64_dev's
-    if (!ev && !ev64 && !evml && !evml64) return FD_OK;          // no shared-rig evaluation enqueued: nothing reads the models beyond stream order
+    // ... and the reads of the calls that keep a scratch of their own as well
+    hipEvent_t evs[4] = {ev, nullptr, nullptr, nullptr};
+    int n_ev = ev ? 1 : 0;
+    for (const ShotScratch *sc : {&b->s64, &b->sml, &b->sml64})
+        if (sc->consumed) evs[n_ev++] = sc->consumed_ev;
+    if (n_ev == 0) return FD_OK;                 // no shared-rig evaluation enqueued: nothing reads the models beyond stream order
     fd_ctx *c0 = b->ctxs[0];
     int rc = use_device(c0);
     if (rc) { batch_err(b, "%s", c0->err); return rc; }
     hipStream_t stream = hip_stream ? (hipStream_t)hip_stream : cur_stream(c0);
-    if ((ev && hipStreamWaitEvent(stream, ev, 0) != hipSuccess) || (ev64 && hipStreamWaitEvent(stream, ev64, 0) != hipSuccess) ||
-        (evml && hipStreamWaitEvent(stream, evml, 0) != hipSuccess) || (evml64 && hipStreamWaitEvent(stream, evml64, 0) != hipSuccess)) {
-        batch_err(b, "fd_batch_wait_consumed: hipStreamWaitEvent failed: %s", hipGetErrorString(hipGetLastError()));
-        return FD_E_DEVICE;
-    }
+    for (int i = 0; i < n_ev; ++i)
+        if (hipStreamWaitEvent(stream, evs[i], 0) != hipSuccess) {
+            batch_err(b, "fd_batch_wait_consumed: hipStreamWaitEvent failed: %s", hipGetErrorString(hipGetLastError()));
+            return FD_E_DEVICE;
+        }
     return FD_OK;
 }
 
