@@ -163,6 +163,8 @@ struct fd_batch {
     int shared_factor = 0;               // fd_batch_set_shared_factor: one factorisation per build where the contexts share the rest rig
     double *d_fac = nullptr;             // ... and its scratch (reg_factor_doubles())
     int last_shared_factor = 0;          // the last build took that path
+    void *d_mlfac = nullptr;             // multilayer batches: the L layer factors' scratch (ml_shared_scratch_bytes), allocated at the first such build
+    size_t cap_mlfac = 0;
     int cur_set = 0;                     // the set packed last
     bool packed_valid = false;           // sets[cur_set].packed_ev is recorded (fd_batch_wait_consumed)
     bool prepared = false;               // sets[cur_set] holds the contexts' CURRENT models and prep_* outputs
@@ -1617,6 +1619,7 @@ void fd_batch_destroy(fd_batch *b)
         if (st.eval_ev) (void)hipEventDestroy(st.eval_ev);
     }
     if (b->d_fac) (void)hipFree(b->d_fac);
+    if (b->d_mlfac) (void)hipFree(b->d_mlfac);
     if (b->fallback_ev) (void)hipEventDestroy(b->fallback_ev);
     for (ShotScratch *sc : {&b->s64, &b->sml, &b->sml64}) shot_free(*sc);
     if (b->group_ev) (void)hipEventDestroy(b->group_ev);
@@ -1716,8 +1719,23 @@ int fd_batch_build_async(fd_batch *b, void *hip_stream)
     bb.reg_front = (b->eval_cus <= 0 || b->eval_cus >= (int)device_cus()) ? 1 : 0;
     bb.group_panels = b->n >= 4 ? 1 : 0;
 
+    // every context reads its rest rig in place from ONE array, in this one launch sequence: their centres are equal by construction
+    bool same_rest_launch = b->have_src;
+    for (int i = 1; i < b->n && same_rest_launch; ++i) same_rest_launch = b->src.rest[i] == b->src.rest[0];
+    // A shot of multilayer models (fd_batch_set_shared_factor): one factorisation per LAYER for the group, every frame's
+    // right-hand sides through them in one launch (launch_build_ml_shared).  Anything it does not take -- other rest arrays,
+    // one context, more than 1024 points, no scratch -- builds every model on its own as ever.
+    bool shared_ml = b->shared_factor != 0 && bb.ml_layers > 0 && same_rest_launch && ml_shared_applies(bb.M, bb.ml_layers, b->n);
+    if (shared_ml && ml_shared_init() != hipSuccess) { (void)hipGetLastError(); shared_ml = false; }
+    if (shared_ml && ml_shared_scratch_bytes(bb) > b->cap_mlfac) {
+        if (b->d_mlfac) (void)hipFree(b->d_mlfac);          // (hipFree drains the device: nobody reads the old scratch)
+        b->d_mlfac = nullptr; b->cap_mlfac = 0;
+        if (hipMalloc(&b->d_mlfac, ml_shared_scratch_bytes(bb)) != hipSuccess) { (void)hipGetLastError(); b->d_mlfac = nullptr; shared_ml = false; }
+        else b->cap_mlfac = ml_shared_scratch_bytes(bb);
+    }
+
     const GraphKey key = graph_key(c0, (bb.spd << 9) | (bb.small << 10) | (bb.reg << 11) | (bb.nopivot << 12), false);
-    if (!bb.reg && b->use_graph &&
+    if (!bb.reg && !shared_ml && b->use_graph &&
         ensure_graph(stream, &b->exec, &b->key, key, [&] { return launch_build(bb, stream, nullptr); }) != hipSuccess)
         b->use_graph = false;
 #define FD_BHIP(call)                                                                         \
@@ -1728,15 +1746,12 @@ int fd_batch_build_async(fd_batch *b, void *hip_stream)
     // One factorisation for the group (fd_batch_set_shared_factor): the register-resident build applies and every context reads
     // its rest rig, in place, from the SAME device array (fd_batch_set_points_dev with one rest pointer); anything else builds
     // every model on its own as ever.
-    // every context reads its rest rig in place from ONE array, in this one launch sequence: their centres are equal by construction
-    bool same_rest_launch = b->have_src;
-    for (int i = 1; i < b->n && same_rest_launch; ++i) same_rest_launch = b->src.rest[i] == b->src.rest[0];
     const bool shared_fac_ok = same_rest_launch;
     bool shared_fac = b->shared_factor != 0 && bb.reg && shared_fac_ok && b->n > 1;
     if (shared_fac && !b->d_fac && hipMalloc((void **)&b->d_fac, sizeof(double) * reg_factor_doubles()) != hipSuccess) {
         (void)hipGetLastError(); b->d_fac = nullptr; shared_fac = false;
     }
-    b->last_shared_factor = shared_fac ? 1 : 0;
+    b->last_shared_factor = (shared_fac || shared_ml) ? 1 : 0;
     if (!b->lean) FD_BHIP(hipEventRecord(b->ev0, stream));      // (lean: the group's first packet is its first kernel; the reports carry no phase times)
     if (shared_fac) {
         FD_BHIP(launch_build_reg_shared(bb, stream, &b->src, nullptr, b->d_fac));
@@ -1750,7 +1765,11 @@ int fd_batch_build_async(fd_batch *b, void *hip_stream)
     // outside the captured graph
     FD_BHIP(launch_prepare(bb, stream, b->have_src ? &b->src : nullptr));
     b->have_src = false;
-    if (b->use_graph && b->exec) {
+    if (shared_ml) {
+        // plain launches, outside the captured graph (which is the per-context chain's)
+        FD_BHIP(hipEventRecord(b->ev_mid, stream));
+        FD_BHIP(launch_build_ml_shared(bb, stream, b->d_mlfac));
+    } else if (b->use_graph && b->exec) {
         FD_BHIP(hipEventRecord(b->ev_mid, stream));
         FD_BHIP(hipGraphLaunch(b->exec, stream));
     } else {
@@ -2695,6 +2714,8 @@ int fd_batch_set_shared_factor(fd_batch *b, int on)
 }
 
 int fd_batch_last_build_shared_factor(const fd_batch *b) { return b ? b->last_shared_factor : 0; }
+
+const char *fd_shared_ml_build_kernel_name(int M, int layers, int frames) { return ml_shared_kernel_name(M, layers, frames); }
 
 int fd_batch_size(const fd_batch *b) { return b ? b->n : 0; }
 

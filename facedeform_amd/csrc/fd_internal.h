@@ -215,6 +215,23 @@ size_t reg_factor_doubles();
 hipError_t reg_build_init();          // once per device, outside stream capture
 constexpr int kMaxLayers = 8;
 hipError_t launch_build_ml(const BuildBuffers &b, hipStream_t stream, hipEvent_t ev_mid);
+// ---- a shot of multilayer models from one factorisation per layer (fd_batch_set_shared_factor; fd_build_ml_shared.hip)
+// The L layer matrices are factorised once, side by side, in scratch slots of the batch (ml_shared_scratch_bytes; slot l is
+// layer l's A, solver state and DevModel on context 0's centres), and k_ml_solve_shared takes every frame's right-hand sides
+// through them in one launch.  launch_build_ml_shared is everything after k_prepare, as launch_build_ml is.
+bool ml_shared_applies(int M, int layers, int frames);      // sizes the path takes; fewer frames than ml_shared_min_frames: no
+int ml_shared_min_frames();
+const char *ml_shared_kernel_name(int M, int layers, int frames);
+hipError_t ml_shared_init();                                // once per device, outside stream capture
+size_t ml_shared_scratch_bytes(const BuildBuffers &b);
+const BatchSlot *ml_shared_slots(void *scratch);            // the scratch slot table, b.ml_layers entries
+hipError_t launch_build_ml_shared(const BuildBuffers &b, hipStream_t stream, void *scratch);
+// where fd_nullspace.hip keeps what the solve reads of the solver state (BatchSlot::ns), in doubles: tau, R and the
+// multilayer polynomial inside the small block at 12 M; the diagonal blocks from `ld` past 12 M on, `ld_stride` apart,
+// inverse(L11) at `ld_inv` inside each
+struct MlSharedLayout { int tau, R, aff, ld, ld_stride, ld_inv; };
+hipError_t launch_ml_shared_init(const BuildBuffers &b, hipStream_t stream, void *scratch);
+hipError_t launch_ml_solve_shared(const BuildBuffers &b, hipStream_t stream, void *scratch, const MlSharedLayout &at);
 // FD_KERNEL_GAUSSIAN_QNN, the SOP's model = 0: least-squares polynomial first, then the pivoted LU
 // of the (non-symmetric) kernel block on what is left
 hipError_t launch_build_qnn(const BuildBuffers &b, hipStream_t stream, hipEvent_t ev_mid);

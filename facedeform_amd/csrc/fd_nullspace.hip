@@ -1636,6 +1636,32 @@ hipError_t launch_build_ml(const BuildBuffers &b, hipStream_t stream, hipEvent_t
     return launch_pack_records(b, stream, M * L, FD_KERNEL_GAUSSIAN_QNN, 2, L);
 }
 
+// The same shot from ONE factorisation per layer (fd_batch_set_shared_factor): every context read the same rest
+// array, so Phi_l + lambda I is the same matrix in every frame.  The L layer matrices are assembled and factorised side by
+// side in the batch's scratch slots (blockIdx.z = layer: the layers do not depend on each other, only the right-hand sides
+// chain), the reflectors of P are formed once, and k_ml_solve_shared (fd_build_ml_shared.hip) takes all frames through them.
+hipError_t launch_build_ml_shared(const BuildBuffers &b, hipStream_t stream, void *scratch)
+{
+    const unsigned nb = (unsigned)b.nbatch;
+    const int M = b.M, T = b.T, L = b.ml_layers;
+    const int npc = round_up(M, kNB);
+    hipLaunchKernelGGL(k_ml_setup, dim3((M * L + 255) / 256, 1, nb), dim3(256), 0, stream, b.d_slots, M, L, b.gauss_R);
+    hipError_t e = launch_ml_shared_init(b, stream, scratch);
+    if (e != hipSuccess) return e;
+    BuildBuffers lb = b;                  // the layers as a batch of L systems
+    lb.d_slots = ml_shared_slots(scratch);
+    lb.nbatch = L;
+    if (T > 0) hipLaunchKernelGGL(k_ns_reflectors, dim3(1, 1, 1), dim3(256), 0, stream, lb.d_slots, M, T, b.npad, b.lda, 0);
+    e = launch_assemble_block(lb, stream, npc, 0);
+    if (e != hipSuccess) return e;
+    launch_factor(lb, stream, npc, M, 0);
+    const MlSharedLayout at = {kTau, kR, kAff, kSmall, kLdStride, kLdInv};
+    e = launch_ml_solve_shared(b, stream, scratch, at);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_ml_finish, dim3(1, 1, nb), dim3(64), 0, stream, b.d_slots, M, T, L);
+    return launch_pack_records(b, stream, M * L, FD_KERNEL_GAUSSIAN_QNN, 2, L);
+}
+
 // The SOP's default model (model = 0, rbfsetalgoqnn, reference src/SOP_FaceDeform.cpp:343-345) in
 // ALGLIB's order: the term's polynomial is a least-squares fit to the deltas
 // -- through the QR of P the reflectors give, no normal equations -- and is removed; the Gaussians

@@ -833,15 +833,36 @@ int fd_batch_set_eval_cus(fd_batch *batch, int n_cus);
 /* One factorisation per batched build where the contexts share the rest rig ("factor once and treat frames as extra
  * right-hand sides").  The reference rebuilds its model on every cook (src/SOP_FaceDeform.cpp:331-363); the system matrix depends
  * on the rest points, the kernel and the term only, so the frames of a shot -- one rest rig, other deltas -- can share it.
- * With `on`, fd_batch_build_async (and fd_batch_cook_group) assembles, projects and factorises ONCE, in the register-resident
- * one-launch build of the batch's first context, and carries every other context's right-hand sides through that factor, one
- * workgroup per context (Q^T f, both substitutions, the polynomial, packing).  It applies when the register-resident build does
- * (a definite kernel + term pair, up to 256 control points) AND every context was given the SAME rest array by
- * fd_batch_set_points_dev; otherwise -- other rigs, other kernels, larger rigs -- the call builds every model on its own, as
- * without the switch.  Weights equal the per-context builds' to rounding (1e-12 of max |w|), not bit for bit.  Off by default.
- * fd_batch_last_build_shared_factor: 1 if the batch's last build took the shared path. */
+ * With `on`, fd_batch_build_async (and fd_batch_cook_group through it) takes one of two shared paths; off by default.
+ *
+ * Thin-plate family: the call assembles, projects and factorises ONCE, in the register-resident one-launch build of the batch's
+ * first context, and carries every other context's right-hand sides through that factor, one workgroup per context (Q^T f, both
+ * substitutions, the polynomial, packing).  Conditions: the register-resident build applies (a definite kernel + term pair, up
+ * to 256 control points), every context was given the SAME rest array by fd_batch_set_points_dev, and the batch has at least
+ * two contexts.
+ *
+ * Multilayer model (FD_KERNEL_GAUSSIAN_ML): "the factor" is L factors, one per layer -- Phi_l + lambda I depends on the rest
+ * rig, R, lambda and l alone.  The call forms the reflectors of the polynomial block once, assembles and Cholesky-factorises
+ * the L layer matrices once, side by side, and takes all 3 F right-hand-side columns through them in ONE launch
+ * (k_ml_solve_shared: least-squares polynomial, then per layer both substitutions, the weights, lambda w on to the next
+ * layer); setup, the records and every frame's terminationtype come from the same kernels as a per-context build, so all
+ * that follows -- the shot calls, the per-context launches, fd_export_model -- sees ordinary built models.  Conditions: every
+ * context is FD_KERNEL_GAUSSIAN_ML with the same (R, layers, lambda) and term (a batch's contexts always are), every context
+ * was given the SAME rest array by fd_batch_set_points_dev, the batch has at least two contexts, and M <= 1024 (a workgroup
+ * keeps M x 16 doubles in LDS).  fd_shared_ml_build_kernel_name tells whether a size is taken.  The factors live in scratch of
+ * the batch for the one call: nothing is kept for fd_set_deltas, which stays FD_E_NOT_BUILT on a multilayer context.
+ *
+ * Delegation: a batch that misses a condition -- other rest arrays, other kernels (QNN, lambda > 0 on the thin-plate family),
+ * one context, larger rigs, no memory for the scratch -- is built model by model exactly as without the switch, bit for bit.
+ * On a shared path the weights equal the per-context builds' to rounding, not bit for bit (1e-12 of max |w| at the sizes
+ * tested); the same inputs give the same bits on every call.
+ * fd_batch_last_build_shared_factor: 1 if the batch's last build took a shared path. */
 int fd_batch_set_shared_factor(fd_batch *batch, int on);
 int fd_batch_last_build_shared_factor(const fd_batch *batch);
+/* Which kernel takes a multilayer batch's right-hand sides through the shared layer factors when fd_batch_set_shared_factor is
+ * on and the contexts share the rest array: "k_ml_solve_shared" for M in 1..1024, layers in 1..8 and 2..32 frames, "" where the
+ * build is the per-context one. */
+const char *fd_shared_ml_build_kernel_name(int M, int layers, int frames);
 /* Which kernel fd_batch_deform_shared_dev launches for `frames` frames of an M-centre model of `kind` (a name for profiles and
  * benchmark lines -- the one rocprofv3 prints): "k_deform32_shared_w1" (17..32 frames, the model resident in LDS),
  * "k_deform32_tps_shared_wide" (17..32 frames, staged in chunks), "k_deform32_tps_shared" (up to 16 frames), or "" where the
