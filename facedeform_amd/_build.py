@@ -20,10 +20,11 @@ EXTRA_FLAGS = {"fd_eval.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
                "fd_eval_shared.hip": ["-fno-slp-vectorize"],
                "fd_eval_shared_ml.hip": ["-fno-slp-vectorize"],      # the same kernel form, the same reason
                # the fp64 exp / log constants stay inside the K loop: hoisted, nine register pairs sit under the epilogue of
-               # the 32-frame instantiations, which then spill; with this every instantiation has no scratch
+               # the 32-frame instantiations of both files, which then spill; with this every instantiation
+               # has no scratch
                "fd_vectors_shared64.hip": ["-mllvm", "-disable-machine-licm"],
-               "fd_vectors_shared_ml64.hip": ["-mllvm", "-disable-machine-licm"]}      # the same epilogue, the same reason (4.7d)
-HEADERS = [os.path.join(CSRC, "fd_internal.h"), os.path.join(CSRC, "fd_tuning.h"), os.path.join(CSRC, "fd_pack.h"), os.path.join(CSRC, "fd_eval_common.h"), os.path.join(CSRC, "fd_transport.h"), os.path.join(CSRC, "fd_shared64.h"), os.path.join(CSRC, "fd_shared_ml64.h"), os.path.join(CSRC, "fd_shared_ml.h"), os.path.join(CSRC, "fd_shared_common.h"), os.path.join(_ROOT, "include", "facedeform_hip.h")]
+               "fd_vectors_shared_ml64.hip": ["-mllvm", "-disable-machine-licm"]}
+HEADERS = [os.path.join(CSRC, "fd_internal.h"), os.path.join(CSRC, "fd_tuning.h"), os.path.join(CSRC, "fd_pack.h"), os.path.join(CSRC, "fd_eval_common.h"), os.path.join(CSRC, "fd_transport.h"), os.path.join(CSRC, "fd_vectors_shot.h"), os.path.join(CSRC, "fd_shared64.h"), os.path.join(CSRC, "fd_shared_ml64.h"), os.path.join(CSRC, "fd_shared_ml.h"), os.path.join(CSRC, "fd_shared_common.h"), os.path.join(_ROOT, "include", "facedeform_hip.h")]
 
 
 def hipcc_path() -> str:

@@ -303,17 +303,22 @@ struct SharedPacking {
     size_t poly_at, copy_at, norm_at;
 };
 SharedPacking shared_packing(int Mpad, int nF);
-// The Jacobian and the vectors it carries for every frame of a shared-rig evaluation (fd_vectors_shared.hip): reads the
-// scratch set launch_deform_shared packed (wtiles, frames), the mesh and the vectors; nothing of the contexts.
-struct SharedVectorArgs {
+// What the arguments of the four shot vector launches have in common (fd_vectors_shot.h fills the kernels' arguments from it):
+// the mesh, the vectors to carry and the per-frame outputs.
+struct SharedVectorCommon {
     int64_t N;
     const float *P_in, *dist2, *tu, *tv, *nrm;
     float radius2, falloffrate;
-    int Mpad, nF, kind;
+    int nF;
     const float *vN, *vtu, *vtv;
     float *N_out[kMaxBatch], *tu_out[kMaxBatch], *tv_out[kMaxBatch], *jacobian[kMaxBatch];
-    const void *wtiles, *frames;
     int max_wgs;
+};
+// The Jacobian and the vectors it carries for every frame of a shared-rig evaluation (fd_vectors_shared.hip): reads the
+// scratch set launch_deform_shared packed (wtiles, frames), the mesh and the vectors; nothing of the contexts.
+struct SharedVectorArgs : SharedVectorCommon {
+    int Mpad, kind;
+    const void *wtiles, *frames;
 };
 hipError_t launch_vectors_shared(const SharedVectorArgs &a, hipStream_t stream);
 const char *shared_vectors_kernel_name(int Mpad, int nF, int kind);
@@ -341,15 +346,9 @@ const char *shared64_kernel_name(int Mpad, int nF, int kind);
 // The Jacobian and the vectors it carries for every frame of that batch, in fp64 by one matrix-pipe launch
 // (fd_vectors_shared64.hip, fd_batch_deform_vectors_shared_fp64_dev): reads the scratch launch_deform_shared64's pack kernel
 // wrote for the same Mpad and nF, the mesh and the vectors; nothing of the contexts.
-struct SharedVector64Args {
-    int64_t N;
-    const float *P_in, *dist2, *tu, *tv, *nrm;
-    float radius2, falloffrate;
-    int Mpad, nF, kind;
-    const float *vN, *vtu, *vtv;
-    float *N_out[kMaxBatch], *tu_out[kMaxBatch], *tv_out[kMaxBatch], *jacobian[kMaxBatch];
+struct SharedVector64Args : SharedVectorCommon {
+    int Mpad, kind;
     const void *scratch;
-    int max_wgs;
 };
 hipError_t launch_vectors_shared64(const SharedVector64Args &a, hipStream_t stream);
 const char *shared_vectors64_kernel_name(int Mpad, int nF, int kind);      // "" below shared_vectors64_min_frames too
@@ -403,15 +402,9 @@ const char *shared_ml64_kernel_name(int M, int layers, int nF);
 // The Jacobian and the vectors it carries for every frame of that batch, in fp64 by one matrix-pipe launch
 // (fd_vectors_shared_ml64.hip, fd_batch_deform_vectors_shared_ml_fp64_dev): reads the scratch launch_deform_shared_ml64's
 // pack kernel wrote for the same M, layers and nF, the mesh and the vectors; nothing of the contexts.
-struct SharedVectorMl64Args {
-    int64_t N;
-    const float *P_in, *dist2, *tu, *tv, *nrm;
-    float radius2, falloffrate;
-    int M, layers, nF;
-    const float *vN, *vtu, *vtv;
-    float *N_out[kMaxBatch], *tu_out[kMaxBatch], *tv_out[kMaxBatch], *jacobian[kMaxBatch];
+struct SharedVectorMl64Args : SharedVectorCommon {
+    int M, layers;
     const void *scratch;
-    int max_wgs;
 };
 hipError_t launch_vectors_shared_ml64(const SharedVectorMl64Args &a, hipStream_t stream);
 const char *shared_vectors_ml64_kernel_name(int M, int layers, int nF);    // "" below shared_vectors_ml64_min_frames too
@@ -419,15 +412,9 @@ int shared_vectors_ml64_min_frames(int layers);                             // f
 // The Jacobian and the vectors it carries for every frame of a shared-rig batch of MULTILAYER models, in fp32 by one
 // matrix-pipe launch (fd_vectors_shared_ml.hip, fd_batch_deform_vectors_shared_ml_dev): reads the scratch
 // launch_deform_shared_ml's pack kernel wrote for the same M, layers and nF, the mesh and the vectors; nothing of the contexts.
-struct SharedVectorMlArgs {
-    int64_t N;
-    const float *P_in, *dist2, *tu, *tv, *nrm;
-    float radius2, falloffrate;
-    int M, layers, nF;
-    const float *vN, *vtu, *vtv;
-    float *N_out[kMaxBatch], *tu_out[kMaxBatch], *tv_out[kMaxBatch], *jacobian[kMaxBatch];
+struct SharedVectorMlArgs : SharedVectorCommon {
+    int M, layers;
     const void *scratch;
-    int max_wgs;
 };
 hipError_t launch_vectors_shared_ml(const SharedVectorMlArgs &a, hipStream_t stream);
 const char *shared_vectors_ml_kernel_name(int M, int layers, int nF);      // "" below shared_vectors_ml_min_frames too

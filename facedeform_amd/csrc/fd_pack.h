@@ -135,7 +135,7 @@ __device__ __forceinline__ double grad64(double d2, double s)
 
 // (256 threads; a kernel of its own in fd_build.hip, the last phase of the one-launch build in fd_nullspace.hip)
 template <class Src>
-__device__ __forceinline__ void pack_body_from(const Src &in, const BatchSlot &slot, int npad, int M, int Mpad, int T, int kind, int from_w, int layers)
+__device__ __forceinline__ void pack_body_from(const Src &in, const BatchSlot &slot, int /* npad */, int M, int Mpad, int T, int kind, int from_w, int layers)
 {
     double *W = slot.W;
     Rec32 *rec32 = slot.rec32;

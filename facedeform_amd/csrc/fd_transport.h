@@ -1,5 +1,6 @@
 // fd_transport.h -- the transport epilogue of fd_deform_vectors* (DESIGN.md 4.7): ONE copy for the one-frame launch
-// (fd_vectors.hip, k_vectors{32,64}_<kind>) and the shared-rig launches (fd_vectors_shared.hip, fd_vectors_shared64.hip).
+// (fd_vectors.hip, k_vectors{32,64}_<kind>) and the four shot launches (fd_vectors_shared.hip and fd_vectors_shared_ml.hip call
+// transport(), fd_vectors_shared64.hip and fd_vectors_shared_ml64.hip jacobian() and carry(); their FrameIO is fd_vectors_shot.h's).
 //
 // A = I + f Pi R per vertex, R = J before the projection; t' = A t, n' = cof(A) n rescaled to |n|
 // (include/facedeform_hip.h states the definition).  `p` names the arrays of ONE frame: the projection frames tu, tv, nrm
@@ -159,7 +160,7 @@ __device__ __forceinline__ float falloff(bool has_dist2, float radius2, float fa
 }
 
 // transport() in its two halves, the same operations in the same order, for a launch that holds many frames of a vertex in
-// registers (fd_vectors_shared64.hip): it runs the first half for all of them before the second, so that the projection axes are
+// registers (fd_vectors_shared64.hip, fd_vectors_shared_ml64.hip): it runs the first half for all of them before the second, so that the projection axes are
 // not live under the cofactors.  The launches above keep transport() as it is: composed of these two, their code objects come
 // out with other register assignments and schedules.
 //   jacobian(): R = (J before the projection, row c = output c, column k = d/dx_k), f the fall-off -> A = I + f Pi R;

@@ -22,7 +22,7 @@
 
 #include "fd_eval_common.h"
 #include "fd_pack.h"
-#include "fd_transport.h"
+#include "fd_vectors_shot.h"
 
 namespace fd {
 
@@ -32,9 +32,6 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
-constexpr int kVsWaves = 8;
-constexpr int kVsThreads = 64 * kVsWaves;
-constexpr int kVsGroup = 16 * kVsWaves;          // vertices per workgroup and group
 constexpr size_t kVsLdsBudget = 158 * 1024;
 // The basis enters the matrix pipe pre-scaled by a power of two per kind, so that its fp16 pieces stay clear of the subnormals
 // where it matters and the hi piece below the fp16 maximum (65504) over the range the kind can reach:
@@ -45,41 +42,14 @@ constexpr size_t kVsLdsBudget = 158 * 1024;
 //     (include/facedeform_hip.h states it); lo pieces exact down to 2^-11.
 constexpr int grad_shift(bool gauss) { return gauss ? 8 : 4; }
 constexpr int kPackGaussShift = 10;                // fd_eval_shared.hip's kGaussShift, carried by the Gaussian frame records
-constexpr int kFrameWords = 16;                    // per frame in LDS: {basis scale, built, L'[3][3], q[3], 2 unused}
 
-struct VsOut {                    // per-frame outputs (the kernel's first argument; dealt into LDS)
-    float *N[kMaxBatch], *tu[kMaxBatch], *tv[kMaxBatch], *jac[kMaxBatch];
-};
-
-struct VsParams {
-    int64_t N;
-    const float *P_in, *dist2;
-    const float *tu, *tv, *nrm;          // projection frames (all or none)
-    const float *vN, *vtu, *vtv;         // vectors to transport (shared by the frames)
-    float radius2, falloffrate;
+struct VsParams : ShotMesh {
     int nF, nkb, kchunk;
     int layout, srcNT;                   // SharedPacking
     unsigned poly_at, copy_at, norm_at;
     const uint4 *wtiles;
     const unsigned *frames;              // the pack kernel's frame records, 8 words each: {inv_scale, built, ...}
 };
-
-// one frame of one vertex, as fd_transport.h's transport() reads it
-struct FrameIO {
-    const float *tu, *tv, *nrm;
-    float a1[3], a2[3];
-    const float *vN, *vtu, *vtv;
-    float *oN, *otu, *otv, *jac;
-    static constexpr bool kGivenAxes = true;
-    // (written once, read by nobody in this launch: past L2, like the position launch's stores)
-    static __device__ __forceinline__ void store(float *dst, float v) { __builtin_nontemporal_store(v, dst); }
-};
-
-__device__ __forceinline__ float half_at(const uint4 *base, size_t word, int e)
-{
-    const unsigned short u = reinterpret_cast<const unsigned short *>(base + word)[e];
-    return (float)__builtin_bit_cast(_Float16, u);
-}
 
 // lane row (r of 32) and row tile of component c of frame f in the 32-row layouts (k_pack_shared_wide)
 __device__ __forceinline__ void wide_row(int layout, int f, int c, int &T, int &r)
@@ -148,17 +118,11 @@ __device__ __forceinline__ void vectors_shared_body(const VsParams &p, int ngrou
             fc[11 + c] = coef[4];
         }
     }
-    if (tid < 4 * kMaxBatch) {
-        // VsOut is the kernel's FIRST argument: its table read straight from the argument segment (indexed by the thread, the
-        // argument itself would be copied to scratch memory first; unrolled over constant indices, it is held in SGPRs and spilled)
-        const int f = tid >> 2, w = tid & 3;
-        float *const *tab = (float *const *)(uintptr_t)__builtin_amdgcn_kernarg_segment_ptr();
-        s_ptr[tid] = f < p.nF ? tab[kMaxBatch * w + f] : nullptr;
-    }
+    deal_out_pointers(s_ptr, p.nF);
     // the model's K blocks kb0 .. kb0 + nk - 1 into LDS, in the 16-row order (above)
     auto stage = [&](int kb0, int nk) {
         __syncthreads();
-        for (int q = tid; q < nk * 32; q += kVsThreads) {
+        for (int q = tid; q < nk * 32; q += kShotThreads) {
             const int kb = kb0 + q / 32, m = q % 32;
             float4 c;
             if (GAUSS) {
@@ -185,7 +149,7 @@ __device__ __forceinline__ void vectors_shared_body(const VsParams &p, int ngrou
             }
             s_c[q] = c;
         }
-        for (int q = tid; q < nk * NT * 128; q += kVsThreads) {
+        for (int q = tid; q < nk * NT * 128; q += kShotThreads) {
             const int kb = kb0 + q / (NT * 128), rem = q % (NT * 128);
             const int T = rem / 128, hl = (rem >> 6) & 1, ln = rem & 63;
             if (!wide) {
@@ -220,7 +184,7 @@ __device__ __forceinline__ void vectors_shared_body(const VsParams &p, int ngrou
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
     const float gs = packing::grad_scale32(GAUSS ? FD_KERNEL_GAUSSIAN : FD_KERNEL_THIN_PLATE);
     for (int grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
-        const int64_t vi = ((int64_t)grp * kVsWaves + wave) * 16 + j;
+        const int64_t vi = ((int64_t)grp * kShotWaves + wave) * 16 + j;
         const bool inb = vi < p.N;
         const int64_t vc = inb ? vi : p.N - 1;
         const float x = (p.P_in[3 * vc] - n0) * inv_s, y = (p.P_in[3 * vc + 1] - n1) * inv_s, z = (p.P_in[3 * vc + 2] - n2) * inv_s;
@@ -295,7 +259,7 @@ __device__ __forceinline__ void vectors_shared_body(const VsParams &p, int ngrou
             fall = fminf(d2v / p.radius2, 1.f);
             fall = powf(1.f - fall, p.falloffrate);
         }
-        FrameIO io;
+        FrameIO<float> io;
         io.tu = p.tu; io.tv = p.tv; io.nrm = p.nrm;
         io.vN = p.vN; io.vtu = p.vtu; io.vtv = p.vtv;
         if (live && p.tu && fall != 0.f) transport::axes(p.tu, p.tv, p.nrm, vi, io.a1, io.a2);
@@ -305,15 +269,7 @@ __device__ __forceinline__ void vectors_shared_body(const VsParams &p, int ngrou
             const float *fc = s_fc + kFrameWords * f;
             io.oN = s_ptr[4 * f]; io.otu = s_ptr[4 * f + 1]; io.otv = s_ptr[4 * f + 2]; io.jac = s_ptr[4 * f + 3];
             if (!live || fc[1] == 0.f) {
-                // gated vertex / unbuilt frame: the vectors bit for bit, A = I
-                for (int c = 0; c < 3; ++c) {
-                    if (io.vN) FrameIO::store(&io.oN[3 * vi + c], io.vN[3 * vi + c]);
-                    if (io.vtu) FrameIO::store(&io.otu[3 * vi + c], io.vtu[3 * vi + c]);
-                    if (io.vtv) FrameIO::store(&io.otv[3 * vi + c], io.vtv[3 * vi + c]);
-                }
-                if (io.jac)
-#pragma unroll
-                    for (int q = 0; q < 9; ++q) FrameIO::store(&io.jac[9 * vi + q], (q % 4 == 0) ? 1.f : 0.f);
+                pass_through(io, vi);
                 return;
             }
             const float S[9] = {j00, j01, j02, j10, j11, j12, j20, j21, j22};
@@ -347,19 +303,17 @@ __device__ __forceinline__ void vectors_shared_body(const VsParams &p, int ngrou
 
 // stable names for profiles: k_vectors32_shared_<kind> (the Gaussian kinds share one)
 template <int NT, bool DENSE>
-__global__ __launch_bounds__(kVsThreads) void k_vectors32_shared_thin_plate(const VsOut out, const VsParams p, int ngroups)
+__global__ __launch_bounds__(kShotThreads) void k_vectors32_shared_thin_plate(const ShotOut out, const VsParams p, int ngroups)
 {
     (void)out;
     vectors_shared_body<false, NT, DENSE>(p, ngroups);
 }
 template <int NT, bool DENSE>
-__global__ __launch_bounds__(kVsThreads) void k_vectors32_shared_gaussian(const VsOut out, const VsParams p, int ngroups)
+__global__ __launch_bounds__(kShotThreads) void k_vectors32_shared_gaussian(const ShotOut out, const VsParams p, int ngroups)
 {
     (void)out;
     vectors_shared_body<true, NT, DENSE>(p, ngroups);
 }
-
-int vs_tiles(int nF) { return nF > 12 ? 3 * ((nF + 15) / 16) : (nF + 3) / 4; }
 
 }  // namespace
 
@@ -369,56 +323,27 @@ hipError_t launch_vectors_shared(const SharedVectorArgs &a, hipStream_t stream)
     if (a.nF > kMaxBatch || a.Mpad % 16 != 0) return hipErrorInvalidValue;
     const SharedPacking pk = shared_packing(a.Mpad, a.nF);
     const int nkb = (a.Mpad / 16 + 1) / 2;
-    const int NT = vs_tiles(a.nF);
-    const bool dense = a.nF > 12;
+    const int NT = shot_tiles(a.nF);
     VsParams p{};
-    p.N = a.N; p.P_in = a.P_in; p.dist2 = a.dist2; p.tu = a.tu; p.tv = a.tv; p.nrm = a.nrm;
-    p.vN = a.vN; p.vtu = a.vtu; p.vtv = a.vtv;
-    p.radius2 = a.radius2; p.falloffrate = a.falloffrate;
+    ShotOut out{};
+    fill_shot(p, out, a);
     p.nF = a.nF; p.nkb = nkb;
     p.layout = pk.layout; p.srcNT = pk.ntiles;
     p.poly_at = (unsigned)pk.poly_at; p.copy_at = (unsigned)pk.copy_at; p.norm_at = (unsigned)pk.norm_at;
     p.wtiles = (const uint4 *)a.wtiles; p.frames = (const unsigned *)a.frames;
-    VsOut out{};
-    for (int f = 0; f < a.nF; ++f) { out.N[f] = a.N_out[f]; out.tu[f] = a.tu_out[f]; out.tv[f] = a.tv_out[f]; out.jac[f] = a.jacobian[f]; }
     const size_t fixed = sizeof(float) * kFrameWords * kMaxBatch + sizeof(float *) * 4 * kMaxBatch;
     const size_t per_kb = 32 * 16 + (size_t)NT * 128 * 16;
     int kchunk = (int)((kVsLdsBudget - fixed) / per_kb);
     if (kchunk < 1) return hipErrorInvalidValue;
     if (kchunk > nkb) kchunk = nkb;
     p.kchunk = kchunk;
-    const size_t lds = fixed + per_kb * (size_t)kchunk;
-    const int64_t ngroups = (a.N + kVsGroup - 1) / kVsGroup;
-    // persistent workgroups: as many per CU as the LDS admits, two at most (two waves per SIMD each)
-    const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(2, (int64_t)(160 * 1024 / lds)));
-    const int64_t max_wgs = a.max_wgs > 0 ? (a.max_wgs < 4096 ? a.max_wgs : 4096) : (int64_t)device_cus() * per_cu;
-    const unsigned grid = (unsigned)(ngroups < max_wgs ? ngroups : max_wgs);
+    ShotGrid gr;
+    if (hipError_t e = shot_grid(a, fixed + per_kb * (size_t)kchunk, gr); e != hipSuccess) return e;
     const bool gauss = a.kind != FD_KERNEL_THIN_PLATE;
-#define FD_VS_CASE(NTV, DNS)                                                                                              \
-    {                                                                                                                     \
-        static LdsAttrOnce once_t, once_g;                                                                                    \
-        if (gauss) {                                                                                                      \
-            hipError_t e = once_g.ensure((const void *)k_vectors32_shared_gaussian<NTV, DNS>, 160 * 1024);               \
-            if (e != hipSuccess) return e;                                                                                \
-            hipLaunchKernelGGL((k_vectors32_shared_gaussian<NTV, DNS>), dim3(grid), dim3(kVsThreads), lds, stream, out, p, (int)ngroups); \
-        } else {                                                                                                          \
-            hipError_t e = once_t.ensure((const void *)k_vectors32_shared_thin_plate<NTV, DNS>, 160 * 1024);             \
-            if (e != hipSuccess) return e;                                                                                \
-            hipLaunchKernelGGL((k_vectors32_shared_thin_plate<NTV, DNS>), dim3(grid), dim3(kVsThreads), lds, stream, out, p, (int)ngroups); \
-        }                                                                                                                 \
-    }
-    if (dense) {
-        if (NT == 3) FD_VS_CASE(3, true)
-        else if (NT == 6) FD_VS_CASE(6, true)
-        else return hipErrorInvalidValue;
-    } else {
-        if (NT == 1) FD_VS_CASE(1, false)
-        else if (NT == 2) FD_VS_CASE(2, false)
-        else if (NT == 3) FD_VS_CASE(3, false)
-        else return hipErrorInvalidValue;
-    }
-#undef FD_VS_CASE
-    return hipGetLastError();
+    return for_tiles(NT, a.nF > 12, [&](auto nt, auto dns) {
+        return gauss ? launch_shot<k_vectors32_shared_gaussian<nt.value, dns.value>>(out, p, gr, stream)
+                     : launch_shot<k_vectors32_shared_thin_plate<nt.value, dns.value>>(out, p, gr, stream);
+    });
 }
 
 const char *shared_vectors_kernel_name(int Mpad, int nF, int kind)

@@ -29,41 +29,19 @@
 #include "fd_eval_common.h"
 #include "fd_pack.h"
 #include "fd_shared64.h"
-#include "fd_transport.h"
+#include "fd_vectors_shot.h"
 
 namespace fd {
 
 namespace {
 
-constexpr int kV64Group = 16 * kS64Waves;          // vertices per workgroup and group
-
-struct V64Out {                    // per-frame outputs (the kernel's first argument; dealt into LDS)
-    float *N[kMaxBatch], *tu[kMaxBatch], *tv[kMaxBatch], *jac[kMaxBatch];
-};
-
-struct V64Params {
-    int64_t N;
-    const float *P_in, *dist2;
-    const float *tu, *tv, *nrm;          // projection frames (all or none)
-    const float *vN, *vtu, *vtv;         // vectors to transport (shared by the frames)
-    float radius2, falloffrate;
+struct V64Params : ShotMesh {
     int nF, nks, kchunk, Mpad;
     const double *scratch;
 };
 
-// one frame of one vertex, as fd_transport.h's transport() reads it
-struct FrameIO64 {
-    const float *tu, *tv, *nrm;
-    double a1[3], a2[3];
-    const float *vN, *vtu, *vtv;
-    float *oN, *otu, *otv, *jac;
-    static constexpr bool kGivenAxes = true;
-    // (written once, read by nobody in this launch: past L2, like the position launch's stores)
-    static __device__ __forceinline__ void store(float *dst, float v) { __builtin_nontemporal_store(v, dst); }
-};
-
 template <int KIND, int NT, bool DENSE>
-__global__ __launch_bounds__(kS64Threads) void k_vectors64_shared(const V64Out out, const V64Params p, int ngroups)
+__global__ __launch_bounds__(kS64Threads) void k_vectors64_shared(const ShotOut out, const V64Params p, int ngroups)
 {
     (void)out;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -83,13 +61,7 @@ __global__ __launch_bounds__(kS64Threads) void k_vectors64_shared(const V64Out o
         f64x2 *dst = reinterpret_cast<f64x2 *>(smem);
         for (int q = tid; q < (int)(s64_cen_at(NT) / 2); q += kS64Threads) dst[q] = src[q];
     }
-    if (tid < 4 * kMaxBatch) {
-        // V64Out is the kernel's FIRST argument: its tables read straight from the argument segment (indexed by the thread,
-        // the argument itself would be copied to scratch memory first)
-        const int f = tid >> 2, w = tid & 3;
-        float *const *tab = (float *const *)(uintptr_t)__builtin_amdgcn_kernarg_segment_ptr();
-        s_ptr[tid] = f < p.nF ? tab[kMaxBatch * w + f] : nullptr;
-    }
+    deal_out_pointers(s_ptr, p.nF);
     // K steps ks0 .. ks0 + nk - 1 of the model into LDS
     auto stage = [&](int ks0, int nk) {
         __syncthreads();
@@ -151,7 +123,7 @@ __global__ __launch_bounds__(kS64Threads) void k_vectors64_shared(const V64Out o
 
         // ---- epilogue: lane (g, j) finishes its vertex for the frames whose rows its lane group holds
         if (!inb) continue;
-        FrameIO64 io;
+        FrameIO<double> io;
         io.tu = p.tu; io.tv = p.tv; io.nrm = p.nrm;
         io.vN = p.vN; io.vtu = p.vtu; io.vtv = p.vtv;
         if (live && p.tu && fall != 0.f) transport::axes<double>(p.tu, p.tv, p.nrm, vi, io.a1, io.a2);
@@ -187,15 +159,7 @@ __global__ __launch_bounds__(kS64Threads) void k_vectors64_shared(const V64Out o
             if (f >= p.nF) continue;
             io.oN = s_ptr[4 * f]; io.otu = s_ptr[4 * f + 1]; io.otv = s_ptr[4 * f + 2]; io.jac = s_ptr[4 * f + 3];
             if (!live || !s_head->built[f]) {
-                // gated vertex / unbuilt frame: the vectors bit for bit, A = I
-                for (int c = 0; c < 3; ++c) {
-                    if (io.vN) FrameIO64::store(&io.oN[3 * vi + c], io.vN[3 * vi + c]);
-                    if (io.vtu) FrameIO64::store(&io.otu[3 * vi + c], io.vtu[3 * vi + c]);
-                    if (io.vtv) FrameIO64::store(&io.otv[3 * vi + c], io.vtv[3 * vi + c]);
-                }
-                if (io.jac)
-#pragma unroll
-                    for (int e = 0; e < 9; ++e) FrameIO64::store(&io.jac[9 * vi + e], (e % 4 == 0) ? 1.f : 0.f);
+                pass_through(io, vi);
                 continue;
             }
             double A[9];
@@ -209,26 +173,9 @@ __global__ __launch_bounds__(kS64Threads) void k_vectors64_shared(const V64Out o
 }
 
 template <int KIND>
-hipError_t launch_kind(const V64Out &out, const V64Params &p, int NT, bool dense, unsigned grid, size_t lds, int ngroups, hipStream_t stream)
+hipError_t launch_kind(const ShotOut &out, const V64Params &p, int NT, bool dense, const ShotGrid &gr, hipStream_t stream)
 {
-#define FD_V64_CASE(NTV, DNS)                                                                                                  \
-    {                                                                                                                          \
-        static LdsAttrOnce once;                                                                                               \
-        hipError_t e = once.ensure((const void *)k_vectors64_shared<KIND, NTV, DNS>, 160 * 1024);                              \
-        if (e != hipSuccess) return e;                                                                                         \
-        hipLaunchKernelGGL((k_vectors64_shared<KIND, NTV, DNS>), dim3(grid), dim3(kS64Threads), lds, stream, out, p, ngroups); \
-        return hipGetLastError();                                                                                              \
-    }
-    if (dense) {
-        if (NT == 3) FD_V64_CASE(3, true)
-        if (NT == 6) FD_V64_CASE(6, true)
-    } else {
-        if (NT == 1) FD_V64_CASE(1, false)
-        if (NT == 2) FD_V64_CASE(2, false)
-        if (NT == 3) FD_V64_CASE(3, false)
-    }
-#undef FD_V64_CASE
-    return hipErrorInvalidValue;
+    return for_tiles(NT, dense, [&](auto nt, auto dns) { return launch_shot<k_vectors64_shared<KIND, nt.value, dns.value>>(out, p, gr, stream); });
 }
 
 }  // namespace
@@ -238,34 +185,24 @@ hipError_t launch_vectors_shared64(const SharedVector64Args &a, hipStream_t stre
     if (a.N <= 0 || a.nF <= 0) return hipSuccess;
     if (a.nF > kMaxBatch || a.Mpad <= 0 || a.Mpad % 16 != 0 || !a.scratch) return hipErrorInvalidValue;
     const int NT = s64_tiles(a.nF);
-    const bool dense = a.nF > 12;
     const int nks = a.Mpad / 4;
     V64Params p{};
-    p.N = a.N; p.P_in = a.P_in; p.dist2 = a.dist2; p.tu = a.tu; p.tv = a.tv; p.nrm = a.nrm;
-    p.vN = a.vN; p.vtu = a.vtu; p.vtv = a.vtv;
-    p.radius2 = a.radius2; p.falloffrate = a.falloffrate;
+    ShotOut out{};
+    fill_shot(p, out, a);
     p.nF = a.nF; p.nks = nks; p.Mpad = a.Mpad;
     p.scratch = (const double *)a.scratch;
-    V64Out out{};
-    for (int f = 0; f < a.nF; ++f) { out.N[f] = a.N_out[f]; out.tu[f] = a.tu_out[f]; out.tv[f] = a.tv_out[f]; out.jac[f] = a.jacobian[f]; }
     const size_t fixed = 8 * s64_cen_at(NT) + sizeof(float *) * 4 * kMaxBatch;
     const size_t per_ks = 8 * (16 + (size_t)NT * 64);
-    const int kmax = (int)((kS64LdsBudget - fixed) / per_ks);
-    const int nchunks = (nks + kmax - 1) / kmax;
-    p.kchunk = (nks + nchunks - 1) / nchunks;           // even chunks, as the position launch stages them
-    const size_t lds = fixed + per_ks * (size_t)p.kchunk;
-    const int64_t ngroups = (a.N + kV64Group - 1) / kV64Group;
-    if (ngroups > 0x7fffffff) return hipErrorInvalidValue;
-    // persistent workgroups: as many per CU as the LDS admits, two at most
-    const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(2, (int64_t)(160 * 1024 / lds)));
-    const int64_t max_wgs = a.max_wgs > 0 ? (a.max_wgs < 4096 ? a.max_wgs : 4096) : (int64_t)device_cus() * per_cu;
-    const unsigned grid = (unsigned)(ngroups < max_wgs ? ngroups : max_wgs);
+    p.kchunk = even_chunks(nks, (int)((kS64LdsBudget - fixed) / per_ks));
+    ShotGrid gr;
+    if (hipError_t e = shot_grid(a, fixed + per_ks * (size_t)p.kchunk, gr); e != hipSuccess) return e;
+    const bool dense = a.nF > 12;
     switch (a.kind) {
     case FD_KERNEL_GAUSSIAN:
-    case FD_KERNEL_GAUSSIAN_QNN: return launch_kind<FD_KERNEL_GAUSSIAN>(out, p, NT, dense, grid, lds, (int)ngroups, stream);
-    case FD_KERNEL_THIN_PLATE: return launch_kind<FD_KERNEL_THIN_PLATE>(out, p, NT, dense, grid, lds, (int)ngroups, stream);
-    case FD_KERNEL_BIHARMONIC: return launch_kind<FD_KERNEL_BIHARMONIC>(out, p, NT, dense, grid, lds, (int)ngroups, stream);
-    case FD_KERNEL_CUBIC: return launch_kind<FD_KERNEL_CUBIC>(out, p, NT, dense, grid, lds, (int)ngroups, stream);
+    case FD_KERNEL_GAUSSIAN_QNN: return launch_kind<FD_KERNEL_GAUSSIAN>(out, p, NT, dense, gr, stream);
+    case FD_KERNEL_THIN_PLATE: return launch_kind<FD_KERNEL_THIN_PLATE>(out, p, NT, dense, gr, stream);
+    case FD_KERNEL_BIHARMONIC: return launch_kind<FD_KERNEL_BIHARMONIC>(out, p, NT, dense, gr, stream);
+    case FD_KERNEL_CUBIC: return launch_kind<FD_KERNEL_CUBIC>(out, p, NT, dense, gr, stream);
     default: return hipErrorInvalidValue;
     }
 }

@@ -36,65 +36,35 @@
 #include "fd_eval_common.h"
 #include "fd_pack.h"
 #include "fd_shared_ml.h"
-#include "fd_transport.h"
+#include "fd_vectors_shot.h"
 #include "fd_tuning.h"
 
 namespace fd {
 
 namespace {
 
-constexpr int kVmlWaves = 8;
-constexpr int kVmlThreads = 64 * kVmlWaves;
-constexpr int kVmlGroup = 16 * kVmlWaves;         // vertices per workgroup and group
 // The basis enters the matrix pipe as 2^8 g (x' - c'), the one-layer launch's prescale (fd_vectors_shared.hip):
 // |g (x' - c')| <= 0.52 sqrt(|s_l|), s_l = -log2(e) / R_l'^2, so its hi piece stays below the fp16 maximum for R_l' above
 // ~0.0024 rig radii -- the FINEST layer's radius, R' / 2^(L - 1) (include/facedeform_hip.h states it); lo pieces are exact
 // down to 2^-11.
 constexpr int kVmlGradShift = 8;
-constexpr int kVmlFrameWords = 16;                // per frame in LDS: {basis scale, built, L'[3][3], q[3], 2 unused}
 
-struct VmlOut {                   // per-frame outputs (the kernel's first argument; dealt into LDS)
-    float *N[kMaxBatch], *tu[kMaxBatch], *tv[kMaxBatch], *jac[kMaxBatch];
-};
-
-struct VmlParams {
-    int64_t N;
-    const float *P_in, *dist2;
-    const float *tu, *tv, *nrm;          // projection frames (all or none)
-    const float *vN, *vtu, *vtv;         // vectors to transport (shared by the frames)
-    float radius2, falloffrate;
-    int nF, nkb, kchunk, srcNT;          // srcNT: ml_tiles(nF), the 32-row tiles the pack kernel wrote
+struct VmlParams : ShotMesh {
+    int nF, nkb, kchunk, srcNT;             // srcNT: ml_tiles(nF), the 32-row tiles the pack kernel wrote
     const uint4 *scratch;
 };
-
-// one frame of one vertex, as fd_transport.h's transport() reads it
-struct FrameIOMl {
-    const float *tu, *tv, *nrm;
-    float a1[3], a2[3];
-    const float *vN, *vtu, *vtv;
-    float *oN, *otu, *otv, *jac;
-    static constexpr bool kGivenAxes = true;
-    // (written once, read by nobody in this launch: past L2, like the position launch's stores)
-    static __device__ __forceinline__ void store(float *dst, float v) { __builtin_nontemporal_store(v, dst); }
-};
-
-__device__ __forceinline__ float vml_half_at(const uint4 *base, size_t word, int e)
-{
-    const unsigned short u = reinterpret_cast<const unsigned short *>(base + word)[e];
-    return (float)__builtin_bit_cast(_Float16, u);
-}
 
 // NT row tiles of 16: padded (tile T = frames 4 T .. 4 T + 3, row 4 (f % 4) + c) or DENSE (tile 3 B + c = component c of
 // frames 16 B + row); SHARE consecutive records are layers of one centre
 template <int NT, bool DENSE, int SHARE>
-__global__ __launch_bounds__(kVmlThreads) void k_vectors32_shared_ml(const VmlOut out, const VmlParams p, int ngroups)
+__global__ __launch_bounds__(kShotThreads) void k_vectors32_shared_ml(const ShotOut out, const VmlParams p, int ngroups)
 {
     (void)out;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // LDS: [frame constants 32 x 16 words][output pointers 32 x 4][records kchunk x 32 x 16 B][weight tiles kchunk x NT x 2 KiB]
     float *s_fc = reinterpret_cast<float *>(smem);
-    float **s_ptr = reinterpret_cast<float **>(smem + sizeof(float) * kVmlFrameWords * kMaxBatch);
-    float4 *s_c = reinterpret_cast<float4 *>(smem + sizeof(float) * kVmlFrameWords * kMaxBatch + sizeof(float *) * 4 * kMaxBatch);
+    float **s_ptr = reinterpret_cast<float **>(smem + sizeof(float) * kFrameWords * kMaxBatch);
+    float4 *s_c = reinterpret_cast<float4 *>(smem + sizeof(float) * kFrameWords * kMaxBatch + sizeof(float *) * 4 * kMaxBatch);
     uint4 *s_w = reinterpret_cast<uint4 *>(s_c + 32 * p.kchunk);
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -110,7 +80,7 @@ __global__ __launch_bounds__(kVmlThreads) void k_vectors32_shared_ml(const VmlOu
         const unsigned *frames = reinterpret_cast<const unsigned *>(p.scratch);      // SharedFrame: {inv_scale, built, ...}, 8 words
         const float inv = __uint_as_float(frames[8 * f]);
         const float unscale = inv * (float)(1 << kGaussShift);                        // 2^-k
-        float *fc = s_fc + kVmlFrameWords * f;
+        float *fc = s_fc + kFrameWords * f;
         fc[0] = unscale * (1.f / (float)(1 << kVmlGradShift));
         fc[1] = frames[8 * f + 1] != 0u ? 1.f : 0.f;
 #pragma unroll
@@ -121,27 +91,21 @@ __global__ __launch_bounds__(kVmlThreads) void k_vectors32_shared_ml(const VmlOu
             const size_t w = kMlPolyAt + (size_t)T * 64;
             float coef[5];
 #pragma unroll
-            for (int e = 0; e < 5; ++e) coef[e] = (vml_half_at(p.scratch, w + r, e) + vml_half_at(p.scratch, w + 32 + r, e + 1)) * unscale;
+            for (int e = 0; e < 5; ++e) coef[e] = (half_at(p.scratch, w + r, e) + half_at(p.scratch, w + 32 + r, e + 1)) * unscale;
 #pragma unroll
             for (int k = 0; k < 3; ++k) fc[2 + 3 * c + k] = coef[1 + k];
             fc[11 + c] = coef[4];
         }
     }
-    if (tid < 4 * kMaxBatch) {
-        // VmlOut is the kernel's FIRST argument: its tables read straight from the argument segment (indexed by the thread,
-        // the argument itself would be copied to scratch memory first)
-        const int f = tid >> 2, w = tid & 3;
-        float *const *tab = (float *const *)(uintptr_t)__builtin_amdgcn_kernarg_segment_ptr();
-        s_ptr[tid] = f < p.nF ? tab[kMaxBatch * w + f] : nullptr;
-    }
+    deal_out_pointers(s_ptr, p.nF);
     // K blocks kb0 .. kb0 + nk - 1 of the model into LDS: the records as they are, the weight tiles dealt by whole words
     // from row 3 f + c of the 32-row stack into the 16-row order (above)
     auto stage = [&](int kb0, int nk) {
         __syncthreads();
         const uint4 *rsrc = p.scratch + ml_rec_at(p.srcNT) + (size_t)kb0 * 32;
-        for (int q = tid; q < nk * 32; q += kVmlThreads) reinterpret_cast<uint4 *>(s_c)[q] = rsrc[q];
+        for (int q = tid; q < nk * 32; q += kShotThreads) reinterpret_cast<uint4 *>(s_c)[q] = rsrc[q];
         const uint4 *wsrc = p.scratch + ml_w_at(p.srcNT, p.nkb);
-        for (int q = tid; q < nk * NT * 128; q += kVmlThreads) {
+        for (int q = tid; q < nk * NT * 128; q += kShotThreads) {
             const int kb = kb0 + q / (NT * 128), rem = q % (NT * 128);
             const int T = rem / 128, hl = (rem >> 6) & 1, ln = rem & 63;
             const int gg = ln >> 4, rho = ln & 15;
@@ -162,7 +126,7 @@ __global__ __launch_bounds__(kVmlThreads) void k_vectors32_shared_ml(const VmlOu
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
     const float gs = packing::grad_scale32(FD_KERNEL_GAUSSIAN);
     for (int grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
-        const int64_t vi = ((int64_t)grp * kVmlWaves + wave) * 16 + j;
+        const int64_t vi = ((int64_t)grp * kShotWaves + wave) * 16 + j;
         const bool inb = vi < p.N;
         const int64_t vc = inb ? vi : p.N - 1;
         const float x = (p.P_in[3 * vc] - n0) * inv_s, y = (p.P_in[3 * vc + 1] - n1) * inv_s, z = (p.P_in[3 * vc + 2] - n2) * inv_s;
@@ -235,32 +199,24 @@ __global__ __launch_bounds__(kVmlThreads) void k_vectors32_shared_ml(const VmlOu
             }
         }
 
-        // ---- epilogue (k_vectors32_shared's): lane (g, j) finishes its vertex for the frames whose rows its lane group holds
+        // ---- epilogue: lane (g, j) finishes its vertex for the frames whose rows its lane group holds
         if (!inb) continue;
         float fall = 1.f;
         if (p.dist2 != nullptr || !(p.radius2 != 0.f)) {       // fd_eval.hip's fall-off, the same operations
             fall = fminf(d2v / p.radius2, 1.f);
             fall = powf(1.f - fall, p.falloffrate);
         }
-        FrameIOMl io;
+        FrameIO<float> io;
         io.tu = p.tu; io.tv = p.tv; io.nrm = p.nrm;
         io.vN = p.vN; io.vtu = p.vtu; io.vtv = p.vtv;
         if (live && p.tu && fall != 0.f) transport::axes(p.tu, p.tv, p.nrm, vi, io.a1, io.a2);
         const float xp[3] = {x, y, z};
         auto frame = [&](int f, float j00, float j01, float j02, float j10, float j11, float j12, float j20, float j21, float j22) {
             if (f >= p.nF) return;
-            const float *fc = s_fc + kVmlFrameWords * f;
+            const float *fc = s_fc + kFrameWords * f;
             io.oN = s_ptr[4 * f]; io.otu = s_ptr[4 * f + 1]; io.otv = s_ptr[4 * f + 2]; io.jac = s_ptr[4 * f + 3];
             if (!live || fc[1] == 0.f) {
-                // gated vertex / unbuilt frame: the vectors bit for bit, A = I
-                for (int c = 0; c < 3; ++c) {
-                    if (io.vN) FrameIOMl::store(&io.oN[3 * vi + c], io.vN[3 * vi + c]);
-                    if (io.vtu) FrameIOMl::store(&io.otu[3 * vi + c], io.vtu[3 * vi + c]);
-                    if (io.vtv) FrameIOMl::store(&io.otv[3 * vi + c], io.vtv[3 * vi + c]);
-                }
-                if (io.jac)
-#pragma unroll
-                    for (int q = 0; q < 9; ++q) FrameIOMl::store(&io.jac[9 * vi + q], (q % 4 == 0) ? 1.f : 0.f);
+                pass_through(io, vi);
                 return;
             }
             const float S[9] = {j00, j01, j02, j10, j11, j12, j20, j21, j22};
@@ -292,25 +248,6 @@ __global__ __launch_bounds__(kVmlThreads) void k_vectors32_shared_ml(const VmlOu
     }
 }
 
-int vml_tiles(int nF) { return nF > 12 ? 3 * ((nF + 15) / 16) : (nF + 3) / 4; }
-
-template <int NT, bool DENSE>
-hipError_t launch_vml_share(const VmlOut &out, const VmlParams &p, int share, unsigned grid, size_t lds, int ngroups, hipStream_t stream)
-{
-#define FD_VML_CASE(SH)                                                                                                       \
-    {                                                                                                                         \
-        static LdsAttrOnce once;                                                                                              \
-        hipError_t e = once.ensure((const void *)k_vectors32_shared_ml<NT, DENSE, SH>, 160 * 1024);                           \
-        if (e != hipSuccess) return e;                                                                                        \
-        hipLaunchKernelGGL((k_vectors32_shared_ml<NT, DENSE, SH>), dim3(grid), dim3(kVmlThreads), lds, stream, out, p, ngroups); \
-        return hipGetLastError();                                                                                             \
-    }
-    if (share == 4) FD_VML_CASE(4)
-    if (share == 2) FD_VML_CASE(2)
-    FD_VML_CASE(1)
-#undef FD_VML_CASE
-}
-
 }  // namespace
 
 hipError_t launch_vectors_shared_ml(const SharedVectorMlArgs &a, hipStream_t stream)
@@ -318,38 +255,26 @@ hipError_t launch_vectors_shared_ml(const SharedVectorMlArgs &a, hipStream_t str
     if (a.N <= 0 || a.nF <= 0) return hipSuccess;
     if (!shared_ml_applies(a.M, a.layers, a.nF) || !a.scratch) return hipErrorInvalidValue;
     const int nrec = a.M * a.layers, nkb = (nrec + 31) / 32;
-    const int NT = vml_tiles(a.nF);
-    const bool dense = a.nF > 12;
+    const int NT = shot_tiles(a.nF);
     VmlParams p{};
-    p.N = a.N; p.P_in = a.P_in; p.dist2 = a.dist2; p.tu = a.tu; p.tv = a.tv; p.nrm = a.nrm;
-    p.vN = a.vN; p.vtu = a.vtu; p.vtv = a.vtv;
-    p.radius2 = a.radius2; p.falloffrate = a.falloffrate;
+    ShotOut out{};
+    fill_shot(p, out, a);
     p.nF = a.nF; p.nkb = nkb; p.srcNT = ml_tiles(a.nF);
     p.scratch = (const uint4 *)a.scratch;
-    VmlOut out{};
-    for (int f = 0; f < a.nF; ++f) { out.N[f] = a.N_out[f]; out.tu[f] = a.tu_out[f]; out.tv[f] = a.tv_out[f]; out.jac[f] = a.jacobian[f]; }
-    const size_t fixed = sizeof(float) * kVmlFrameWords * kMaxBatch + sizeof(float *) * 4 * kMaxBatch;
+    const size_t fixed = sizeof(float) * kFrameWords * kMaxBatch + sizeof(float *) * 4 * kMaxBatch;
     const size_t per_kb = 32 * 16 + (size_t)NT * 128 * 16;
-    const int kmax = (int)((kSharedLdsBudget - fixed) / per_kb);       // >= 12: six tiles are 12.5 KiB a block
-    const int nchunks = (nkb + kmax - 1) / kmax;
-    p.kchunk = (nkb + nchunks - 1) / nchunks;           // even chunks
-    const size_t lds = fixed + per_kb * (size_t)p.kchunk;
-    const int64_t ngroups = (a.N + kVmlGroup - 1) / kVmlGroup;
-    if (ngroups > 0x7fffffff) return hipErrorInvalidValue;
-    // persistent workgroups: as many per CU as the LDS admits, two at most (two waves per SIMD each)
-    const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(2, (int64_t)(160 * 1024 / lds)));
-    const int64_t max_wgs = a.max_wgs > 0 ? (a.max_wgs < 4096 ? a.max_wgs : 4096) : (int64_t)device_cus() * per_cu;
-    const unsigned grid = (unsigned)(ngroups < max_wgs ? ngroups : max_wgs);
-    const int share = ml_share(a.layers);
-    if (dense) {
-        if (NT == 3) return launch_vml_share<3, true>(out, p, share, grid, lds, (int)ngroups, stream);
-        if (NT == 6) return launch_vml_share<6, true>(out, p, share, grid, lds, (int)ngroups, stream);
-    } else {
-        if (NT == 1) return launch_vml_share<1, false>(out, p, share, grid, lds, (int)ngroups, stream);
-        if (NT == 2) return launch_vml_share<2, false>(out, p, share, grid, lds, (int)ngroups, stream);
-        if (NT == 3) return launch_vml_share<3, false>(out, p, share, grid, lds, (int)ngroups, stream);
-    }
-    return hipErrorInvalidValue;
+    p.kchunk = even_chunks(nkb, (int)((kSharedLdsBudget - fixed) / per_kb));       // kmax >= 12: six tiles are 12.5 KiB a block
+    ShotGrid gr;
+    if (hipError_t e = shot_grid(a, fixed + per_kb * (size_t)p.kchunk, gr); e != hipSuccess) return e;
+    return for_tiles(NT, a.nF > 12, [&](auto nt, auto dns) {
+        constexpr int kNT = nt.value;
+        constexpr bool kDense = dns.value;
+        switch (ml_share(a.layers)) {
+        case 4: return launch_shot<k_vectors32_shared_ml<kNT, kDense, 4>>(out, p, gr, stream);
+        case 2: return launch_shot<k_vectors32_shared_ml<kNT, kDense, 2>>(out, p, gr, stream);
+        default: return launch_shot<k_vectors32_shared_ml<kNT, kDense, 1>>(out, p, gr, stream);
+        }
+    });
 }
 
 // The fewest frames at which the one launch is ahead of the per-context k_vectors32_gaussian launches over the M L records,

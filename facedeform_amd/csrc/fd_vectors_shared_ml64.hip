@@ -35,44 +35,22 @@
 #include "fd_pack.h"
 #include "fd_shared64.h"
 #include "fd_shared_ml64.h"
-#include "fd_transport.h"
+#include "fd_vectors_shot.h"
 #include "fd_tuning.h"
 
 namespace fd {
 
 namespace {
 
-constexpr int kVMl64Group = 16 * kS64Waves;        // vertices per workgroup and group
-
-struct VMl64Out {                  // per-frame outputs (the kernel's first argument; dealt into LDS)
-    float *N[kMaxBatch], *tu[kMaxBatch], *tv[kMaxBatch], *jac[kMaxBatch];
-};
-
-struct VMl64Params {
-    int64_t N;
-    const float *P_in, *dist2;
-    const float *tu, *tv, *nrm;          // projection frames (all or none)
-    const float *vN, *vtu, *vtv;         // vectors to transport (shared by the frames)
-    float radius2, falloffrate;
+struct VMl64Params : ShotMesh {
     int nF, nkc, kchunk, L, Mc4;
     const double *scratch;
 };
 
-// one frame of one vertex, as fd_transport.h's jacobian() and carry() read it
-struct FrameIOMl64 {
-    const float *tu, *tv, *nrm;
-    double a1[3], a2[3];
-    const float *vN, *vtu, *vtv;
-    float *oN, *otu, *otv, *jac;
-    static constexpr bool kGivenAxes = true;
-    // (written once, read by nobody in this launch: past L2, like the position launch's stores)
-    static __device__ __forceinline__ void store(float *dst, float v) { __builtin_nontemporal_store(v, dst); }
-};
-
-// (prologue, staging and epilogue are k_vectors64_shared's, fd_vectors_shared64.hip, line for line: a file of its own, so a
-// change to one of the two epilogues is made in the other by hand)
+// (the head of the scratch, the affine step and the epilogue are k_vectors64_shared's, fd_vectors_shared64.hip; the epilogue is
+// each file's own text because a shared function compiles to a slower schedule: DESIGN.md 4.7f)
 template <int NT, bool DENSE>
-__global__ __launch_bounds__(kS64Threads) void k_vectors64_shared_ml(const VMl64Out out, const VMl64Params p, int ngroups)
+__global__ __launch_bounds__(kS64Threads) void k_vectors64_shared_ml(const ShotOut out, const VMl64Params p, int ngroups)
 {
     (void)out;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -94,13 +72,7 @@ __global__ __launch_bounds__(kS64Threads) void k_vectors64_shared_ml(const VMl64
         f64x2 *dst = reinterpret_cast<f64x2 *>(smem);
         for (int q = tid; q < (int)(ml64_cen_at(NT) / 2); q += kS64Threads) dst[q] = src[q];
     }
-    if (tid < 4 * kMaxBatch) {
-        // VMl64Out is the kernel's FIRST argument: its tables read straight from the argument segment (indexed by the thread,
-        // the argument itself would be copied to scratch memory first)
-        const int f = tid >> 2, w = tid & 3;
-        float *const *tab = (float *const *)(uintptr_t)__builtin_amdgcn_kernarg_segment_ptr();
-        s_ptr[tid] = f < p.nF ? tab[kMaxBatch * w + f] : nullptr;
-    }
+    deal_out_pointers(s_ptr, p.nF);
     // centre steps kc0 .. kc0 + nk - 1 of the model into LDS
     auto stage = [&](int kc0, int nk) {
         __syncthreads();
@@ -175,7 +147,7 @@ __global__ __launch_bounds__(kS64Threads) void k_vectors64_shared_ml(const VMl64
 
         // ---- epilogue: lane (g, j) finishes its vertex for the frames whose rows its lane group holds
         if (!inb) continue;
-        FrameIOMl64 io;
+        FrameIO<double> io;
         io.tu = p.tu; io.tv = p.tv; io.nrm = p.nrm;
         io.vN = p.vN; io.vtu = p.vtu; io.vtv = p.vtv;
         if (live && p.tu && fall != 0.f) transport::axes<double>(p.tu, p.tv, p.nrm, vi, io.a1, io.a2);
@@ -211,15 +183,7 @@ __global__ __launch_bounds__(kS64Threads) void k_vectors64_shared_ml(const VMl64
             if (f >= p.nF) continue;
             io.oN = s_ptr[4 * f]; io.otu = s_ptr[4 * f + 1]; io.otv = s_ptr[4 * f + 2]; io.jac = s_ptr[4 * f + 3];
             if (!live || !s_head->built[f]) {
-                // gated vertex / unbuilt frame: the vectors bit for bit, A = I
-                for (int c = 0; c < 3; ++c) {
-                    if (io.vN) FrameIOMl64::store(&io.oN[3 * vi + c], io.vN[3 * vi + c]);
-                    if (io.vtu) FrameIOMl64::store(&io.otu[3 * vi + c], io.vtu[3 * vi + c]);
-                    if (io.vtv) FrameIOMl64::store(&io.otv[3 * vi + c], io.vtv[3 * vi + c]);
-                }
-                if (io.jac)
-#pragma unroll
-                    for (int e = 0; e < 9; ++e) FrameIOMl64::store(&io.jac[9 * vi + e], (e % 4 == 0) ? 1.f : 0.f);
+                pass_through(io, vi);
                 continue;
             }
             double A[9];
@@ -232,28 +196,6 @@ __global__ __launch_bounds__(kS64Threads) void k_vectors64_shared_ml(const VMl64
     }
 }
 
-hipError_t launch_vml64(const VMl64Out &out, const VMl64Params &p, int NT, bool dense, unsigned grid, size_t lds, int ngroups, hipStream_t stream)
-{
-#define FD_VML64_CASE(NTV, DNS)                                                                                               \
-    {                                                                                                                         \
-        static LdsAttrOnce once;                                                                                              \
-        hipError_t e = once.ensure((const void *)k_vectors64_shared_ml<NTV, DNS>, 160 * 1024);                                \
-        if (e != hipSuccess) return e;                                                                                        \
-        hipLaunchKernelGGL((k_vectors64_shared_ml<NTV, DNS>), dim3(grid), dim3(kS64Threads), lds, stream, out, p, ngroups);   \
-        return hipGetLastError();                                                                                             \
-    }
-    if (dense) {
-        if (NT == 3) FD_VML64_CASE(3, true)
-        if (NT == 6) FD_VML64_CASE(6, true)
-    } else {
-        if (NT == 1) FD_VML64_CASE(1, false)
-        if (NT == 2) FD_VML64_CASE(2, false)
-        if (NT == 3) FD_VML64_CASE(3, false)
-    }
-#undef FD_VML64_CASE
-    return hipErrorInvalidValue;
-}
-
 }  // namespace
 
 hipError_t launch_vectors_shared_ml64(const SharedVectorMl64Args &a, hipStream_t stream)
@@ -261,29 +203,18 @@ hipError_t launch_vectors_shared_ml64(const SharedVectorMl64Args &a, hipStream_t
     if (a.N <= 0 || a.nF <= 0) return hipSuccess;
     if (!shared_ml64_applies(a.M, a.layers, a.nF) || !a.scratch) return hipErrorInvalidValue;
     const int NT = s64_tiles(a.nF);
-    const bool dense = a.nF > 12;
     const int Mc4 = round_up(a.M, 4), nkc = Mc4 / 4, L = a.layers;
     VMl64Params p{};
-    p.N = a.N; p.P_in = a.P_in; p.dist2 = a.dist2; p.tu = a.tu; p.tv = a.tv; p.nrm = a.nrm;
-    p.vN = a.vN; p.vtu = a.vtu; p.vtv = a.vtv;
-    p.radius2 = a.radius2; p.falloffrate = a.falloffrate;
+    ShotOut out{};
+    fill_shot(p, out, a);
     p.nF = a.nF; p.nkc = nkc; p.L = L; p.Mc4 = Mc4;
     p.scratch = (const double *)a.scratch;
-    VMl64Out out{};
-    for (int f = 0; f < a.nF; ++f) { out.N[f] = a.N_out[f]; out.tu[f] = a.tu_out[f]; out.tv[f] = a.tv_out[f]; out.jac[f] = a.jacobian[f]; }
     const size_t fixed = 8 * ml64_cen_at(NT) + sizeof(float *) * 4 * kMaxBatch;
     const size_t per_kc = 8 * ((size_t)4 * kMl64Cen + ml64_step_w(NT, L));
-    const int kmax = (int)((kS64LdsBudget - fixed) / per_kc);         // >= 6: 8 layers x 6 tiles are 24.2 KiB a step
-    const int nchunks = (nkc + kmax - 1) / kmax;
-    p.kchunk = (nkc + nchunks - 1) / nchunks;           // even chunks of whole centre steps
-    const size_t lds = fixed + per_kc * (size_t)p.kchunk;
-    const int64_t ngroups = (a.N + kVMl64Group - 1) / kVMl64Group;
-    if (ngroups > 0x7fffffff) return hipErrorInvalidValue;
-    // persistent workgroups: as many per CU as the LDS admits, two at most
-    const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(2, (int64_t)(160 * 1024 / lds)));
-    const int64_t max_wgs = a.max_wgs > 0 ? (a.max_wgs < 4096 ? a.max_wgs : 4096) : (int64_t)device_cus() * per_cu;
-    const unsigned grid = (unsigned)(ngroups < max_wgs ? ngroups : max_wgs);
-    return launch_vml64(out, p, NT, dense, grid, lds, (int)ngroups, stream);
+    p.kchunk = even_chunks(nkc, (int)((kS64LdsBudget - fixed) / per_kc));         // kmax >= 6: 8 layers x 6 tiles are 24.2 KiB a step
+    ShotGrid gr;
+    if (hipError_t e = shot_grid(a, fixed + per_kc * (size_t)p.kchunk, gr); e != hipSuccess) return e;
+    return for_tiles(NT, a.nF > 12, [&](auto nt, auto dns) { return launch_shot<k_vectors64_shared_ml<nt.value, dns.value>>(out, p, gr, stream); });
 }
 
 // The fewest frames at which the one launch is ahead of the per-context k_vectors64_gaussian launches over the M L records,

@@ -1,0 +1,152 @@
+// fd_vectors_shot.h -- what the four one-launch vector kernels of a shot share (fd_vectors_shared.hip, fd_vectors_shared64.hip,
+// fd_vectors_shared_ml.hip, fd_vectors_shared_ml64.hip): the kernel arguments every one of them takes, the
+// deal of the output pointers into LDS, the pass-through of a gated vertex, and the host side of a launch -- arguments,
+// chunking, grid, the (NT, DENSE) dispatch.  ONE copy.  The files keep their frame constants, staging, K loops and their
+// epilogues: in functions here the epilogues compile to other schedules, measurably slower in fp64; as
+// the header stands, every kernel's instruction stream is what it was with the copies in the files.
+//
+// All four launches run 8 waves per workgroup, a wave owning one vertex tile of 16 per group, and deal the frames onto NT row
+// tiles of 16: padded up to 12 frames (tile T = frames 4 T .. 4 T + 3), dense from 13.
+#pragma once
+#include <algorithm>
+#include <type_traits>
+
+#include "fd_eval_common.h"
+#include "fd_shared64.h"
+#include "fd_transport.h"
+
+namespace fd {
+namespace {
+
+constexpr int kShotWaves = 8;
+constexpr int kShotThreads = 64 * kShotWaves;
+constexpr int kShotGroup = 16 * kShotWaves;        // vertices per workgroup and group
+static_assert(kShotThreads == kS64Threads, "the fp64 launches stage with the position launch's thread count");
+constexpr int kFrameWords = 16;                    // fp32 launches, per frame in LDS: {basis scale, built, L'[3][3], q[3], 2 unused}
+
+// ---- kernel arguments ----
+struct ShotOut {                  // per-frame outputs (the kernel's FIRST argument; dealt into LDS by deal_out_pointers)
+    float *N[kMaxBatch], *tu[kMaxBatch], *tv[kMaxBatch], *jac[kMaxBatch];
+};
+
+// the head of every launch's Params: the mesh and the vectors (nF follows in the Params themselves: in here it would end the
+// struct with four bytes of padding and move every field behind it in the argument segment)
+struct ShotMesh {
+    int64_t N;
+    const float *P_in, *dist2;
+    const float *tu, *tv, *nrm;          // projection frames (all or none)
+    const float *vN, *vtu, *vtv;         // vectors to transport (shared by the frames)
+    float radius2, falloffrate;
+};
+
+// ---- device side ----
+// one frame of one vertex, as fd_transport.h's transport(), jacobian() and carry() read it; T: the precision of the axes
+template <typename T>
+struct FrameIO {
+    const float *tu, *tv, *nrm;
+    T a1[3], a2[3];
+    const float *vN, *vtu, *vtv;
+    float *oN, *otu, *otv, *jac;
+    static constexpr bool kGivenAxes = true;
+    // (written once, read by nobody in this launch: past L2, like the position launch's stores)
+    static __device__ __forceinline__ void store(float *dst, float v) { __builtin_nontemporal_store(v, dst); }
+};
+
+__device__ __forceinline__ float half_at(const uint4 *base, size_t word, int e)
+{
+    const unsigned short u = reinterpret_cast<const unsigned short *>(base + word)[e];
+    return (float)__builtin_bit_cast(_Float16, u);
+}
+
+// ShotOut is the kernel's FIRST argument: its tables are read straight from the argument segment (indexed by the thread, the
+// argument itself would be copied to scratch memory first; unrolled over constant indices, it is held in SGPRs and spilled)
+__device__ __forceinline__ void deal_out_pointers(float **s_ptr, int nF)
+{
+    const int tid = threadIdx.x;
+    if (tid < 4 * kMaxBatch) {
+        const int f = tid >> 2, w = tid & 3;
+        float *const *tab = (float *const *)(uintptr_t)__builtin_amdgcn_kernarg_segment_ptr();
+        s_ptr[tid] = f < nF ? tab[kMaxBatch * w + f] : nullptr;
+    }
+}
+
+// gated vertex / unbuilt frame: the vectors bit for bit, A = I
+template <class IO>
+__device__ __forceinline__ void pass_through(const IO &io, int64_t vi)
+{
+    for (int c = 0; c < 3; ++c) {
+        if (io.vN) IO::store(&io.oN[3 * vi + c], io.vN[3 * vi + c]);
+        if (io.vtu) IO::store(&io.otu[3 * vi + c], io.vtu[3 * vi + c]);
+        if (io.vtv) IO::store(&io.otv[3 * vi + c], io.vtv[3 * vi + c]);
+    }
+    if (io.jac)
+#pragma unroll
+        for (int q = 0; q < 9; ++q) IO::store(&io.jac[9 * vi + q], (q % 4 == 0) ? 1.f : 0.f);
+}
+
+// ---- host side ----
+inline int shot_tiles(int nF) { return nF > 12 ? 3 * ((nF + 15) / 16) : (nF + 3) / 4; }      // as s64_tiles
+
+inline void fill_shot(ShotMesh &p, ShotOut &out, const SharedVectorCommon &a)
+{
+    p.N = a.N; p.P_in = a.P_in; p.dist2 = a.dist2; p.tu = a.tu; p.tv = a.tv; p.nrm = a.nrm;
+    p.vN = a.vN; p.vtu = a.vtu; p.vtv = a.vtv;
+    p.radius2 = a.radius2; p.falloffrate = a.falloffrate;
+    for (int f = 0; f < a.nF; ++f) { out.N[f] = a.N_out[f]; out.tu[f] = a.tu_out[f]; out.tv[f] = a.tv_out[f]; out.jac[f] = a.jacobian[f]; }
+}
+
+// n K steps in the fewest chunks of at most kmax, evened out (as the position launches stage them)
+inline int even_chunks(int n, int kmax)
+{
+    const int nchunks = (n + kmax - 1) / kmax;
+    return (n + nchunks - 1) / nchunks;
+}
+
+struct ShotGrid {
+    size_t lds;
+    unsigned grid;
+    int ngroups;
+};
+
+// persistent workgroups: as many per CU as the LDS admits, two at most (two waves per SIMD each)
+inline hipError_t shot_grid(const SharedVectorCommon &a, size_t lds, ShotGrid &gr)
+{
+    const int64_t ngroups = (a.N + kShotGroup - 1) / kShotGroup;
+    if (ngroups > 0x7fffffff) return hipErrorInvalidValue;
+    const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(2, (int64_t)(160 * 1024 / lds)));
+    const int64_t max_wgs = a.max_wgs > 0 ? (a.max_wgs < 4096 ? a.max_wgs : 4096) : (int64_t)device_cus() * per_cu;
+    gr.lds = lds;
+    gr.grid = (unsigned)(ngroups < max_wgs ? ngroups : max_wgs);
+    gr.ngroups = (int)ngroups;
+    return hipSuccess;
+}
+
+template <auto Kernel, class Params>
+hipError_t launch_shot(const ShotOut &out, const Params &p, const ShotGrid &gr, hipStream_t stream)
+{
+    static LdsAttrOnce once;          // one per kernel instantiation
+    hipError_t e = once.ensure((const void *)Kernel, 160 * 1024);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(Kernel, dim3(gr.grid), dim3(kShotThreads), gr.lds, stream, out, p, gr.ngroups);
+    return hipGetLastError();
+}
+
+// f(NT, DENSE) as compile-time constants for the tile counts a shot can have (s64_tiles, dense from 13 frames):
+//   for_tiles(NT, dense, [&](auto nt, auto dns) { return launch_shot<k<nt.value, dns.value>>(...); })
+template <class F>
+hipError_t for_tiles(int NT, bool dense, F &&f)
+{
+    using std::integral_constant;
+    if (dense) {
+        if (NT == 3) return f(integral_constant<int, 3>{}, std::true_type{});
+        if (NT == 6) return f(integral_constant<int, 6>{}, std::true_type{});
+    } else {
+        if (NT == 1) return f(integral_constant<int, 1>{}, std::false_type{});
+        if (NT == 2) return f(integral_constant<int, 2>{}, std::false_type{});
+        if (NT == 3) return f(integral_constant<int, 3>{}, std::false_type{});
+    }
+    return hipErrorInvalidValue;
+}
+
+}  // namespace
+}  // namespace fd
