@@ -80,7 +80,7 @@ EXPORTS = [
     "fd_morph_set_rest", "fd_morph_is_initialised", "fd_morph_is_computed", "fd_morph_shape_count", "fd_morph_last_init_ms",
     "fd_morph_compute_weights_dev", "fd_morph_displace_dev", "fd_morph_apply", "fd_morph_get_weights",
     "fd_morph_get_qr", "fd_morph_compute_weights_batch_dev", "fd_morph_displace_batch_dev", "fd_morph_get_weights_batch",
-    "fd_batch_create", "fd_batch_destroy", "fd_batch_size", "fd_batch_last_error", "fd_batch_wait_consumed", "fd_batch_prepare_shared", "fd_batch_set_eval_cus", "fd_batch_cook_group", "fd_shared_kernel_name", "fd_batch_set_shared_factor", "fd_batch_last_build_shared_factor", "fd_shared_ml_build_kernel_name",
+    "fd_batch_create", "fd_batch_destroy", "fd_batch_size", "fd_batch_last_error", "fd_batch_wait_consumed", "fd_batch_prepare_shared", "fd_batch_set_eval_cus", "fd_batch_cook_group", "fd_shared_kernel_name", "fd_batch_set_shared_factor", "fd_batch_last_build_shared_factor", "fd_shared_ml_build_kernel_name", "fd_batch_set_shared_lu", "fd_shared_qnn_build_kernel_name",
     "fd_batch_set_points_dev", "fd_batch_build_async", "fd_batch_build_result", "fd_batch_deform_dev",
     "fd_batch_deform_shared_dev", "fd_batch_deform_vectors_shared_dev", "fd_shared_vectors_kernel_name",
     "fd_batch_deform_shared_fp64_dev", "fd_shared_fp64_kernel_name",
@@ -209,6 +209,8 @@ def load() -> C.CDLL:
     L.fd_batch_deform_shared_ml_dev.restype = i32
     L.fd_shared_ml_kernel_name.argtypes = [i32, i32, i32]; L.fd_shared_ml_kernel_name.restype = C.c_char_p
     L.fd_shared_ml_build_kernel_name.argtypes = [i32, i32, i32]; L.fd_shared_ml_build_kernel_name.restype = C.c_char_p
+    L.fd_batch_set_shared_lu.argtypes = [vp, i32]; L.fd_batch_set_shared_lu.restype = i32
+    L.fd_shared_qnn_build_kernel_name.argtypes = [i32, i32]; L.fd_shared_qnn_build_kernel_name.restype = C.c_char_p
     L.fd_batch_deform_shared_ml_fp64_dev.argtypes = [vp, vp, i64, vp, pv, vp, pv, vp, vp, vp, C.c_float, C.c_float]
     L.fd_batch_deform_shared_ml_fp64_dev.restype = i32
     L.fd_shared_ml_fp64_kernel_name.argtypes = [i32, i32, i32]; L.fd_shared_ml_fp64_kernel_name.restype = C.c_char_p
@@ -701,6 +703,10 @@ class Batch:
         """fd_batch_set_shared_factor: one factorisation per batched build where the contexts share the rest array."""
         self._check(self.L.fd_batch_set_shared_factor(self.h, 1 if on else 0))
 
+    def set_shared_lu(self, on: bool = True):
+        """fd_batch_set_shared_lu: one LU of the rest rig's kernel block per batched build of QNN contexts that share the rest array."""
+        self._check(self.L.fd_batch_set_shared_lu(self.h, 1 if on else 0))
+
     def last_build_shared_factor(self) -> bool:
         return bool(self.L.fd_batch_last_build_shared_factor(self.h))
 
@@ -889,6 +895,11 @@ def fd_shared_ml_kernel_name(M: int, layers: int, frames: int) -> str:
 def fd_shared_ml_build_kernel_name(M: int, layers: int, frames: int) -> str:
     """The kernel a multilayer batch's build solves all frames with under set_shared_factor ("" where every model is built on its own)."""
     return load().fd_shared_ml_build_kernel_name(int(M), int(layers), int(frames)).decode()
+
+
+def fd_shared_qnn_build_kernel_name(M: int, frames: int) -> str:
+    """The kernel a QNN batch's build solves all frames with under set_shared_lu ("" where every model is built on its own)."""
+    return load().fd_shared_qnn_build_kernel_name(int(M), int(frames)).decode()
 
 
 def fd_shared_ml_fp64_kernel_name(M: int, layers: int, frames: int) -> str:

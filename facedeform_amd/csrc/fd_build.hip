@@ -1090,9 +1090,9 @@ hipError_t launch_qnn_radii(const BuildBuffers &b, hipStream_t stream)
     return hipGetLastError();
 }
 
-// the pivoted LU of the assembled order-npad system (right-hand sides in the columns npad ..) and
-// its back-substitution into X; b.n real unknowns, the rest identity padding
-hipError_t launch_lu_factor_solve(const BuildBuffers &b, hipStream_t stream)
+// the LU of the assembled order-npad system (the right-hand sides in the columns npad .. ride along);
+// b.n real unknowns, the rest identity padding
+hipError_t launch_lu_factor(const BuildBuffers &b, hipStream_t stream)
 {
     int k0 = 0, step = 0;
     while (k0 < b.npad) {
@@ -1113,6 +1113,14 @@ hipError_t launch_lu_factor_solve(const BuildBuffers &b, hipStream_t stream)
         k0 += w;
         ++step;
     }
+    return hipGetLastError();
+}
+
+// ... and its back-substitution into X
+hipError_t launch_lu_factor_solve(const BuildBuffers &b, hipStream_t stream)
+{
+    hipError_t e = launch_lu_factor(b, stream);
+    if (e != hipSuccess) return e;
     launch_backsub(b, stream, b.npad);
     return hipGetLastError();
 }

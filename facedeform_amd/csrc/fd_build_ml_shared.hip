@@ -17,24 +17,22 @@
 //                       v_mfma_f64_16x16x4_f64, right-looking, the row tiles dealt to the four
 //                       waves (no sum crosses a wave) with the next tile's piece of L in flight
 //                       under the current one -- w into the owning context's W, lambda w on.
+//                       (Prologue, sweeps and tile products: fd_shared_solve.h, shared with the
+//                       QNN model's k_qnn_solve_shared.)
 //   k_ml_shared_flags   what the factorisations reported, into every frame's DevModel
 //
 // No atomics, fixed summation orders: the same inputs give the same bits on every call.
 #include "fd_internal.h"
 #include "fd_eval_common.h"
+#include "fd_shared_solve.h"
 
 namespace fd {
 
 namespace {
 
-typedef double double4_t __attribute__((ext_vector_type(4)));
+using namespace shared_solve;          // what this kernel shares with k_qnn_solve_shared (fd_shared_solve.h)
 
-// one 128-VGPR slot: this runs beside evaluation launches (see fd_nullspace.hip)
-#define FD_FIT_BESIDE_EVAL __attribute__((amdgpu_waves_per_eu(4, 8)))
-
-constexpr int kTile = 16;               // right-hand-side columns per workgroup: one MFMA tile
-constexpr int kNB = 32;                 // the Cholesky block width of fd_nullspace.hip
-constexpr int kMaxM = 1024;             // 128 M bytes of LDS per workgroup
+constexpr int kMaxM = kMaxRows;         // 128 M bytes of LDS per workgroup
 constexpr int kMinFrames = 2;           // fewer frames: the per-context chain
 
 struct SolveArgs {
@@ -77,67 +75,7 @@ __global__ void k_ml_shared_flags(const BatchSlot *frames, const BatchSlot *laye
 {
     const int f = threadIdx.x;
     if (f >= nF) return;
-    DevModel *m = frames[f].model;
-    int dup = m->dup_flag, sing = m->sing_flag;
-    unsigned long long amax = m->amax_bits, pmin = m->pivmin_bits, pmax = m->pivmax_bits;    // non-negative doubles: ordered as their bits
-    for (int l = 0; l < L; ++l) {
-        const DevModel *s = layers[l].model;
-        dup |= s->dup_flag;
-        sing |= s->sing_flag;
-        amax = s->amax_bits > amax ? s->amax_bits : amax;
-        pmin = s->pivmin_bits < pmin ? s->pivmin_bits : pmin;
-        pmax = s->pivmax_bits > pmax ? s->pivmax_bits : pmax;
-    }
-    m->dup_flag = dup; m->sing_flag = sing;
-    m->amax_bits = amax; m->pivmin_bits = pmin; m->pivmax_bits = pmax;
-    m->iterations = layers[L - 1].model->iterations;       // as the per-context chain leaves it: the last layer's
-}
-
-// the eight A operands of one 16-row tile against a 32-column block: -op[c][g + 4 s], element (row, col) at base[col * lda + row].
-// `base` is wave-uniform (column kb, row 0), the lane's part a 32-bit offset: scalar base + one address register per load
-__device__ __forceinline__ void load_ops(double (&a)[8], gcdouble *base, int lda, unsigned lane_off)
-{
-#pragma unroll
-    for (int s = 0; s < 8; ++s) a[s] = -(base + (size_t)(4 * s) * lda)[lane_off];
-}
-
-// rows r0 .. r0+15 of the block take the contribution of the 32 solved rows whose values wait in yb (B operands)
-__device__ __forceinline__ void update_tile(double *Bs, int r0, int c, int g, const double (&a)[8], const double (&yb)[8])
-{
-    double *p = Bs + (size_t)(r0 + g) * kTile + c;
-    double4_t acc;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) acc[r] = p[4 * r * kTile];
-#pragma unroll
-    for (int s = 0; s < 8; ++s) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s], yb[s], acc, 0, 0, 0);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) p[4 * r * kTile] = acc[r];
-}
-
-// wave 0: rows kb .. kb+31 of the block <- inverse(L11) (forward) or inverse(L11)^T (backward) times themselves.
-// inv: row-major [k][j] = inverse(L11)[k][j], lower triangular -- the half that is zero is skipped.
-__device__ __forceinline__ void diag_step(double *Bs, int kb, int c, int g, gcdouble *inv, bool transposed)
-{
-    double yb[8];
-#pragma unroll
-    for (int s = 0; s < 8; ++s) yb[s] = Bs[(size_t)(kb + g + 4 * s) * kTile + c];
-    double4_t acc[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        acc[t] = double4_t{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int s = 0; s < 8; ++s) {
-            // forward: rows 0..15 see columns 0..15 only; backward: rows 16..31 see rows 16..31 of the inverse only
-            if ((!transposed && t == 0 && s >= 4) || (transposed && t == 1 && s < 4)) continue;
-            const unsigned at = transposed ? (unsigned)((g + 4 * s) * kNB + 16 * t + c) : (unsigned)((16 * t + c) * kNB + g + 4 * s);
-            const double a = inv[at];
-            acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, yb[s], acc[t], 0, 0, 0);
-        }
-    }
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) Bs[(size_t)(kb + 16 * t + g + 4 * r) * kTile + c] = acc[t][r];
+    hand_flags(frames[f].model, layers, L);       // (fd_shared_solve.h: the QNN model's shared build hands its one slot's on inside its solve kernel)
 }
 
 __global__ __launch_bounds__(256) FD_FIT_BESIDE_EVAL void k_ml_solve_shared(const SolveArgs a)
@@ -149,110 +87,26 @@ __global__ __launch_bounds__(256) FD_FIT_BESIDE_EVAL void k_ml_solve_shared(cons
     const int M = a.M, T = a.T, npc = a.npc, lda = a.lda;
 
     // fit and hand-off: thread (j, rg) owns column j of the tile in the rows rg, rg + 16, ...
-    const int j = tid & 15, rg = tid >> 4;
-    const int gc = (int)blockIdx.x * kTile + j;
-    const bool live = gc < 3 * a.nF;
-    const int f = live ? gc / 3 : 0, comp = live ? gc % 3 : 0;
-    const BatchSlot &fs = a.frames[f];
-    const float FD_GLOBAL *delta = as_global(fs.delta);
+    const Column o = own_column(tid, a.nF);
+    const int j = o.j, rg = o.rg, comp = o.comp;
+    const bool live = o.live;
+    const BatchSlot &fs = a.frames[o.f];
     gdouble *W = as_global(fs.W);
     const BatchSlot &s0 = a.layers[0];
-    gcdouble *V = as_global(s0.ns), *small = V + (size_t)12 * M, *centres = as_global(s0.centres);
+    gcdouble *V = as_global(s0.ns);
 
-    for (int i = rg; i < npc; i += 16) Bs[(size_t)i * kTile + j] = (live && i < M) ? (double)delta[3 * (size_t)i + comp] : 0.0;
-    if (T > 0) {
-        // Q^T f through the shared reflectors, in place; the polynomial from its pivot rows; then f - P a from the deltas anew
-        for (int k = 0; k < T; ++k) {
-            const int piv = M - 1 - k;
-            const double tau = small[a.at.tau + k];
-            double d = 0.0;
-            for (int i = rg; i <= piv; i += 16) d = fma(V[4 * (size_t)i + k], Bs[(size_t)i * kTile + j], d);
-            s_red[rg * kTile + j] = d;
-            __syncthreads();
-            d = 0.0;
-#pragma unroll
-            for (int q = 0; q < 16; ++q) d += s_red[q * kTile + j];
-            for (int i = rg; i <= piv; i += 16) Bs[(size_t)i * kTile + j] = fma(-tau * d, V[4 * (size_t)i + k], Bs[(size_t)i * kTile + j]);
-            __syncthreads();
-        }
-        double pa[4] = {0.0, 0.0, 0.0, 0.0};
-        for (int k = T - 1; k >= 0; --k) {
-            if (M - 1 - k < 0) continue;
-            double v = Bs[(size_t)(M - 1 - k) * kTile + j];
-            for (int cc = k + 1; cc < T; ++cc) v = fma(-small[a.at.R + 4 * k + cc], pa[cc], v);
-            pa[k] = v / small[a.at.R + 4 * k + k];
-        }
-        __syncthreads();                  // everyone has read the pivot rows
-        for (int i = rg; i < M; i += 16) {
-            const double px = centres[3 * (size_t)i], py = centres[3 * (size_t)i + 1], pz = centres[3 * (size_t)i + 2];
-            double v = live ? (double)delta[3 * (size_t)i + comp] : 0.0;
-            v -= fma(pa[3], pz, fma(pa[2], py, fma(pa[1], px, pa[0])));
-            Bs[(size_t)i * kTile + j] = live ? v : 0.0;
-        }
-        if (live && rg == 0) {
-            gdouble *mine = as_global(fs.ns) + (size_t)12 * M;      // where k_ml_finish looks for the polynomial
-#pragma unroll
-            for (int k = 0; k < 4; ++k) mine[a.at.aff + 3 * k + comp] = pa[k];
-        }
-    }
-    __syncthreads();
+    // Q^T f through the shared reflectors, in place; the polynomial from its pivot rows; then f - P a from the deltas anew
+    fit_polynomial(Bs, s_red, o, as_global(fs.delta), V, V + (size_t)12 * M, as_global(s0.centres), as_global(fs.ns) + (size_t)12 * M,
+                   M, T, npc, a.at);
 
-    const unsigned goff = (unsigned)(g * lda + c);        // the lane's place in a 16-row, 4-column piece of L
     for (int l = 0; l < a.L; ++l) {
         const BatchSlot &sl = a.layers[l];
         gcdouble *A = as_global(sl.A);
-        gcdouble *ld = as_global(sl.ns) + (size_t)12 * M + a.at.ld;
+        gcdouble *inv = as_global(sl.ns) + (size_t)12 * M + a.at.ld + a.at.ld_inv;      // inverse(L11) of block 0
 
-        // ---- L y = r, top down: block kb solved, the rows below it updated
-#pragma unroll 1
-        for (int kb = 0; kb < npc; kb += kNB) {
-            const int nt = (npc - kb - kNB) / 16;             // row tiles below the block
-            int t = wave;
-            double an[8];
-            if (t < nt) load_ops(an, A + (size_t)kb * lda, lda, goff + (unsigned)(kb + kNB + 16 * t));     // in flight under the diagonal step
-            if (wave == 0) diag_step(Bs, kb, c, g, ld + (size_t)(kb / kNB) * a.at.ld_stride + a.at.ld_inv, false);
-            __syncthreads();
-            if (nt > 0) {
-                double yb[8];
-#pragma unroll
-                for (int s = 0; s < 8; ++s) yb[s] = Bs[(size_t)(kb + g + 4 * s) * kTile + c];
-                while (t < nt) {
-                    double ac[8];
-#pragma unroll
-                    for (int s = 0; s < 8; ++s) ac[s] = an[s];
-                    const int tn = t + 4;
-                    if (tn < nt) load_ops(an, A + (size_t)kb * lda, lda, goff + (unsigned)(kb + kNB + 16 * tn));
-                    update_tile(Bs, kb + kNB + 16 * t, c, g, ac, yb);
-                    t = tn;
-                }
-                __syncthreads();
-            }
-        }
-        // ---- L^T w = y, bottom up: the rows above block kb read L^T from the mirrored upper triangle
-#pragma unroll 1
-        for (int kb = npc - kNB; kb >= 0; kb -= kNB) {
-            const int nt = kb / 16;
-            int t = wave;
-            double an[8];
-            if (t < nt) load_ops(an, A + (size_t)kb * lda, lda, goff + (unsigned)(16 * t));
-            if (wave == 0) diag_step(Bs, kb, c, g, ld + (size_t)(kb / kNB) * a.at.ld_stride + a.at.ld_inv, true);
-            __syncthreads();
-            if (nt > 0) {
-                double yb[8];
-#pragma unroll
-                for (int s = 0; s < 8; ++s) yb[s] = Bs[(size_t)(kb + g + 4 * s) * kTile + c];
-                while (t < nt) {
-                    double ac[8];
-#pragma unroll
-                    for (int s = 0; s < 8; ++s) ac[s] = an[s];
-                    const int tn = t + 4;
-                    if (tn < nt) load_ops(an, A + (size_t)kb * lda, lda, goff + (unsigned)(16 * tn));
-                    update_tile(Bs, 16 * t, c, g, ac, yb);
-                    t = tn;
-                }
-                __syncthreads();
-            }
-        }
+        // ---- L y = r, top down; L^T w = y, bottom up: the rows above a block read L^T from the mirrored upper triangle
+        sweep_down(Bs, A, lda, npc, inv, (size_t)a.at.ld_stride, wave, c, g);
+        sweep_up(Bs, A, lda, npc, inv, (size_t)a.at.ld_stride, wave, c, g);
         // ---- layer l solved: its weights into the owning model (layer-major, as k_ml_layer writes them), lambda w_l on
         const bool last = l + 1 == a.L;
         for (int i = rg; i < M; i += 16) {

@@ -165,6 +165,11 @@ struct fd_batch {
     int last_shared_factor = 0;          // the last build took that path
     void *d_mlfac = nullptr;             // multilayer batches: the L layer factors' scratch (ml_shared_scratch_bytes), allocated at the first such build
     size_t cap_mlfac = 0;
+    int shared_lu = 0;                   // fd_batch_set_shared_lu: QNN batches, one LU of the rest rig's kernel block per build
+    void *d_qnnfac = nullptr;            // ... and its scratch (qnn_shared_scratch_bytes), allocated at the first such build, grown by need
+    size_t cap_qnnfac = 0;
+    bool qnn_slot_ready = false;         // the last shared build went out whole: its solve kernel left the scratch slot filled and reset
+    int qnn_slot_M = 0, qnn_slot_npad = 0;   // ... for a system of these sizes (they decide where the slot's pieces lie in the scratch)
     int cur_set = 0;                     // the set packed last
     bool packed_valid = false;           // sets[cur_set].packed_ev is recorded (fd_batch_wait_consumed)
     bool prepared = false;               // sets[cur_set] holds the contexts' CURRENT models and prep_* outputs
@@ -1620,6 +1625,7 @@ void fd_batch_destroy(fd_batch *b)
     }
     if (b->d_fac) (void)hipFree(b->d_fac);
     if (b->d_mlfac) (void)hipFree(b->d_mlfac);
+    if (b->d_qnnfac) (void)hipFree(b->d_qnnfac);
     if (b->fallback_ev) (void)hipEventDestroy(b->fallback_ev);
     for (ShotScratch *sc : {&b->s64, &b->sml, &b->sml64}) shot_free(*sc);
     if (b->group_ev) (void)hipEventDestroy(b->group_ev);
@@ -1703,6 +1709,7 @@ int fd_batch_build_async(fd_batch *b, void *hip_stream)
         if (b->gens[i] != c->alloc_gen) table_stale = true;
     }
     if (table_stale) {
+        b->qnn_slot_ready = false;       // the scratch slot of the shared QNN build borrows context 0's buffers
         BatchSlot tab[kMaxBatch];
         for (int i = 0; i < b->n; ++i) { tab[i] = b->ctxs[i]->h_slot; b->gens[i] = b->ctxs[i]->alloc_gen; }
         // buffers only move through hipFree, which has drained the device: nobody reads the old table
@@ -1733,9 +1740,23 @@ int fd_batch_build_async(fd_batch *b, void *hip_stream)
         if (hipMalloc(&b->d_mlfac, ml_shared_scratch_bytes(bb)) != hipSuccess) { (void)hipGetLastError(); b->d_mlfac = nullptr; shared_ml = false; }
         else b->cap_mlfac = ml_shared_scratch_bytes(bb);
     }
+    // A shot of QNN models (fd_batch_set_shared_lu): radii per frame, then reflectors, kernel block and its LU without pivot
+    // search once for the group, every frame's right-hand sides through that factor in one launch (launch_build_qnn_shared).
+    // Anything it does not take -- other rest arrays, too few contexts, a context that fell back to the pivoted LU, fewer points
+    // than polynomial columns, no scratch -- builds every model on its own as ever.
+    bool shared_qnn = b->shared_lu != 0 && c0->kind == FD_KERNEL_GAUSSIAN_QNN && bb.ml_layers == 0 && bb.nopivot && !bb.spd &&
+                      bb.npad <= 1024 && bb.M >= bb.T && same_rest_launch && qnn_shared_applies(bb.M, b->n);
+    for (int i = 0; i < b->n && shared_qnn; ++i) shared_qnn = b->ctxs[i]->solver == FD_SOLVER_AUTO;
+    if (shared_qnn && qnn_shared_init() != hipSuccess) { (void)hipGetLastError(); shared_qnn = false; }
+    if (shared_qnn && qnn_shared_scratch_bytes(bb) > b->cap_qnnfac) {
+        if (b->d_qnnfac) (void)hipFree(b->d_qnnfac);        // (hipFree drains the device: nobody reads the old scratch)
+        b->d_qnnfac = nullptr; b->cap_qnnfac = 0; b->qnn_slot_ready = false;
+        if (hipMalloc(&b->d_qnnfac, qnn_shared_scratch_bytes(bb)) != hipSuccess) { (void)hipGetLastError(); b->d_qnnfac = nullptr; shared_qnn = false; }
+        else b->cap_qnnfac = qnn_shared_scratch_bytes(bb);
+    }
 
     const GraphKey key = graph_key(c0, (bb.spd << 9) | (bb.small << 10) | (bb.reg << 11) | (bb.nopivot << 12), false);
-    if (!bb.reg && !shared_ml && b->use_graph &&
+    if (!bb.reg && !shared_ml && !shared_qnn && b->use_graph &&
         ensure_graph(stream, &b->exec, &b->key, key, [&] { return launch_build(bb, stream, nullptr); }) != hipSuccess)
         b->use_graph = false;
 #define FD_BHIP(call)                                                                         \
@@ -1751,7 +1772,7 @@ int fd_batch_build_async(fd_batch *b, void *hip_stream)
     if (shared_fac && !b->d_fac && hipMalloc((void **)&b->d_fac, sizeof(double) * reg_factor_doubles()) != hipSuccess) {
         (void)hipGetLastError(); b->d_fac = nullptr; shared_fac = false;
     }
-    b->last_shared_factor = (shared_fac || shared_ml) ? 1 : 0;
+    b->last_shared_factor = (shared_fac || shared_ml || shared_qnn) ? 1 : 0;
     if (!b->lean) FD_BHIP(hipEventRecord(b->ev0, stream));      // (lean: the group's first packet is its first kernel; the reports carry no phase times)
     if (shared_fac) {
         FD_BHIP(launch_build_reg_shared(bb, stream, &b->src, nullptr, b->d_fac));
@@ -1769,6 +1790,13 @@ int fd_batch_build_async(fd_batch *b, void *hip_stream)
         // plain launches, outside the captured graph (which is the per-context chain's)
         FD_BHIP(hipEventRecord(b->ev_mid, stream));
         FD_BHIP(launch_build_ml_shared(bb, stream, b->d_mlfac));
+    } else if (shared_qnn) {
+        FD_BHIP(hipEventRecord(b->ev_mid, stream));
+        // plain launches, outside the captured graph (measured: replaying them from a graph of their own changes nothing)
+        const bool fill = !(b->qnn_slot_ready && b->qnn_slot_M == bb.M && b->qnn_slot_npad == bb.npad);
+        b->qnn_slot_ready = false;
+        FD_BHIP(launch_build_qnn_shared(bb, stream, b->d_qnnfac, fill));
+        b->qnn_slot_ready = true; b->qnn_slot_M = bb.M; b->qnn_slot_npad = bb.npad;
     } else if (b->use_graph && b->exec) {
         FD_BHIP(hipEventRecord(b->ev_mid, stream));
         FD_BHIP(hipGraphLaunch(b->exec, stream));
@@ -1784,6 +1812,8 @@ int fd_batch_build_async(fd_batch *b, void *hip_stream)
     // (lean: the reports carry no phase times; the register-resident build has no phases to split)
     hipEvent_t t0 = b->lean ? nullptr : b->ev0, t_mid = b->lean ? nullptr : (bb.reg ? b->ev0 : b->ev_mid), t1 = b->lean ? nullptr : b->ev1;
     for (int i = 0; i < b->n; ++i) note_build_enqueued(b->ctxs[i], b->ev1, stream, b, t0, t_mid, t1, &bb, this_build);
+    if (shared_qnn)      // the factor stays in the batch's scratch: nothing of it in the contexts for fd_set_deltas
+        for (int i = 0; i < b->n; ++i) b->ctxs[i]->have_factor = false;
     arm_status(b->ctxs, b->n, stream, bb.reg != 0, b->ev1, b->status_ev);
     return FD_OK;
 }
@@ -2716,6 +2746,15 @@ int fd_batch_set_shared_factor(fd_batch *b, int on)
 int fd_batch_last_build_shared_factor(const fd_batch *b) { return b ? b->last_shared_factor : 0; }
 
 const char *fd_shared_ml_build_kernel_name(int M, int layers, int frames) { return ml_shared_kernel_name(M, layers, frames); }
+
+int fd_batch_set_shared_lu(fd_batch *b, int on)
+{
+    if (!b) return FD_E_INVALID;
+    b->shared_lu = on ? 1 : 0;
+    return FD_OK;
+}
+
+const char *fd_shared_qnn_build_kernel_name(int M, int frames) { return qnn_shared_kernel_name(M, frames); }
 
 int fd_batch_size(const fd_batch *b) { return b ? b->n : 0; }
 

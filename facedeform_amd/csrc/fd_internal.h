@@ -198,6 +198,7 @@ hipError_t launch_backsub_update(const BuildBuffers &b, hipStream_t stream, int 
 // factorisation + back-substitution of whatever has been assembled, full build or right-hand sides only
 hipError_t launch_qnn_radii(const BuildBuffers &b, hipStream_t stream);
 hipError_t launch_lu_factor_solve(const BuildBuffers &b, hipStream_t stream);
+hipError_t launch_lu_factor(const BuildBuffers &b, hipStream_t stream);      // ... the factorisation alone: no back-substitution
 hipError_t launch_lu_resolve_core(const BuildBuffers &b, hipStream_t stream);
 
 // ---- null-space Cholesky build (fd_nullspace.hip) -----------------------------------
@@ -232,6 +233,22 @@ hipError_t launch_build_ml_shared(const BuildBuffers &b, hipStream_t stream, voi
 struct MlSharedLayout { int tau, R, aff, ld, ld_stride, ld_inv; };
 hipError_t launch_ml_shared_init(const BuildBuffers &b, hipStream_t stream, void *scratch);
 hipError_t launch_ml_solve_shared(const BuildBuffers &b, hipStream_t stream, void *scratch, const MlSharedLayout &at);
+// ---- a shot of QNN models from one LU of the rest rig's kernel block (fd_batch_set_shared_lu; fd_build_qnn_shared.hip)
+// Radii per frame as ever; reflectors, kernel block and its LU without pivot search once, in a scratch slot of the batch
+// (qnn_shared_scratch_bytes: its own A, solver state, DevModel, move lists, inverted diagonal blocks, on context 0's centres and
+// radii); k_qnn_solve_shared takes every frame's right-hand sides through it in one launch.  launch_build_qnn_shared
+// (fd_nullspace.hip) is everything after k_prepare, as launch_build_qnn is; b.nopivot must be set.
+bool qnn_shared_applies(int M, int frames);                 // sizes the path takes; fewer frames than qnn_shared_min_frames: no
+int qnn_shared_min_frames();
+const char *qnn_shared_kernel_name(int M, int frames);
+hipError_t qnn_shared_init();                               // once per device, outside stream capture
+size_t qnn_shared_scratch_bytes(const BuildBuffers &b);
+const BatchSlot *qnn_shared_slot(void *scratch);            // the scratch slot table, one entry
+// fill_slot: the slot's table entry and status words have to be written first (k_qnn_shared_init); false when the batch's last
+// shared build went out whole on this scratch and these contexts' buffers -- its solve kernel left the slot ready
+hipError_t launch_build_qnn_shared(const BuildBuffers &b, hipStream_t stream, void *scratch, bool fill_slot);
+hipError_t launch_qnn_shared_init(const BuildBuffers &b, hipStream_t stream, void *scratch);
+hipError_t launch_qnn_solve_shared(const BuildBuffers &b, hipStream_t stream, void *scratch, const MlSharedLayout &at);
 // FD_KERNEL_GAUSSIAN_QNN, the SOP's model = 0: least-squares polynomial first, then the pivoted LU
 // of the (non-symmetric) kernel block on what is left
 hipError_t launch_build_qnn(const BuildBuffers &b, hipStream_t stream, hipEvent_t ev_mid);

@@ -1698,6 +1698,40 @@ hipError_t launch_build_qnn(const BuildBuffers &b, hipStream_t stream, hipEvent_
     return launch_pack(b, stream);
 }
 
+// The same shot from ONE LU (fd_batch_set_shared_lu): every context read the same rest array, so the radii and
+// Phi + lambda I are the same in every frame.  Radii per frame as ever (one workgroup each: every frame's equal its own
+// build's bit for bit); then, in the batch's scratch slot, the reflectors of P, the kernel block and its LU without pivot
+// search once -- the ordinary kernels on a batch of one, ungrouped: a lone system is launch-bound -- without the
+// back-substitution (launch_lu_factor); k_qnn_solve_shared (fd_build_qnn_shared.hip) takes all frames through the factor.
+// The caller has checked M >= T and b.nopivot.
+hipError_t launch_build_qnn_shared(const BuildBuffers &b, hipStream_t stream, void *scratch, bool fill_slot)
+{
+    const unsigned nb = (unsigned)b.nbatch;
+    const int M = b.M, T = b.T;
+    hipError_t e = launch_qnn_radii(b, stream);
+    if (e != hipSuccess) return e;
+    if (fill_slot) {                      // otherwise the last build's solve kernel left the slot as k_qnn_shared_init would
+        e = launch_qnn_shared_init(b, stream, scratch);
+        if (e != hipSuccess) return e;
+    }
+    BuildBuffers sb = b;                  // the slot as a batch of one system
+    sb.d_slots = qnn_shared_slot(scratch);
+    sb.nbatch = 1;
+    sb.group_panels = 0;
+    if (T > 0) hipLaunchKernelGGL(k_ns_reflectors, dim3(1, 1, 1), dim3(256), 0, stream, sb.d_slots, M, T, b.npad, b.lda, 0);
+    BuildBuffers k = kernel_block_only(sb);
+    e = launch_assemble_block(k, stream, b.npad);
+    if (e != hipSuccess) return e;
+    k.ncols = b.npad;                     // the matrix alone: no right-hand-side columns ride along (one launch and one workgroup per step less)
+    e = launch_lu_factor(k, stream);
+    if (e != hipSuccess) return e;
+    const MlSharedLayout at = {kTau, kR, kAff, kSmall, kLdStride, kLdInv};
+    e = launch_qnn_solve_shared(b, stream, scratch, at);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_qnn_finish, dim3(1, 1, nb), dim3(64), 0, stream, b.d_slots, M, T, b.npad, 1);
+    return launch_pack(b, stream);
+}
+
 // fd_set_deltas for the QNN model: the polynomial of the new deltas, then their remainder through the stored LU
 hipError_t launch_resolve_qnn(const BuildBuffers &b, hipStream_t stream, const PointSrc *src)
 {

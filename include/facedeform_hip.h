@@ -863,6 +863,46 @@ int fd_batch_last_build_shared_factor(const fd_batch *batch);
  * on and the contexts share the rest array: "k_ml_solve_shared" for M in 1..1024, layers in 1..8 and 2..32 frames, "" where the
  * build is the per-context one. */
 const char *fd_shared_ml_build_kernel_name(int M, int layers, int frames);
+/* One LU factorisation per batched build for a shot of QNN models (FD_KERNEL_GAUSSIAN_QNN, the SOP's default model = 0,
+ * src/SOP_FaceDeform.cpp:342-345).  A switch of its own, off by default: fd_batch_set_shared_factor keeps its meaning, and a QNN
+ * batch under that switch alone is built per frame as ever.  The QNN kernel block Phi + lambda I depends on the rest rig, q, z
+ * and the smoothing alone and carries no right-hand sides: in a shot only the deltas differ between frames.
+ *
+ * What is shared: with `on`, fd_batch_build_async (and fd_batch_cook_group through it) computes the radii, the reflectors of the
+ * polynomial block, the assembled kernel block and its LU without pivot search ONCE (the kernels of a per-context build, on one
+ * system), inverts the factor's 32 x 32 diagonal blocks, and takes all 3 F right-hand-side columns through that factor in ONE
+ * launch (k_qnn_solve_shared: least-squares polynomial, forward and backward substitution, the weights); the records and every
+ * frame's terminationtype come from the same kernels as a per-context build, so all that follows -- the shot calls, the
+ * per-context launches, fd_export_model -- sees ordinary built models.
+ *
+ * Conditions: every context is FD_KERNEL_GAUSSIAN_QNN (a batch's contexts already agree on q, z, smoothing, term and M); the LU
+ * without pivot search applies -- the padded order is at most 1024, every context has FD_SOLVER_AUTO and none has fallen back to
+ * the pivoted LU on this rig; M >= the term's polynomial columns; every context was given the SAME rest array by
+ * fd_batch_set_points_dev; the batch has at least the path's minimum frame count (fd_shared_qnn_build_kernel_name is its
+ * statement: 2); and the scratch could be allocated.  Measured on MI355X against the per-context batched build:
+ * 1.12x faster at 256 points x 32 frames and 1.44x at 1000 x 32, but SLOWER below 8 frames at 256 points (1.6 % at 2 frames) and
+ * below 16 frames at 1000 points (13 % at 2 frames) -- the per-context chains already run side by side; leave the switch off for
+ * such small groups.
+ *
+ * Delegation: a batch that misses a condition is built model by model exactly as without the switch, bit for bit; the switch
+ * does not touch batches of other kernels.
+ *
+ * Results: the weights equal the per-context builds' to rounding, not bit for bit; the same inputs give the same bits on every
+ * call; the radii are bit-identical to the per-context build's; each frame's fd_report says terminationtype, iterationscount, n
+ * and solver_used (= FD_SOLVER_LU_NOPIVOT) as its own build would; coincident centres give -5 in every frame.
+ *
+ * Fallback: when the shared factorisation finds a multiplier above 4 or a pivot at or below the threshold, every frame reports
+ * -4 and the existing host repair applies -- from fd_build_result and from the poll in front of an evaluation each context is
+ * rebuilt with the pivoted LU and keeps it for this rig; from then on the batch misses the condition and builds per context.
+ *
+ * Nothing is kept: the factor lives in scratch of the batch for the one call; fd_set_deltas on a context built this way is
+ * FD_E_NOT_BUILT, as after the multilayer shared build.
+ * fd_batch_last_build_shared_factor answers 1 when the batch's last build took this path, too. */
+int fd_batch_set_shared_lu(fd_batch *batch, int on);
+/* Which kernel takes a QNN batch's right-hand sides through the shared LU when fd_batch_set_shared_lu is on and the conditions
+ * hold: "k_qnn_solve_shared" for M in 1..1020 (the padded order of every term within 1024) and 2..32 frames, "" where the build
+ * is the per-context one. */
+const char *fd_shared_qnn_build_kernel_name(int M, int frames);
 /* Which kernel fd_batch_deform_shared_dev launches for `frames` frames of an M-centre model of `kind` (a name for profiles and
  * benchmark lines -- the one rocprofv3 prints): "k_deform32_shared_w1" (17..32 frames, the model resident in LDS),
  * "k_deform32_tps_shared_wide" (17..32 frames, staged in chunks), "k_deform32_tps_shared" (up to 16 frames), or "" where the
