@@ -68,6 +68,13 @@ class FdsopGeo(C.Structure):
                 ("rig_ntris", C.c_int64), ("rig_tris", _f32p), ("dist2_out", _f32p)]
 
 
+class FdsopShot(C.Structure):
+    """fdsop_shot: the frames of fdsop_cook_shot -- tables of F host pointers (one per frame) beside the shared fdsop_geo."""
+    _fields_ = [("struct_size", C.c_int), ("nframes", C.c_int), ("deform_P", C.POINTER(C.c_void_p)),
+                ("P_out", C.POINTER(C.c_void_p)), ("fd_falloff", C.POINTER(C.c_void_p)), ("frame_severity", C.POINTER(C.c_int)),
+                ("N_out", C.POINTER(C.c_void_p)), ("tangentu_out", C.POINTER(C.c_void_p)), ("tangentv_out", C.POINTER(C.c_void_p))]
+
+
 # every symbol include/facedeform_hip.h declares
 EXPORTS = [
     "fd_create", "fd_destroy", "fd_last_error", "fd_abi_version", "fd_set_stream", "fd_set_eval_precision", "fd_set_output", "fd_fp32_holds", "fd_set_points",
@@ -91,7 +98,7 @@ EXPORTS = [
     "fd_batch_deform_vectors_shared_ml_dev", "fd_shared_vectors_ml_kernel_name",
     "fdsop_create", "fdsop_destroy", "fdsop_set_float", "fdsop_set_int", "fdsop_set_string",
     "fdsop_get_float", "fdsop_get_int", "fdsop_parm_count", "fdsop_parm_token", "fdsop_cook",
-    "fdsop_messages", "fdsop_effective_float", "fdsop_engine",
+    "fdsop_messages", "fdsop_effective_float", "fdsop_engine", "fdsop_cook_shot", "fdsop_shot_paths",
 ]
 
 _lib = None
@@ -236,6 +243,8 @@ def load() -> C.CDLL:
     L.fdsop_messages.argtypes = [vp]; L.fdsop_messages.restype = C.c_char_p
     L.fdsop_effective_float.argtypes = [vp, C.c_char_p, _f64p]; L.fdsop_effective_float.restype = i32
     L.fdsop_engine.argtypes = [vp]; L.fdsop_engine.restype = vp
+    L.fdsop_cook_shot.argtypes = [vp, C.POINTER(FdsopGeo), C.POINTER(FdsopShot)]; L.fdsop_cook_shot.restype = i32
+    L.fdsop_shot_paths.argtypes = [vp]; L.fdsop_shot_paths.restype = C.c_char_p
     _lib = L
     return L
 
@@ -905,6 +914,11 @@ def fd_shared_qnn_build_kernel_name(M: int, frames: int) -> str:
 def fd_shared_ml_fp64_kernel_name(M: int, layers: int, frames: int) -> str:
     """The kernel fd_batch_deform_shared_ml_fp64_dev launches ("" where it is fd_batch_deform_shared_fp64_dev)."""
     return load().fd_shared_ml_fp64_kernel_name(int(M), int(layers), int(frames)).decode()
+
+
+def fd_shared_kernel_name(M: int, frames: int, kind: int) -> str:
+    """The kernel fd_batch_deform_shared_dev launches ("" where it runs the per-frame launches)."""
+    return load().fd_shared_kernel_name(int(M), int(frames), int(kind)).decode()
 
 
 def fd_shared_fp64_kernel_name(M: int, frames: int, kind: int) -> str:

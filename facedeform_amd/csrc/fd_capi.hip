@@ -2766,3 +2766,325 @@ const char *fd_shared_kernel_name(int M, int frames, int kind)
 }
 
 }  // extern "C"
+
+// ---- the device side of fdsop_cook_shot (fd_shot_dev.h) ----------------------------------------------------------------
+#include "fd_shot_dev.h"
+
+struct fd_shot_dev {
+    fd_ctx *engine = nullptr;
+    hipStream_t work = nullptr, copy = nullptr;
+    float *d_rig = nullptr;             // rest (M x 3), then F x M x 3 deltas
+    size_t cap_rig = 0;
+    int M = 0, F = 0;
+    float *d_vecs = nullptr;            // the mesh's N, tu, tv as uploaded by fd_shot_dev_set_vectors (a slice each)
+    int64_t cap_vecs = 0;
+    const float *v_in[3] = {nullptr, nullptr, nullptr};   // N, tu, tv inputs, or null
+    struct Set {
+        float *d = nullptr;
+        size_t bytes = 0;
+        hipEvent_t eval_ev = nullptr, delivered_ev = nullptr;
+        bool delivering = false;
+    } sets[2];
+    int set_frames = 0;                 // what the two sets were laid out for
+    int64_t set_Np = 0;
+    bool set_fall = false;
+    int set_nvec = 0;
+    char err[512] = {0};
+};
+
+static void shot_err(fd_shot_dev *sd, const char *fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(sd->err, sizeof(sd->err), fmt, ap);
+    va_end(ap);
+}
+
+#define FD_SHIP(sd, call)                                                                          \
+    do {                                                                                           \
+        hipError_t e_ = (call);                                                                    \
+        if (e_ != hipSuccess) {                                                                    \
+            (void)hipGetLastError();                                                               \
+            shot_err(sd, "%s failed: %s", #call, hipGetErrorString(e_));                          \
+            return e_ == hipErrorOutOfMemory ? FD_E_NOMEM : FD_E_DEVICE;                           \
+        }                                                                                          \
+    } while (0)
+
+// slices of a staging set: positions of every frame, then the fall-off of every frame, then the vectors
+static int64_t shot_pad(int64_t N) { return (N + 63) / 64 * 64; }
+static float *shot_slice_P(const fd_shot_dev *sd, int set, int slot) { return sd->sets[set].d + (size_t)slot * 3 * (size_t)sd->set_Np; }
+static float *shot_slice_fall(const fd_shot_dev *sd, int set, int slot)
+{
+    return sd->set_fall ? sd->sets[set].d + ((size_t)sd->set_frames * 3 + (size_t)slot) * (size_t)sd->set_Np : nullptr;
+}
+static float *shot_slice_vec(const fd_shot_dev *sd, int set, int which, int slot)
+{
+    const size_t base = (size_t)sd->set_frames * (sd->set_fall ? 4 : 3);
+    return sd->sets[set].d + (base + ((size_t)which * sd->set_frames + (size_t)slot) * 3) * (size_t)sd->set_Np;
+}
+static int shot_nvec(const fd_shot_dev *sd) { return (sd->v_in[0] != nullptr) + (sd->v_in[1] != nullptr) + (sd->v_in[2] != nullptr); }
+
+fd_shot_dev *fd_shot_dev_create(fd_ctx *engine)
+{
+    if (!engine || use_device(engine) != FD_OK) return nullptr;
+    fd_shot_dev *sd = new (std::nothrow) fd_shot_dev();
+    if (!sd) return nullptr;
+    sd->engine = engine;
+    bool ok = hipStreamCreateWithFlags(&sd->work, hipStreamNonBlocking) == hipSuccess &&
+              hipStreamCreateWithFlags(&sd->copy, hipStreamNonBlocking) == hipSuccess;
+    for (auto &st : sd->sets)
+        ok = ok && hipEventCreateWithFlags(&st.eval_ev, hipEventDisableTiming) == hipSuccess &&
+             hipEventCreateWithFlags(&st.delivered_ev, hipEventDisableTiming) == hipSuccess;
+    if (!ok) {
+        set_err(nullptr, "fd_shot_dev_create: device resource allocation failed: %s", hipGetErrorString(hipGetLastError()));
+        fd_shot_dev_destroy(sd);
+        return nullptr;
+    }
+    return sd;
+}
+
+void fd_shot_dev_destroy(fd_shot_dev *sd)
+{
+    if (!sd) return;
+    (void)hipSetDevice(sd->engine->device);
+    if (sd->work) { (void)hipStreamSynchronize(sd->work); }
+    if (sd->copy) { (void)hipStreamSynchronize(sd->copy); }
+    for (auto &st : sd->sets) {
+        if (st.d) (void)hipFree(st.d);
+        if (st.eval_ev) (void)hipEventDestroy(st.eval_ev);
+        if (st.delivered_ev) (void)hipEventDestroy(st.delivered_ev);
+    }
+    if (sd->d_rig) (void)hipFree(sd->d_rig);
+    if (sd->d_vecs) (void)hipFree(sd->d_vecs);
+    if (sd->work) (void)hipStreamDestroy(sd->work);
+    if (sd->copy) (void)hipStreamDestroy(sd->copy);
+    delete sd;
+}
+
+const char *fd_shot_dev_error(const fd_shot_dev *sd) { return sd ? sd->err : g_err; }
+void *fd_shot_dev_work_stream(fd_shot_dev *sd) { return sd ? (void *)sd->work : nullptr; }
+
+int fd_shot_dev_set_rig(fd_shot_dev *sd, const float *rest, const float *deltas, int M, int F)
+{
+    if (!sd || !rest || !deltas || M <= 0 || F <= 0) return FD_E_INVALID;
+    int rc = use_device(sd->engine);
+    if (rc) { shot_err(sd, "%s", sd->engine->err); return rc; }
+    const size_t floats = (size_t)(F + 1) * (size_t)M * 3;
+    if (floats > sd->cap_rig) {
+        // (the batches read the old block in place: nothing of them may still be in flight)
+        FD_SHIP(sd, hipStreamSynchronize(sd->work));
+        if (sd->d_rig) { (void)hipFree(sd->d_rig); sd->d_rig = nullptr; sd->cap_rig = 0; }
+        FD_SHIP(sd, hipMalloc((void **)&sd->d_rig, sizeof(float) * floats));
+        sd->cap_rig = floats;
+    }
+    sd->M = M; sd->F = F;
+    const size_t rb = sizeof(float) * 3 * (size_t)M;
+    FD_SHIP(sd, hipMemcpyAsync(sd->d_rig, rest, rb, hipMemcpyHostToDevice, sd->work));
+    FD_SHIP(sd, hipMemcpyAsync(sd->d_rig + 3 * (size_t)M, deltas, rb * (size_t)F, hipMemcpyHostToDevice, sd->work));
+    FD_SHIP(sd, hipStreamSynchronize(sd->work));          // pageable sources: the caller's vectors may go away
+    return FD_OK;
+}
+
+const float *fd_shot_dev_rest(const fd_shot_dev *sd) { return sd ? sd->d_rig : nullptr; }
+const float *fd_shot_dev_delta(const fd_shot_dev *sd, int frame)
+{
+    return (sd && sd->d_rig && frame >= 0 && frame < sd->F) ? sd->d_rig + (size_t)(frame + 1) * 3 * (size_t)sd->M : nullptr;
+}
+
+int fd_shot_dev_set_vectors(fd_shot_dev *sd, const float *N, const float *tu, const float *tv)
+{
+    if (!sd) return FD_E_INVALID;
+    sd->v_in[0] = sd->v_in[1] = sd->v_in[2] = nullptr;
+    if (!N && !tu && !tv) return FD_OK;
+    const int64_t n = sd->engine->mesh_N;
+    if (n <= 0) { shot_err(sd, "fd_shot_dev_set_vectors: the engine has no mesh"); return FD_E_INVALID; }
+    int rc = use_device(sd->engine);
+    if (rc) { shot_err(sd, "%s", sd->engine->err); return rc; }
+    const int64_t Np = shot_pad(n);
+    if (Np > sd->cap_vecs) {
+        FD_SHIP(sd, hipStreamSynchronize(sd->work));
+        if (sd->d_vecs) { (void)hipFree(sd->d_vecs); sd->d_vecs = nullptr; sd->cap_vecs = 0; }
+        FD_SHIP(sd, hipMalloc((void **)&sd->d_vecs, sizeof(float) * 9 * (size_t)Np));
+        sd->cap_vecs = Np;
+    }
+    const float *src[3] = {N, tu, tv};
+    for (int i = 0; i < 3; ++i) {
+        if (!src[i]) continue;
+        float *dst = sd->d_vecs + (size_t)i * 3 * (size_t)sd->cap_vecs;
+        FD_SHIP(sd, hipMemcpyAsync(dst, src[i], sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, sd->work));
+        sd->v_in[i] = dst;
+    }
+    FD_SHIP(sd, hipStreamSynchronize(sd->work));
+    return FD_OK;
+}
+
+int fd_shot_dev_reserve(fd_shot_dev *sd, int frames, int want_falloff)
+{
+    if (!sd || frames <= 0 || frames > kMaxBatch) return 0;
+    const int64_t n = sd->engine->mesh_N;
+    if (n <= 0 || use_device(sd->engine) != FD_OK) return 0;
+    const int64_t Np = shot_pad(n);
+    const int nvec = shot_nvec(sd);
+    const bool fall = want_falloff != 0;
+    if (sd->sets[0].d && sd->sets[1].d && sd->set_frames >= frames && sd->set_Np == Np && sd->set_fall == fall && sd->set_nvec == nvec)
+        return frames;
+    // another layout: the old sets go (nothing reads them once both streams have drained)
+    (void)hipStreamSynchronize(sd->work);
+    (void)hipStreamSynchronize(sd->copy);
+    for (auto &st : sd->sets) { if (st.d) (void)hipFree(st.d); st.d = nullptr; st.bytes = 0; st.delivering = false; }
+    sd->set_frames = 0;
+    for (int f = frames; f >= 1; f = f / 2) {
+        const size_t bytes = sizeof(float) * (size_t)f * (size_t)Np * (size_t)(3 + (fall ? 1 : 0) + 3 * nvec);
+        bool ok = true;
+        for (auto &st : sd->sets) ok = ok && hipMalloc((void **)&st.d, bytes) == hipSuccess;
+        if (ok) {
+            for (auto &st : sd->sets) st.bytes = bytes;
+            sd->set_frames = f; sd->set_Np = Np; sd->set_fall = fall; sd->set_nvec = nvec;
+            return f;
+        }
+        (void)hipGetLastError();
+        for (auto &st : sd->sets) { if (st.d) (void)hipFree(st.d); st.d = nullptr; }
+    }
+    shot_err(sd, "hipMalloc of the shot's staging sets failed: %s", hipGetErrorString(hipErrorOutOfMemory));
+    return 0;
+}
+
+int fd_shot_dev_wait(fd_shot_dev *sd, int set)
+{
+    if (!sd || set < 0 || set > 1) return FD_E_INVALID;
+    if (!sd->sets[set].delivering) return FD_OK;
+    sd->sets[set].delivering = false;
+    FD_SHIP(sd, hipEventSynchronize(sd->sets[set].delivered_ev));
+    return FD_OK;
+}
+
+// the engine's device-resident mesh as the evaluation calls take it
+struct ShotMesh { int64_t N; const float *P, *d2, *tu, *tv, *nr; };
+static ShotMesh shot_mesh(const fd_ctx *e)
+{
+    ShotMesh m{e->mesh_N, e->m_P, e->mesh_has_dist2 ? e->m_dist2 : nullptr, nullptr, nullptr, nullptr};
+    if (e->mesh_has_frames) { m.tu = e->m_tu; m.tv = e->m_tv; m.nr = e->m_nrm; }
+    return m;
+}
+
+int fd_shot_dev_eval(fd_shot_dev *sd, fd_batch *b, int set, int fp64, int multilayer, float radius2, float falloffrate)
+{
+    if (!sd || !b || set < 0 || set > 1) return FD_E_INVALID;
+    const int n = b->n;
+    if (!sd->sets[set].d || n > sd->set_frames) { shot_err(sd, "fd_shot_dev_eval: no staging set for %d frames", n); return FD_E_INVALID; }
+    int rc = fd_shot_dev_wait(sd, set);
+    if (rc) return rc;
+    const ShotMesh m = shot_mesh(sd->engine);
+    if (m.N <= 0 || shot_pad(m.N) != sd->set_Np) { shot_err(sd, "fd_shot_dev_eval: the staging sets were laid out for another mesh"); return FD_E_INVALID; }
+    float *P_out[kMaxBatch], *fall[kMaxBatch], *vo[3][kMaxBatch];
+    for (int i = 0; i < n; ++i) {
+        P_out[i] = shot_slice_P(sd, set, i);
+        fall[i] = shot_slice_fall(sd, set, i);
+    }
+    fd_batch_vectors vec{};
+    vec.struct_size = (int)sizeof(vec);
+    int which = 0;
+    for (int k = 0; k < 3; ++k) {
+        if (!sd->v_in[k]) continue;
+        for (int i = 0; i < n; ++i) vo[k][i] = shot_slice_vec(sd, set, which, i);
+        ++which;
+    }
+    if (sd->v_in[0]) { vec.N = sd->v_in[0]; vec.N_out = vo[0]; }
+    if (sd->v_in[1]) { vec.tu = sd->v_in[1]; vec.tu_out = vo[1]; }
+    if (sd->v_in[2]) { vec.tv = sd->v_in[2]; vec.tv_out = vo[2]; }
+    const bool with_vec = which > 0;
+    // a gated vertex's fd_falloff entry is not written by the launches: it reads 0, the attribute's default (:401)
+    if (sd->set_fall && (m.d2 || radius2 < 0.f))
+        FD_SHIP(sd, hipMemsetAsync(shot_slice_fall(sd, set, 0), 0, sizeof(float) * (size_t)n * (size_t)sd->set_Np, sd->work));
+    float *const *fo = sd->set_fall ? fall : nullptr;
+    if (with_vec) {
+        auto call = fp64 ? (multilayer ? fd_batch_deform_vectors_shared_ml_fp64_dev : fd_batch_deform_vectors_shared_fp64_dev)
+                         : (multilayer ? fd_batch_deform_vectors_shared_ml_dev : fd_batch_deform_vectors_shared_dev);
+        rc = call(b, sd->work, m.N, m.P, P_out, m.d2, fo, m.tu, m.tv, m.nr, radius2, falloffrate, &vec);
+    } else {
+        auto call = fp64 ? (multilayer ? fd_batch_deform_shared_ml_fp64_dev : fd_batch_deform_shared_fp64_dev)
+                         : (multilayer ? fd_batch_deform_shared_ml_dev : fd_batch_deform_shared_dev);
+        rc = call(b, sd->work, m.N, m.P, P_out, m.d2, fo, m.tu, m.tv, m.nr, radius2, falloffrate);
+    }
+    if (rc) { shot_err(sd, "%s", b->err); return rc; }
+    FD_SHIP(sd, hipEventRecord(sd->sets[set].eval_ev, sd->work));
+    return FD_OK;
+}
+
+int fd_shot_dev_eval_fp64_over(fd_shot_dev *sd, fd_ctx *ctx, int set, int slot, float radius2, float falloffrate)
+{
+    if (!sd || !ctx || set < 0 || set > 1 || slot < 0 || slot >= sd->set_frames || !sd->sets[set].d) return FD_E_INVALID;
+    const ShotMesh m = shot_mesh(sd->engine);
+    fd_vectors vec{};
+    vec.struct_size = (int)sizeof(vec);
+    int which = 0;
+    float *vo[3] = {nullptr, nullptr, nullptr};
+    for (int k = 0; k < 3; ++k)
+        if (sd->v_in[k]) vo[k] = shot_slice_vec(sd, set, which++, slot);
+    if (sd->v_in[0]) { vec.N = sd->v_in[0]; vec.N_out = vo[0]; }
+    if (sd->v_in[1]) { vec.tu = sd->v_in[1]; vec.tu_out = vo[1]; }
+    if (sd->v_in[2]) { vec.tv = sd->v_in[2]; vec.tv_out = vo[2]; }
+    const int before = ctx->eval_precision;
+    ctx->eval_precision = FD_EVAL_FP64;
+    const int rc = deform_dev_common(ctx, sd->work, m.N, m.P, shot_slice_P(sd, set, slot), m.d2, shot_slice_fall(sd, set, slot), m.tu, m.tv,
+                                     m.nr, radius2, falloffrate, which > 0 ? &vec : nullptr);
+    ctx->eval_precision = before;
+    if (rc) { shot_err(sd, "%s", ctx->err); return rc; }
+    FD_SHIP(sd, hipEventRecord(sd->sets[set].eval_ev, sd->work));
+    return FD_OK;
+}
+
+int fd_shot_dev_deliver(fd_shot_dev *sd, int set, int n, const unsigned char *skip, float *const *P_out, float *const *falloff,
+                        float *const *N_out, float *const *tu_out, float *const *tv_out)
+{
+    if (!sd || set < 0 || set > 1 || n <= 0 || n > sd->set_frames || !P_out || !sd->sets[set].d) return FD_E_INVALID;
+    const int64_t N = sd->engine->mesh_N;
+    const size_t b3 = sizeof(float) * 3 * (size_t)N, b1 = sizeof(float) * (size_t)N;
+    FD_SHIP(sd, hipStreamWaitEvent(sd->copy, sd->sets[set].eval_ev, 0));
+    float *const *vt[3] = {N_out, tu_out, tv_out};
+    for (int i = 0; i < n; ++i) {
+        if (skip && skip[i]) continue;
+        // page-locked arrays are written asynchronously; pageable ones go through the runtime's staging, as in fd_deform_mesh
+        if (P_out[i]) FD_SHIP(sd, hipMemcpyAsync(P_out[i], shot_slice_P(sd, set, i), b3, hipMemcpyDeviceToHost, sd->copy));
+        if (falloff && falloff[i] && sd->set_fall)
+            FD_SHIP(sd, hipMemcpyAsync(falloff[i], shot_slice_fall(sd, set, i), b1, hipMemcpyDeviceToHost, sd->copy));
+        int which = 0;
+        for (int k = 0; k < 3; ++k) {
+            if (!sd->v_in[k]) continue;
+            if (vt[k] && vt[k][i]) FD_SHIP(sd, hipMemcpyAsync(vt[k][i], shot_slice_vec(sd, set, which, i), b3, hipMemcpyDeviceToHost, sd->copy));
+            ++which;
+        }
+    }
+    FD_SHIP(sd, hipEventRecord(sd->sets[set].delivered_ev, sd->copy));
+    sd->sets[set].delivering = true;
+    return FD_OK;
+}
+
+int fd_shot_dev_vectors_engine(fd_shot_dev *sd, float radius2, float falloffrate, float *N_out, float *tu_out, float *tv_out)
+{
+    if (!sd || !sd->sets[0].d || sd->set_frames < 1) return FD_E_INVALID;
+    int rc = fd_shot_dev_wait(sd, 0);
+    if (rc) return rc;
+    fd_ctx *e = sd->engine;
+    const ShotMesh m = shot_mesh(e);
+    fd_vectors vec{};
+    vec.struct_size = (int)sizeof(vec);
+    int which = 0;
+    float *vo[3] = {nullptr, nullptr, nullptr};
+    for (int k = 0; k < 3; ++k)
+        if (sd->v_in[k]) vo[k] = shot_slice_vec(sd, 0, which++, 0);
+    if (which == 0) { shot_err(sd, "fd_shot_dev_vectors_engine: no vectors were set"); return FD_E_INVALID; }
+    if (sd->v_in[0]) { vec.N = sd->v_in[0]; vec.N_out = vo[0]; }
+    if (sd->v_in[1]) { vec.tu = sd->v_in[1]; vec.tu_out = vo[1]; }
+    if (sd->v_in[2]) { vec.tv = sd->v_in[2]; vec.tv_out = vo[2]; }
+    hipStream_t s = cur_stream(e);
+    if (sd->set_fall && (m.d2 || radius2 < 0.f)) FD_SHIP(sd, hipMemsetAsync(shot_slice_fall(sd, 0, 0), 0, sizeof(float) * (size_t)sd->set_Np, s));
+    rc = deform_dev_common(e, s, m.N, m.P, shot_slice_P(sd, 0, 0), m.d2, shot_slice_fall(sd, 0, 0), m.tu, m.tv, m.nr, radius2, falloffrate, &vec);
+    if (rc) { shot_err(sd, "%s", e->err); return rc; }
+    float *const host[3] = {N_out, tu_out, tv_out};
+    const size_t b3 = sizeof(float) * 3 * (size_t)m.N;
+    for (int k = 0; k < 3; ++k)
+        if (vo[k] && host[k]) FD_SHIP(sd, hipMemcpyAsync(host[k], vo[k], b3, hipMemcpyDeviceToHost, s));
+    FD_SHIP(sd, hipStreamSynchronize(s));
+    return FD_OK;
+}

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/facedeform_hip.h"
+#include "fd_shot_dev.h"
 
 namespace {
 
@@ -91,6 +92,26 @@ struct fdsop_node {
     int e_layers = 0, e_maxedges = 0;
     int engine_precision = -1, engine_device = -2;
     bool fp64_warned = false;         // the "evaluating in fp64" warning has been given for the current rest rig (once per rig, not per cook)
+    bool last_cook_fp64 = false;      // the last fdsop_cook evaluated in fp64
+    // fdsop_cook_shot: the frames' own contexts (up to FD_MAX_BATCH, created on first use), a batch object per group size over
+    // the first n of them, and the device side (streams, control tables, staging sets).  All of one device with the engine;
+    // freed before the engine goes.
+    fd_ctx *shot_ctx[FD_MAX_BATCH] = {};
+    int shot_nctx = 0;
+    fd_batch *shot_batch[FD_MAX_BATCH + 1] = {};
+    fd_shot_dev *shot_dev = nullptr;
+    // a batched shot built its models on another rest rig than the one the engine factorised last: the engine's factorisation
+    // must not be reused by fd_set_deltas until the engine has seen the rig itself
+    bool engine_rig_stale = false;
+    std::string shot_paths;
+
+    void free_shot()
+    {
+        for (fd_batch *&b : shot_batch) { if (b) fd_batch_destroy(b); b = nullptr; }
+        for (int i = 0; i < shot_nctx; ++i) { fd_destroy(shot_ctx[i]); shot_ctx[i] = nullptr; }
+        shot_nctx = 0;
+        if (shot_dev) { fd_shot_dev_destroy(shot_dev); shot_dev = nullptr; }
+    }
 
     void add(int sev, const char *text)
     {
@@ -129,6 +150,7 @@ fdsop_node *fdsop_create(const fd_config *cfg)
 void fdsop_destroy(fdsop_node *node)
 {
     if (!node) return;
+    node->free_shot();
     if (node->engine) fd_destroy(node->engine);
     if (node->morph) fd_morph_destroy(node->morph);
     delete node;
@@ -193,71 +215,61 @@ int fdsop_effective_float(const fdsop_node *node, const char *token, double *val
     return FD_OK;
 }
 
-// The cook: reference src/SOP_FaceDeform.cpp:215-489, step for step.
-int fdsop_cook(fdsop_node *node, const fdsop_geo *geo)
-{
-    if (!node || !geo) return FDSOP_ERROR;
-    node->messages.clear();
-    node->severity = FDSOP_OK;
-    if (geo->npoints < 0 || (geo->npoints > 0 && (!geo->P || !geo->P_out)) || !geo->rest_P || !geo->deform_P) {
-        node->add(FDSOP_ERROR, "Invalid geometry arrays.");
-        return node->severity;
-    }
-    // duplicatePointSource(0) (:226): the output starts as a copy of input 0.  On the success
-    // path fd_deform writes every point of P_out from P (gated points are copied through), so
-    // the 12 B/point host copy is only made where the cook stops early.
-    struct PassThrough {
-        const fdsop_geo *g; bool armed;
-        ~PassThrough() {
-            if (armed && g->P_out != g->P && g->npoints > 0)
-                memcpy(g->P_out, g->P, sizeof(float) * 3 * (size_t)g->npoints);
-        }
-    } pass{geo, true};
+// What a cook settles before it turns to the deformed rig: the clamped parms, the morph engine, the GPU engine, input 0 on the
+// device, the capture.  fdsop_cook and fdsop_cook_shot run this part once, from the same code.
+struct CookSetup {
+    int model_index, term_index, layers, tangent_disp, morph_space, max_edges, kernel_ext, precision_parm, precision, device, M;
+    float qcoef, zcoef, radius, lambda, falloffrate;
+    double smoothing;
+    bool do_tangent_disp, have_blends, morph_inited_this_cook, use_capture, mesh_ready;
+    const float *rest_attr;
+    int dofalloff_parm;
+};
 
+// :228-322.  false: the cook stops here (the message has been added).
+static bool cook_setup(fdsop_node *node, const fdsop_geo *geo, CookSetup &cs)
+{
     // :228-234
     if (geo->rest_npoints != geo->deform_npoints) {
         node->add(FDSOP_ERROR, "Rest and deform geometry should match.");
-        return node->severity;
+        return false;
     }
 
     // :244-263 -- SYSmax(0.1, fpreal) is evaluated in double, then narrowed to float
-    const int model_index = node->ord(find_parm("model"));
-    const int term_index = node->ord(find_parm("term"));
-    const float qcoef = (float)sys_max(0.1, node->fval[find_parm("qcoef")][0]);
-    const float zcoef = (float)sys_max(0.1, node->fval[find_parm("zcoef")][0]);
-    const float radius = (float)sys_max(0.01, node->fval[find_parm("radius")][0]);
-    const int layers = sys_max(1, (int)node->fval[find_parm("layers")][0]);
-    const float lambda = (float)sys_max(0.01, node->fval[find_parm("lambda")][0]);
-    const int tangent_disp = (int)node->fval[find_parm("tangent")][0];
-    const int morph_space = (int)node->fval[find_parm("morphspace")][0];
-    const int max_edges = sys_max(1, (int)node->fval[find_parm("maxedges")][0]);
-    const float falloffrate = (float)node->fval[find_parm("falloffrate")][0];
+    const int model_index = cs.model_index = node->ord(find_parm("model"));
+    cs.term_index = node->ord(find_parm("term"));
+    const float qcoef = cs.qcoef = (float)sys_max(0.1, node->fval[find_parm("qcoef")][0]);
+    const float zcoef = cs.zcoef = (float)sys_max(0.1, node->fval[find_parm("zcoef")][0]);
+    const float radius = cs.radius = (float)sys_max(0.01, node->fval[find_parm("radius")][0]);
+    const int layers = cs.layers = sys_max(1, (int)node->fval[find_parm("layers")][0]);
+    const float lambda = cs.lambda = (float)sys_max(0.01, node->fval[find_parm("lambda")][0]);
+    const int tangent_disp = cs.tangent_disp = (int)node->fval[find_parm("tangent")][0];
+    const int morph_space = cs.morph_space = (int)node->fval[find_parm("morphspace")][0];
+    const int max_edges = cs.max_edges = sys_max(1, (int)node->fval[find_parm("maxedges")][0]);
+    cs.falloffrate = (float)node->fval[find_parm("falloffrate")][0];
     node->e_qcoef = qcoef; node->e_zcoef = zcoef; node->e_radius = radius; node->e_lambda = lambda;
     node->e_layers = layers; node->e_maxedges = max_edges;
-    const int kernel_ext = node->ord(find_parm("kernel"));
-    const double smoothing = node->fval[find_parm("smoothing")][0];
-    const int precision_parm = node->ord(find_parm("precision"));
-    const int precision = precision_parm == 1 ? FD_EVAL_FP64 : FD_EVAL_FP32;
-    const int device = (int)node->fval[find_parm("device")][0];
+    cs.kernel_ext = node->ord(find_parm("kernel"));
+    cs.smoothing = node->fval[find_parm("smoothing")][0];
+    const int precision_parm = cs.precision_parm = node->ord(find_parm("precision"));
+    const int precision = cs.precision = precision_parm == 1 ? FD_EVAL_FP64 : FD_EVAL_FP32;
+    const int device = cs.device = (int)node->fval[find_parm("device")][0];
+    (void)model_index;
 
-    // :268-287 -- M x 6 table: rest position and fp32 delta
-    const int M = (int)geo->rest_npoints;
-    std::vector<float> delta((size_t)(M > 0 ? M : 0) * 3);
-    for (int i = 0; i < M; ++i)
-        for (int c = 0; c < 3; ++c) delta[3 * (size_t)i + c] = geo->deform_P[3 * (size_t)i + c] - geo->rest_P[3 * (size_t)i + c];
+    const int M = cs.M = (int)geo->rest_npoints;
 
     // :289-298
-    const bool do_tangent_disp = tangent_disp && geo->tangentu && geo->tangentv && geo->N;
+    const bool do_tangent_disp = cs.do_tangent_disp = tangent_disp && geo->tangentu && geo->tangentv && geo->N;
     if (tangent_disp && !do_tangent_disp)
         node->add(FDSOP_WARNING, "Append PolyFrameSOP and enable tangent[u/v] and N attribute to allow tangent displacement.");
 
     // :323-329 -- morph space needs blendshapes on inputs 3..; setupBlends (:175-213)
-    const bool have_blends = geo->nshapes > 0 && geo->shapes_P && geo->shapes_npoints;
+    const bool have_blends = cs.have_blends = geo->nshapes > 0 && geo->shapes_P && geo->shapes_npoints;
     if (geo->weights_count) *geo->weights_count = 0;
     // the `rest` attribute: input 0's own unless the rest pose changed or there is none, in
     // which case it is a copy of the incoming P (:178-184)
-    const float *rest_attr = (geo->rest && !geo->rest_changed) ? geo->rest : geo->P;
-    bool morph_inited_this_cook = false;
+    cs.rest_attr = (geo->rest && !geo->rest_changed) ? geo->rest : geo->P;
+    bool &morph_inited_this_cook = cs.morph_inited_this_cook = false;
     if (morph_space && have_blends) {
         if (!node->morph || node->morph_device != device) {
             if (node->morph) { fd_morph_destroy(node->morph); node->morph = nullptr; }
@@ -290,7 +302,9 @@ int fdsop_cook(fdsop_node *node, const fdsop_geo *geo)
 
     // engine (re)creation when the device changed (the precision is set per cook, below)
     if (!node->engine || node->engine_device != device) {
+        node->free_shot();             // the shot's contexts and streams are of the engine's device
         if (node->engine) { fd_destroy(node->engine); node->engine = nullptr; }
+        node->engine_rig_stale = false;
         fd_config cfg = node->cfg;
         cfg.struct_size = (int)sizeof(fd_config);
         cfg.device = device;
@@ -301,7 +315,7 @@ int fdsop_cook(fdsop_node *node, const fdsop_geo *geo)
         if (!node->engine) {
             std::string t = std::string("Can't create the GPU deformation engine: ") + fd_last_error(nullptr);
             node->add(FDSOP_ERROR, t.c_str());
-            return node->severity;
+            return false;
         }
     }
     fd_ctx *ctx = node->engine;
@@ -312,10 +326,10 @@ int fdsop_cook(fdsop_node *node, const fdsop_geo *geo)
     // islands and squared distances are produced there.  Re-captured on the first cook and when the
     // rest pose or the rest rig changed; NOT when radius / maxedges / dofalloff alone changed (the
     // FIXME at :309: kept, B12).
-    const int dofalloff_parm = (int)node->fval[find_parm("dofalloff")][0];
+    const int dofalloff_parm = cs.dofalloff_parm = (int)node->fval[find_parm("dofalloff")][0];
     const bool want_d2 = geo->dist2 != nullptr;
-    const bool use_capture = !want_d2 && geo->edge_offsets && geo->rig_ntris >= 0 && (geo->rig_ntris == 0 || geo->rig_tris);
-    bool mesh_ready = false;
+    const bool use_capture = cs.use_capture = !want_d2 && geo->edge_offsets && geo->rig_ntris >= 0 && (geo->rig_ntris == 0 || geo->rig_tris);
+    cs.mesh_ready = false;
     if (geo->npoints > 0) {
         // (a mesh that still carries an earlier cook's CAPTURED dist2 is not reusable once the capture's inputs are gone:
         // the reference then applies neither radius nor fall-off, :396-399 -- fd_mesh_set drops the stale attribute)
@@ -333,9 +347,9 @@ int fdsop_cook(fdsop_node *node, const fdsop_geo *geo)
         if (mrc != FD_OK) {
             std::string t = std::string("GPU deformation failed: ") + fd_last_error(ctx);
             node->add(FDSOP_ERROR, t.c_str());
-            return node->severity;
+            return false;
         }
-        mesh_ready = true;
+        cs.mesh_ready = true;
         if (!use_capture) node->captured = false;
         if (use_capture && (!node->captured || !geo->rig_rest_unchanged)) {
             // capture(max_edges, radius, dofalloff, falloffrate) (:317): radius^2 is the search bound
@@ -343,15 +357,20 @@ int fdsop_cook(fdsop_node *node, const fdsop_geo *geo)
                                   (int)geo->rig_ntris, geo->rig_tris, radius * radius, dofalloff_parm, nullptr);
             if (mrc != FD_OK) {
                 node->add(FDSOP_ERROR, "Can't capture geometry with a rig!");     // :318
-                return node->severity;
+                return false;
             }
             node->captured = true;
         }
     }
+    return true;
+}
 
-    // :342-349 -- model select; `kernel` (addition) overrides the Gaussian family.  (Set before
-    // the points here: an unchanged kernel / term leaves the engine's factorisation in place, and
-    // fd_set_deltas below depends on that; every failure ends in the same message as at :337-340.)
+// :342-361 -- model select on one context; `kernel` (addition) overrides the Gaussian family.
+static int cook_select_model(fd_ctx *ctx, const CookSetup &cs)
+{
+    const int kernel_ext = cs.kernel_ext, model_index = cs.model_index, term_index = cs.term_index, layers = cs.layers;
+    const float radius = cs.radius, lambda = cs.lambda, qcoef = cs.qcoef, zcoef = cs.zcoef;
+    const double smoothing = cs.smoothing;
     int rc = FD_OK;
     if (kernel_ext == 1 || kernel_ext == 2 || kernel_ext == 3) {
         const int kind = kernel_ext == 1 ? FD_KERNEL_THIN_PLATE : (kernel_ext == 2 ? FD_KERNEL_BIHARMONIC : FD_KERNEL_CUBIC);
@@ -369,6 +388,47 @@ int fdsop_cook(fdsop_node *node, const fdsop_geo *geo)
     // :351-361 -- any other ordinal leaves ALGLIB's default (linear) in place
     const int term = (term_index == 1) ? FD_TERM_CONST : (term_index == 2 ? FD_TERM_ZERO : FD_TERM_LINEAR);
     if (rc == FD_OK) rc = fd_set_term(ctx, term);
+    return rc;
+}
+
+// The cook: reference src/SOP_FaceDeform.cpp:215-489, step for step.
+int fdsop_cook(fdsop_node *node, const fdsop_geo *geo)
+{
+    if (!node || !geo) return FDSOP_ERROR;
+    node->messages.clear();
+    node->severity = FDSOP_OK;
+    if (geo->npoints < 0 || (geo->npoints > 0 && (!geo->P || !geo->P_out)) || !geo->rest_P || !geo->deform_P) {
+        node->add(FDSOP_ERROR, "Invalid geometry arrays.");
+        return node->severity;
+    }
+    // duplicatePointSource(0) (:226): the output starts as a copy of input 0.  On the success
+    // path fd_deform writes every point of P_out from P (gated points are copied through), so
+    // the 12 B/point host copy is only made where the cook stops early.
+    struct PassThrough {
+        const fdsop_geo *g; bool armed;
+        ~PassThrough() {
+            if (armed && g->P_out != g->P && g->npoints > 0)
+                memcpy(g->P_out, g->P, sizeof(float) * 3 * (size_t)g->npoints);
+        }
+    } pass{geo, true};
+
+    CookSetup cs;
+    if (!cook_setup(node, geo, cs)) return node->severity;
+    const int M = cs.M, precision = cs.precision, precision_parm = cs.precision_parm, morph_space = cs.morph_space,
+              dofalloff_parm = cs.dofalloff_parm;
+    const float radius = cs.radius, falloffrate = cs.falloffrate;
+    const bool have_blends = cs.have_blends, morph_inited_this_cook = cs.morph_inited_this_cook, use_capture = cs.use_capture,
+               mesh_ready = cs.mesh_ready;
+    const float *rest_attr = cs.rest_attr;
+    fd_ctx *ctx = node->engine;
+    // :268-287 -- M x 6 table: rest position and fp32 delta
+    std::vector<float> delta((size_t)(M > 0 ? M : 0) * 3);
+    for (int i = 0; i < M; ++i)
+        for (int c = 0; c < 3; ++c) delta[3 * (size_t)i + c] = geo->deform_P[3 * (size_t)i + c] - geo->rest_P[3 * (size_t)i + c];
+
+    // :342-361 -- the model.  (Set before the points here: an unchanged kernel / term leaves the engine's factorisation in
+    // place, and fd_set_deltas below depends on that; every failure ends in the same message as at :337-340.)
+    int rc = cook_select_model(ctx, cs);
     // :331-340 -- rbfcreate + rbfsetpoints.  The reference rebuilds its model on every cook (B12);
     // when the caller vouches that the rest rig has not changed since the last cook
     // (checkChangedSourceFlags(1) in the wrapper) only the deltas are new and the engine reuses
@@ -376,8 +436,11 @@ int fdsop_cook(fdsop_node *node, const fdsop_geo *geo)
     // (first cook, another M, kernel or term) falls back to the full path.
     if (rc == FD_OK) {
         rc = FD_E_NOT_BUILT;
-        if (M > 0 && geo->rig_rest_unchanged) rc = fd_set_deltas(ctx, delta.data(), M);
-        if (rc != FD_OK) rc = M > 0 ? fd_set_points(ctx, geo->rest_P, delta.data(), M) : FD_E_INVALID;
+        if (M > 0 && geo->rig_rest_unchanged && !node->engine_rig_stale) rc = fd_set_deltas(ctx, delta.data(), M);
+        if (rc != FD_OK) {
+            rc = M > 0 ? fd_set_points(ctx, geo->rest_P, delta.data(), M) : FD_E_INVALID;
+            if (rc == FD_OK) node->engine_rig_stale = false;
+        }
     }
     if (rc != FD_OK) {
         node->add(FDSOP_ERROR, "Can't build RBF model.");
@@ -407,6 +470,7 @@ int fdsop_cook(fdsop_node *node, const fdsop_geo *geo)
         }
     }
     fd_set_eval_precision(ctx, cook_precision);
+    node->last_cook_fp64 = cook_precision == FD_EVAL_FP64;
     // :370-373
     char info[200];
     snprintf(info, sizeof(info), "Termination type: %d, Iterations: %d", report.terminationtype, report.iterationscount);
@@ -469,6 +533,413 @@ int fdsop_cook(fdsop_node *node, const fdsop_geo *geo)
             node->add(FDSOP_WARNING, "Can't compute weights for morphspace deformation. Ingoring it.");   // :452
     }
     return node->severity;
+}
+
+// ---- fdsop_cook_shot ----------------------------------------------------------------------------------------------------
+namespace {
+
+int severity_of(const std::string &name) { return name == "error" ? FDSOP_ERROR : (name == "warning" ? FDSOP_WARNING : FDSOP_MESSAGE); }
+
+bool starts_with(const std::string &s, const char *p) { return s.compare(0, strlen(p), p) == 0; }
+
+// a line of one frame's cook that belongs to that frame (the others are the mesh's, the parms' or the capture's: once per shot)
+bool is_frame_line(const std::string &text, int frame)
+{
+    if (starts_with(text, "Termination type:") || starts_with(text, "Can't solve the problem.") ||
+        starts_with(text, "fp32 evaluation would not hold") || starts_with(text, "GPU deformation failed:"))
+        return true;
+    return frame >= 1 && starts_with(text, "Can't compute weights for morphspace deformation.");
+}
+
+// the messages of a shot as they add up
+struct ShotLog {
+    std::string text;
+    std::vector<std::string> seen;       // shot-wide lines already in `text`
+    int severity = FDSOP_OK;
+    int common = FDSOP_OK;               // worst severity among the shot-wide lines
+    void frame(int k, int sev, const std::string &t)
+    {
+        text += sev == FDSOP_ERROR ? "error" : (sev == FDSOP_WARNING ? "warning" : "message");
+        text += "\tframe " + std::to_string(k) + ": " + t + "\n";
+        if (sev > severity) severity = sev;
+    }
+    void shot(int sev, const std::string &t)
+    {
+        if (sev > severity) severity = sev;
+        if (sev > common) common = sev;
+        for (const std::string &s : seen) if (s == t) return;
+        seen.push_back(t);
+        text += sev == FDSOP_ERROR ? "error" : (sev == FDSOP_WARNING ? "warning" : "message");
+        text += "\t" + t + "\n";
+    }
+    // the lines fdsop_cook left in the node: frame lines prefixed, the others once.  true: an ERROR among the shot-wide ones
+    bool take(const fdsop_node *node, int k)
+    {
+        bool shot_error = false;
+        size_t pos = 0;
+        const std::string &m = node->messages;
+        while (pos < m.size()) {
+            size_t end = m.find('\n', pos);
+            if (end == std::string::npos) end = m.size();
+            const std::string line = m.substr(pos, end - pos);
+            pos = end + 1;
+            const size_t tab = line.find('\t');
+            if (tab == std::string::npos) continue;
+            const int sev = severity_of(line.substr(0, tab));
+            const std::string t = line.substr(tab + 1);
+            if (is_frame_line(t, k)) frame(k, sev, t);
+            else { shot(sev, t); shot_error = shot_error || sev == FDSOP_ERROR; }
+        }
+        return shot_error;
+    }
+};
+
+// frame k's transported vectors are the mesh's own
+void shot_pass_vectors(const fdsop_geo *geo, const fdsop_shot *shot, int k)
+{
+    const size_t b3 = sizeof(float) * 3 * (size_t)(geo->npoints > 0 ? geo->npoints : 0);
+    if (b3 == 0) return;
+    const float *const src[3] = {geo->N, geo->tangentu, geo->tangentv};
+    float *const *const dst[3] = {shot->N_out, shot->tangentu_out, shot->tangentv_out};
+    for (int v = 0; v < 3; ++v)
+        if (dst[v] && dst[v][k] && src[v] && dst[v][k] != src[v]) memcpy(dst[v][k], src[v], b3);
+}
+
+// frame k is the copy of input 0 (duplicatePointSource, :226)
+void shot_pass_through(const fdsop_geo *geo, const fdsop_shot *shot, int k)
+{
+    if (geo->npoints > 0 && geo->P && shot->P_out[k] && shot->P_out[k] != geo->P)
+        memcpy(shot->P_out[k], geo->P, sizeof(float) * 3 * (size_t)geo->npoints);
+    shot_pass_vectors(geo, shot, k);
+}
+
+bool shot_transport(const fdsop_shot *shot) { return shot->N_out || shot->tangentu_out || shot->tangentv_out; }
+
+void add_path(fdsop_node *node, int first, int n, const char *build, const char *e32, int n32, const char *e64, int n64)
+{
+    char line[320];
+    snprintf(line, sizeof(line), "%d\t%d\t%s\t%s\t%d\t%s\t%d\n", first, n, build ? build : "", e32 ? e32 : "", n32, e64 ? e64 : "", n64);
+    node->shot_paths += line;
+}
+
+// Frames [first, first + count) as consecutive fdsop_cook calls.  `fresh`: no cook of this shot has set the node up yet, so
+// the first call here takes geo's flags as given; every other call has the flags of a cook that follows one.  Frame 0 alone
+// writes Cd, dist2_out and the weights.  true: a shot-wide error ended the sequence (the remaining frames are passed through).
+bool cook_frames_sequential(fdsop_node *node, const fdsop_geo *geo, const fdsop_shot *shot, int first, int count, bool fresh,
+                            ShotLog &log)
+{
+    int n32 = 0, n64 = 0;
+    bool stopped = false;
+    for (int k = first; k < first + count; ++k) {
+        if (stopped) {
+            shot_pass_through(geo, shot, k);
+            if (shot->frame_severity) shot->frame_severity[k] = FDSOP_ERROR;
+            continue;
+        }
+        fdsop_geo g = *geo;
+        g.deform_P = shot->deform_P[k];
+        g.P_out = shot->P_out[k];
+        g.fd_falloff = shot->fd_falloff ? shot->fd_falloff[k] : nullptr;
+        if (!(fresh && k == first)) {
+            g.rig_rest_unchanged = g.mesh_unchanged = 1;
+            g.rest_changed = g.blends_changed = 0;
+        }
+        if (k != 0) {
+            g.Cd = nullptr; g.dist2_out = nullptr;
+            // (a later frame reaches the morph pass only if frame 0 did not: then the weights are that frame's)
+            if (node->morph && fd_morph_is_computed(node->morph)) { g.weights = nullptr; g.weights_count = nullptr; }
+        }
+        const int sev = fdsop_cook(node, &g);
+        if (shot->frame_severity) shot->frame_severity[k] = sev;
+        const bool shot_error = log.take(node, k);
+        if (sev != FDSOP_ERROR) (node->last_cook_fp64 ? n64 : n32) += 1;
+        // the mesh's own vectors through this frame's deformation, or unchanged where the frame was passed through
+        if (shot_transport(shot) && geo->npoints > 0) {
+            int vrc = FD_E_INVALID;
+            if (sev != FDSOP_ERROR && node->shot_dev)
+                vrc = fd_shot_dev_vectors_engine(node->shot_dev, node->e_radius * node->e_radius, (float)node->fval[find_parm("falloffrate")][0],
+                                                 shot->N_out ? shot->N_out[k] : nullptr, shot->tangentu_out ? shot->tangentu_out[k] : nullptr,
+                                                 shot->tangentv_out ? shot->tangentv_out[k] : nullptr);
+            if (vrc != FD_OK) {
+                shot_pass_vectors(geo, shot, k);
+                if (sev != FDSOP_ERROR) {
+                    log.frame(k, FDSOP_ERROR, std::string("GPU deformation failed: ") + (node->shot_dev ? fd_shot_dev_error(node->shot_dev) : "no device resources for the vectors"));
+                    if (shot->frame_severity) shot->frame_severity[k] = FDSOP_ERROR;
+                }
+            }
+        }
+        if (shot_error) stopped = true;
+    }
+    add_path(node, first, count, "", "", n32, "", n64);
+    return stopped;
+}
+
+// the transported vectors' inputs on the device
+bool shot_prepare_vectors(fdsop_node *node, const fdsop_geo *geo, const fdsop_shot *shot)
+{
+    return node->shot_dev && geo->npoints > 0 &&
+           fd_shot_dev_set_vectors(node->shot_dev, shot->N_out ? geo->N : nullptr, shot->tangentu_out ? geo->tangentu : nullptr,
+                                   shot->tangentv_out ? geo->tangentv : nullptr) == FD_OK;
+}
+
+}  // namespace
+
+const char *fdsop_shot_paths(const fdsop_node *node) { return node ? node->shot_paths.c_str() : ""; }
+
+int fdsop_cook_shot(fdsop_node *node, const fdsop_geo *geo, const fdsop_shot *shot)
+{
+    if (!node) return FDSOP_ERROR;
+    node->messages.clear();
+    node->severity = FDSOP_OK;
+    node->shot_paths.clear();
+    // the struct first, then its tables: nothing else is read before they are known to be there
+    if (!geo || !shot || shot->struct_size < (int)sizeof(fdsop_shot) || shot->nframes <= 0 || !shot->deform_P || !shot->P_out) {
+        node->add(FDSOP_ERROR, "Invalid shot arguments.");
+        if (shot && shot->struct_size >= (int)sizeof(fdsop_shot) && shot->frame_severity)
+            for (int k = 0; k < shot->nframes; ++k) shot->frame_severity[k] = FDSOP_ERROR;
+        return node->severity;
+    }
+    const int F = shot->nframes;
+    auto all_frames_error = [&] { if (shot->frame_severity) for (int k = 0; k < F; ++k) shot->frame_severity[k] = FDSOP_ERROR; };
+    for (int k = 0; k < F; ++k) {
+        const bool bad = !shot->deform_P[k] || !shot->P_out[k] || (shot->fd_falloff && !shot->fd_falloff[k]) ||
+                         (shot->N_out && !shot->N_out[k]) || (shot->tangentu_out && !shot->tangentu_out[k]) ||
+                         (shot->tangentv_out && !shot->tangentv_out[k]);
+        if (bad) {
+            node->add(FDSOP_ERROR, "Invalid shot arguments.");
+            all_frames_error();
+            return node->severity;
+        }
+    }
+    if (geo->npoints < 0 || (geo->npoints > 0 && !geo->P) || !geo->rest_P || (shot->N_out && !geo->N) ||
+        (shot->tangentu_out && !geo->tangentu) || (shot->tangentv_out && !geo->tangentv)) {
+        node->add(FDSOP_ERROR, "Invalid geometry arrays.");
+        all_frames_error();
+        return node->severity;
+    }
+
+    ShotLog log;
+    auto finish = [&] {
+        node->messages = log.text;
+        node->severity = log.severity;
+        return node->severity;
+    };
+    const bool transport = shot_transport(shot);
+
+    // F = 1 is fdsop_cook; so is a shot over an empty mesh (nothing to batch)
+    if ((F == 1 && !transport) || geo->npoints == 0) {
+        cook_frames_sequential(node, geo, shot, 0, F, true, log);
+        return finish();
+    }
+
+    // ---- what the first cook settles, once (:228-322)
+    struct PassAll {
+        const fdsop_geo *g; const fdsop_shot *s; bool armed;
+        ~PassAll() { if (armed) for (int k = 0; k < s->nframes; ++k) shot_pass_through(g, s, k); }
+    } pass{geo, shot, true};
+    CookSetup cs;
+    bool ok = cook_setup(node, geo, cs);
+    int rc = FD_OK;
+    if (ok) {
+        rc = cook_select_model(node->engine, cs);
+        if (rc == FD_OK && cs.M <= 0) rc = FD_E_INVALID;
+        if (rc != FD_OK) { node->add(FDSOP_ERROR, "Can't build RBF model."); ok = false; }
+    }
+    log.take(node, 0);               // (no frame lines yet: everything so far is the shot's)
+    if (!ok) {
+        all_frames_error();
+        return finish();
+    }
+    pass.armed = false;              // from here on every frame is written by its own path
+    const int M = cs.M;
+    const int64_t npoints = geo->npoints;
+    if (!geo->rig_rest_unchanged) { node->fp64_warned = false; node->engine_rig_stale = true; }
+
+    // ---- the node's device side, contexts and staging
+    if (!node->shot_dev) node->shot_dev = fd_shot_dev_create(node->engine);
+    bool batched = node->shot_dev != nullptr && F > 1;
+    if (transport && !shot_prepare_vectors(node, geo, shot)) batched = false;
+    int G = 0;
+    if (node->shot_dev) {
+        G = fd_shot_dev_reserve(node->shot_dev, F < FD_MAX_BATCH ? F : FD_MAX_BATCH, shot->fd_falloff != nullptr);
+        if (G <= 0) batched = false;
+    }
+    if (batched) {
+        for (int i = node->shot_nctx; i < G; ++i) {
+            fd_config cfg = node->cfg;
+            cfg.struct_size = (int)sizeof(fd_config);
+            cfg.device = cs.device;
+            cfg.eval_precision = FD_EVAL_FP32;
+            node->shot_ctx[i] = fd_create(&cfg);
+            if (!node->shot_ctx[i]) break;
+            node->shot_nctx = i + 1;
+        }
+        if (node->shot_nctx < 1) batched = false;
+        else if (node->shot_nctx < G) G = node->shot_nctx;
+    }
+    // all frames' deltas as fp32 deform - rest (:278), one block with the rest rig
+    if (batched) {
+        std::vector<float> deltas((size_t)F * (size_t)M * 3);
+        for (int k = 0; k < F; ++k) {
+            const float *dp = shot->deform_P[k];
+            float *d = deltas.data() + (size_t)k * (size_t)M * 3;
+            for (size_t i = 0; i < (size_t)M * 3; ++i) d[i] = dp[i] - geo->rest_P[i];
+        }
+        if (fd_shot_dev_set_rig(node->shot_dev, geo->rest_P, deltas.data(), M, F) != FD_OK) batched = false;
+    }
+    if (!batched) {
+        // (the node is set up: every call of the sequence follows a cook)
+        cook_frames_sequential(node, geo, shot, 0, F, false, log);
+        return finish();
+    }
+
+    fd_shot_dev *sd = node->shot_dev;
+    const int kind = cs.kernel_ext == 1 ? FD_KERNEL_THIN_PLATE : (cs.kernel_ext == 2 ? FD_KERNEL_BIHARMONIC : (cs.kernel_ext == 3 ? FD_KERNEL_CUBIC :
+                     (cs.model_index == 1 ? FD_KERNEL_GAUSSIAN_ML : FD_KERNEL_GAUSSIAN_QNN)));
+    const bool ml = kind == FD_KERNEL_GAUSSIAN_ML;
+    const int ml_layers = cs.layers < 8 ? cs.layers : 8;
+    const float radius2 = cs.radius * cs.radius;   // :402 (a square, despite the name)
+    std::vector<unsigned char> frame_ok((size_t)F, 0);
+    std::vector<int> frame_sev((size_t)F, FDSOP_OK);
+    int set = 0;
+    for (int first = 0; first < F; first += G) {
+        const int n = F - first < G ? F - first : G;
+        fd_batch *&b = node->shot_batch[n];
+        bool group_ok = true;
+        if (!b) b = fd_batch_create(node->shot_ctx, n);
+        if (!b) group_ok = false;
+        for (int i = 0; i < n && group_ok; ++i) group_ok = cook_select_model(node->shot_ctx[i], cs) == FD_OK;
+        fd_report reports[FD_MAX_BATCH];
+        memset(reports, 0, sizeof(reports));
+        const char *build_name = "";
+        if (group_ok) {
+            // the shared builds where they were measured ahead (see the header)
+            const bool qnn_shared = kind == FD_KERNEL_GAUSSIAN_QNN && (M <= 256 ? n >= 8 : n >= 16);
+            fd_batch_set_shared_lu(b, qnn_shared ? 1 : 0);
+            fd_batch_set_shared_factor(b, 0);
+            const float *rest[FD_MAX_BATCH], *delta[FD_MAX_BATCH];
+            for (int i = 0; i < n; ++i) { rest[i] = fd_shot_dev_rest(sd); delta[i] = fd_shot_dev_delta(sd, first + i); }
+            rc = fd_batch_set_points_dev(b, rest, delta, M);
+            if (rc == FD_OK) rc = fd_batch_build_async(b, fd_shot_dev_work_stream(sd));
+            if (rc == FD_OK) rc = fd_batch_build_result(b, reports);
+            for (int i = 0; i < n; ++i) group_ok = group_ok && reports[i].terminationtype == 1;
+            group_ok = group_ok && rc == FD_OK;
+            if (group_ok && fd_batch_last_build_shared_factor(b)) build_name = fd_shared_qnn_build_kernel_name(M, n);
+        }
+        if (!group_ok) {
+            // a model that does not build (or no batch object): the group's frames report as their own cooks do
+            const bool stopped = cook_frames_sequential(node, geo, shot, first, n, false, log);
+            for (int k = first; k < first + n; ++k) frame_sev[(size_t)k] = -1;      // (written by the sequence)
+            if (stopped) {
+                for (int k = first + n; k < F; ++k) { shot_pass_through(geo, shot, k); frame_sev[(size_t)k] = FDSOP_ERROR; }
+                break;
+            }
+            continue;
+        }
+        // the precision, per frame
+        unsigned char need64[FD_MAX_BATCH];
+        int n64 = 0;
+        for (int i = 0; i < n; ++i) {
+            const int k = first + i;
+            need64[i] = cs.precision_parm == 1 || (cs.precision_parm == 0 && !fd_fp32_holds(&reports[i], 1e-5));
+            if (need64[i] && cs.precision_parm == 0 && !node->fp64_warned) {       // once per rig
+                char t[240];
+                snprintf(t, sizeof(t), "fp32 evaluation would not hold 1e-5 of this rig's displacements (error ~%.2g, smallest delta %.2g): "
+                                       "evaluating in fp64.", reports[i].fp32_error, reports[i].delta_min);
+                log.frame(k, FDSOP_WARNING, t);
+                if (frame_sev[(size_t)k] < FDSOP_WARNING) frame_sev[(size_t)k] = FDSOP_WARNING;
+                node->fp64_warned = true;
+            }
+            n64 += need64[i] ? 1 : 0;
+            char info[200];
+            snprintf(info, sizeof(info), "Termination type: %d, Iterations: %d", reports[i].terminationtype, reports[i].iterationscount);
+            log.frame(k, FDSOP_MESSAGE, info);
+            if (frame_sev[(size_t)k] < FDSOP_MESSAGE) frame_sev[(size_t)k] = FDSOP_MESSAGE;
+        }
+        const bool all64 = n64 == n;
+        rc = fd_shot_dev_eval(sd, b, set, all64 ? 1 : 0, ml ? 1 : 0, radius2, cs.falloffrate);
+        if (rc == FD_OK && !all64)
+            for (int i = 0; i < n && rc == FD_OK; ++i)
+                if (need64[i]) rc = fd_shot_dev_eval_fp64_over(sd, node->shot_ctx[i], set, i, radius2, cs.falloffrate);
+        if (rc == FD_OK)
+            rc = fd_shot_dev_deliver(sd, set, n, nullptr, shot->P_out + first, shot->fd_falloff ? shot->fd_falloff + first : nullptr,
+                                     shot->N_out ? shot->N_out + first : nullptr, shot->tangentu_out ? shot->tangentu_out + first : nullptr,
+                                     shot->tangentv_out ? shot->tangentv_out + first : nullptr);
+        if (rc != FD_OK) {
+            const std::string t = std::string("GPU deformation failed: ") + fd_shot_dev_error(sd);
+            for (int k = first; k < first + n; ++k) {
+                log.frame(k, FDSOP_ERROR, t);
+                frame_sev[(size_t)k] = FDSOP_ERROR;
+                shot_pass_through(geo, shot, k);
+            }
+            continue;
+        }
+        for (int k = first; k < first + n; ++k) frame_ok[(size_t)k] = 1;
+        const int nl = n;    // the fp32 launch of a mixed group covers the whole group
+        const char *e32 = all64 ? "" : (ml ? fd_shared_ml_kernel_name(M, ml_layers, nl) : fd_shared_kernel_name(M, nl, kind));
+        const char *e64 = all64 ? (ml ? fd_shared_ml_fp64_kernel_name(M, ml_layers, n) : fd_shared_fp64_kernel_name(M, n, kind)) : "";
+        add_path(node, first, n, build_name, e32, n - n64, e64, n64);
+        set ^= 1;
+    }
+    bool arrived = fd_shot_dev_wait(sd, 0) == FD_OK;
+    arrived = (fd_shot_dev_wait(sd, 1) == FD_OK) && arrived;
+    if (!arrived) {
+        const std::string t = std::string("GPU deformation failed: ") + fd_shot_dev_error(sd);
+        for (int k = 0; k < F; ++k)
+            if (frame_ok[(size_t)k]) { log.frame(k, FDSOP_ERROR, t); frame_sev[(size_t)k] = FDSOP_ERROR; frame_ok[(size_t)k] = 0; shot_pass_through(geo, shot, k); }
+    }
+    bool any_ok = false;
+    for (int k = 0; k < F; ++k) any_ok = any_ok || frame_ok[(size_t)k];
+
+    // ---- what a cook does once around its evaluation, for the frames cooked here
+    if (any_ok) {
+        // :386-388 -- Cd is added white and never written again
+        if (geo->Cd)
+            for (int64_t i = 0; i < npoints * 3; ++i) geo->Cd[i] = 1.f;
+        // :396-399
+        if (!geo->dist2 && !(cs.use_capture && node->captured))
+            log.shot(FDSOP_WARNING, "Can't find distance capture attribute. Won't apply radius nor falloff.");
+        if (geo->dist2_out && cs.use_capture && node->captured && fd_mesh_get_dist2(node->engine, geo->dist2_out) != FD_OK)
+            log.shot(FDSOP_ERROR, std::string("GPU deformation failed: ") + fd_last_error(node->engine));
+    }
+    // :444-482 -- the morph-space pass, in frame order: the first frame that reaches it with the weights not computed yet
+    // gets the reprojection (frame 0); every later one the reference's warning
+    if (cs.morph_space && cs.have_blends && node->morph && fd_morph_is_initialised(node->morph)) {
+        for (int k = 0; k < F; ++k) {
+            if (!frame_ok[(size_t)k]) continue;
+            bool weights_done = false;
+            const int S = fd_morph_shape_count(node->morph);
+            if (!fd_morph_is_computed(node->morph)) {
+                const int doclampweight = (int)node->fval[find_parm("doclampweight")][0];
+                const float falloffradius = (float)node->fval[find_parm("falloffradius")][0];
+                const float weightrange[2] = {(float)node->fval[find_parm("weightrange")][0],
+                                              (float)node->fval[find_parm("weightrange")][1]};
+                std::vector<double> w((size_t)(S > 0 ? S : 1));
+                const bool same_rest = cs.morph_inited_this_cook && cs.rest_attr == geo->P;
+                int mrc = fd_morph_set_rest(node->morph, same_rest ? nullptr : cs.rest_attr, 0);
+                if (mrc == FD_OK)
+                    mrc = fd_morph_apply(node->morph, shot->P_out[k], doclampweight ? weightrange : nullptr,
+                                         cs.dofalloff_parm && falloffradius != 0.f, falloffradius, w.data());
+                weights_done = mrc == FD_OK;
+                if (weights_done) {
+                    if (geo->weights) memcpy(geo->weights, w.data(), sizeof(double) * (size_t)S);
+                    if (geo->weights_count) *geo->weights_count = S;
+                }
+            }
+            if (!weights_done) {
+                const char *t = "Can't compute weights for morphspace deformation. Ingoring it.";   // :452
+                if (k == 0) log.shot(FDSOP_WARNING, t);
+                else log.frame(k, FDSOP_WARNING, t);
+                if (frame_sev[(size_t)k] < FDSOP_WARNING) frame_sev[(size_t)k] = FDSOP_WARNING;
+            }
+        }
+    }
+    if (shot->frame_severity)
+        for (int k = 0; k < F; ++k)
+            if (frame_sev[(size_t)k] >= 0)      // (-1: the sequence wrote it)
+                shot->frame_severity[k] = frame_sev[(size_t)k] == FDSOP_ERROR ? FDSOP_ERROR
+                                          : (frame_sev[(size_t)k] > log.common ? frame_sev[(size_t)k] : log.common);
+    return finish();
 }
 
 }  // extern "C"

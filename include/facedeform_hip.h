@@ -1123,6 +1123,76 @@ const char *fdsop_messages(const fdsop_node *node);
 int fdsop_effective_float(const fdsop_node *node, const char *token, double *value);
 fd_ctx *fdsop_engine(fdsop_node *node);
 
+/* ---- all frames of a shot through the node in one call ------------------------
+ * One mesh, one rest rig, F deformed rigs (input 2 at F times).  `geo` supplies everything that does not change over the
+ * shot -- the mesh and its attributes, the rest rig and the point counts, the capture inputs, the blendshapes, the change
+ * flags; geo->deform_P, geo->P_out and geo->fd_falloff are not read and may be NULL; geo->Cd, dist2_out, weights and
+ * weights_count are written once.  fdsop_shot (additive: the ABI version stays; fdsop_geo is unchanged) carries the frames.
+ *
+ * Contract: frame k is the k-th of F consecutive fdsop_cook calls on this node.  Call 0 uses geo's flags as given; calls
+ * k >= 1 use rig_rest_unchanged = mesh_unchanged = 1 and rest_changed = blends_changed = 0; each call's deform_P and outputs
+ * are the shot's k-th.  Hence:
+ *   Capture runs where the first cook would run it, and never again.
+ *   Morph space: the pass applies to the first frame that reaches it while fd_morph_is_computed is false -- frame 0 -- and
+ *     every later frame gets the reference's warning (:448-452, the quirk fdsop_cook keeps).  `weights` is that frame's.
+ *   Clamps and fdsop_effective_float values are the single cook's.
+ *   Gating: a gated vertex is bit-identical to P in every frame, and its fd_falloff entry is 0.
+ *   Precision, per frame: with `precision` = 0 frame k is evaluated in fp64 exactly when fd_fp32_holds(report_k, 1e-5) is 0,
+ *     its neighbours stay fp32, and the warning comes once per rig; 1: every frame fp64; 2: every frame fp32.
+ *   Errors: a shot-wide error (bad arrays, differing rig counts, no engine, a capture failure, a model the engine refuses)
+ *     makes every P_out[k] the copy of input 0 and every frame_severity[k] an error, with fdsop_cook's text.  A failure that
+ *     belongs to a frame passes that frame through and the others are cooked.
+ *   Node state: afterwards a following fdsop_cook(..., rig_rest_unchanged = 1, mesh_unchanged = 1) is correct.
+ *   F = 1 IS fdsop_cook, bit for bit (positions, fall-off, messages apart from the frame prefix).
+ * Messages: lines a single cook emits for the mesh, the parms or the capture come once, as in fdsop_cook.  Lines that belong
+ * to a frame read "<severity>\tframe <k>: <text>\n": `Termination type`, a solve failure, a failed evaluation, the fp64
+ * warning (on the first frame that needs it) and the morph warning of frames >= 1.  The return value is the worst severity;
+ * frame_severity[k] is what the k-th cook would have returned.
+ *
+ * How the frames are cooked.  Groups of up to FD_MAX_BATCH frames, on contexts and batch objects the node owns (created on
+ * first use, re-created with the engine when `device` changes, freed in fdsop_destroy; a tail group has a batch object of its
+ * size over the first contexts -- everything of a shot is enqueued on ONE stream and every group's build is collected before
+ * the next batch object touches the contexts).  The rest rig and all frames' fp32 deltas (deform - rest, :278) go to the
+ * device as one block; every context of a group gets the SAME rest pointer (fd_batch_set_points_dev).  One batched build per
+ * group, then the group is evaluated on the engine's device-resident mesh (fd_mesh_set's arrays, the captured dist2) by ONE
+ * launch: fd_batch_deform_shared_dev / _ml_dev (fp32), _fp64_dev / _ml_fp64_dev (fp64), and their *_vectors_* forms when
+ * transport tables are given; those calls' own fall-backs cover what they do not take.  A group in which only some frames
+ * need fp64 is evaluated in fp32 as a whole -- so an fp32 frame's bits do not depend on which neighbours needed fp64 -- and
+ * the frames that need it are then evaluated again in fp64, per context, over their outputs.  Results are staged in HBM in
+ * two sets: group g is downloaded on a stream of its own while group g + 1 is built and evaluated.  Page-locked output arrays
+ * are copied asynchronously, pageable ones through the runtime's staging.  When the staging sets cannot be allocated the
+ * groups get smaller (halved), and with no room for one frame the shot is cooked frame by frame.
+ * The contexts, the batch objects and the staging sets (two sets of 16 B per vertex and frame of a group, 36 B more per
+ * transported vector) stay with the node for the next shot and go in fdsop_destroy.
+ * Shared builds (one factorisation of the rest rig per group): QNN (fd_batch_set_shared_lu) from 8 frames a group up to 256
+ * control points and from 16 frames above, where DESIGN 4.2i measured it ahead; off for the thin-plate family (4.2f: slower
+ * as latency) and for the multilayer model (4.2h: not measured yet).
+ * Sequential route: F = 1 (by contract), an empty mesh, a group with a model that did not solve (its frames then report as
+ * their own cooks do), and no memory for staging take consecutive fdsop_cook calls inside this call.  Nothing else does:
+ * at 1M vertices and 256 control points every F >= 2 measured at or ahead of F cooks with rig and mesh unchanged, for the
+ * node's defaults, kernel = 1 and model = 1, page-locked and pageable outputs (the least: 2 QNN frames, 1.01x .. 1.10x over
+ * two runs; 1.8x .. 3.4x at 32 frames).
+ * Transport: N_out / tangentu_out / tangentv_out, each NULL or F arrays of npoints x 3, receive geo->N / tangentu / tangentv
+ * carried through each frame's deformation by fd_vectors' rules (geo's attribute must be there: "Invalid geometry arrays."
+ * otherwise); a frame that is passed through gets them unchanged.  NULL tables: the attributes are left alone, as in the
+ * reference. */
+typedef struct fdsop_shot {
+    int struct_size;                 /* = sizeof(fdsop_shot); smaller: error before anything else */
+    int nframes;                     /* F >= 1, any count */
+    const float *const *deform_P;    /* F arrays, geo->deform_npoints x 3: input 2 at each frame */
+    float *const *P_out;             /* F arrays, npoints x 3 */
+    float *const *fd_falloff;        /* F arrays of npoints, or NULL */
+    int *frame_severity;             /* out, F entries, or NULL */
+    float *const *N_out, *const *tangentu_out, *const *tangentv_out;
+} fdsop_shot;
+int fdsop_cook_shot(fdsop_node *node, const fdsop_geo *geo, const fdsop_shot *shot);
+/* One line per group of the last shot: "first_frame\tnframes\tbuild\teval32\tn32\teval64\tn64\n".  build: the shared
+ * build's kernel name, or "" for per-context builds.  eval32 / eval64: what fd_shared_kernel_name / fd_shared_ml_kernel_name
+ * and fd_shared_fp64_kernel_name / fd_shared_ml_fp64_kernel_name answer for the group's launch of that precision, or ""
+ * where the frames went per context (a sequential group; the fp64 frames of a mixed group).  n32 / n64: the frames
+ * delivered in each precision. */
+const char *fdsop_shot_paths(const fdsop_node *node);
+
 #ifdef __cplusplus
 }
 #endif
