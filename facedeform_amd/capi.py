@@ -47,6 +47,12 @@ class FdVectors(C.Structure):
                 ("tv", C.c_void_p), ("tv_out", C.c_void_p), ("jacobian", C.c_void_p)]
 
 
+class FdInvertOpts(C.Structure):
+    """fd_invert_opts: the Newton iteration's limits (0 = the defaults) and its optional per-vertex outputs."""
+    _fields_ = [("struct_size", C.c_int), ("max_iter", C.c_int), ("tol", C.c_double), ("residual_out", C.c_void_p),
+                ("iters_out", C.c_void_p)]
+
+
 class FdBatchVectors(C.Structure):
     """fd_batch_vectors: ONE input array per vector (the shared mesh's, N x 3) with a table of one output pointer per
     context, and a table of Jacobian outputs (N x 9 each) or NULL."""
@@ -79,7 +85,7 @@ class FdsopShot(C.Structure):
 EXPORTS = [
     "fd_create", "fd_destroy", "fd_last_error", "fd_abi_version", "fd_set_stream", "fd_set_eval_precision", "fd_set_output", "fd_fp32_holds", "fd_set_points",
     "fd_set_points_dev", "fd_set_deltas", "fd_set_deltas_dev", "fd_set_kernel", "fd_set_term", "fd_build", "fd_build_async",
-    "fd_build_result", "fd_deform", "fd_deform_dev", "fd_deform_dev_stream", "fd_deform_vectors", "fd_deform_vectors_dev", "fd_get_weights", "fd_model_centres", "fd_model_bytes",
+    "fd_build_result", "fd_deform", "fd_deform_dev", "fd_deform_dev_stream", "fd_deform_vectors", "fd_deform_vectors_dev", "fd_invert", "fd_invert_dev", "fd_get_weights", "fd_model_centres", "fd_model_bytes",
     "fd_export_model", "fd_import_model", "fd_synchronize", "fd_host_alloc", "fd_host_free",
     "fd_mesh_set", "fd_mesh_size", "fd_deform_mesh", "fd_mesh_capture", "fd_mesh_get_dist2",
     "fd_capture_dist2", "fd_capture_dist2_dev", "fd_capture_islands", "fd_capture_islands_dev",
@@ -152,6 +158,10 @@ def load() -> C.CDLL:
     L.fd_deform_vectors.restype = i32
     L.fd_deform_vectors_dev.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, C.POINTER(FdVectors)]
     L.fd_deform_vectors_dev.restype = i32
+    L.fd_invert.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, C.POINTER(FdInvertOpts)]
+    L.fd_invert.restype = i32
+    L.fd_invert_dev.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, C.POINTER(FdInvertOpts)]
+    L.fd_invert_dev.restype = i32
     L.fd_get_weights.argtypes = [vp, _f64p, _f64p]; L.fd_get_weights.restype = i32
     L.fd_model_centres.argtypes = [vp]; L.fd_model_centres.restype = i32
     L.fd_model_bytes.argtypes = [vp]; L.fd_model_bytes.restype = sz
@@ -482,6 +492,34 @@ class Engine:
         self._check(self.L.fd_deform_vectors_dev(self.ctx, N, vp(d_P_in), vp(d_P_out), vp(d_dist2 or None), vp(d_falloff or None),
                                                  vp(d_tu or None), vp(d_tv or None), vp(d_nrm or None), float(radius2),
                                                  float(falloffrate), C.byref(vec)))
+
+    def invert(self, Y, dist2=None, tangents=None, radius2=1.0, falloffrate=1.0, max_iter=0, tol=0.0,
+               want_residual=True, want_iters=True):
+        """fd_invert: the rest-space x with x + f Pi d(x) = y for every deformed point y, by Newton in fp64 on the device.
+        dist2 and tangents = (tu, tv, nrm) are the vertices' attributes, as in deform().  Returns (X, residual, iters):
+        iters >= 0 steps taken, -1 max_iter reached, -2 broke down (X then holds the best iterate seen); None for an
+        output that was not asked for."""
+        Y = np.ascontiguousarray(Y, np.float32).reshape(-1, 3)
+        n = Y.shape[0]
+        X = Y.copy()
+        d2 = None if dist2 is None else np.ascontiguousarray(dist2, np.float32)
+        tu = tv = nr = None
+        if tangents is not None:
+            tu, tv, nr = (np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in tangents)
+        res = np.zeros(n, np.float32) if want_residual else None
+        its = np.zeros(n, np.int32) if want_iters else None
+        opts = FdInvertOpts(C.sizeof(FdInvertOpts), int(max_iter), float(tol), _np_ptr(res), _np_ptr(its))
+        self._check(self.L.fd_invert(self.ctx, n, _np_ptr(X), _np_ptr(X), _np_ptr(d2), _np_ptr(tu), _np_ptr(tv), _np_ptr(nr),
+                                     float(radius2), float(falloffrate), C.byref(opts)))
+        return X, res, its
+
+    def invert_dev(self, N: int, d_Y: int, d_X_out: int, d_dist2: int = 0, d_tu: int = 0, d_tv: int = 0, d_nrm: int = 0,
+                   radius2=1.0, falloffrate=1.0, max_iter=0, tol=0.0, d_residual: int = 0, d_iters: int = 0):
+        """fd_invert_dev: device pointers (ints), one launch, asynchronous on the context's stream."""
+        vp = C.c_void_p
+        opts = FdInvertOpts(C.sizeof(FdInvertOpts), int(max_iter), float(tol), vp(d_residual or None), vp(d_iters or None))
+        self._check(self.L.fd_invert_dev(self.ctx, N, vp(d_Y), vp(d_X_out), vp(d_dist2 or None), vp(d_tu or None),
+                                         vp(d_tv or None), vp(d_nrm or None), float(radius2), float(falloffrate), C.byref(opts)))
 
     def get_weights(self):
         n = int(self.L.fd_model_centres(self.ctx))     # M, or M * layers for the multilayer model

@@ -99,6 +99,9 @@ struct fd_ctx {
     // fd_deform_vectors: staging of the transported vectors + Jacobian (N x 18), and P_in set aside when it is overwritten
     int64_t cap_vec = 0, cap_vecP = 0;
     float *d_vec = nullptr, *d_vecP = nullptr;
+    // fd_invert: staging of iters_out (residual_out goes through d_fall)
+    int64_t cap_iters = 0;
+    int *d_iters = nullptr;
     // fd_mesh_set: the mesh arrays that stay the same from cook to cook live in their own
     // device buffers (the staging above is evaluated in place, so it cannot serve as a cache)
     int64_t mesh_N = 0, mesh_cap = 0;
@@ -443,6 +446,8 @@ static bool frames_ok(const void *tu, const void *tv, const void *nrm)
 static int poll_status(fd_ctx *ctx);
 static int deform_host(fd_ctx *ctx, int64_t N, const float *P_in, float *P_out, const float *dist2, float *falloff_out,
                        const float *tu, const float *tv, const float *nrm, float radius2, float falloffrate, const fd_vectors *vec);
+static int invert_host(fd_ctx *ctx, int64_t N, const float *Y, float *X_out, const float *dist2, const float *tu, const float *tv,
+                       const float *nrm, float radius2, float falloffrate, const fd_invert_opts *opts);
 
 extern "C" {
 
@@ -515,7 +520,7 @@ void fd_destroy(fd_ctx *ctx)
     if (ctx->stream_ || ctx->own_stream) (void)hipStreamSynchronize(cur_stream(ctx));
     void *bufs[] = {ctx->d_rest, ctx->d_delta, ctx->d_centres, ctx->d_radii, ctx->d_W, ctx->d_A,
                     ctx->d_X, ctx->d_ipiv, ctx->d_moves, ctx->d_rec32, ctx->d_rec64, ctx->d_tiles, ctx->d_tiles16, ctx->d_ns, ctx->d_model, ctx->d_slot,
-                    ctx->d_P, ctx->d_dist2, ctx->d_fall, ctx->d_tu, ctx->d_tv, ctx->d_nrm, ctx->d_vec, ctx->d_vecP,
+                    ctx->d_P, ctx->d_dist2, ctx->d_fall, ctx->d_tu, ctx->d_tv, ctx->d_nrm, ctx->d_vec, ctx->d_vecP, ctx->d_iters,
                     ctx->m_P, ctx->m_dist2, ctx->m_tu, ctx->m_tv, ctx->m_nrm, ctx->m_out, ctx->m_fall};
     for (void *p : bufs) if (p) (void)hipFree(p);
     if (ctx->h_model) (void)hipHostFree(ctx->h_model);
@@ -962,10 +967,25 @@ static bool vectors_ok(fd_ctx *ctx, const fd_vectors *vec)
 }
 static bool vectors_wanted(const fd_vectors *vec) { return vec && (vec->N || vec->tu || vec->tv || vec->jacobian); }
 
-// fd_deform_dev_stream / fd_deform_vectors_dev / the staged host calls: vec == nullptr is the deformation alone
+// fd_invert*: a struct of at least this ABI's size
+static bool invert_opts_ok(fd_ctx *ctx, const fd_invert_opts *opts)
+{
+    if (!opts) { set_err(ctx, "fd_invert: opts is NULL"); return false; }
+    if (opts->struct_size < (int)sizeof(fd_invert_opts)) {
+        set_err(ctx, "fd_invert: opts->struct_size is %d, must be sizeof(fd_invert_opts) = %d", opts->struct_size,
+                (int)sizeof(fd_invert_opts));
+        return false;
+    }
+    return true;
+}
+
+// fd_deform_dev_stream / fd_deform_vectors_dev / the staged host calls: vec == nullptr is the deformation alone.
+// fd_invert_dev: inv != nullptr -- the same checks, status poll and ordering, then the inverse's one launch in place of the
+// deformation's (d_P_in = the deformed points, d_P_out = the rest-space points; no fall-off output, no vectors).
 static int deform_dev_common(fd_ctx *ctx, void *hip_stream, int64_t N, const float *d_P_in, float *d_P_out,
                              const float *d_dist2, float *d_falloff_out, const float *d_tu, const float *d_tv,
-                             const float *d_nrm, float radius2, float falloffrate, const fd_vectors *vec)
+                             const float *d_nrm, float radius2, float falloffrate, const fd_vectors *vec,
+                             const InvertArgs *inv = nullptr)
 {
     hipStream_t launch_stream = hip_stream ? (hipStream_t)hip_stream : cur_stream(ctx);
     if (N < 0 || (N > 0 && (!d_P_in || !d_P_out))) { set_err(ctx, "fd_deform: bad N / P pointers"); return FD_E_INVALID; }
@@ -977,6 +997,10 @@ static int deform_dev_common(fd_ctx *ctx, void *hip_stream, int64_t N, const flo
     if ((rc = poll_status(ctx))) return rc;           // a failed asynchronous build: repaired here, or reported
     const DeformArgs a = deform_args(ctx, N, d_P_in, d_P_out, d_dist2, d_falloff_out, d_tu, d_tv, d_nrm, radius2, falloffrate);
     if ((rc = order_after_batch(ctx, launch_stream))) return rc;
+    if (inv) {
+        FD_HIP(ctx, launch_invert(a, *inv, launch_stream));
+        return FD_OK;
+    }
     if (!vec) {
         FD_HIP(ctx, launch_deform(a, launch_stream));
         return FD_OK;
@@ -1055,7 +1079,46 @@ int fd_deform_vectors(fd_ctx *ctx, int64_t N, const float *P_in, float *P_out, c
                        vectors_wanted(vec) ? vec : nullptr);
 }
 
+int fd_invert_dev(fd_ctx *ctx, int64_t N, const float *d_Y, float *d_X_out, const float *d_dist2, const float *d_tu,
+                  const float *d_tv, const float *d_nrm, float radius2, float falloffrate, const fd_invert_opts *opts)
+{
+    if (!ctx) return FD_E_INVALID;
+    if (!invert_opts_ok(ctx, opts)) return FD_E_INVALID;
+    const InvertArgs inv{opts->max_iter, opts->tol, opts->residual_out, opts->iters_out};
+    return deform_dev_common(ctx, nullptr, N, d_Y, d_X_out, d_dist2, nullptr, d_tu, d_tv, d_nrm, radius2, falloffrate, nullptr, &inv);
+}
+
+int fd_invert(fd_ctx *ctx, int64_t N, const float *Y, float *X_out, const float *dist2, const float *tu, const float *tv,
+              const float *nrm, float radius2, float falloffrate, const fd_invert_opts *opts)
+{
+    if (!ctx) return FD_E_INVALID;
+    if (!invert_opts_ok(ctx, opts)) return FD_E_INVALID;
+    return invert_host(ctx, N, Y, X_out, dist2, tu, tv, nrm, radius2, falloffrate, opts);
+}
+
 }  // extern "C"
+
+// the staging arrays of the host calls for N vertices: d_P, d_dist2, d_fall; the frames' on first use
+static int ensure_staging(fd_ctx *ctx, int64_t N, bool frames)
+{
+    int rc;
+    if (N > ctx->cap_N) {
+        if ((rc = dev_alloc(ctx, &ctx->d_P, (size_t)N * 3))) return rc;
+        if ((rc = dev_alloc(ctx, &ctx->d_dist2, (size_t)N))) return rc;
+        if ((rc = dev_alloc(ctx, &ctx->d_fall, (size_t)N))) return rc;
+        // tangent frames are optional and 3x as large: allocate on first use
+        if (ctx->d_tu) { (void)hipFree(ctx->d_tu); ctx->d_tu = nullptr; }
+        if (ctx->d_tv) { (void)hipFree(ctx->d_tv); ctx->d_tv = nullptr; }
+        if (ctx->d_nrm) { (void)hipFree(ctx->d_nrm); ctx->d_nrm = nullptr; }
+        ctx->cap_N = N;
+    }
+    if (frames && !ctx->d_tu) {
+        if ((rc = dev_alloc(ctx, &ctx->d_tu, (size_t)ctx->cap_N * 3))) return rc;
+        if ((rc = dev_alloc(ctx, &ctx->d_tv, (size_t)ctx->cap_N * 3))) return rc;
+        if ((rc = dev_alloc(ctx, &ctx->d_nrm, (size_t)ctx->cap_N * 3))) return rc;
+    }
+    return FD_OK;
+}
 
 // fd_deform / fd_deform_vectors on host arrays: staged through the context's device buffers, or -- page-locked arrays and
 // no vectors -- read and written in place
@@ -1094,21 +1157,7 @@ static int deform_host(fd_ctx *ctx, int64_t N, const float *P_in, float *P_out, 
             return FD_OK;
         }
     }
-    if (N > ctx->cap_N) {
-        if ((rc = dev_alloc(ctx, &ctx->d_P, (size_t)N * 3))) return rc;
-        if ((rc = dev_alloc(ctx, &ctx->d_dist2, (size_t)N))) return rc;
-        if ((rc = dev_alloc(ctx, &ctx->d_fall, (size_t)N))) return rc;
-        // tangent frames are optional and 3x as large: allocate on first use
-        if (ctx->d_tu) { (void)hipFree(ctx->d_tu); ctx->d_tu = nullptr; }
-        if (ctx->d_tv) { (void)hipFree(ctx->d_tv); ctx->d_tv = nullptr; }
-        if (ctx->d_nrm) { (void)hipFree(ctx->d_nrm); ctx->d_nrm = nullptr; }
-        ctx->cap_N = N;
-    }
-    if (tu && !ctx->d_tu) {
-        if ((rc = dev_alloc(ctx, &ctx->d_tu, (size_t)ctx->cap_N * 3))) return rc;
-        if ((rc = dev_alloc(ctx, &ctx->d_tv, (size_t)ctx->cap_N * 3))) return rc;
-        if ((rc = dev_alloc(ctx, &ctx->d_nrm, (size_t)ctx->cap_N * 3))) return rc;
-    }
+    if ((rc = ensure_staging(ctx, N, tu != nullptr))) return rc;
     // A vertex whose gate fails keeps the caller's fd_falloff entry, so that array goes up as
     // well -- unless no vertex can be gated (no dist2 and a non-negative radius^2).
     const bool fall_up = falloff_out && (dist2 || radius2 < 0.f);
@@ -1151,6 +1200,42 @@ static int deform_host(fd_ctx *ctx, int64_t N, const float *P_in, float *P_out, 
         if (vec->tv) FD_HIP(ctx, hipMemcpyAsync(vec->tv_out, dv.tv_out, b3, hipMemcpyDeviceToHost, s));
         if (vec->jacobian) FD_HIP(ctx, hipMemcpyAsync(vec->jacobian, dv.jacobian, 3 * b3, hipMemcpyDeviceToHost, s));
     }
+    FD_HIP(ctx, hipStreamSynchronize(s));
+    return FD_OK;
+}
+
+// fd_invert on host arrays: staged through the context's device buffers like deform_host with vectors (no zero-copy form);
+// solved in place in d_P, residual_out through d_fall, iters_out through d_iters
+static int invert_host(fd_ctx *ctx, int64_t N, const float *Y, float *X_out, const float *dist2, const float *tu, const float *tv,
+                       const float *nrm, float radius2, float falloffrate, const fd_invert_opts *opts)
+{
+    if (N < 0 || (N > 0 && (!Y || !X_out))) { set_err(ctx, "fd_invert: bad N / Y / X_out pointers"); return FD_E_INVALID; }
+    if (!frames_ok(tu, tv, nrm)) { set_err(ctx, "fd_invert: tu, tv, nrm must be all set or all NULL"); return FD_E_INVALID; }
+    if (!ctx->built && !ctx->build_pending) { set_err(ctx, "fd_invert: no successfully built model"); return FD_E_NOT_BUILT; }
+    if (N == 0) return FD_OK;
+    int rc = use_device(ctx);
+    if (rc) return rc;
+    if ((rc = ensure_staging(ctx, N, tu != nullptr))) return rc;
+    if (opts->iters_out && N > ctx->cap_iters) {
+        if ((rc = dev_alloc(ctx, &ctx->d_iters, (size_t)N))) return rc;
+        ctx->cap_iters = N;
+    }
+    hipStream_t s = cur_stream(ctx);
+    const size_t b3 = sizeof(float) * 3 * (size_t)N, b1 = sizeof(float) * (size_t)N;
+    FD_HIP(ctx, hipMemcpyAsync(ctx->d_P, Y, b3, hipMemcpyHostToDevice, s));
+    if (dist2) FD_HIP(ctx, hipMemcpyAsync(ctx->d_dist2, dist2, b1, hipMemcpyHostToDevice, s));
+    if (tu) {
+        FD_HIP(ctx, hipMemcpyAsync(ctx->d_tu, tu, b3, hipMemcpyHostToDevice, s));
+        FD_HIP(ctx, hipMemcpyAsync(ctx->d_tv, tv, b3, hipMemcpyHostToDevice, s));
+        FD_HIP(ctx, hipMemcpyAsync(ctx->d_nrm, nrm, b3, hipMemcpyHostToDevice, s));
+    }
+    const InvertArgs inv{opts->max_iter, opts->tol, opts->residual_out ? ctx->d_fall : nullptr, opts->iters_out ? ctx->d_iters : nullptr};
+    rc = deform_dev_common(ctx, nullptr, N, ctx->d_P, ctx->d_P, dist2 ? ctx->d_dist2 : nullptr, nullptr, tu ? ctx->d_tu : nullptr,
+                           tu ? ctx->d_tv : nullptr, tu ? ctx->d_nrm : nullptr, radius2, falloffrate, nullptr, &inv);
+    if (rc) return rc;
+    FD_HIP(ctx, hipMemcpyAsync(X_out, ctx->d_P, b3, hipMemcpyDeviceToHost, s));
+    if (opts->residual_out) FD_HIP(ctx, hipMemcpyAsync(opts->residual_out, ctx->d_fall, b1, hipMemcpyDeviceToHost, s));
+    if (opts->iters_out) FD_HIP(ctx, hipMemcpyAsync(opts->iters_out, ctx->d_iters, sizeof(int) * (size_t)N, hipMemcpyDeviceToHost, s));
     FD_HIP(ctx, hipStreamSynchronize(s));
     return FD_OK;
 }

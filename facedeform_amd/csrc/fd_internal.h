@@ -279,6 +279,17 @@ struct VectorArgs {
     float *jacobian;      // N x 9, row-major A
 };
 hipError_t launch_vectors(const DeformArgs &a, const VectorArgs &v, hipStream_t stream);
+// the inverse of the deformation (fd_invert.hip, fd_invert*): `a` names the mesh attributes and the model as for the
+// deformation, P_in = the deformed points y, P_out = the rest-space points x (may alias P_in); falloff_out, precision, variant
+// and delta_out are not read: the iteration is fp64 and takes positions to positions.
+constexpr int kInvertDefaultIter = 20, kInvertMaxIter = 64;
+struct InvertArgs {
+    int max_iter;          // <= 0: kInvertDefaultIter; capped at kInvertMaxIter
+    double tol;            // <= 0: per vertex 2^-25 max(|y|_inf, 1 / norm32[3])
+    float *residual_out;   // N or null
+    int *iters_out;        // N or null
+};
+hipError_t launch_invert(const DeformArgs &a, const InvertArgs &v, hipStream_t stream);
 hipError_t launch_deform_batch(const DeformArgs *a, int n, hipStream_t stream);
 // frames that share the mesh and the rest rig (fd_eval.hip, k_deform32_tps_shared): phi once per
 // (vertex, centre), the 3 F-wide weight contraction on the matrix pipe

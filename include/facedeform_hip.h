@@ -305,6 +305,52 @@ int fd_deform_vectors_dev(fd_ctx *ctx, int64_t N, const float *d_P_in, float *d_
                           float *d_falloff_out, const float *d_tu, const float *d_tv, const float *d_nrm,
                           float radius2, float falloffrate, const fd_vectors *vec);
 
+/* ---- the inverse of the deformation -------------------------------------------
+ * Given a point y of the deformed mesh, fd_invert finds the rest-space point x with
+ *   x + f . Pi . d(x) = y
+ * (d, Pi, f as above).  Uses: pulling a corrective sculpt made on the posed mesh back to the rest pose, re-binding
+ * data captured in a pose, round-tripping a cache.
+ *
+ * Vertex attributes.  dist2[i] and tu/tv/nrm[i] belong to vertex i, exactly as in fd_deform, so f_i and Pi_i are
+ *   constants of vertex i's equation: the call solves F_i(x) = x + f_i Pi_i d(x) - y_i = 0, d the built model's field
+ *   including its polynomial term.
+ * Iteration.  x0 = y_i; while |F(x)|_2 > tol_i:  x <- x - A(x)^-1 F(x),  A = I + f_i Pi_i J(x) (fd_vectors' definition).
+ *   The 3x3 solve uses cofactors and one division by det A.  Everything is fp64 whatever fd_set_eval_precision says: the
+ *   fp32 positions widened, direct differences x - c_j in raw coordinates, phi and grad phi of the kind in fp64 from one
+ *   shared transcendental.  No line search and no damping: the algorithm is fixed, so step counts can be compared with
+ *   a reference.
+ * Result.  X_out[i] is the converged x rounded once to fp32.  Status -1 or -2: the iterate with the smallest residual
+ *   seen is written, y_i at worst; it is always finite.  -2 means a non-finite iterate (or residual) or det A == 0.
+ *   For such a vertex residual_out is taken at the fp32 value that is written (one more evaluation, only in waves that
+ *   hold such a vertex), so that it describes what the caller holds; rounding that value to fp32 changes nothing.
+ * Pass-through.  X_out[i] = Y[i] bit for bit, iters = 0, residual = 0 for a gated vertex (dist2 > radius2) and for a model
+ *   with terminationtype != 1.  With f = 0, step 0 already converges: F(y) = 0 exactly.
+ * Determinism.  The same inputs give the same bits on every call; a vertex's result does not depend on N or on its
+ *   place in the launch.
+ * Aliasing.  X_out may alias Y; nothing else may.
+ * Non-injective maps.  Where the forward map is not injective (folds; the tangent projection with det A near 0) the
+ *   call returns *a* preimage when Newton finds one.  This is not an error.
+ * Checks and errors.  The build-status poll and repair, FD_E_NOT_BUILT, the all-or-none rule for tu/tv/nrm and the ordering
+ *   behind a batched build are fd_deform's.  FD_E_INVALID for a NULL context, NULL opts or a bad struct_size comes before
+ *   any device work.  fd_set_output has no effect: the call takes positions and returns positions. */
+typedef struct fd_invert_opts {
+    int struct_size;      /* = sizeof(fd_invert_opts); smaller is FD_E_INVALID */
+    int max_iter;         /* Newton steps allowed per vertex; <= 0: 20; capped at 64 */
+    double tol;           /* position units; <= 0: per vertex 2^-25 * max(|y|_inf, s), s the model's normalisation scale
+                             (the rest rig's extent rounded to a power of two) */
+    float *residual_out;  /* N, or NULL: |x + f Pi d(x) - y|_2 at the x that is written, before its rounding to fp32 */
+    int *iters_out;       /* N, or NULL: steps taken (>= 0) when converged; -1 max_iter reached; -2 broke down */
+} fd_invert_opts;
+
+/* Host arrays (those in `opts` too), synchronous. */
+int fd_invert(fd_ctx *ctx, int64_t N, const float *Y, float *X_out, const float *dist2,
+              const float *tu, const float *tv, const float *nrm,
+              float radius2, float falloffrate, const fd_invert_opts *opts);
+/* Same, device pointers (those in `opts` too), asynchronous on the context's stream, like fd_deform_dev: one launch. */
+int fd_invert_dev(fd_ctx *ctx, int64_t N, const float *d_Y, float *d_X_out, const float *d_dist2,
+                  const float *d_tu, const float *d_tv, const float *d_nrm,
+                  float radius2, float falloffrate, const fd_invert_opts *opts);
+
 /* ---- device-resident mesh (next row N3, engine side) --------------------------
  * In an animated shot the mesh on input 0 -- P, the capture's dist2, the tangent
  * frames -- is the same from cook to cook (Houdini tells by the attributes' data
