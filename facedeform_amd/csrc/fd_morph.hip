@@ -1042,6 +1042,13 @@ static int morph_init_common(fd_morph *m, int64_t N, int S, const float *rest, c
     if (!m) return FD_E_INVALID;
     if (N <= 0 || S < 0 || !rest || (S > 0 && !shapes)) { merr(m, "fd_morph_init: need N > 0, S >= 0 and the arrays"); return FD_E_INVALID; }
     if ((int64_t)S > 3 * N) { merr(m, "fd_morph_init: more blendshapes (%d) than rows (%lld)", S, (long long)(3 * N)); return FD_E_INVALID; }
+    // every launch's dynamic LDS within the 64 KB a kernel gets without asking for more: k_morph_weights 32 S bytes,
+    // k_qr_dots 32 (S - 1), k_morph_displace 4 S; the blocked form (S <= 256) 64 512 at most
+    static_assert(sizeof(double) * 4 * (size_t)FD_MORPH_MAX_SHAPES <= 65536, "k_morph_weights keeps [4][S] doubles in LDS");
+    if (S > FD_MORPH_MAX_SHAPES) {
+        merr(m, "fd_morph_init: %d blendshapes, at most %d (FD_MORPH_MAX_SHAPES) are supported", S, FD_MORPH_MAX_SHAPES);
+        return FD_E_INVALID;
+    }
     for (int s = 0; s < S; ++s)
         if (!shapes[s]) { merr(m, "fd_morph_init: shape %d is NULL", s); return FD_E_INVALID; }
     FDM_HIP(m, hipSetDevice(m->device));

@@ -1024,7 +1024,11 @@ int fd_capture_islands(fd_ctx *ctx, int64_t N, const float *P, const int64_t *of
  * stream over it once each (HBM-bound).
  *   fd_morph_init            DirectBSEdit::init (dbse.cpp:9-37): deltas
  *                            float(shape - rest) widened to fp64, Householder QR
- *                            in Eigen's packed form.  S <= 3N.  Synchronous.
+ *                            in Eigen's packed form.  S <= 3N and
+ *                            S <= FD_MORPH_MAX_SHAPES (the per-cook launches keep
+ *                            32 bytes of workgroup memory per blendshape, 64 KB in
+ *                            all); more is FD_E_INVALID before any device work and
+ *                            leaves the object as it was.  Synchronous.
  *   fd_morph_compute_weights_dev  computeWeights (dbse.cpp:39-60):
  *                            w_s = sum_i float(P_i - rest_i) * QRpacked[i][s]
  *   fd_morph_displace_dev    displaceVector + the loop at SOP :458-473:
@@ -1034,6 +1038,7 @@ int fd_capture_islands(fd_ctx *ctx, int64_t N, const float *P, const int64_t *of
  *   fd_morph_apply           both, on a host array in place; w_out (S) may be NULL.
  * hip_stream NULL = the object's own stream.  is_initialised / is_computed
  * mirror DirectBSEdit::isInitialized / isComputed, which the cook logic tests. */
+#define FD_MORPH_MAX_SHAPES 2048
 typedef struct fd_morph fd_morph;
 fd_morph *fd_morph_create(const fd_config *cfg);
 void fd_morph_destroy(fd_morph *m);

@@ -50,6 +50,10 @@ CASES = [  # N, S, F, own rest attribute
     (1, 1, 1, False), (1, 3, 2, False), (63, 5, 7, False), (63, 16, 16, True), (1000, 1, 32, False), (1000, 50, 17, False),
     (1000, 100, 20, True), (1000, 130, 32, False), (20_011, 5, 1, False), (20_011, 16, 2, True), (20_011, 50, 32, False),
     (20_011, 130, 20, False), (20_011, 100, 7, False),
+    # the edges of the 64-column groups and of the 8 / 16 / 32-frame tiles, the column-by-column factorisation (S > 256),
+    # rows an exact multiple of the one-frame weights' 2048; all of them exercise the clamp (checked with the oracle's weights)
+    (1000, 64, 8, False), (1000, 65, 9, False), (1000, 128, 8, False), (1000, 129, 9, False), (1000, 257, 16, False),
+    (1000, 300, 32, False), (2048, 16, 1, False),
 ]
 
 
