@@ -1241,13 +1241,29 @@ static int invert_host(fd_ctx *ctx, int64_t N, const float *Y, float *X_out, con
 }
 
 // ---- fillers of the shot launches' argument structs (fd_batch_deform_*shared*_dev below; templates, so outside the C linkage block) ----
-// the mesh part of a launch's arguments (Shared*Args and SharedVector*Args name these fields alike)
+// the mesh part of a launch's arguments (SharedDeformArgs, SharedEvalCommon and SharedVectorCommon name these fields alike)
 template <typename Args>
 static void fill_mesh(Args &a, int64_t N, const float *d_P_in, const float *d_dist2, const float *d_tu, const float *d_tv,
                       const float *d_nrm, float radius2, float falloffrate)
 {
     a.N = N; a.P_in = d_P_in; a.dist2 = d_dist2; a.tu = d_tu; a.tv = d_tv; a.nrm = d_nrm;
     a.radius2 = radius2; a.falloffrate = falloffrate;
+}
+
+// what the three staged position launches' arguments have in common (SharedEvalCommon), on the scratch shot_reserve gave
+static void fill_eval_common(SharedEvalCommon &a, const fd_batch *b, const ShotScratch &sc, int64_t N, const float *d_P_in,
+                             float *const *d_P_out, const float *d_dist2, float *const *d_falloff_out, const float *d_tu,
+                             const float *d_tv, const float *d_nrm, float radius2, float falloffrate)
+{
+    fill_mesh(a, N, d_P_in, d_dist2, d_tu, d_tv, d_nrm, radius2, falloffrate);
+    a.nF = b->n;
+    for (int i = 0; i < b->n; ++i) { a.model[i] = b->ctxs[i]->d_model; a.P_out[i] = d_P_out[i]; }
+    a.falloff_out = d_falloff_out;
+    a.delta_out = b->ctxs[0]->output == FD_OUTPUT_DISPLACEMENT;
+    a.max_wgs = b->eval_cus;
+    a.scratch = sc.d;
+    a.packed_ev = sc.consumed_ev;
+    if (b->h_mismatch && hipHostGetDevicePointer((void **)&a.mismatch, b->h_mismatch, 0) != hipSuccess) { (void)hipGetLastError(); a.mismatch = nullptr; }
 }
 
 // the vector tables of a SharedVector*Args
@@ -2443,22 +2459,16 @@ int fd_batch_deform_shared_fp64_dev(fd_batch *b, void *hip_stream, int64_t N, co
         return FD_OK;
     }
     Shared64Args a{};
-    fill_mesh(a, N, d_P_in, d_dist2, d_tu, d_tv, d_nrm, radius2, falloffrate);
-    a.M = c0->M; a.Mpad = round_up(c0->M, kRecPad); a.nF = b->n; a.kind = eval_kind(c0);
+    a.M = c0->M; a.Mpad = round_up(c0->M, kRecPad); a.kind = eval_kind(c0);
     const bool same_rig = one_build(b);
     for (int i = 0; i < b->n; ++i) {
         fd_ctx *c = b->ctxs[i];
-        a.rec64[i] = c->d_rec64; a.model[i] = c->d_model; a.P_out[i] = d_P_out[i];
+        a.rec64[i] = c->d_rec64;
         a.centres[i] = same_rig ? c0->d_centres : c->d_centres;       // (one batched build read one array: equal by construction)
     }
-    a.falloff_out = d_falloff_out;
-    a.delta_out = c0->output == FD_OUTPUT_DISPLACEMENT;
-    a.max_wgs = b->eval_cus;
-    const size_t bytes = shared64_scratch_bytes(a.Mpad, a.nF);
+    const size_t bytes = shared64_scratch_bytes(a.Mpad, b->n);
     if ((rc = shot_reserve(b, who, sc, bytes, stream))) return rc;
-    a.scratch = sc.d;
-    a.packed_ev = sc.consumed_ev;
-    if (b->h_mismatch && hipHostGetDevicePointer((void **)&a.mismatch, b->h_mismatch, 0) != hipSuccess) { (void)hipGetLastError(); a.mismatch = nullptr; }
+    fill_eval_common(a, b, sc, N, d_P_in, d_P_out, d_dist2, d_falloff_out, d_tu, d_tv, d_nrm, radius2, falloffrate);
     hipError_t e = launch_deform_shared64(a, stream);
     if (e != hipSuccess) { batch_err(b, "launch_deform_shared64 failed: %s", hipGetErrorString(e)); return FD_E_DEVICE; }
     shot_evaluated(sc, stream);
@@ -2549,18 +2559,12 @@ int fd_batch_deform_shared_ml_dev(fd_batch *b, void *hip_stream, int64_t N, cons
     ShotScratch &sc = b->sml;
     if ((rc = shot_begin(b, who, sc, stream))) return rc;
     SharedMlArgs a{};
-    fill_mesh(a, N, d_P_in, d_dist2, d_tu, d_tv, d_nrm, radius2, falloffrate);
-    a.M = c0->M; a.layers = ml_layers(c0); a.nF = b->n;
+    a.M = c0->M; a.layers = ml_layers(c0);
     a.check_rig = one_build(b) ? 0 : 1;                        // (one batched build read one array: equal by construction)
-    for (int i = 0; i < b->n; ++i) { a.rec32[i] = b->ctxs[i]->d_rec32; a.model[i] = b->ctxs[i]->d_model; a.P_out[i] = d_P_out[i]; }
-    a.falloff_out = d_falloff_out;
-    a.delta_out = c0->output == FD_OUTPUT_DISPLACEMENT;
-    a.max_wgs = b->eval_cus;
-    const size_t bytes = shared_ml_scratch_bytes(a.M, a.layers, a.nF);
+    for (int i = 0; i < b->n; ++i) a.rec32[i] = b->ctxs[i]->d_rec32;
+    const size_t bytes = shared_ml_scratch_bytes(a.M, a.layers, b->n);
     if ((rc = shot_reserve(b, who, sc, bytes, stream))) return rc;
-    a.scratch = sc.d;
-    a.packed_ev = sc.consumed_ev;
-    if (b->h_mismatch && hipHostGetDevicePointer((void **)&a.mismatch, b->h_mismatch, 0) != hipSuccess) { (void)hipGetLastError(); a.mismatch = nullptr; }
+    fill_eval_common(a, b, sc, N, d_P_in, d_P_out, d_dist2, d_falloff_out, d_tu, d_tv, d_nrm, radius2, falloffrate);
     hipError_t e = launch_deform_shared_ml(a, stream);
     if (e != hipSuccess) { batch_err(b, "launch_deform_shared_ml failed: %s", hipGetErrorString(e)); return FD_E_DEVICE; }
     shot_evaluated(sc, stream);
@@ -2656,18 +2660,12 @@ int fd_batch_deform_shared_ml_fp64_dev(fd_batch *b, void *hip_stream, int64_t N,
     ShotScratch &sc = b->sml64;
     if ((rc = shot_begin(b, who, sc, stream))) return rc;
     SharedMl64Args a{};
-    fill_mesh(a, N, d_P_in, d_dist2, d_tu, d_tv, d_nrm, radius2, falloffrate);
-    a.M = c0->M; a.layers = ml_layers(c0); a.nF = b->n;
+    a.M = c0->M; a.layers = ml_layers(c0);
     a.check_rig = one_build(b) ? 0 : 1;                        // (one batched build read one array: equal by construction)
-    for (int i = 0; i < b->n; ++i) { a.rec64[i] = b->ctxs[i]->d_rec64; a.model[i] = b->ctxs[i]->d_model; a.P_out[i] = d_P_out[i]; }
-    a.falloff_out = d_falloff_out;
-    a.delta_out = c0->output == FD_OUTPUT_DISPLACEMENT;
-    a.max_wgs = b->eval_cus;
-    const size_t bytes = shared_ml64_scratch_bytes(a.M, a.layers, a.nF);
+    for (int i = 0; i < b->n; ++i) a.rec64[i] = b->ctxs[i]->d_rec64;
+    const size_t bytes = shared_ml64_scratch_bytes(a.M, a.layers, b->n);
     if ((rc = shot_reserve(b, who, sc, bytes, stream))) return rc;
-    a.scratch = sc.d;
-    a.packed_ev = sc.consumed_ev;
-    if (b->h_mismatch && hipHostGetDevicePointer((void **)&a.mismatch, b->h_mismatch, 0) != hipSuccess) { (void)hipGetLastError(); a.mismatch = nullptr; }
+    fill_eval_common(a, b, sc, N, d_P_in, d_P_out, d_dist2, d_falloff_out, d_tu, d_tv, d_nrm, radius2, falloffrate);
     hipError_t e = launch_deform_shared_ml64(a, stream);
     if (e != hipSuccess) { batch_err(b, "launch_deform_shared_ml64 failed: %s", hipGetErrorString(e)); return FD_E_DEVICE; }
     shot_evaluated(sc, stream);

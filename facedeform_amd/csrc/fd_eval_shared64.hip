@@ -7,10 +7,8 @@
 // top of the fp64 affine part, ONE rounding of the three sums to fp32, then epilogue_store.  Only the order of the fp64
 // summation differs (four centres per matrix instruction, the affine part as one more K = 4 step).
 //
-// Those pieces are fd_eval.hip's own: that file is included below as text, in a namespace of this translation unit and with
-// the launch macro switched off, so that none of its kernel templates is instantiated a second time and its host
-// functions compile to nothing -- what remains are phi64 / fast_log_pos, EvalParams and epilogue_store, the very code
-// the one-frame launch runs, with no second copy to keep in step.
+// Those pieces -- phi64 / fast_log_pos, EvalParams and epilogue_store -- are fd_eval_point.h's: the very code the one-frame
+// launch runs, with no second copy to keep in step.  The host side of the launch is fd_shot_launch.h's.
 //
 // Two kernels:
 //   k_pack_shared64  the only reader of the contexts' models.  Writes, into scratch of the batch that nothing else uses:
@@ -36,27 +34,9 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include <algorithm>
-#include <type_traits>
-
-#include "fd_eval_common.h"
+#include "fd_eval_point.h"
 #include "fd_shared64.h"
-
-#pragma push_macro("hipLaunchKernelGGL")
-#undef hipLaunchKernelGGL
-#define hipLaunchKernelGGL(...) ((void)0)
-// (its launch_deform calls itself by an unqualified name, which argument-dependent lookup would also find in fd::)
-#pragma push_macro("launch_deform")
-#define launch_deform launch_deform_unused
-namespace fd {
-namespace {
-namespace one_frame {
-#include "fd_eval.hip"
-}  // namespace one_frame
-}  // namespace
-}  // namespace fd
-#pragma pop_macro("launch_deform")
-#pragma pop_macro("hipLaunchKernelGGL")
+#include "fd_shot_launch.h"
 
 namespace fd {
 
@@ -65,6 +45,7 @@ namespace {
 constexpr int kS64VT = 2;                                 // vertex tiles per wave
 constexpr int kS64Group = 16 * kS64VT * kS64Waves;        // vertices per workgroup and group
 constexpr int kS64PackThreads = 256;
+static_assert(kS64Threads == kShotThreads, "launch_shot's workgroup");
 
 // (the scratch layout, S64Head, s64_tiles and s64_row: fd_shared64.h, shared with the vector launch)
 
@@ -132,16 +113,10 @@ __global__ __launch_bounds__(kS64PackThreads) void k_pack_shared64(const S64Pack
     }
 }
 
-struct S64Params {
-    int64_t N;
-    const float *P_in, *dist2;
-    const float *tu, *tv, *nrm;
-    float radius2, falloffrate;
+struct S64Params : ShotEvalMesh {
     int nF, nks, kchunk, delta, Mpad;
     const double *scratch;
 };
-
-using one_frame::fd::EvalParams;
 
 template <int KIND, int NT, bool DENSE>
 __global__ __launch_bounds__(kS64Threads) void k_deform64_shared(const S64Params p, int ngroups)
@@ -219,7 +194,7 @@ __global__ __launch_bounds__(kS64Threads) void k_deform64_shared(const S64Params
                     const double dy = (double)pf[t][1] - c01[1];
                     const double dz = (double)pf[t][2] - c23[0];
                     const double d2 = fma(dz, dz, fma(dy, dy, dx * dx));
-                    ph[t] = one_frame::fd::phi64<KIND>(d2, c23[1]);
+                    ph[t] = phi64<KIND>(d2, c23[1]);
                 }
                 const double *wk = s_w + (size_t)ks * NT * 64 + lane;
 #pragma unroll
@@ -248,16 +223,9 @@ __global__ __launch_bounds__(kS64Threads) void k_deform64_shared(const S64Params
                     }
                     return;
                 }
-                EvalParams ep;
-                ep.N = p.N;
-                ep.P_in = p.P_in; ep.P_out = out;
-                ep.dist2 = p.dist2; ep.falloff_out = s_head->fall[f];
-                ep.tu = p.tu; ep.tv = p.tv; ep.nrm = p.nrm;
-                ep.radius2 = p.radius2; ep.falloffrate = p.falloffrate;
-                ep.Mpad = p.Mpad; ep.delta = p.delta;
-                ep.rec32 = nullptr; ep.rec64 = nullptr; ep.tiles = nullptr; ep.tiles16 = nullptr; ep.model = nullptr;
+                const EvalParams ep = shot_eval_params(p, out, s_head->fall[f], p.Mpad, p.delta);
                 float disp[3] = {(float)a0, (float)a1, (float)a2};           // the ONE rounding
-                one_frame::fd::epilogue_store(ep, i, pos, disp, d2v[t]);
+                epilogue_store(ep, i, pos, disp, d2v[t]);
             };
             if constexpr (DENSE) {
 #pragma unroll
@@ -275,26 +243,9 @@ __global__ __launch_bounds__(kS64Threads) void k_deform64_shared(const S64Params
 }
 
 template <int KIND>
-hipError_t launch_kind64(const S64Params &p, int NT, bool dense, unsigned grid, size_t lds, int ngroups, hipStream_t stream)
+hipError_t launch_kind64(const S64Params &p, int NT, bool dense, const ShotGrid &gr, hipStream_t stream)
 {
-#define FD_S64_CASE(NTV, DNS)                                                                                            \
-    {                                                                                                                    \
-        static LdsAttrOnce once;                                                                                         \
-        hipError_t e = once.ensure((const void *)k_deform64_shared<KIND, NTV, DNS>, 160 * 1024);                         \
-        if (e != hipSuccess) return e;                                                                                   \
-        hipLaunchKernelGGL((k_deform64_shared<KIND, NTV, DNS>), dim3(grid), dim3(kS64Threads), lds, stream, p, ngroups); \
-        return hipGetLastError();                                                                                        \
-    }
-    if (dense) {
-        if (NT == 3) FD_S64_CASE(3, true)
-        if (NT == 6) FD_S64_CASE(6, true)
-    } else {
-        if (NT == 1) FD_S64_CASE(1, false)
-        if (NT == 2) FD_S64_CASE(2, false)
-        if (NT == 3) FD_S64_CASE(3, false)
-    }
-#undef FD_S64_CASE
-    return hipErrorInvalidValue;
+    return for_tiles(NT, dense, [&](auto nt, auto dns) { return launch_shot<k_deform64_shared<KIND, nt.value, dns.value>>(gr, stream, p); });
 }
 
 }  // namespace
@@ -314,42 +265,29 @@ hipError_t launch_deform_shared64(const Shared64Args &a, hipStream_t stream)
     const int nks = a.Mpad / 4;
 
     S64PackArgs pa{};
-    for (int f = 0; f < a.nF; ++f) {
-        pa.rec[f] = a.rec64[f]; pa.model[f] = a.model[f]; pa.centres[f] = a.centres[f];
-        pa.P_out[f] = a.P_out[f]; pa.fall[f] = a.falloff_out ? a.falloff_out[f] : nullptr;
-    }
+    fill_pack(pa, a, a.rec64);
+    for (int f = 0; f < a.nF; ++f) pa.centres[f] = a.centres[f];
     const size_t nthreads = (size_t)64 * kMaxBatch + (size_t)NT * 64 + (size_t)a.Mpad * 4 + (size_t)nks * NT * 64;
     const unsigned pgrid = (unsigned)((nthreads + kS64PackThreads - 1) / kS64PackThreads);
     hipLaunchKernelGGL(k_pack_shared64, dim3(pgrid), dim3(kS64PackThreads), 0, stream, pa, (double *)a.scratch, a.nF, a.M, a.Mpad, NT,
                        dense ? 1 : 0, a.mismatch);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    // from here on nothing of the contexts is read
-    if (a.packed_ev && (e = hipEventRecord(a.packed_ev, stream)) != hipSuccess) return e;
+    if (hipError_t e = shot_packed(a, stream); e != hipSuccess) return e;
 
     S64Params p{};
-    p.N = a.N; p.P_in = a.P_in; p.dist2 = a.dist2; p.tu = a.tu; p.tv = a.tv; p.nrm = a.nrm;
-    p.radius2 = a.radius2; p.falloffrate = a.falloffrate;
+    fill_eval_mesh(p, a);
     p.nF = a.nF; p.nks = nks; p.delta = a.delta_out; p.Mpad = a.Mpad;
     p.scratch = (const double *)a.scratch;
     const size_t fixed = 8 * s64_cen_at(NT);
     const size_t per_ks = 8 * (16 + (size_t)NT * 64);
-    const int kmax = (int)((kS64LdsBudget - fixed) / per_ks);
-    const int nchunks = (nks + kmax - 1) / kmax;
-    p.kchunk = (nks + nchunks - 1) / nchunks;           // even chunks: 256 centres x 32 frames are two of 32 K steps
-    const size_t lds = fixed + per_ks * (size_t)p.kchunk;
-    const int64_t ngroups = (a.N + kS64Group - 1) / kS64Group;
-    if (ngroups > 0x7fffffff) return hipErrorInvalidValue;
-    // persistent workgroups: as many per CU as the LDS admits, two at most
-    const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(2, (int64_t)(160 * 1024 / lds)));
-    const int64_t max_wgs = a.max_wgs > 0 ? (a.max_wgs < 4096 ? a.max_wgs : 4096) : (int64_t)device_cus() * per_cu;
-    const unsigned grid = (unsigned)(ngroups < max_wgs ? ngroups : max_wgs);
+    p.kchunk = even_chunks(nks, (int)((kS64LdsBudget - fixed) / per_ks));
+    ShotGrid gr;          // two workgroups per CU at most
+    if (hipError_t e = shot_grid(a.N, kS64Group, a.max_wgs, fixed + per_ks * (size_t)p.kchunk, 2, gr); e != hipSuccess) return e;
     switch (a.kind) {
     case FD_KERNEL_GAUSSIAN:
-    case FD_KERNEL_GAUSSIAN_QNN: return launch_kind64<FD_KERNEL_GAUSSIAN>(p, NT, dense, grid, lds, (int)ngroups, stream);
-    case FD_KERNEL_THIN_PLATE: return launch_kind64<FD_KERNEL_THIN_PLATE>(p, NT, dense, grid, lds, (int)ngroups, stream);
-    case FD_KERNEL_BIHARMONIC: return launch_kind64<FD_KERNEL_BIHARMONIC>(p, NT, dense, grid, lds, (int)ngroups, stream);
-    case FD_KERNEL_CUBIC: return launch_kind64<FD_KERNEL_CUBIC>(p, NT, dense, grid, lds, (int)ngroups, stream);
+    case FD_KERNEL_GAUSSIAN_QNN: return launch_kind64<FD_KERNEL_GAUSSIAN>(p, NT, dense, gr, stream);
+    case FD_KERNEL_THIN_PLATE: return launch_kind64<FD_KERNEL_THIN_PLATE>(p, NT, dense, gr, stream);
+    case FD_KERNEL_BIHARMONIC: return launch_kind64<FD_KERNEL_BIHARMONIC>(p, NT, dense, gr, stream);
+    case FD_KERNEL_CUBIC: return launch_kind64<FD_KERNEL_CUBIC>(p, NT, dense, gr, stream);
     default: return hipErrorInvalidValue;
     }
 }

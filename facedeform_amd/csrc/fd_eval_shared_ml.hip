@@ -17,8 +17,8 @@
 //     would quadruple the relative error per layer.
 //   * The model never fits LDS at the sizes that matter (M = 256 x 4 layers x 32 frames: 400 KiB), so it is staged in
 //     chunks of K blocks with the accumulators kept live across them: the normal case here.
-//   * The epilogue is the one-frame launch's own epilogue_store (fd_eval.hip, included below as text the way
-//     fd_eval_shared64.hip does): gate, tangent projection, fall-off and the stores are the very code fd_deform_dev runs.
+//   * The epilogue is the one-frame launch's own epilogue_store (fd_eval_point.h): gate, tangent projection, fall-off and
+//     the stores are the very code fd_deform_dev runs.
 //   * One pack kernel, the only reader of the contexts' models, into scratch of the batch that nothing else uses.
 // No floating-point atomics; a vertex's bits depend on its own column of its own matrix instructions only -- not on its
 // place in the launch, nor on the number of workgroups.  Built with -ffp-contract=off and -fno-slp-vectorize like
@@ -26,26 +26,10 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include <type_traits>
-
-#include "fd_eval_common.h"
+#include "fd_eval_point.h"
 #include "fd_shared_common.h"
 #include "fd_shared_ml.h"
-
-#pragma push_macro("hipLaunchKernelGGL")
-#undef hipLaunchKernelGGL
-#define hipLaunchKernelGGL(...) ((void)0)
-#pragma push_macro("launch_deform")
-#define launch_deform launch_deform_unused
-namespace fd {
-namespace {
-namespace one_frame {
-#include "fd_eval.hip"
-}  // namespace one_frame
-}  // namespace
-}  // namespace fd
-#pragma pop_macro("launch_deform")
-#pragma pop_macro("hipLaunchKernelGGL")
+#include "fd_shot_launch.h"
 
 namespace fd {
 
@@ -55,6 +39,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kMlWaves = 8;                       // two per SIMD, 64 vertices (two vertex tiles of 32) each per group
 constexpr int kMlThreads = 64 * kMlWaves;
+static_assert(kMlThreads == kShotThreads, "launch_shot's workgroup");
 constexpr int kMlGroup = 64 * kMlWaves;           // vertices per workgroup and group
 
 // (the scratch layout -- kMlNormAt, kMlPolyAt, ml_rec_at, ml_w_at, ml_w16, ml_tiles, ml_share -- and kMlMinFrames are
@@ -62,7 +47,7 @@ constexpr int kMlGroup = 64 * kMlWaves;           // vertices per workgroup and 
 constexpr int ml_tile_frames(int nt) { return 32 * nt / 3; }           // frames whose three rows fit nt tiles
 
 struct MlPackArgs {
-    const Rec32 *rec32[kMaxBatch];
+    const Rec32 *rec[kMaxBatch];
     const DevModel *model[kMaxBatch];
     float *P_out[kMaxBatch];
     float *fall[kMaxBatch];
@@ -82,7 +67,7 @@ __global__ __launch_bounds__(256) void k_pack_shared_ml(const MlPackArgs a, uint
         // its weights are zero.
         const int r = 32 * kb + tid;
         scratch[ml_rec_at(NT) + (size_t)kb * 32 + tid] =
-            r < a.nrec ? *reinterpret_cast<const uint4 *>(&a.rec32[0][r]) : make_uint4(0u, 0u, 0u, 0u);
+            r < a.nrec ? *reinterpret_cast<const uint4 *>(&a.rec[0][r]) : make_uint4(0u, 0u, 0u, 0u);
     }
     // per-frame scale: the largest |weight| or |polynomial coefficient| (left in the model by the build's packing code) to
     // [2^13, 2^14); 8 lanes per frame
@@ -90,10 +75,10 @@ __global__ __launch_bounds__(256) void k_pack_shared_ml(const MlPackArgs a, uint
     {
         const int f = tid >> 3, l = tid & 7;
         bool same = true;
-        if (kb == 0 && T == 0 && a.check_rig && f > 0 && f < a.nF && a.rec32[f] != a.rec32[0]) {
+        if (kb == 0 && T == 0 && a.check_rig && f > 0 && f < a.nF && a.rec[f] != a.rec[0]) {
             bool diff = false;
             for (int r = l; r < a.nrec; r += 8) {
-                const uint4 x = *reinterpret_cast<const uint4 *>(&a.rec32[f][r]), y = *reinterpret_cast<const uint4 *>(&a.rec32[0][r]);
+                const uint4 x = *reinterpret_cast<const uint4 *>(&a.rec[f][r]), y = *reinterpret_cast<const uint4 *>(&a.rec[0][r]);
                 diff |= x.x != y.x || x.y != y.y || x.z != y.z || x.w != y.w;
             }
             same = !diff;
@@ -136,7 +121,7 @@ __global__ __launch_bounds__(256) void k_pack_shared_ml(const MlPackArgs a, uint
         const int r = 32 * kb + 8 * (2 * s + (m >> 2)) + 4 * h + (m & 3);
         float w = 0.f;
         if (live && r < a.nrec) {
-            const Rec32 &q = a.rec32[f][r];
+            const Rec32 &q = a.rec[f][r];
             w = (c == 0 ? q.wx : (c == 1 ? q.wy : q.wz)) * sc;
         }
         const _Float16 hh = (_Float16)w;
@@ -164,16 +149,10 @@ __global__ __launch_bounds__(256) void k_pack_shared_ml(const MlPackArgs a, uint
     }
 }
 
-struct MlParams {
-    int64_t N;
-    const float *P_in, *dist2;
-    const float *tu, *tv, *nrm;
-    float radius2, falloffrate;
+struct MlParams : ShotEvalMesh {
     int nF, nkb, kchunk, delta, Mpad;
     const uint4 *scratch;
 };
-
-using one_frame::fd::EvalParams;
 
 // NT row tiles of 32 (up to 10, 21, 32 frames); SHARE consecutive records are layers of one centre
 template <int NT, int SHARE>
@@ -352,35 +331,19 @@ void k_deform32_shared_ml(const MlParams p, int ngroups)
                 else if (fr.P_out != p.P_in) store_pos3(dstP, pos[0], pos[1], pos[2]);
                 continue;
             }
-            EvalParams ep;
-            ep.N = p.N;
-            ep.P_in = p.P_in; ep.P_out = fr.P_out;
-            ep.dist2 = p.dist2; ep.falloff_out = fr.falloff_out;
-            ep.tu = p.tu; ep.tv = p.tv; ep.nrm = p.nrm;
-            ep.radius2 = p.radius2; ep.falloffrate = p.falloffrate;
-            ep.Mpad = p.Mpad; ep.delta = p.delta;
-            ep.rec32 = nullptr; ep.rec64 = nullptr; ep.tiles = nullptr; ep.tiles16 = nullptr; ep.model = nullptr;
+            const EvalParams ep = shot_eval_params(p, fr.P_out, fr.falloff_out, p.Mpad, p.delta);
             float disp[3] = {row_of(f, 0) * fr.inv_scale, row_of(f, 1) * fr.inv_scale, row_of(f, 2) * fr.inv_scale};    // 2^-k is exact
-            one_frame::fd::epilogue_store(ep, i, pos, disp, own_d2);
+            epilogue_store(ep, i, pos, disp, own_d2);
         }
     }
 }
 
 template <int NT>
-hipError_t launch_ml_share(const MlParams &p, int share, unsigned grid, size_t lds, int ngroups, hipStream_t stream)
+hipError_t launch_ml_share(const MlParams &p, int share, const ShotGrid &gr, hipStream_t stream)
 {
-#define FD_ML_CASE(SH)                                                                                                   \
-    {                                                                                                                    \
-        static LdsAttrOnce once;                                                                                         \
-        hipError_t e = once.ensure((const void *)k_deform32_shared_ml<NT, SH>, 160 * 1024);                              \
-        if (e != hipSuccess) return e;                                                                                   \
-        hipLaunchKernelGGL((k_deform32_shared_ml<NT, SH>), dim3(grid), dim3(kMlThreads), lds, stream, p, ngroups);       \
-        return hipGetLastError();                                                                                        \
-    }
-    if (share == 4) FD_ML_CASE(4)
-    if (share == 2) FD_ML_CASE(2)
-    FD_ML_CASE(1)
-#undef FD_ML_CASE
+    if (share == 4) return launch_shot<k_deform32_shared_ml<NT, 4>>(gr, stream, p);
+    if (share == 2) return launch_shot<k_deform32_shared_ml<NT, 2>>(gr, stream, p);
+    return launch_shot<k_deform32_shared_ml<NT, 1>>(gr, stream, p);
 }
 
 }  // namespace
@@ -410,37 +373,24 @@ hipError_t launch_deform_shared_ml(const SharedMlArgs &a, hipStream_t stream)
     const int nrec = a.M * a.layers, nkb = (nrec + 31) / 32, NT = ml_tiles(a.nF);
 
     MlPackArgs pa{};
-    for (int f = 0; f < a.nF; ++f) {
-        pa.rec32[f] = a.rec32[f]; pa.model[f] = a.model[f];
-        pa.P_out[f] = a.P_out[f]; pa.fall[f] = a.falloff_out ? a.falloff_out[f] : nullptr;
-    }
+    fill_pack(pa, a, a.rec32);
     pa.nF = a.nF; pa.nrec = nrec; pa.check_rig = a.check_rig; pa.mismatch = a.mismatch;
     hipLaunchKernelGGL(k_pack_shared_ml, dim3(nkb, NT), dim3(256), 0, stream, pa, (uint4 *)a.scratch);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    // from here on nothing of the contexts is read
-    if (a.packed_ev && (e = hipEventRecord(a.packed_ev, stream)) != hipSuccess) return e;
+    if (hipError_t e = shot_packed(a, stream); e != hipSuccess) return e;
 
     MlParams p{};
-    p.N = a.N; p.P_in = a.P_in; p.dist2 = a.dist2; p.tu = a.tu; p.tv = a.tv; p.nrm = a.nrm;
-    p.radius2 = a.radius2; p.falloffrate = a.falloffrate;
+    fill_eval_mesh(p, a);
     p.nF = a.nF; p.nkb = nkb; p.delta = a.delta_out; p.Mpad = round_up(nrec, kRecPad);
     p.scratch = (const uint4 *)a.scratch;
     const size_t fixed = sizeof(SharedFrame) * (size_t)kMaxBatch + (size_t)NT * 64 * 16;
     const size_t per_kb = 32 * 16 + ml_w16(NT) * 16;
-    const int kmax = (int)((kSharedLdsBudget - fixed) / per_kb);
-    const int nchunks = (nkb + kmax - 1) / kmax;
-    p.kchunk = (nkb + nchunks - 1) / nchunks;           // even chunks
-    const size_t lds = fixed + per_kb * (size_t)p.kchunk;
-    const int64_t ngroups = (a.N + kMlGroup - 1) / kMlGroup;
-    if (ngroups > 0x7fffffff) return hipErrorInvalidValue;
-    // one persistent workgroup per CU (two 256-register waves per SIMD); a.max_wgs: fd_batch_set_eval_cus
-    const int64_t max_wgs = a.max_wgs > 0 ? (a.max_wgs < 4096 ? a.max_wgs : 4096) : (int64_t)device_cus();
-    const unsigned grid = (unsigned)(ngroups < max_wgs ? ngroups : max_wgs);
+    p.kchunk = even_chunks(nkb, (int)((kSharedLdsBudget - fixed) / per_kb));
+    ShotGrid gr;          // one persistent workgroup per CU (two 256-register waves per SIMD)
+    if (hipError_t e = shot_grid(a.N, kMlGroup, a.max_wgs, fixed + per_kb * (size_t)p.kchunk, 1, gr); e != hipSuccess) return e;
     const int share = ml_share(a.layers);
-    if (NT == 1) return launch_ml_share<1>(p, share, grid, lds, (int)ngroups, stream);
-    if (NT == 2) return launch_ml_share<2>(p, share, grid, lds, (int)ngroups, stream);
-    return launch_ml_share<3>(p, share, grid, lds, (int)ngroups, stream);
+    if (NT == 1) return launch_ml_share<1>(p, share, gr, stream);
+    if (NT == 2) return launch_ml_share<2>(p, share, gr, stream);
+    return launch_ml_share<3>(p, share, gr, stream);
 }
 
 }  // namespace fd

@@ -6,8 +6,8 @@
 // reused as they are.
 //
 // Definition: k_deform64's (fd_eval.hip) on the multilayer records, per frame -- the same d2 expression on raw coordinates,
-// fp64 accumulation on top of the fp64 affine part, ONE rounding of the three sums to fp32, then epilogue_store (that file
-// included below as text, as fd_eval_shared64.hip does) -- but for
+// fp64 accumulation on top of the fp64 affine part, ONE rounding of the three sums to fp32, then epilogue_store (both
+// fd_eval_point.h's, the one-frame launch's own code) -- but for
 //   * the order of the fp64 summation (four centres of one layer per matrix instruction, the affine part as one more
 //     K = 4 step), and
 //   * ONE exponential per centre and chain, not per record: the layers of a centre share d2, and R_l = R / 2^l makes
@@ -37,27 +37,10 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include <algorithm>
-#include <type_traits>
-
-#include "fd_eval_common.h"
+#include "fd_eval_point.h"
 #include "fd_shared64.h"
 #include "fd_shared_ml64.h"
-
-#pragma push_macro("hipLaunchKernelGGL")
-#undef hipLaunchKernelGGL
-#define hipLaunchKernelGGL(...) ((void)0)
-#pragma push_macro("launch_deform")
-#define launch_deform launch_deform_unused
-namespace fd {
-namespace {
-namespace one_frame {
-#include "fd_eval.hip"
-}  // namespace one_frame
-}  // namespace
-}  // namespace fd
-#pragma pop_macro("launch_deform")
-#pragma pop_macro("hipLaunchKernelGGL")
+#include "fd_shot_launch.h"
 
 namespace fd {
 
@@ -145,16 +128,10 @@ __global__ __launch_bounds__(kMl64PackThreads) void k_pack_shared_ml64(const Ml6
     }
 }
 
-struct Ml64Params {
-    int64_t N;
-    const float *P_in, *dist2;
-    const float *tu, *tv, *nrm;
-    float radius2, falloffrate;
+struct Ml64Params : ShotEvalMesh {
     int nF, nkc, kchunk, L, delta, Mpad, Mc4;
     const double *scratch;
 };
-
-using one_frame::fd::EvalParams;
 
 template <int NT, bool DENSE>
 __global__ __launch_bounds__(kS64Threads) void k_deform64_shared_ml(const Ml64Params p, int ngroups)
@@ -241,7 +218,7 @@ __global__ __launch_bounds__(kS64Threads) void k_deform64_shared_ml(const Ml64Pa
                     const double sc = l0 == 0 ? c2s[1] : s4p[0];
                     double E[kMl64VT];
 #pragma unroll
-                    for (int t = 0; t < kMl64VT; ++t) E[t] = one_frame::fd::phi64<FD_KERNEL_GAUSSIAN>(d2[t], sc);
+                    for (int t = 0; t < kMl64VT; ++t) E[t] = phi64<FD_KERNEL_GAUSSIAN>(d2[t], sc);
                     const int lend = L - l0 < kMl64Restart ? L : l0 + kMl64Restart;
                     for (int l = l0; l < lend; ++l) {
 #pragma unroll
@@ -278,16 +255,9 @@ __global__ __launch_bounds__(kS64Threads) void k_deform64_shared_ml(const Ml64Pa
                     }
                     return;
                 }
-                EvalParams ep;
-                ep.N = p.N;
-                ep.P_in = p.P_in; ep.P_out = out;
-                ep.dist2 = p.dist2; ep.falloff_out = s_head->fall[f];
-                ep.tu = p.tu; ep.tv = p.tv; ep.nrm = p.nrm;
-                ep.radius2 = p.radius2; ep.falloffrate = p.falloffrate;
-                ep.Mpad = p.Mpad; ep.delta = p.delta;
-                ep.rec32 = nullptr; ep.rec64 = nullptr; ep.tiles = nullptr; ep.tiles16 = nullptr; ep.model = nullptr;
+                const EvalParams ep = shot_eval_params(p, out, s_head->fall[f], p.Mpad, p.delta);
                 float disp[3] = {(float)a0, (float)a1, (float)a2};           // the ONE rounding
-                one_frame::fd::epilogue_store(ep, i, pos, disp, d2v[t]);
+                epilogue_store(ep, i, pos, disp, d2v[t]);
             };
             if constexpr (DENSE) {
 #pragma unroll
@@ -302,28 +272,6 @@ __global__ __launch_bounds__(kS64Threads) void k_deform64_shared_ml(const Ml64Pa
             }
         }
     }
-}
-
-hipError_t launch_ml64(const Ml64Params &p, int NT, bool dense, unsigned grid, size_t lds, int ngroups, hipStream_t stream)
-{
-#define FD_ML64_CASE(NTV, DNS)                                                                                          \
-    {                                                                                                                   \
-        static LdsAttrOnce once;                                                                                        \
-        hipError_t e = once.ensure((const void *)k_deform64_shared_ml<NTV, DNS>, 160 * 1024);                           \
-        if (e != hipSuccess) return e;                                                                                  \
-        hipLaunchKernelGGL((k_deform64_shared_ml<NTV, DNS>), dim3(grid), dim3(kS64Threads), lds, stream, p, ngroups);   \
-        return hipGetLastError();                                                                                       \
-    }
-    if (dense) {
-        if (NT == 3) FD_ML64_CASE(3, true)
-        if (NT == 6) FD_ML64_CASE(6, true)
-    } else {
-        if (NT == 1) FD_ML64_CASE(1, false)
-        if (NT == 2) FD_ML64_CASE(2, false)
-        if (NT == 3) FD_ML64_CASE(3, false)
-    }
-#undef FD_ML64_CASE
-    return hipErrorInvalidValue;
 }
 
 }  // namespace
@@ -355,37 +303,24 @@ hipError_t launch_deform_shared_ml64(const SharedMl64Args &a, hipStream_t stream
     const int Mc4 = round_up(a.M, 4), nkc = Mc4 / 4, L = a.layers;
 
     Ml64PackArgs pa{};
-    for (int f = 0; f < a.nF; ++f) {
-        pa.rec[f] = a.rec64[f]; pa.model[f] = a.model[f];
-        pa.P_out[f] = a.P_out[f]; pa.fall[f] = a.falloff_out ? a.falloff_out[f] : nullptr;
-    }
+    fill_pack(pa, a, a.rec64);
     const size_t nthreads = (size_t)64 * kMaxBatch + (size_t)NT * 64 + (size_t)Mc4 * kMl64Cen + (size_t)nkc * ml64_step_w(NT, L);
     const unsigned pgrid = (unsigned)((nthreads + kMl64PackThreads - 1) / kMl64PackThreads);
     hipLaunchKernelGGL(k_pack_shared_ml64, dim3(pgrid), dim3(kMl64PackThreads), 0, stream, pa, (double *)a.scratch, a.nF, a.M, L, Mc4, NT,
                        dense ? 1 : 0, a.check_rig, a.mismatch);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    // from here on nothing of the contexts is read
-    if (a.packed_ev && (e = hipEventRecord(a.packed_ev, stream)) != hipSuccess) return e;
+    if (hipError_t e = shot_packed(a, stream); e != hipSuccess) return e;
 
     Ml64Params p{};
-    p.N = a.N; p.P_in = a.P_in; p.dist2 = a.dist2; p.tu = a.tu; p.tv = a.tv; p.nrm = a.nrm;
-    p.radius2 = a.radius2; p.falloffrate = a.falloffrate;
+    fill_eval_mesh(p, a);
     p.nF = a.nF; p.nkc = nkc; p.L = L; p.delta = a.delta_out; p.Mpad = round_up(a.M * L, kRecPad); p.Mc4 = Mc4;
     p.scratch = (const double *)a.scratch;
     const size_t fixed = 8 * ml64_cen_at(NT);
     const size_t per_kc = 8 * ((size_t)4 * kMl64Cen + ml64_step_w(NT, L));
-    const int kmax = (int)((kS64LdsBudget - fixed) / per_kc);         // >= 6: 8 layers x 6 tiles are 24.2 KiB a step
-    const int nchunks = (nkc + kmax - 1) / kmax;
-    p.kchunk = (nkc + nchunks - 1) / nchunks;           // even chunks of whole centre steps
-    const size_t lds = fixed + per_kc * (size_t)p.kchunk;
-    const int64_t ngroups = (a.N + kMl64Group - 1) / kMl64Group;
-    if (ngroups > 0x7fffffff) return hipErrorInvalidValue;
-    // persistent workgroups: as many per CU as the LDS admits, two at most
-    const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(2, (int64_t)(160 * 1024 / lds)));
-    const int64_t max_wgs = a.max_wgs > 0 ? (a.max_wgs < 4096 ? a.max_wgs : 4096) : (int64_t)device_cus() * per_cu;
-    const unsigned grid = (unsigned)(ngroups < max_wgs ? ngroups : max_wgs);
-    return launch_ml64(p, NT, dense, grid, lds, (int)ngroups, stream);
+    // even chunks of whole centre steps; kmax >= 6: 8 layers x 6 tiles are 24.2 KiB a step
+    p.kchunk = even_chunks(nkc, (int)((kS64LdsBudget - fixed) / per_kc));
+    ShotGrid gr;          // two workgroups per CU at most
+    if (hipError_t e = shot_grid(a.N, kMl64Group, a.max_wgs, fixed + per_kc * (size_t)p.kchunk, 2, gr); e != hipSuccess) return e;
+    return for_tiles(NT, dense, [&](auto nt, auto dns) { return launch_shot<k_deform64_shared_ml<nt.value, dns.value>>(gr, stream, p); });
 }
 
 }  // namespace fd

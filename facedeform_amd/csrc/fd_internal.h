@@ -350,23 +350,29 @@ struct SharedVectorArgs : SharedVectorCommon {
 };
 hipError_t launch_vectors_shared(const SharedVectorArgs &a, hipStream_t stream);
 const char *shared_vectors_kernel_name(int Mpad, int nF, int kind);
-// Every frame of a shared-rig batch in fp64 by one matrix-pipe launch (fd_eval_shared64.hip, fd_batch_deform_shared_fp64_dev):
-// a pack kernel copies what the launch needs of the models into `scratch` (shared64_scratch_bytes; packed_ev is recorded
-// behind it, may be null), the evaluation reads only that copy.
-struct Shared64Args {
+// What the arguments of the three staged shot evaluations have in common (fd_eval_shared64.hip, fd_eval_shared_ml.hip,
+// fd_eval_shared_ml64.hip; fd_shot_launch.h fills the kernels' arguments from it): the mesh, the frames' models and outputs, the
+// scratch the pack kernel fills and what the launch reports.
+struct SharedEvalCommon {
     int64_t N;
     const float *P_in, *dist2, *tu, *tv, *nrm;
     float radius2, falloffrate;
-    int M, Mpad, nF, kind;                // kind: any but the multilayer model's
-    const Rec64 *rec64[kMaxBatch];
+    int nF;
     const DevModel *model[kMaxBatch];
-    const double *centres[kMaxBatch];     // compared with entry 0 by content unless equal to it by address; a frame that differs is passed through
     float *P_out[kMaxBatch];
     float *const *falloff_out;            // nF entries or nullptr
     void *scratch;
-    hipEvent_t packed_ev;
+    hipEvent_t packed_ev;                 // as SharedDeformArgs::packed_ev
     int delta_out, max_wgs;
     int *mismatch;                        // as SharedDeformArgs::mismatch
+};
+// Every frame of a shared-rig batch in fp64 by one matrix-pipe launch (fd_eval_shared64.hip, fd_batch_deform_shared_fp64_dev):
+// a pack kernel copies what the launch needs of the models into `scratch` (shared64_scratch_bytes; packed_ev is recorded
+// behind it, may be null), the evaluation reads only that copy.
+struct Shared64Args : SharedEvalCommon {
+    int M, Mpad, kind;                    // kind: any but the multilayer model's
+    const Rec64 *rec64[kMaxBatch];
+    const double *centres[kMaxBatch];     // compared with entry 0 by content unless equal to it by address; a frame that differs is passed through
 };
 hipError_t launch_deform_shared64(const Shared64Args &a, hipStream_t stream);
 size_t shared64_scratch_bytes(int Mpad, int nF);
@@ -384,20 +390,10 @@ int shared_vectors64_min_frames(int kind);                                  // f
 // Every frame of a shared-rig batch of MULTILAYER models by one matrix-pipe launch (fd_eval_shared_ml.hip,
 // fd_batch_deform_shared_ml_dev): a pack kernel copies what the launch needs of the models into `scratch`
 // (shared_ml_scratch_bytes; packed_ev is recorded behind it, may be null), the evaluation reads only that copy.
-struct SharedMlArgs {
-    int64_t N;
-    const float *P_in, *dist2, *tu, *tv, *nrm;
-    float radius2, falloffrate;
-    int M, layers, nF;                    // centres, layers per centre (1..kMaxLayers), frames (shared_ml_applies)
+struct SharedMlArgs : SharedEvalCommon {
+    int M, layers;                        // centres, layers per centre (1..kMaxLayers); with nF: shared_ml_applies
     const Rec32 *rec32[kMaxBatch];        // per frame: M x layers records, centre-major (k_pack)
-    const DevModel *model[kMaxBatch];
-    float *P_out[kMaxBatch];
-    float *const *falloff_out;            // nF entries or nullptr
-    void *scratch;
-    hipEvent_t packed_ev;
-    int delta_out, max_wgs;
     int check_rig;                        // compare every frame's records {c', scale} with frame 0's; a frame that differs is passed through
-    int *mismatch;                        // as SharedDeformArgs::mismatch
 };
 hipError_t launch_deform_shared_ml(const SharedMlArgs &a, hipStream_t stream);
 bool shared_ml_applies(int M, int layers, int nF);      // sizes the launch takes; fewer frames than shared_ml_min_frames: no
@@ -407,20 +403,10 @@ const char *shared_ml_kernel_name(int M, int layers, int nF);
 // Every frame of a shared-rig batch of MULTILAYER models in fp64 by one matrix-pipe launch (fd_eval_shared_ml64.hip,
 // fd_batch_deform_shared_ml_fp64_dev): a pack kernel copies what the launch needs of the models into `scratch`
 // (shared_ml64_scratch_bytes; packed_ev is recorded behind it, may be null), the evaluation reads only that copy.
-struct SharedMl64Args {
-    int64_t N;
-    const float *P_in, *dist2, *tu, *tv, *nrm;
-    float radius2, falloffrate;
-    int M, layers, nF;                    // centres, layers per centre (1..kMaxLayers), frames (shared_ml64_applies)
+struct SharedMl64Args : SharedEvalCommon {
+    int M, layers;                        // centres, layers per centre (1..kMaxLayers); with nF: shared_ml64_applies
     const Rec64 *rec64[kMaxBatch];        // per frame: M x layers records, centre-major (k_pack)
-    const DevModel *model[kMaxBatch];
-    float *P_out[kMaxBatch];
-    float *const *falloff_out;            // nF entries or nullptr
-    void *scratch;
-    hipEvent_t packed_ev;
-    int delta_out, max_wgs;
     int check_rig;                        // compare every frame's records {c, s} with frame 0's; a frame that differs is passed through
-    int *mismatch;                        // as SharedDeformArgs::mismatch
 };
 hipError_t launch_deform_shared_ml64(const SharedMl64Args &a, hipStream_t stream);
 bool shared_ml64_applies(int M, int layers, int nF);    // sizes the launch takes; fewer frames than shared_ml64_min_frames: no

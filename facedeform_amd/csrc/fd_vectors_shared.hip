@@ -341,8 +341,8 @@ hipError_t launch_vectors_shared(const SharedVectorArgs &a, hipStream_t stream)
     if (hipError_t e = shot_grid(a, fixed + per_kb * (size_t)kchunk, gr); e != hipSuccess) return e;
     const bool gauss = a.kind != FD_KERNEL_THIN_PLATE;
     return for_tiles(NT, a.nF > 12, [&](auto nt, auto dns) {
-        return gauss ? launch_shot<k_vectors32_shared_gaussian<nt.value, dns.value>>(out, p, gr, stream)
-                     : launch_shot<k_vectors32_shared_thin_plate<nt.value, dns.value>>(out, p, gr, stream);
+        return gauss ? launch_shot<k_vectors32_shared_gaussian<nt.value, dns.value>>(gr, stream, out, p)
+                     : launch_shot<k_vectors32_shared_thin_plate<nt.value, dns.value>>(gr, stream, out, p);
     });
 }
 

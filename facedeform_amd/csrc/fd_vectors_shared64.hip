@@ -175,7 +175,7 @@ __global__ __launch_bounds__(kS64Threads) void k_vectors64_shared(const ShotOut 
 template <int KIND>
 hipError_t launch_kind(const ShotOut &out, const V64Params &p, int NT, bool dense, const ShotGrid &gr, hipStream_t stream)
 {
-    return for_tiles(NT, dense, [&](auto nt, auto dns) { return launch_shot<k_vectors64_shared<KIND, nt.value, dns.value>>(out, p, gr, stream); });
+    return for_tiles(NT, dense, [&](auto nt, auto dns) { return launch_shot<k_vectors64_shared<KIND, nt.value, dns.value>>(gr, stream, out, p); });
 }
 
 }  // namespace

@@ -270,9 +270,9 @@ hipError_t launch_vectors_shared_ml(const SharedVectorMlArgs &a, hipStream_t str
         constexpr int kNT = nt.value;
         constexpr bool kDense = dns.value;
         switch (ml_share(a.layers)) {
-        case 4: return launch_shot<k_vectors32_shared_ml<kNT, kDense, 4>>(out, p, gr, stream);
-        case 2: return launch_shot<k_vectors32_shared_ml<kNT, kDense, 2>>(out, p, gr, stream);
-        default: return launch_shot<k_vectors32_shared_ml<kNT, kDense, 1>>(out, p, gr, stream);
+        case 4: return launch_shot<k_vectors32_shared_ml<kNT, kDense, 4>>(gr, stream, out, p);
+        case 2: return launch_shot<k_vectors32_shared_ml<kNT, kDense, 2>>(gr, stream, out, p);
+        default: return launch_shot<k_vectors32_shared_ml<kNT, kDense, 1>>(gr, stream, out, p);
         }
     });
 }

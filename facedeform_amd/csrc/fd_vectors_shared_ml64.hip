@@ -214,7 +214,7 @@ hipError_t launch_vectors_shared_ml64(const SharedVectorMl64Args &a, hipStream_t
     p.kchunk = even_chunks(nkc, (int)((kS64LdsBudget - fixed) / per_kc));         // kmax >= 6: 8 layers x 6 tiles are 24.2 KiB a step
     ShotGrid gr;
     if (hipError_t e = shot_grid(a, fixed + per_kc * (size_t)p.kchunk, gr); e != hipSuccess) return e;
-    return for_tiles(NT, a.nF > 12, [&](auto nt, auto dns) { return launch_shot<k_vectors64_shared_ml<nt.value, dns.value>>(out, p, gr, stream); });
+    return for_tiles(NT, a.nF > 12, [&](auto nt, auto dns) { return launch_shot<k_vectors64_shared_ml<nt.value, dns.value>>(gr, stream, out, p); });
 }
 
 // The fewest frames at which the one launch is ahead of the per-context k_vectors64_gaussian launches over the M L records,

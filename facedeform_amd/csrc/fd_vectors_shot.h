@@ -1,25 +1,21 @@
 // fd_vectors_shot.h -- what the four one-launch vector kernels of a shot share (fd_vectors_shared.hip, fd_vectors_shared64.hip,
 // fd_vectors_shared_ml.hip, fd_vectors_shared_ml64.hip): the kernel arguments every one of them takes, the
-// deal of the output pointers into LDS, the pass-through of a gated vertex, and the host side of a launch -- arguments,
-// chunking, grid, the (NT, DENSE) dispatch.  ONE copy.  The files keep their frame constants, staging, K loops and their
-// epilogues: in functions here the epilogues compile to other schedules, measurably slower in fp64; as
-// the header stands, every kernel's instruction stream is what it was with the copies in the files.
+// deal of the output pointers into LDS, the pass-through of a gated vertex, and the fill of the arguments; chunking, grid and
+// the (NT, DENSE) dispatch are fd_shot_launch.h's, shared with the position launches.  ONE copy.  The files keep their frame
+// constants, staging, K loops and their epilogues: in functions here the epilogues compile to other schedules, measurably
+// slower in fp64; as the header stands, every kernel's instruction stream is what it was with the copies in
+// the files.
 //
 // All four launches run 8 waves per workgroup, a wave owning one vertex tile of 16 per group, and deal the frames onto NT row
 // tiles of 16: padded up to 12 frames (tile T = frames 4 T .. 4 T + 3), dense from 13.
 #pragma once
-#include <algorithm>
-#include <type_traits>
-
-#include "fd_eval_common.h"
 #include "fd_shared64.h"
+#include "fd_shot_launch.h"
 #include "fd_transport.h"
 
 namespace fd {
 namespace {
 
-constexpr int kShotWaves = 8;
-constexpr int kShotThreads = 64 * kShotWaves;
 constexpr int kShotGroup = 16 * kShotWaves;        // vertices per workgroup and group
 static_assert(kShotThreads == kS64Threads, "the fp64 launches stage with the position launch's thread count");
 constexpr int kFrameWords = 16;                    // fp32 launches, per frame in LDS: {basis scale, built, L'[3][3], q[3], 2 unused}
@@ -95,58 +91,9 @@ inline void fill_shot(ShotMesh &p, ShotOut &out, const SharedVectorCommon &a)
     for (int f = 0; f < a.nF; ++f) { out.N[f] = a.N_out[f]; out.tu[f] = a.tu_out[f]; out.tv[f] = a.tv_out[f]; out.jac[f] = a.jacobian[f]; }
 }
 
-// n K steps in the fewest chunks of at most kmax, evened out (as the position launches stage them)
-inline int even_chunks(int n, int kmax)
-{
-    const int nchunks = (n + kmax - 1) / kmax;
-    return (n + nchunks - 1) / nchunks;
-}
-
-struct ShotGrid {
-    size_t lds;
-    unsigned grid;
-    int ngroups;
-};
-
-// persistent workgroups: as many per CU as the LDS admits, two at most (two waves per SIMD each)
-inline hipError_t shot_grid(const SharedVectorCommon &a, size_t lds, ShotGrid &gr)
-{
-    const int64_t ngroups = (a.N + kShotGroup - 1) / kShotGroup;
-    if (ngroups > 0x7fffffff) return hipErrorInvalidValue;
-    const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(2, (int64_t)(160 * 1024 / lds)));
-    const int64_t max_wgs = a.max_wgs > 0 ? (a.max_wgs < 4096 ? a.max_wgs : 4096) : (int64_t)device_cus() * per_cu;
-    gr.lds = lds;
-    gr.grid = (unsigned)(ngroups < max_wgs ? ngroups : max_wgs);
-    gr.ngroups = (int)ngroups;
-    return hipSuccess;
-}
-
-template <auto Kernel, class Params>
-hipError_t launch_shot(const ShotOut &out, const Params &p, const ShotGrid &gr, hipStream_t stream)
-{
-    static LdsAttrOnce once;          // one per kernel instantiation
-    hipError_t e = once.ensure((const void *)Kernel, 160 * 1024);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(Kernel, dim3(gr.grid), dim3(kShotThreads), gr.lds, stream, out, p, gr.ngroups);
-    return hipGetLastError();
-}
-
-// f(NT, DENSE) as compile-time constants for the tile counts a shot can have (s64_tiles, dense from 13 frames):
-//   for_tiles(NT, dense, [&](auto nt, auto dns) { return launch_shot<k<nt.value, dns.value>>(...); })
-template <class F>
-hipError_t for_tiles(int NT, bool dense, F &&f)
-{
-    using std::integral_constant;
-    if (dense) {
-        if (NT == 3) return f(integral_constant<int, 3>{}, std::true_type{});
-        if (NT == 6) return f(integral_constant<int, 6>{}, std::true_type{});
-    } else {
-        if (NT == 1) return f(integral_constant<int, 1>{}, std::false_type{});
-        if (NT == 2) return f(integral_constant<int, 2>{}, std::false_type{});
-        if (NT == 3) return f(integral_constant<int, 3>{}, std::false_type{});
-    }
-    return hipErrorInvalidValue;
-}
+// groups of kShotGroup vertices; two workgroups per CU at most (two waves per SIMD each)
+inline hipError_t shot_grid(const SharedVectorCommon &a, size_t lds, ShotGrid &gr) { return shot_grid(a.N, kShotGroup, a.max_wgs, lds, 2, gr); }
 
 }  // namespace
 }  // namespace fd
+

@@ -66,3 +66,14 @@ def test_source_is_built(hip_lib):
     assert "fd_build_qnn_shared.hip" in _build.SOURCES
     assert os.path.exists(os.path.join(_build.CSRC, "fd_build_qnn_shared.hip"))
     assert os.path.join(_build.CSRC, "fd_shared_solve.h") in _build.HEADERS
+    # every header of csrc/ is a dependency of the build, and no translation unit reaches another one's text: what two of them
+    # share is in a header (the one-frame helpers of the shot evaluations: fd_eval_point.h)
+    names = sorted(os.listdir(_build.CSRC))
+    for name in names:
+        if name.endswith(".h"):
+            assert os.path.join(_build.CSRC, name) in _build.HEADERS, name
+        text = open(os.path.join(_build.CSRC, name)).read()
+        assert "one_frame" not in text, name
+        for line in text.splitlines():
+            if line.lstrip().startswith("#") and "include" in line:
+                assert ".hip" not in line, (name, line)
