@@ -85,7 +85,7 @@ class FdsopShot(C.Structure):
 EXPORTS = [
     "fd_create", "fd_destroy", "fd_last_error", "fd_abi_version", "fd_set_stream", "fd_set_eval_precision", "fd_set_output", "fd_fp32_holds", "fd_set_points",
     "fd_set_points_dev", "fd_set_deltas", "fd_set_deltas_dev", "fd_set_kernel", "fd_set_term", "fd_build", "fd_build_async",
-    "fd_build_result", "fd_deform", "fd_deform_dev", "fd_deform_dev_stream", "fd_deform_vectors", "fd_deform_vectors_dev", "fd_invert", "fd_invert_dev", "fd_get_weights", "fd_model_centres", "fd_model_bytes",
+    "fd_build_result", "fd_deform", "fd_deform_dev", "fd_deform_dev_stream", "fd_deform_vectors", "fd_deform_vectors_dev", "fd_invert", "fd_invert_dev", "fd_deform_adjoint", "fd_deform_adjoint_dev", "fd_solve_operator", "fd_get_weights", "fd_model_centres", "fd_model_bytes",
     "fd_export_model", "fd_import_model", "fd_synchronize", "fd_host_alloc", "fd_host_free",
     "fd_mesh_set", "fd_mesh_size", "fd_deform_mesh", "fd_mesh_capture", "fd_mesh_get_dist2",
     "fd_capture_dist2", "fd_capture_dist2_dev", "fd_capture_islands", "fd_capture_islands_dev",
@@ -162,6 +162,11 @@ def load() -> C.CDLL:
     L.fd_invert.restype = i32
     L.fd_invert_dev.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, C.POINTER(FdInvertOpts)]
     L.fd_invert_dev.restype = i32
+    L.fd_deform_adjoint.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, vp]
+    L.fd_deform_adjoint.restype = i32
+    L.fd_deform_adjoint_dev.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, vp]
+    L.fd_deform_adjoint_dev.restype = i32
+    L.fd_solve_operator.argtypes = [vp, _f64p]; L.fd_solve_operator.restype = i32
     L.fd_get_weights.argtypes = [vp, _f64p, _f64p]; L.fd_get_weights.restype = i32
     L.fd_model_centres.argtypes = [vp]; L.fd_model_centres.restype = i32
     L.fd_model_bytes.argtypes = [vp]; L.fd_model_bytes.restype = sz
@@ -520,6 +525,37 @@ class Engine:
         opts = FdInvertOpts(C.sizeof(FdInvertOpts), int(max_iter), float(tol), vp(d_residual or None), vp(d_iters or None))
         self._check(self.L.fd_invert_dev(self.ctx, N, vp(d_Y), vp(d_X_out), vp(d_dist2 or None), vp(d_tu or None),
                                          vp(d_tv or None), vp(d_nrm or None), float(radius2), float(falloffrate), C.byref(opts)))
+
+    def deform_adjoint(self, P, G, dist2=None, tangents=None, radius2=1.0, falloffrate=1.0):
+        """fd_deform_adjoint: dL/dW, (C + 4, 3) float64 in get_weights' layout, for the sensitivity G = dL/dP' at the deformed
+        vertices (N x 3).  dist2 and tangents = (tu, tv, nrm) are the vertices' attributes, as in deform().  The gradient for
+        the deltas is solve_operator().T @ deform_adjoint(...)."""
+        P = np.ascontiguousarray(P, np.float32).reshape(-1, 3)
+        G = np.ascontiguousarray(G, np.float32).reshape(-1, 3)
+        if G.shape != P.shape:
+            raise ValueError("P and G must have the same shape")
+        d2 = None if dist2 is None else np.ascontiguousarray(dist2, np.float32)
+        tu = tv = nr = None
+        if tangents is not None:
+            tu, tv, nr = (np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in tangents)
+        out = np.empty((int(self.L.fd_model_centres(self.ctx)) + 4, 3), np.float64)
+        self._check(self.L.fd_deform_adjoint(self.ctx, P.shape[0], _np_ptr(P), _np_ptr(G), _np_ptr(d2), _np_ptr(tu), _np_ptr(tv),
+                                             _np_ptr(nr), float(radius2), float(falloffrate), _np_ptr(out)))
+        return out
+
+    def deform_adjoint_dev(self, N: int, d_P_in: int, d_G: int, d_grad_W: int, d_dist2: int = 0, d_tu: int = 0, d_tv: int = 0,
+                           d_nrm: int = 0, radius2=1.0, falloffrate=1.0):
+        """fd_deform_adjoint_dev: device pointers (ints), asynchronous on the context's stream; d_grad_W is (C + 4) x 3 float64."""
+        vp = C.c_void_p
+        self._check(self.L.fd_deform_adjoint_dev(self.ctx, N, vp(d_P_in or None), vp(d_G or None), vp(d_dist2 or None),
+                                                 vp(d_tu or None), vp(d_tv or None), vp(d_nrm or None), float(radius2),
+                                                 float(falloffrate), vp(d_grad_W or None)))
+
+    def solve_operator(self):
+        """fd_solve_operator: S, (C + 4, M) float64 with W[:, a] = S @ delta[:, a] for the context's rest rig, kernel and term."""
+        S = np.empty((int(self.L.fd_model_centres(self.ctx)) + 4, self.M), np.float64)
+        self._check(self.L.fd_solve_operator(self.ctx, S.ctypes.data_as(_f64p)))
+        return S
 
     def get_weights(self):
         n = int(self.L.fd_model_centres(self.ctx))     # M, or M * layers for the multilayer model

@@ -1,5 +1,6 @@
 // fd_capi.hip -- the C ABI of include/facedeform_hip.h over the HIP kernels.
 // No CPU fallback anywhere: without a gfx950 device fd_create fails loudly.
+#include <algorithm>
 #include <atomic>
 #include <cstdarg>
 #include <cstdio>
@@ -7,6 +8,7 @@
 #include <cstring>
 #include <initializer_list>
 #include <new>
+#include <vector>
 
 #include "fd_internal.h"
 
@@ -102,6 +104,10 @@ struct fd_ctx {
     // fd_invert: staging of iters_out (residual_out goes through d_fall)
     int64_t cap_iters = 0;
     int *d_iters = nullptr;
+    // fd_deform_adjoint*: the workgroups' partial blocks and, behind them, the host call's staging of grad_W (adjoint_reserve);
+    // the host call's G goes through d_vecP
+    size_t cap_adj = 0;
+    double *d_adj = nullptr;
     // fd_mesh_set: the mesh arrays that stay the same from cook to cook live in their own
     // device buffers (the staging above is evaluated in place, so it cannot serve as a cache)
     int64_t mesh_N = 0, mesh_cap = 0;
@@ -448,6 +454,8 @@ static int deform_host(fd_ctx *ctx, int64_t N, const float *P_in, float *P_out, 
                        const float *tu, const float *tv, const float *nrm, float radius2, float falloffrate, const fd_vectors *vec);
 static int invert_host(fd_ctx *ctx, int64_t N, const float *Y, float *X_out, const float *dist2, const float *tu, const float *tv,
                        const float *nrm, float radius2, float falloffrate, const fd_invert_opts *opts);
+static int adjoint_host(fd_ctx *ctx, int64_t N, const float *P_in, const float *G, const float *dist2, const float *tu, const float *tv,
+                        const float *nrm, float radius2, float falloffrate, double *grad_W);
 
 extern "C" {
 
@@ -520,7 +528,7 @@ void fd_destroy(fd_ctx *ctx)
     if (ctx->stream_ || ctx->own_stream) (void)hipStreamSynchronize(cur_stream(ctx));
     void *bufs[] = {ctx->d_rest, ctx->d_delta, ctx->d_centres, ctx->d_radii, ctx->d_W, ctx->d_A,
                     ctx->d_X, ctx->d_ipiv, ctx->d_moves, ctx->d_rec32, ctx->d_rec64, ctx->d_tiles, ctx->d_tiles16, ctx->d_ns, ctx->d_model, ctx->d_slot,
-                    ctx->d_P, ctx->d_dist2, ctx->d_fall, ctx->d_tu, ctx->d_tv, ctx->d_nrm, ctx->d_vec, ctx->d_vecP, ctx->d_iters,
+                    ctx->d_P, ctx->d_dist2, ctx->d_fall, ctx->d_tu, ctx->d_tv, ctx->d_nrm, ctx->d_vec, ctx->d_vecP, ctx->d_iters, ctx->d_adj,
                     ctx->m_P, ctx->m_dist2, ctx->m_tu, ctx->m_tv, ctx->m_nrm, ctx->m_out, ctx->m_fall};
     for (void *p : bufs) if (p) (void)hipFree(p);
     if (ctx->h_model) (void)hipHostFree(ctx->h_model);
@@ -979,16 +987,33 @@ static bool invert_opts_ok(fd_ctx *ctx, const fd_invert_opts *opts)
     return true;
 }
 
+// fd_deform_adjoint*: the scratch for N vertices and C records -- adjoint_groups(N) partial blocks of (C + 4) x 3 doubles, and one
+// more block behind them where the host call stages grad_W (adjoint_staging).  Grows on demand (hipFree drains the device).
+static size_t adjoint_block(int C) { return (size_t)(C + 4) * 3; }
+static int adjoint_reserve(fd_ctx *ctx, int64_t N, int C)
+{
+    const size_t need = ((size_t)adjoint_groups(N) + 1) * adjoint_block(C);
+    if (need <= ctx->cap_adj) return FD_OK;
+    ctx->cap_adj = 0;
+    const int rc = dev_alloc(ctx, &ctx->d_adj, need);
+    if (rc) return rc;
+    ctx->cap_adj = need;
+    return FD_OK;
+}
+static double *adjoint_staging(const fd_ctx *ctx, int64_t N, int C) { return ctx->d_adj + (size_t)adjoint_groups(N) * adjoint_block(C); }
+
 // fd_deform_dev_stream / fd_deform_vectors_dev / the staged host calls: vec == nullptr is the deformation alone.
 // fd_invert_dev: inv != nullptr -- the same checks, status poll and ordering, then the inverse's one launch in place of the
 // deformation's (d_P_in = the deformed points, d_P_out = the rest-space points; no fall-off output, no vectors).
+// fd_deform_adjoint_dev: adj != nullptr -- likewise, then the adjoint's two launches (no d_P_out; adj names G and grad_W, the
+// partial blocks are the context's).
 static int deform_dev_common(fd_ctx *ctx, void *hip_stream, int64_t N, const float *d_P_in, float *d_P_out,
                              const float *d_dist2, float *d_falloff_out, const float *d_tu, const float *d_tv,
                              const float *d_nrm, float radius2, float falloffrate, const fd_vectors *vec,
-                             const InvertArgs *inv = nullptr)
+                             const InvertArgs *inv = nullptr, const AdjointArgs *adj = nullptr)
 {
     hipStream_t launch_stream = hip_stream ? (hipStream_t)hip_stream : cur_stream(ctx);
-    if (N < 0 || (N > 0 && (!d_P_in || !d_P_out))) { set_err(ctx, "fd_deform: bad N / P pointers"); return FD_E_INVALID; }
+    if (N < 0 || (N > 0 && (!d_P_in || (!d_P_out && !adj)))) { set_err(ctx, "fd_deform: bad N / P pointers"); return FD_E_INVALID; }
     if (!frames_ok(d_tu, d_tv, d_nrm)) { set_err(ctx, "fd_deform: tu, tv, nrm must be all set or all NULL"); return FD_E_INVALID; }
     if (!ctx->built && !ctx->build_pending) { set_err(ctx, "fd_deform: no successfully built model"); return FD_E_NOT_BUILT; }
     if (N == 0) return FD_OK;
@@ -999,6 +1024,12 @@ static int deform_dev_common(fd_ctx *ctx, void *hip_stream, int64_t N, const flo
     if ((rc = order_after_batch(ctx, launch_stream))) return rc;
     if (inv) {
         FD_HIP(ctx, launch_invert(a, *inv, launch_stream));
+        return FD_OK;
+    }
+    if (adj) {
+        if ((rc = adjoint_reserve(ctx, N, a.M))) return rc;
+        const AdjointArgs g{adj->G, adj->grad_W, ctx->d_adj, term_cols(ctx->term)};
+        FD_HIP(ctx, launch_adjoint(a, g, launch_stream));
         return FD_OK;
     }
     if (!vec) {
@@ -1094,6 +1125,29 @@ int fd_invert(fd_ctx *ctx, int64_t N, const float *Y, float *X_out, const float 
     if (!ctx) return FD_E_INVALID;
     if (!invert_opts_ok(ctx, opts)) return FD_E_INVALID;
     return invert_host(ctx, N, Y, X_out, dist2, tu, tv, nrm, radius2, falloffrate, opts);
+}
+
+int fd_deform_adjoint_dev(fd_ctx *ctx, int64_t N, const float *d_P_in, const float *d_G, const float *d_dist2, const float *d_tu,
+                          const float *d_tv, const float *d_nrm, float radius2, float falloffrate, double *d_grad_W)
+{
+    if (!ctx) return FD_E_INVALID;
+    if (!d_G || !d_grad_W || N < 0) { set_err(ctx, "fd_deform_adjoint: bad N / G / grad_W pointers"); return FD_E_INVALID; }
+    const AdjointArgs adj{d_G, d_grad_W, nullptr, 0};
+    int rc = deform_dev_common(ctx, nullptr, N, d_P_in, nullptr, d_dist2, nullptr, d_tu, d_tv, d_nrm, radius2, falloffrate, nullptr,
+                               nullptr, &adj);
+    if (rc || N > 0) return rc;
+    // no vertex: no launch, zeros
+    if ((rc = use_device(ctx))) return rc;
+    FD_HIP(ctx, hipMemsetAsync(d_grad_W, 0, sizeof(double) * adjoint_block(model_centres(ctx)), cur_stream(ctx)));
+    return FD_OK;
+}
+
+int fd_deform_adjoint(fd_ctx *ctx, int64_t N, const float *P_in, const float *G, const float *dist2, const float *tu, const float *tv,
+                      const float *nrm, float radius2, float falloffrate, double *grad_W)
+{
+    if (!ctx) return FD_E_INVALID;
+    if (!G || !grad_W || N < 0) { set_err(ctx, "fd_deform_adjoint: bad N / G / grad_W pointers"); return FD_E_INVALID; }
+    return adjoint_host(ctx, N, P_in, G, dist2, tu, tv, nrm, radius2, falloffrate, grad_W);
 }
 
 }  // extern "C"
@@ -1236,6 +1290,44 @@ static int invert_host(fd_ctx *ctx, int64_t N, const float *Y, float *X_out, con
     FD_HIP(ctx, hipMemcpyAsync(X_out, ctx->d_P, b3, hipMemcpyDeviceToHost, s));
     if (opts->residual_out) FD_HIP(ctx, hipMemcpyAsync(opts->residual_out, ctx->d_fall, b1, hipMemcpyDeviceToHost, s));
     if (opts->iters_out) FD_HIP(ctx, hipMemcpyAsync(opts->iters_out, ctx->d_iters, sizeof(int) * (size_t)N, hipMemcpyDeviceToHost, s));
+    FD_HIP(ctx, hipStreamSynchronize(s));
+    return FD_OK;
+}
+
+// fd_deform_adjoint on host arrays: staged through the context's device buffers like invert_host; G through d_vecP, grad_W
+// through the block behind the partial sums
+static int adjoint_host(fd_ctx *ctx, int64_t N, const float *P_in, const float *G, const float *dist2, const float *tu, const float *tv,
+                        const float *nrm, float radius2, float falloffrate, double *grad_W)
+{
+    if (N > 0 && !P_in) { set_err(ctx, "fd_deform_adjoint: bad N / P pointers"); return FD_E_INVALID; }
+    if (!frames_ok(tu, tv, nrm)) { set_err(ctx, "fd_deform_adjoint: tu, tv, nrm must be all set or all NULL"); return FD_E_INVALID; }
+    if (!ctx->built && !ctx->build_pending) { set_err(ctx, "fd_deform_adjoint: no successfully built model"); return FD_E_NOT_BUILT; }
+    const int C = model_centres(ctx);
+    if (N == 0) { memset(grad_W, 0, sizeof(double) * adjoint_block(C)); return FD_OK; }
+    int rc = use_device(ctx);
+    if (rc) return rc;
+    if ((rc = ensure_staging(ctx, N, tu != nullptr))) return rc;
+    if (N > ctx->cap_vecP) {
+        if ((rc = dev_alloc(ctx, &ctx->d_vecP, (size_t)N * 3))) return rc;
+        ctx->cap_vecP = N;
+    }
+    if ((rc = adjoint_reserve(ctx, N, C))) return rc;
+    hipStream_t s = cur_stream(ctx);
+    const size_t b3 = sizeof(float) * 3 * (size_t)N, b1 = sizeof(float) * (size_t)N;
+    FD_HIP(ctx, hipMemcpyAsync(ctx->d_P, P_in, b3, hipMemcpyHostToDevice, s));
+    FD_HIP(ctx, hipMemcpyAsync(ctx->d_vecP, G, b3, hipMemcpyHostToDevice, s));
+    if (dist2) FD_HIP(ctx, hipMemcpyAsync(ctx->d_dist2, dist2, b1, hipMemcpyHostToDevice, s));
+    if (tu) {
+        FD_HIP(ctx, hipMemcpyAsync(ctx->d_tu, tu, b3, hipMemcpyHostToDevice, s));
+        FD_HIP(ctx, hipMemcpyAsync(ctx->d_tv, tv, b3, hipMemcpyHostToDevice, s));
+        FD_HIP(ctx, hipMemcpyAsync(ctx->d_nrm, nrm, b3, hipMemcpyHostToDevice, s));
+    }
+    double *d_out = adjoint_staging(ctx, N, C);
+    const AdjointArgs adj{ctx->d_vecP, d_out, nullptr, 0};
+    rc = deform_dev_common(ctx, nullptr, N, ctx->d_P, nullptr, dist2 ? ctx->d_dist2 : nullptr, nullptr, tu ? ctx->d_tu : nullptr,
+                           tu ? ctx->d_tv : nullptr, tu ? ctx->d_nrm : nullptr, radius2, falloffrate, nullptr, nullptr, &adj);
+    if (rc) return rc;
+    FD_HIP(ctx, hipMemcpyAsync(grad_W, d_out, sizeof(double) * adjoint_block(C), hipMemcpyDeviceToHost, s));
     FD_HIP(ctx, hipStreamSynchronize(s));
     return FD_OK;
 }
@@ -1958,6 +2050,83 @@ int fd_batch_build_result(fd_batch *b, fd_report *reports)
         if (rc && !first) { first = rc; batch_err(b, "context %d: %s", i, b->ctxs[i]->err); }
     }
     return first;
+}
+
+// The map deltas -> weights of ctx's rest rig, column by column: helper contexts with ctx's kernel, parameters, term and solver
+// read ctx's own copy of the rest points in place and are built in batches on unit deltas -- build k has 1 in x of point 3k, in
+// y of point 3k + 1 and in z of point 3k + 2, so its weight columns are columns 3k, 3k + 1, 3k + 2 of S.  Nothing of ctx changes.
+int fd_solve_operator(fd_ctx *ctx, double *S)
+{
+    if (!ctx || !S) return FD_E_INVALID;
+    if (!ctx->points_set) { set_err(ctx, "fd_solve_operator: no control points (call fd_set_points first)"); return FD_E_NOT_BUILT; }
+    int rc = use_device(ctx);
+    if (rc) return rc;
+    FD_HIP(ctx, hipStreamSynchronize(cur_stream(ctx)));             // d_rest may still be on its way (fd_set_points_dev)
+    const int M = ctx->M, rows = model_centres(ctx) + 4;
+    const int builds = (M + 2) / 3;
+    const int nh = builds < kMaxBatch ? builds : kMaxBatch;
+    fd_ctx *helpers[kMaxBatch] = {};
+    float *d_unit = nullptr;
+    fd_batch *batch = nullptr;
+    auto done = [&](int code) {
+        if (batch) fd_batch_destroy(batch);
+        for (fd_ctx *h : helpers) if (h) fd_destroy(h);
+        if (d_unit) (void)hipFree(d_unit);
+        return code;
+    };
+    fd_config cfg{};
+    cfg.struct_size = (int)sizeof(cfg);
+    cfg.device = ctx->device; cfg.eval_precision = ctx->eval_precision; cfg.solver = ctx->solver;
+    for (int i = 0; i < nh; ++i) {
+        fd_ctx *h = helpers[i] = fd_create(&cfg);
+        if (!h) { set_err(ctx, "fd_solve_operator: %s", g_err); return done(FD_E_NOMEM); }
+        if ((rc = fd_set_kernel(h, ctx->kind, ctx->params, ctx->nparams)) || (rc = fd_set_term(h, ctx->term))) {
+            set_err(ctx, "fd_solve_operator: %s", h->err);
+            return done(rc);
+        }
+        h->prefer_lu = ctx->prefer_lu;      // a rig that has asked for the pivoted LU asks for it under any deltas
+        h->stream_ = cur_stream(ctx);       // one stream for all: no hardware queue per helper
+    }
+    const size_t per = (size_t)M * 3;
+    if (hipMalloc((void **)&d_unit, sizeof(float) * per * (size_t)nh) != hipSuccess) {
+        (void)hipGetLastError();
+        set_err(ctx, "fd_solve_operator: hipMalloc(%zu bytes) failed", sizeof(float) * per * (size_t)nh);
+        return done(FD_E_NOMEM);
+    }
+    std::vector<float> unit(per * (size_t)nh);
+    std::vector<double> W((size_t)rows * 3);
+    for (int k0 = 0; k0 < builds; k0 += nh) {
+        const int n = builds - k0 < nh ? builds - k0 : nh;
+        std::fill(unit.begin(), unit.end(), 0.f);
+        for (int i = 0; i < n; ++i)
+            for (int a = 0; a < 3; ++a) {
+                const int col = 3 * (k0 + i) + a;
+                if (col < M) unit[per * (size_t)i + 3 * (size_t)col + a] = 1.f;
+            }
+        if (hipMemcpy(d_unit, unit.data(), sizeof(float) * per * (size_t)n, hipMemcpyHostToDevice) != hipSuccess) {
+            set_err(ctx, "fd_solve_operator: upload of the unit deltas failed: %s", hipGetErrorString(hipGetLastError()));
+            return done(FD_E_DEVICE);
+        }
+        if (!(batch = fd_batch_create(helpers, n))) { set_err(ctx, "fd_solve_operator: %s", g_err); return done(FD_E_NOMEM); }
+        const float *rest[kMaxBatch], *delta[kMaxBatch];
+        for (int i = 0; i < n; ++i) { rest[i] = ctx->d_rest; delta[i] = d_unit + per * (size_t)i; }
+        if ((rc = fd_batch_set_points_dev(batch, rest, delta, M)) || (rc = fd_batch_build_async(batch, nullptr)) ||
+            (rc = fd_batch_build_result(batch, nullptr))) {
+            set_err(ctx, "fd_solve_operator: %s", batch->err);
+            return done(rc);
+        }
+        for (int i = 0; i < n; ++i) {
+            if ((rc = fd_get_weights(helpers[i], W.data(), nullptr))) { set_err(ctx, "fd_solve_operator: %s", helpers[i]->err); return done(rc); }
+            for (int a = 0; a < 3; ++a) {
+                const int col = 3 * (k0 + i) + a;
+                if (col >= M) continue;
+                for (int r = 0; r < rows; ++r) S[(size_t)r * M + col] = W[3 * (size_t)r + a];
+            }
+        }
+        fd_batch_destroy(batch);
+        batch = nullptr;
+    }
+    return done(FD_OK);
 }
 
 // One launch evaluates every context of the batch on its own vertex arrays (grid y = context)

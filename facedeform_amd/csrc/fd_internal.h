@@ -290,6 +290,18 @@ struct InvertArgs {
     int *iters_out;        // N or null
 };
 hipError_t launch_invert(const DeformArgs &a, const InvertArgs &v, hipStream_t stream);
+// the adjoint of the deformation (fd_adjoint.hip, fd_deform_adjoint*): `a` names the mesh attributes and the model as for the
+// deformation (P_out, falloff_out, precision, variant and delta_out are not read: everything is fp64); G is the cotangent at the
+// deformed vertices (N x 3), grad_W the (M + 4) x 3 result in W's layout, T the polynomial rows the term has (the others
+// are written as 0.0), partial a scratch of adjoint_groups(N) * (M + 4) * 3 doubles.  Two launches; N = 0 writes zeros.
+struct AdjointArgs {
+    const float *G;
+    double *grad_W;
+    double *partial;
+    int T;
+};
+int adjoint_groups(int64_t N);        // workgroups along the vertices: a function of N alone
+hipError_t launch_adjoint(const DeformArgs &a, const AdjointArgs &g, hipStream_t stream);
 hipError_t launch_deform_batch(const DeformArgs *a, int n, hipStream_t stream);
 // frames that share the mesh and the rest rig (fd_eval.hip, k_deform32_tps_shared): phi once per
 // (vertex, centre), the 3 F-wide weight contraction on the matrix pipe

@@ -20,6 +20,7 @@ constexpr int kBlock = 256;
 constexpr int kV = 2;        // vertices per lane
 
 using packing::grad_scale64;
+using packing::phi_grad64;       // phi and g of grad phi = grad_scale64 g (x - c) from the kind's one transcendental (fd_pack.h)
 
 typedef const __attribute__((address_space(4))) Rec64 *ConstRec64;
 
@@ -36,27 +37,6 @@ struct InvParams {
     const Rec64 *rec64;
     const DevModel *model;
 };
-
-// phi as fd_eval.hip's phi64 applies it to a record and g of fd_pack.h's derivative table (grad phi = grad_scale64 g (x - c)),
-// both from the kind's one transcendental
-template <int KIND>
-__device__ __forceinline__ void phi_grad64(double d2, double s, double &phi, double &g)
-{
-    if constexpr (KIND == FD_KERNEL_THIN_PLATE) {
-        const double l = d2 > 0.0 ? log(d2) : 0.0;          // (x - c) = 0 there: phi = 0, and g multiplies 0
-        phi = d2 * l;                                       // weights carry the 0.5
-        g = d2 > 0.0 ? l + 1.0 : 0.0;
-    } else if constexpr (KIND == FD_KERNEL_GAUSSIAN || KIND == FD_KERNEL_GAUSSIAN_QNN) {
-        phi = exp(d2 * s);                                  // s = -1/R_j^2
-        g = phi * s;
-    } else if constexpr (KIND == FD_KERNEL_BIHARMONIC) {
-        phi = sqrt(d2);
-        g = d2 > 0.0 ? 1.0 / phi : 0.0;
-    } else {
-        g = sqrt(d2);
-        phi = d2 * g;
-    }
-}
 
 __device__ __forceinline__ bool finite3(const double v[3]) { return isfinite(v[0]) && isfinite(v[1]) && isfinite(v[2]); }
 

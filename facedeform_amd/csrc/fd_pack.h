@@ -133,6 +133,33 @@ __device__ __forceinline__ double grad64(double d2, double s)
     }
 }
 
+// phi as fd_eval.hip's phi64 applies it to a record and g of the table above, both from the kind's one transcendental: the
+// inverse's field and Jacobian (fd_invert.hip), the adjoint's phi (fd_adjoint.hip)
+template <int KIND>
+__device__ __forceinline__ void phi_grad64(double d2, double s, double &phi, double &g)
+{
+    if constexpr (KIND == FD_KERNEL_THIN_PLATE) {
+        const double l = d2 > 0.0 ? log(d2) : 0.0;          // (x - c) = 0 there: phi = 0, and g multiplies 0
+        phi = d2 * l;                                       // weights carry the 0.5
+        g = d2 > 0.0 ? l + 1.0 : 0.0;
+    } else if constexpr (KIND == FD_KERNEL_GAUSSIAN || KIND == FD_KERNEL_GAUSSIAN_QNN) {
+        phi = exp(d2 * s);                                  // s = -1/R_j^2
+        g = phi * s;
+    } else if constexpr (KIND == FD_KERNEL_BIHARMONIC) {
+        phi = sqrt(d2);
+        g = d2 > 0.0 ? 1.0 / phi : 0.0;
+    } else {
+        g = sqrt(d2);
+        phi = d2 * g;
+    }
+}
+// w64 of pack_body_from below: the factor between a row of W and the weight its fp64 record carries.  The adjoint applies it to
+// its sums, which makes grad_W dual to W (fd_get_weights) and not to the records.
+__host__ __device__ constexpr double weight_scale64(int kind)
+{
+    return kind == FD_KERNEL_THIN_PLATE ? 0.5 : (kind == FD_KERNEL_BIHARMONIC ? -1.0 : 1.0);
+}
+
 // (256 threads; a kernel of its own in fd_build.hip, the last phase of the one-launch build in fd_nullspace.hip)
 template <class Src>
 __device__ __forceinline__ void pack_body_from(const Src &in, const BatchSlot &slot, int /* npad */, int M, int Mpad, int T, int kind, int from_w, int layers)

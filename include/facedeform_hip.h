@@ -351,6 +351,48 @@ int fd_invert_dev(fd_ctx *ctx, int64_t N, const float *d_Y, float *d_X_out, cons
                   const float *d_tu, const float *d_tv, const float *d_nrm,
                   float radius2, float falloffrate, const fd_invert_opts *opts);
 
+/* ---- the adjoint of the deformation ---------------------------------------------
+ * Given a sensitivity g_v = dL/dP'_v at the deformed vertices, fd_deform_adjoint returns dL/dW for the built model's
+ * weights.  The forward map P' = x + f . Pi . d(x) is linear in W, so this is its exact transpose, no linearisation:
+ *   grad_W[j][a]     = sum_v phi_j(x_v) r_v[a],   r_v = f_v Pi_v g_v   (Pi is symmetric; d, Pi, f as above)
+ *   grad_W[C][a]     = sum_v r_v[a]                                    (the constant row)
+ *   grad_W[C+1+b][a] = sum_v x_v[b] r_v[a]                             (the linear rows)
+ * grad_W is (C+4) x 3 fp64 row-major, C = fd_model_centres(ctx): the layout of fd_get_weights' W, and dual to it.
+ *
+ * The contract.  For the built model and any W' in fd_get_weights' layout and convention,
+ *   sum_{j,a} grad_W[j][a] W'[j][a] = sum_v g_v . D_v(W'),
+ *   D_v the displacement FD_OUTPUT_DISPLACEMENT defines, evaluated exactly with the weights W'.  This fixes every factor
+ *   between the evaluation records and W (the 0.5 of the thin-plate weights, the biharmonic sign, the normalisation).
+ * Arithmetic.  Everything is fp64 whatever fd_set_eval_precision says: the fp32 positions and g widened, x - c_j in raw
+ *   coordinates, phi of the kind as the inverse forms it; the gate, f and Pi are the forward path's own code.
+ * Vertices that contribute nothing.  A gated vertex (dist2 > radius2) and a vertex with f = 0 contribute exactly nothing
+ *   whatever G holds there, NaN and infinity included (a select, not a product).  A model with terminationtype != 1 gives
+ *   zeros and FD_OK: its forward map is the identity.  N = 0 gives zeros.  Rows of a polynomial term the model lacks are 0.0.
+ * Determinism.  No atomics: workgroups write partial sums that a second launch adds in a fixed order, and the number of
+ *   workgroups and their vertex ranges depend on N alone.  The same inputs give the same bits on every call.
+ * Checks and errors.  The build-status poll and repair, FD_E_NOT_BUILT, the all-or-none rule for tu/tv/nrm and the ordering
+ *   behind a batched build are fd_deform's.  FD_E_INVALID for a NULL context, a NULL G or grad_W or N < 0 comes before any
+ *   device work.  fd_set_output has no effect.  Only the (C+4) x 3 entries are written.
+ * The sensitivity with respect to P_in is not part of this: it is A^T g with the A fd_deform_vectors writes.
+ *
+ * Device pointers, asynchronous on the context's stream (two launches; the partial sums live in the context). */
+int fd_deform_adjoint_dev(fd_ctx *ctx, int64_t N, const float *d_P_in, const float *d_G, const float *d_dist2,
+                          const float *d_tu, const float *d_tv, const float *d_nrm,
+                          float radius2, float falloffrate, double *d_grad_W);
+/* Same, host arrays, staged through the context's buffers as fd_invert's; synchronous. */
+int fd_deform_adjoint(fd_ctx *ctx, int64_t N, const float *P_in, const float *G, const float *dist2,
+                      const float *tu, const float *tv, const float *nrm,
+                      float radius2, float falloffrate, double *grad_W);
+/* The map deltas -> weights of the context's rest points, kernel, parameters and term: S is (C+4) x M fp64 row-major, and for
+ * each component a,  W[:, a] = S . delta[:, a].  Host array, synchronous.  Column i is the weight column a build of the rest rig
+ * gives for the delta e_i: helper contexts that share the context's rest array are built in batches (ceil(M/3) builds in
+ * groups of FD_MAX_BATCH), created and destroyed inside the call.  Valid for every kind, FD_KERNEL_GAUSSIAN_QNN and
+ * FD_KERNEL_GAUSSIAN_ML included: radii and layers depend on the rest rig alone.  The context's own model, its deltas and the
+ * factorisation fd_set_deltas reuses are left as they were; nothing is cached, the caller keeps S for as long as the rest rig
+ * stands.  FD_E_NOT_BUILT before fd_set_points; a helper build's own error if one fails.
+ * The gradient for the deltas is then one small product on the caller's side:  grad_delta = S^T . grad_W  (M x 3). */
+int fd_solve_operator(fd_ctx *ctx, double *S);
+
 /* ---- device-resident mesh (next row N3, engine side) --------------------------
  * In an animated shot the mesh on input 0 -- P, the capture's dist2, the tangent
  * frames -- is the same from cook to cook (Houdini tells by the attributes' data
