@@ -38,6 +38,7 @@ struct fd_ctx {
     unsigned long long model_gen = 0; // counts the models this context has held (every enqueued build, every import): what a
                                      // batch's packed copy of the weights is checked against before it is reused
     bool last_spd = false;           // the build in flight / last finished took the Cholesky path
+    bool last_small = false;         // ... as k_build_small's one workgroup (otherwise, unless last_reg, the launch chain)
     bool last_nopivot = false;       // ... the LU without pivot search (QNN): a -4 from it is answered with the pivoted LU, like the Cholesky's
     bool last_reg = false;           // ... in its register-resident form (no factorisation is kept: fd_set_deltas builds again)
 
@@ -392,6 +393,7 @@ static void note_build_enqueued(fd_ctx *c, hipEvent_t done, hipStream_t s, fd_ba
         c->have_factor = path->ml_layers == 0;
         c->factor_grouped = path->group_panels != 0;
         c->last_spd = path->spd != 0;
+        c->last_small = path->spd != 0 && path->small != 0;
         c->last_reg = path->spd != 0 && path->reg != 0;
         c->last_nopivot = path->nopivot != 0;
         c->deltas_only = false;
@@ -750,6 +752,9 @@ static void choose_build(fd_ctx *const *ctxs, int n, BuildBuffers &b)
         if (!use_nopivot(ctxs[i])) b.nopivot = 0;
     }
     if (!b.spd) b.reg = 0;      // the register-resident build is a form of the definite path
+    // ... and so is the one-workgroup build, up to the size k_build_small takes: beyond it FD_SOLVER_ONE_WORKGROUP is the launch
+    // chain, and fd_report.solver_used says so
+    if (!b.spd || !small_applicable(b.M, b.T)) b.small = 0;
 }
 
 int fd_build_async(fd_ctx *ctx)
@@ -836,7 +841,7 @@ int fd_build_result(fd_ctx *ctx, fd_report *report)
         r.iterationscount = ctx->h_model->iterations;
         r.n = order_of(ctx);
         r.solver_used = ctx->last_reg ? FD_SOLVER_REGISTER
-                        : ctx->last_spd ? (ctx->solver == FD_SOLVER_ONE_WORKGROUP ? FD_SOLVER_ONE_WORKGROUP : FD_SOLVER_CHAIN)
+                        : ctx->last_spd ? (ctx->last_small ? FD_SOLVER_ONE_WORKGROUP : FD_SOLVER_CHAIN)
                         : ctx->last_nopivot ? FD_SOLVER_LU_NOPIVOT : FD_SOLVER_LU;
         double pmin, pmax;
         memcpy(&pmin, &ctx->h_model->pivmin_bits, 8);

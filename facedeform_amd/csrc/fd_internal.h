@@ -165,7 +165,7 @@ struct BuildBuffers {
     // Symmetric definite path (fd_nullspace.hip): the polynomial constraints are eliminated with
     // Householder reflectors and the projected kernel block, order M - T, is Cholesky-factorised
     // -- no pivot search, so the panel is no longer one workgroup's serial chain.
-    int small;                        // FD_SOLVER_ONE_WORKGROUP: k_build_small where it applies
+    int small;                        // FD_SOLVER_ONE_WORKGROUP where k_build_small applies (small_applicable): it runs
     int reg;                          // the register-resident one-launch build (fd_build_reg.hip) where it applies: M <= 256 on the definite path
     // ... with its parallel front end (k_reg_front1 / k_reg_front2 over all CUs, then the factorisation in one workgroup per model):
     // shorter alone; 0 keeps the whole build in its one workgroup -- what a pipeline wants whose evaluation launches hold most CUs
@@ -204,6 +204,8 @@ hipError_t launch_lu_resolve_core(const BuildBuffers &b, hipStream_t stream);
 // ---- null-space Cholesky build (fd_nullspace.hip) -----------------------------------
 // Which (kernel, term, lambda) make the projected block positive definite; M large enough to project.
 bool spd_applicable(int kind, int term, double lambda, int M);
+// ... and small enough for FD_SOLVER_ONE_WORKGROUP's k_build_small (T polynomial columns); beyond it that choice is the launch chain
+bool small_applicable(int M, int T);
 static inline size_t ns_doubles(int M) { return (size_t)12 * (size_t)M + 64 + (size_t)(M / 32 + 2) * 66 * 32; }
 hipError_t launch_build_spd(const BuildBuffers &b, hipStream_t stream, hipEvent_t ev_mid);
 hipError_t launch_resolve_spd(const BuildBuffers &b, hipStream_t stream, const PointSrc *src);

@@ -1558,6 +1558,13 @@ bool spd_applicable(int kind, int term, double lambda, int M)
     }
 }
 
+// k_build_small takes the system when its projected block, order M - T padded to whole 32-column blocks, has at most
+// kSmallMaxNpc rows: up to 516 control points under the linear term, 513 under the constant term, 512 without a term
+bool small_applicable(int M, int T)
+{
+    return round_up(M - T, kNB) <= kSmallMaxNpc;
+}
+
 // everything after k_prepare
 hipError_t launch_build_spd(const BuildBuffers &b, hipStream_t stream, hipEvent_t ev_mid)
 {
@@ -1573,7 +1580,7 @@ hipError_t launch_build_spd(const BuildBuffers &b, hipStream_t stream, hipEvent_
     // 32 frames on most of the device while the next 32 models are solved it is the other way round: 32 workgroups
     // on 32 CUs for 0.65 ms disturb the evaluation less than 18 launches with grids all over the device (bench.py:
     // 120-122k against 112k Mverts/s).
-    if (npc <= kSmallMaxNpc && b.small) {
+    if (b.small) {      // (choose_build: every context asks for it, and small_applicable)
         // one workgroup per model does everything after the assembly
         hipError_t e0 = launch_assemble_block(b, stream, npa);
         if (e0 != hipSuccess) return e0;

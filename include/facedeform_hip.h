@@ -108,7 +108,9 @@ enum { FD_EVAL_FP32 = 0, FD_EVAL_FP64 = 1 };
  * FD_E_DUPLICATE (sticky until the next fd_set_points / fd_set_deltas).  Both
  * are fp64 direct solves of the same system: their weights agree to rounding (~1e-12 relative
  * on the benchmark rigs), far inside the parity tolerance. */
-/* ONE_WORKGROUP (thin-plate / Gaussian family as for AUTO's Cholesky path, up to 512 control points; anything else
+/* ONE_WORKGROUP (thin-plate / Gaussian family as for AUTO's Cholesky path, while M minus the term's polynomial columns,
+ * rounded up to a multiple of 32, is at most 512: up to 516 control points under the linear term, 513 under the constant
+ * term, 512 without a term; a larger definite system takes the launch chain and reports FD_SOLVER_CHAIN, anything else
  * behaves as AUTO): everything after the assembly of K -- projection, Cholesky, substitution, packing -- in ONE
  * launch of ONE workgroup per model.  A single build is slower that way (0.37 against 0.25 ms at 256 control
  * points), but a batch of 32 costs what one does, as 32 workgroups on 32 CUs and nothing else on the device: the

@@ -1,9 +1,10 @@
 """GPU: the two direct solvers of the dense system (include/facedeform_hip.h FD_SOLVER_*).
 
 AUTO sends the conditionally positive definite (kernel, term) pairs through the null-space
-Cholesky (facedeform_amd/csrc/fd_nullspace.hip) and everything else through the pivoted LU
-(fd_build.hip); LU forces the latter.  Both solve the system of reference
-src/SOP_FaceDeform.cpp:331-368 in north_star's dense form, so their weights must agree with each
+Cholesky -- up to 256 control points its register-resident form (fd_build_reg.hip), above that the
+launch chain (facedeform_amd/csrc/fd_nullspace.hip), which CHAIN asks for at every size -- and
+everything else through the pivoted LU (fd_build.hip); LU forces the latter.  All solve the
+system of reference src/SOP_FaceDeform.cpp:331-368 in north_star's dense form, so their weights must agree with each
 other and with the fp64 oracle to rounding, and every behaviour at the boundary (termination
 types, reports, fd_set_deltas, batches) must be the same whichever one ran."""
 import numpy as np
@@ -39,7 +40,9 @@ def _engine(kind, params, term, rest, delta, solver):
 @pytest.mark.parametrize("kind,params,term", SPD_CASES)
 def test_cholesky_and_lu_agree_with_each_other_and_the_oracle(hip_lib, oracle, M, kind, params, term):
     """M = 16 is the smallest system AUTO projects; 37 and 300 leave ragged last blocks and pivot
-    rows that straddle the 32-row tiles; 700 takes the ranged back-substitution."""
+    rows that straddle the 32-row tiles; 700 takes the ranged back-substitution.  AUTO is the
+    register-resident build at 16, 37 and 256 and the launch chain at 300 and 700; CHAIN is the
+    launch chain at all five."""
     rest = synth.control_points(M, "head")
     deform = synth.deformed_rig(rest, 2)
     delta = (deform - rest).astype(np.float32)
@@ -49,12 +52,14 @@ def test_cholesky_and_lu_agree_with_each_other_and_the_oracle(hip_lib, oracle, M
     rc, tt, W, radii = oracle.build(table, kind, params, term)
     assert tt == 1
     got = {}
-    for solver in (capi.SOLVER_AUTO, capi.SOLVER_LU):
+    for solver in (capi.SOLVER_AUTO, capi.SOLVER_LU, capi.SOLVER_CHAIN):
         e = _engine(kind, params, term, rest, delta, solver)
         rep = e.build()
         T = (4, 1, 0)[term]
         assert rep.terminationtype == 1 and rep.n == M + T and rep.iterationscount == M + T
         assert 0.0 < rep.pivot_ratio <= 1.0
+        if solver == capi.SOLVER_CHAIN:
+            assert rep.solver_used == capi.SOLVER_CHAIN
         got[solver], _ = e.get_weights()
         e.close()
     scale = np.abs(W).max()
@@ -90,10 +95,12 @@ def test_pairs_outside_the_definite_family_take_lu_whatever_is_asked(hip_lib):
 
 def test_failures_report_the_same_way(hip_lib):
     """-5 for coincident centres, -4 for a polynomial block without full column rank (all centres
-    in one plane under the linear term) and for a poisoned matrix; never an exception or a hang."""
+    in one plane under the linear term) and for a poisoned matrix; never an exception or a hang.
+    At this size AUTO is the register-resident build; the launch chain and k_build_small are asked
+    for by name."""
     rest = synth.control_points(64, "head")
     delta = synth.smooth_deltas(rest, 0).astype(np.float32)
-    for solver in (capi.SOLVER_AUTO, capi.SOLVER_LU):
+    for solver in (capi.SOLVER_AUTO, capi.SOLVER_LU, capi.SOLVER_CHAIN, capi.SOLVER_ONE_WORKGROUP):
         dup = rest.copy(); dup[9] = dup[40]
         e = _engine(capi.KERNEL_THIN_PLATE, [], capi.TERM_LINEAR, dup, delta, solver)
         assert e.build(check=False).terminationtype == -5
@@ -219,20 +226,25 @@ def test_every_block_shape_of_the_fused_step(hip_lib):
     """A sweep over M walks every relation between the 32-column blocks, the 192-row slabs of the
     step kernel, the 64-row waves inside them and the padding (one block only, one slab exactly,
     a slab plus one row, pivot rows straddling a block boundary ...), thin-plate + linear term and
-    a Gaussian without projection; the LU is the reference."""
+    a Gaussian without projection; the LU is the reference.  The step kernel is the launch chain's:
+    CHAIN runs it at every size, AUTO only above 256 control points (up to there it is the
+    register-resident build, which is held to the LU here as well)."""
     sizes = list(range(16, 140, 5)) + [191, 192, 193, 196, 197, 223, 224, 225, 228, 229, 255, 256, 257, 260, 261, 287, 288, 289, 292, 293, 420, 452, 453]
     for kind, params, term in ((capi.KERNEL_THIN_PLATE, [], capi.TERM_LINEAR), (capi.KERNEL_GAUSSIAN, [0.2, 1e-3], capi.TERM_ZERO)):
         for M in sizes:
             rest = synth.control_points(M, "head")
             delta = synth.smooth_deltas(rest, 1).astype(np.float32)
             W = []
-            for solver in (capi.SOLVER_AUTO, capi.SOLVER_LU):
+            for solver in (capi.SOLVER_AUTO, capi.SOLVER_LU, capi.SOLVER_CHAIN):
                 e = _engine(kind, params, term, rest, delta, solver)
                 rep = e.build()
                 assert rep.terminationtype == 1, (kind, M, solver)
+                if solver == capi.SOLVER_CHAIN:
+                    assert rep.solver_used == capi.SOLVER_CHAIN, (kind, M, rep.solver_used)
                 W.append(e.get_weights()[0])
                 e.close()
             assert np.abs(W[0] - W[1]).max() <= 1e-8 * np.abs(W[1]).max(), (kind, M)
+            assert np.abs(W[2] - W[1]).max() <= 1e-8 * np.abs(W[1]).max(), (kind, M, "chain")
 
 
 def test_failed_async_build_is_repaired_or_reported_without_reading_the_result(hip_lib, oracle):
@@ -402,7 +414,9 @@ def test_one_workgroup_solver_as_a_context_choice(hip_lib, oracle):
     mixed = capi.Batch([ow[0], auto])
     mixed.set_points_dev([d_rest.data_ptr()] * 2, [d_del.data_ptr(), d_del.data_ptr() + M * 12], M)
     mixed.build_async()
-    assert [r.terminationtype for r in mixed.build_result()] == [1, 1]
+    reps = mixed.build_result()
+    assert [r.terminationtype for r in reps] == [1, 1]
+    assert [r.solver_used for r in reps] == [capi.SOLVER_CHAIN] * 2                    # the report says what ran, not what was asked for
     auto2 = engines(capi.SOLVER_CHAIN, 1)[0]
     auto2.set_points(rest, deltas[0]); auto2.build()
     assert np.array_equal(ow[0].get_weights()[0], auto2.get_weights()[0])               # the chain's bits
