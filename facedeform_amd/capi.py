@@ -47,6 +47,13 @@ class FdVectors(C.Structure):
                 ("tv", C.c_void_p), ("tv_out", C.c_void_p), ("jacobian", C.c_void_p)]
 
 
+class FdFitReport(C.Structure):
+    """fd_fit_report: what fd_fit_deltas solved and where its time went."""
+    _fields_ = [("struct_size", C.c_int), ("order", C.c_int), ("E0", C.c_double), ("E_fit", C.c_double),
+                ("pivot_min", C.c_double), ("pivot_max", C.c_double), ("ms_gram", C.c_double), ("ms_adjoint", C.c_double),
+                ("ms_compose", C.c_double), ("ms_solve", C.c_double)]
+
+
 class FdInvertOpts(C.Structure):
     """fd_invert_opts: the Newton iteration's limits (0 = the defaults) and its optional per-vertex outputs."""
     _fields_ = [("struct_size", C.c_int), ("max_iter", C.c_int), ("tol", C.c_double), ("residual_out", C.c_void_p),
@@ -85,7 +92,7 @@ class FdsopShot(C.Structure):
 EXPORTS = [
     "fd_create", "fd_destroy", "fd_last_error", "fd_abi_version", "fd_set_stream", "fd_set_eval_precision", "fd_set_output", "fd_fp32_holds", "fd_set_points",
     "fd_set_points_dev", "fd_set_deltas", "fd_set_deltas_dev", "fd_set_kernel", "fd_set_term", "fd_build", "fd_build_async",
-    "fd_build_result", "fd_deform", "fd_deform_dev", "fd_deform_dev_stream", "fd_deform_vectors", "fd_deform_vectors_dev", "fd_invert", "fd_invert_dev", "fd_deform_adjoint", "fd_deform_adjoint_dev", "fd_solve_operator", "fd_get_weights", "fd_model_centres", "fd_model_bytes",
+    "fd_build_result", "fd_deform", "fd_deform_dev", "fd_deform_dev_stream", "fd_deform_vectors", "fd_deform_vectors_dev", "fd_invert", "fd_invert_dev", "fd_deform_adjoint", "fd_deform_adjoint_dev", "fd_solve_operator", "fd_deform_gram", "fd_deform_gram_dev", "fd_fit_deltas", "fd_get_weights", "fd_model_centres", "fd_model_bytes",
     "fd_export_model", "fd_import_model", "fd_synchronize", "fd_host_alloc", "fd_host_free",
     "fd_mesh_set", "fd_mesh_size", "fd_deform_mesh", "fd_mesh_capture", "fd_mesh_get_dist2",
     "fd_capture_dist2", "fd_capture_dist2_dev", "fd_capture_islands", "fd_capture_islands_dev",
@@ -167,6 +174,12 @@ def load() -> C.CDLL:
     L.fd_deform_adjoint_dev.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, vp]
     L.fd_deform_adjoint_dev.restype = i32
     L.fd_solve_operator.argtypes = [vp, _f64p]; L.fd_solve_operator.restype = i32
+    L.fd_deform_gram.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, vp]
+    L.fd_deform_gram.restype = i32
+    L.fd_deform_gram_dev.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, vp]
+    L.fd_deform_gram_dev.restype = i32
+    L.fd_fit_deltas.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, C.c_double, vp, vp, vp, vp]
+    L.fd_fit_deltas.restype = i32
     L.fd_get_weights.argtypes = [vp, _f64p, _f64p]; L.fd_get_weights.restype = i32
     L.fd_model_centres.argtypes = [vp]; L.fd_model_centres.restype = i32
     L.fd_model_bytes.argtypes = [vp]; L.fd_model_bytes.restype = sz
@@ -556,6 +569,56 @@ class Engine:
         S = np.empty((int(self.L.fd_model_centres(self.ctx)) + 4, self.M), np.float64)
         self._check(self.L.fd_solve_operator(self.ctx, S.ctypes.data_as(_f64p)))
         return S
+
+    def deform_gram(self, P, omega=None, dist2=None, tangents=None, radius2=1.0, falloffrate=1.0):
+        """fd_deform_gram: H, (nq, C + 4, C + 4) float64 with H[q] = sum_v omega_v f_v^2 (Pi_v^2)[b][c] Psi_v^T Psi_v in
+        get_weights' layout; nq = 1 without tangents = (tu, tv, nrm), else 6 ordered xx, xy, xz, yy, yz, zz.  omega: per-vertex
+        weights >= 0 (None: 1)."""
+        P = np.ascontiguousarray(P, np.float32).reshape(-1, 3)
+        om = None if omega is None else np.ascontiguousarray(omega, np.float32)
+        d2 = None if dist2 is None else np.ascontiguousarray(dist2, np.float32)
+        tu = tv = nr = None
+        if tangents is not None:
+            tu, tv, nr = (np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in tangents)
+        n = int(self.L.fd_model_centres(self.ctx)) + 4
+        out = np.empty((1 if tangents is None else 6, n, n), np.float64)
+        self._check(self.L.fd_deform_gram(self.ctx, P.shape[0], _np_ptr(P), _np_ptr(om), _np_ptr(d2), _np_ptr(tu), _np_ptr(tv),
+                                          _np_ptr(nr), float(radius2), float(falloffrate), _np_ptr(out)))
+        return out
+
+    def deform_gram_dev(self, N: int, d_P_in: int, d_H: int, d_omega: int = 0, d_dist2: int = 0, d_tu: int = 0, d_tv: int = 0,
+                        d_nrm: int = 0, radius2=1.0, falloffrate=1.0):
+        """fd_deform_gram_dev: device pointers (ints), asynchronous on the context's stream; d_H is nq x (C + 4) x (C + 4) float64."""
+        vp = C.c_void_p
+        self._check(self.L.fd_deform_gram_dev(self.ctx, N, vp(d_P_in or None), vp(d_omega or None), vp(d_dist2 or None),
+                                              vp(d_tu or None), vp(d_tv or None), vp(d_nrm or None), float(radius2),
+                                              float(falloffrate), vp(d_H or None)))
+
+    def fit_deltas(self, P, T, omega=None, dist2=None, tangents=None, radius2=1.0, falloffrate=1.0, mu=0.0, delta0=None, S=None):
+        """fd_fit_deltas: (delta, report) -- the (M, 3) float64 deltas that minimise sum_v omega_v |D_v(S delta) - (T_v - P_v)|^2
+        + mu |delta - delta0|^2, and the FdFitReport.  S: solve_operator()'s result, or None to have it computed inside."""
+        P = np.ascontiguousarray(P, np.float32).reshape(-1, 3)
+        T = np.ascontiguousarray(T, np.float32).reshape(-1, 3)
+        if T.shape != P.shape:
+            raise ValueError("P and T must have the same shape")
+        om = None if omega is None else np.ascontiguousarray(omega, np.float32)
+        d2 = None if dist2 is None else np.ascontiguousarray(dist2, np.float32)
+        tu = tv = nr = None
+        if tangents is not None:
+            tu, tv, nr = (np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in tangents)
+        d0 = None if delta0 is None else np.ascontiguousarray(delta0, np.float32).reshape(self.M, 3)
+        Sm = None
+        if S is not None:
+            Sm = np.ascontiguousarray(S, np.float64)
+            if Sm.shape != (int(self.L.fd_model_centres(self.ctx)) + 4, self.M):
+                raise ValueError("S must be solve_operator()'s (C + 4, M) array")
+        out = np.empty((self.M, 3), np.float64)
+        rep = FdFitReport()
+        rep.struct_size = C.sizeof(FdFitReport)
+        self._check(self.L.fd_fit_deltas(self.ctx, P.shape[0], _np_ptr(P), _np_ptr(T), _np_ptr(om), _np_ptr(d2), _np_ptr(tu),
+                                         _np_ptr(tv), _np_ptr(nr), float(radius2), float(falloffrate), float(mu), _np_ptr(d0),
+                                         _np_ptr(Sm), _np_ptr(out), C.byref(rep)))
+        return out, rep
 
     def get_weights(self):
         n = int(self.L.fd_model_centres(self.ctx))     # M, or M * layers for the multilayer model

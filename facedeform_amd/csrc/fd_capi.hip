@@ -2,6 +2,8 @@
 // No CPU fallback anywhere: without a gfx950 device fd_create fails loudly.
 #include <algorithm>
 #include <atomic>
+#include <chrono>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -109,6 +111,10 @@ struct fd_ctx {
     // the host call's G goes through d_vecP
     size_t cap_adj = 0;
     double *d_adj = nullptr;
+    // fd_deform_gram*: the workgroups' partial blocks and, behind them, the host call's staging of H (gram_reserve); the host
+    // call's omega goes through d_fall
+    size_t cap_gram = 0;
+    double *d_gram = nullptr;
     // fd_mesh_set: the mesh arrays that stay the same from cook to cook live in their own
     // device buffers (the staging above is evaluated in place, so it cannot serve as a cache)
     int64_t mesh_N = 0, mesh_cap = 0;
@@ -458,6 +464,8 @@ static int invert_host(fd_ctx *ctx, int64_t N, const float *Y, float *X_out, con
                        const float *nrm, float radius2, float falloffrate, const fd_invert_opts *opts);
 static int adjoint_host(fd_ctx *ctx, int64_t N, const float *P_in, const float *G, const float *dist2, const float *tu, const float *tv,
                         const float *nrm, float radius2, float falloffrate, double *grad_W);
+static int gram_host(fd_ctx *ctx, int64_t N, const float *P_in, const float *omega, const float *dist2, const float *tu, const float *tv,
+                     const float *nrm, float radius2, float falloffrate, double *H);
 
 extern "C" {
 
@@ -530,7 +538,7 @@ void fd_destroy(fd_ctx *ctx)
     if (ctx->stream_ || ctx->own_stream) (void)hipStreamSynchronize(cur_stream(ctx));
     void *bufs[] = {ctx->d_rest, ctx->d_delta, ctx->d_centres, ctx->d_radii, ctx->d_W, ctx->d_A,
                     ctx->d_X, ctx->d_ipiv, ctx->d_moves, ctx->d_rec32, ctx->d_rec64, ctx->d_tiles, ctx->d_tiles16, ctx->d_ns, ctx->d_model, ctx->d_slot,
-                    ctx->d_P, ctx->d_dist2, ctx->d_fall, ctx->d_tu, ctx->d_tv, ctx->d_nrm, ctx->d_vec, ctx->d_vecP, ctx->d_iters, ctx->d_adj,
+                    ctx->d_P, ctx->d_dist2, ctx->d_fall, ctx->d_tu, ctx->d_tv, ctx->d_nrm, ctx->d_vec, ctx->d_vecP, ctx->d_iters, ctx->d_adj, ctx->d_gram,
                     ctx->m_P, ctx->m_dist2, ctx->m_tu, ctx->m_tv, ctx->m_nrm, ctx->m_out, ctx->m_fall};
     for (void *p : bufs) if (p) (void)hipFree(p);
     if (ctx->h_model) (void)hipHostFree(ctx->h_model);
@@ -1007,18 +1015,34 @@ static int adjoint_reserve(fd_ctx *ctx, int64_t N, int C)
 }
 static double *adjoint_staging(const fd_ctx *ctx, int64_t N, int C) { return ctx->d_adj + (size_t)adjoint_groups(N) * adjoint_block(C); }
 
+// fd_deform_gram*: the scratch for N vertices, C records and nq components -- gram_partial_doubles partial blocks and, behind
+// them, room for H, where the host call stages it (gram_staging).  Grows on demand.
+static size_t gram_block(int C, int nq) { return (size_t)nq * (size_t)(C + 4) * (size_t)(C + 4); }
+static int gram_reserve(fd_ctx *ctx, int64_t N, int C, int nq)
+{
+    const size_t need = gram_partial_doubles(N, C, nq) + gram_block(C, nq);
+    if (need <= ctx->cap_gram) return FD_OK;
+    ctx->cap_gram = 0;
+    const int rc = dev_alloc(ctx, &ctx->d_gram, need);
+    if (rc) return rc;
+    ctx->cap_gram = need;
+    return FD_OK;
+}
+static double *gram_staging(const fd_ctx *ctx, int64_t N, int C, int nq) { return ctx->d_gram + gram_partial_doubles(N, C, nq); }
+
 // fd_deform_dev_stream / fd_deform_vectors_dev / the staged host calls: vec == nullptr is the deformation alone.
 // fd_invert_dev: inv != nullptr -- the same checks, status poll and ordering, then the inverse's one launch in place of the
 // deformation's (d_P_in = the deformed points, d_P_out = the rest-space points; no fall-off output, no vectors).
 // fd_deform_adjoint_dev: adj != nullptr -- likewise, then the adjoint's two launches (no d_P_out; adj names G and grad_W, the
 // partial blocks are the context's).
+// fd_deform_gram_dev: gram != nullptr -- likewise, the Gram operator's two launches (gram names omega and H).
 static int deform_dev_common(fd_ctx *ctx, void *hip_stream, int64_t N, const float *d_P_in, float *d_P_out,
                              const float *d_dist2, float *d_falloff_out, const float *d_tu, const float *d_tv,
                              const float *d_nrm, float radius2, float falloffrate, const fd_vectors *vec,
-                             const InvertArgs *inv = nullptr, const AdjointArgs *adj = nullptr)
+                             const InvertArgs *inv = nullptr, const AdjointArgs *adj = nullptr, const GramArgs *gram = nullptr)
 {
     hipStream_t launch_stream = hip_stream ? (hipStream_t)hip_stream : cur_stream(ctx);
-    if (N < 0 || (N > 0 && (!d_P_in || (!d_P_out && !adj)))) { set_err(ctx, "fd_deform: bad N / P pointers"); return FD_E_INVALID; }
+    if (N < 0 || (N > 0 && (!d_P_in || (!d_P_out && !adj && !gram)))) { set_err(ctx, "fd_deform: bad N / P pointers"); return FD_E_INVALID; }
     if (!frames_ok(d_tu, d_tv, d_nrm)) { set_err(ctx, "fd_deform: tu, tv, nrm must be all set or all NULL"); return FD_E_INVALID; }
     if (!ctx->built && !ctx->build_pending) { set_err(ctx, "fd_deform: no successfully built model"); return FD_E_NOT_BUILT; }
     if (N == 0) return FD_OK;
@@ -1035,6 +1059,12 @@ static int deform_dev_common(fd_ctx *ctx, void *hip_stream, int64_t N, const flo
         if ((rc = adjoint_reserve(ctx, N, a.M))) return rc;
         const AdjointArgs g{adj->G, adj->grad_W, ctx->d_adj, term_cols(ctx->term)};
         FD_HIP(ctx, launch_adjoint(a, g, launch_stream));
+        return FD_OK;
+    }
+    if (gram) {
+        if ((rc = gram_reserve(ctx, N, a.M, d_tu ? 6 : 1))) return rc;
+        const GramArgs g{gram->omega, gram->H, ctx->d_gram, term_cols(ctx->term)};
+        FD_HIP(ctx, launch_gram(a, g, launch_stream));
         return FD_OK;
     }
     if (!vec) {
@@ -1153,6 +1183,29 @@ int fd_deform_adjoint(fd_ctx *ctx, int64_t N, const float *P_in, const float *G,
     if (!ctx) return FD_E_INVALID;
     if (!G || !grad_W || N < 0) { set_err(ctx, "fd_deform_adjoint: bad N / G / grad_W pointers"); return FD_E_INVALID; }
     return adjoint_host(ctx, N, P_in, G, dist2, tu, tv, nrm, radius2, falloffrate, grad_W);
+}
+
+int fd_deform_gram_dev(fd_ctx *ctx, int64_t N, const float *d_P_in, const float *d_omega, const float *d_dist2, const float *d_tu,
+                       const float *d_tv, const float *d_nrm, float radius2, float falloffrate, double *d_H)
+{
+    if (!ctx) return FD_E_INVALID;
+    if (!d_H || N < 0) { set_err(ctx, "fd_deform_gram: bad N / H pointers"); return FD_E_INVALID; }
+    const GramArgs gram{d_omega, d_H, nullptr, 0};
+    int rc = deform_dev_common(ctx, nullptr, N, d_P_in, nullptr, d_dist2, nullptr, d_tu, d_tv, d_nrm, radius2, falloffrate, nullptr,
+                               nullptr, nullptr, &gram);
+    if (rc || N > 0) return rc;
+    // no vertex: no launch, zeros
+    if ((rc = use_device(ctx))) return rc;
+    FD_HIP(ctx, hipMemsetAsync(d_H, 0, sizeof(double) * gram_block(model_centres(ctx), d_tu ? 6 : 1), cur_stream(ctx)));
+    return FD_OK;
+}
+
+int fd_deform_gram(fd_ctx *ctx, int64_t N, const float *P_in, const float *omega, const float *dist2, const float *tu, const float *tv,
+                   const float *nrm, float radius2, float falloffrate, double *H)
+{
+    if (!ctx) return FD_E_INVALID;
+    if (!H || N < 0) { set_err(ctx, "fd_deform_gram: bad N / H pointers"); return FD_E_INVALID; }
+    return gram_host(ctx, N, P_in, omega, dist2, tu, tv, nrm, radius2, falloffrate, H);
 }
 
 }  // extern "C"
@@ -1333,6 +1386,39 @@ static int adjoint_host(fd_ctx *ctx, int64_t N, const float *P_in, const float *
                            tu ? ctx->d_tv : nullptr, tu ? ctx->d_nrm : nullptr, radius2, falloffrate, nullptr, nullptr, &adj);
     if (rc) return rc;
     FD_HIP(ctx, hipMemcpyAsync(grad_W, d_out, sizeof(double) * adjoint_block(C), hipMemcpyDeviceToHost, s));
+    FD_HIP(ctx, hipStreamSynchronize(s));
+    return FD_OK;
+}
+
+// fd_deform_gram on host arrays: staged like adjoint_host; omega through d_fall, H through the block behind the partial blocks
+static int gram_host(fd_ctx *ctx, int64_t N, const float *P_in, const float *omega, const float *dist2, const float *tu, const float *tv,
+                     const float *nrm, float radius2, float falloffrate, double *H)
+{
+    if (N > 0 && !P_in) { set_err(ctx, "fd_deform_gram: bad N / P pointers"); return FD_E_INVALID; }
+    if (!frames_ok(tu, tv, nrm)) { set_err(ctx, "fd_deform_gram: tu, tv, nrm must be all set or all NULL"); return FD_E_INVALID; }
+    if (!ctx->built && !ctx->build_pending) { set_err(ctx, "fd_deform_gram: no successfully built model"); return FD_E_NOT_BUILT; }
+    const int C = model_centres(ctx), nq = tu ? 6 : 1;
+    if (N == 0) { memset(H, 0, sizeof(double) * gram_block(C, nq)); return FD_OK; }
+    int rc = use_device(ctx);
+    if (rc) return rc;
+    if ((rc = ensure_staging(ctx, N, tu != nullptr))) return rc;
+    if ((rc = gram_reserve(ctx, N, C, nq))) return rc;
+    hipStream_t s = cur_stream(ctx);
+    const size_t b3 = sizeof(float) * 3 * (size_t)N, b1 = sizeof(float) * (size_t)N;
+    FD_HIP(ctx, hipMemcpyAsync(ctx->d_P, P_in, b3, hipMemcpyHostToDevice, s));
+    if (omega) FD_HIP(ctx, hipMemcpyAsync(ctx->d_fall, omega, b1, hipMemcpyHostToDevice, s));
+    if (dist2) FD_HIP(ctx, hipMemcpyAsync(ctx->d_dist2, dist2, b1, hipMemcpyHostToDevice, s));
+    if (tu) {
+        FD_HIP(ctx, hipMemcpyAsync(ctx->d_tu, tu, b3, hipMemcpyHostToDevice, s));
+        FD_HIP(ctx, hipMemcpyAsync(ctx->d_tv, tv, b3, hipMemcpyHostToDevice, s));
+        FD_HIP(ctx, hipMemcpyAsync(ctx->d_nrm, nrm, b3, hipMemcpyHostToDevice, s));
+    }
+    double *d_out = gram_staging(ctx, N, C, nq);
+    const GramArgs gram{omega ? ctx->d_fall : nullptr, d_out, nullptr, 0};
+    rc = deform_dev_common(ctx, nullptr, N, ctx->d_P, nullptr, dist2 ? ctx->d_dist2 : nullptr, nullptr, tu ? ctx->d_tu : nullptr,
+                           tu ? ctx->d_tv : nullptr, tu ? ctx->d_nrm : nullptr, radius2, falloffrate, nullptr, nullptr, nullptr, &gram);
+    if (rc) return rc;
+    FD_HIP(ctx, hipMemcpyAsync(H, d_out, sizeof(double) * gram_block(C, nq), hipMemcpyDeviceToHost, s));
     FD_HIP(ctx, hipStreamSynchronize(s));
     return FD_OK;
 }
@@ -2132,6 +2218,208 @@ int fd_solve_operator(fd_ctx *ctx, double *S)
         batch = nullptr;
     }
     return done(FD_OK);
+}
+
+// ---- fd_fit_deltas: the host composition on top of the Gram operator, the adjoint and the solve operator ----
+// C (m x p) += A^T B for row-major A (k x m), B (k x p): rows of B and C are walked contiguously, k in blocks that stay in cache
+static void fit_atb(int m, int p, int k, const double *A, const double *B, double *Cm)
+{
+    constexpr int kb = 64;
+    for (int k0 = 0; k0 < k; k0 += kb) {
+        const int k1 = k0 + kb < k ? k0 + kb : k;
+        for (int i = 0; i < m; ++i) {
+            double *c = Cm + (size_t)i * p;
+            for (int kk = k0; kk < k1; ++kk) {
+                const double a = A[(size_t)kk * m + i];
+                const double *b = B + (size_t)kk * p;
+                for (int j = 0; j < p; ++j) c[j] += a * b[j];
+            }
+        }
+    }
+}
+
+// a . b with four running sums (a dependent chain of n additions would set the pace of the factorisation)
+static double fit_dot(const double *a, const double *b, int n)
+{
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    int k = 0;
+    for (; k + 4 <= n; k += 4) { s0 += a[k] * b[k]; s1 += a[k + 1] * b[k + 1]; s2 += a[k + 2] * b[k + 2]; s3 += a[k + 3] * b[k + 3]; }
+    for (; k < n; ++k) s0 += a[k] * b[k];
+    return (s0 + s1) + (s2 + s3);
+}
+
+// A = L L^T in place on the lower triangle of the row-major A (order n); the pivots' extremes; false when a pivot is not
+// above n 2^-52 times its diagonal entry, which is where a zero pivot lands in fp64
+static bool fit_cholesky(int n, double *A, double &pmin, double &pmax)
+{
+    pmin = INFINITY; pmax = 0.0;
+    for (int j = 0; j < n; ++j) {
+        double *rj = A + (size_t)j * n;
+        const double ajj = rj[j];
+        const double d = ajj - fit_dot(rj, rj, j);
+        if (!(d > (double)n * 0x1p-52 * ajj) || !(d > 0.0) || !(d < INFINITY)) { pmin = d < pmin || d != d ? d : pmin; return false; }
+        pmin = d < pmin ? d : pmin; pmax = d > pmax ? d : pmax;
+        const double l = sqrt(d), inv = 1.0 / l;
+        rj[j] = l;
+        for (int i = j + 1; i < n; ++i) {
+            double *ri = A + (size_t)i * n;
+            ri[j] = (ri[j] - fit_dot(ri, rj, j)) * inv;
+        }
+    }
+    return true;
+}
+
+// L L^T x = b for nrhs interleaved right-hand sides (b is n x nrhs row-major, overwritten with x)
+static void fit_cholesky_solve(int n, const double *L, int nrhs, double *b)
+{
+    for (int i = 0; i < n; ++i) {
+        const double *ri = L + (size_t)i * n;
+        for (int a = 0; a < nrhs; ++a) {
+            double s = b[(size_t)i * nrhs + a];
+            for (int k = 0; k < i; ++k) s -= ri[k] * b[(size_t)k * nrhs + a];
+            b[(size_t)i * nrhs + a] = s / ri[i];
+        }
+    }
+    for (int i = n - 1; i >= 0; --i) {
+        for (int a = 0; a < nrhs; ++a) {
+            double s = b[(size_t)i * nrhs + a];
+            for (int k = i + 1; k < n; ++k) s -= L[(size_t)k * n + i] * b[(size_t)k * nrhs + a];
+            b[(size_t)i * nrhs + a] = s / L[(size_t)i * n + i];
+        }
+    }
+}
+
+static double fit_ms_since(const std::chrono::steady_clock::time_point &t0)
+{
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+int fd_fit_deltas(fd_ctx *ctx, int64_t N, const float *P_in, const float *T, const float *omega, const float *dist2, const float *tu,
+                  const float *tv, const float *nrm, float radius2, float falloffrate, double mu, const float *delta0,
+                  const double *S, double *delta_out, fd_fit_report *report)
+{
+    if (!ctx) return FD_E_INVALID;
+    if (!T || !delta_out || N < 0 || (N > 0 && !P_in)) { set_err(ctx, "fd_fit_deltas: bad N / P / T / delta_out pointers"); return FD_E_INVALID; }
+    if (!(mu >= 0.0) || !(mu < INFINITY)) { set_err(ctx, "fd_fit_deltas: mu must be finite and >= 0"); return FD_E_INVALID; }
+    if (report && report->struct_size < (int)sizeof(fd_fit_report)) {
+        set_err(ctx, "fd_fit_deltas: report->struct_size is %d, must be sizeof(fd_fit_report) = %d", report->struct_size,
+                (int)sizeof(fd_fit_report));
+        return FD_E_INVALID;
+    }
+    if (!frames_ok(tu, tv, nrm)) { set_err(ctx, "fd_fit_deltas: tu, tv, nrm must be all set or all NULL"); return FD_E_INVALID; }
+    const int M = ctx->M, C = model_centres(ctx), n = C + 4;
+    const bool proj = tu != nullptr;
+    const int nq = proj ? 6 : 1, order = proj ? 3 * M : M;
+    if (n > FD_FIT_MAX_ROWS || order > FD_FIT_MAX_ORDER) {
+        set_err(ctx, "fd_fit_deltas: C + 4 = %d (at most %d) or the order of the normal system %d (at most %d) is beyond the host composition",
+                n, FD_FIT_MAX_ROWS, order, FD_FIT_MAX_ORDER);
+        return FD_E_INVALID;
+    }
+    if (!ctx->built && !ctx->build_pending) { set_err(ctx, "fd_fit_deltas: no successfully built model"); return FD_E_NOT_BUILT; }
+    int rc;
+    std::vector<double> S_own;
+    if (!S) {
+        S_own.resize((size_t)n * M);
+        if ((rc = fd_solve_operator(ctx, S_own.data()))) return rc;
+        S = S_own.data();
+    }
+    // ---- the second-order term
+    auto t0 = std::chrono::steady_clock::now();
+    std::vector<double> H((size_t)nq * n * n);
+    if ((rc = gram_host(ctx, N, P_in, omega, dist2, tu, tv, nrm, radius2, falloffrate, H.data()))) return rc;
+    const double ms_gram = fit_ms_since(t0);
+    // ---- the first-order term: the adjoint of g = omega (T - P), the difference and the product in fp32
+    t0 = std::chrono::steady_clock::now();
+    std::vector<float> g((size_t)N * 3);
+    double tt = 0.0;                                   // sum_v omega_v |T_v - P_v|^2
+    for (int64_t v = 0; v < N; ++v) {
+        const float w = omega ? omega[v] : 1.f;
+        double t2 = 0.0;
+        for (int a = 0; a < 3; ++a) {
+            const float d = T[3 * v + a] - P_in[3 * v + a];
+            g[3 * v + a] = w * d;
+            t2 += (double)d * (double)d;
+        }
+        if (w != 0.f) tt += (double)w * t2;
+    }
+    std::vector<double> c((size_t)n * 3);
+    if ((rc = adjoint_host(ctx, N, P_in, g.data(), dist2, tu, tv, nrm, radius2, falloffrate, c.data()))) return rc;
+    const double ms_adjoint = fit_ms_since(t0);
+    // ---- the normal system in the deltas: unknown 3 i + b with projection (order 3 M), else M with three right-hand sides
+    t0 = std::chrono::steady_clock::now();
+    std::vector<double> G((size_t)nq * M * M, 0.0);     // S^T H_q S
+    {
+        std::vector<double> HS((size_t)n * M);
+        for (int q = 0; q < nq; ++q) {
+            std::fill(HS.begin(), HS.end(), 0.0);
+            fit_atb(n, M, n, H.data() + (size_t)q * n * n, S, HS.data());          // H_q is symmetric: H_q^T S
+            fit_atb(M, M, n, S, HS.data(), G.data() + (size_t)q * M * M);
+        }
+    }
+    std::vector<double> b((size_t)M * 3, 0.0);          // S^T c + mu delta0, M x 3
+    fit_atb(M, 3, n, S, c.data(), b.data());
+    std::vector<double> Stc = b;
+    if (delta0) for (size_t i = 0; i < (size_t)M * 3; ++i) b[i] += mu * (double)delta0[i];
+    static const int qmap[3][3] = {{0, 1, 2}, {1, 3, 4}, {2, 4, 5}};
+    auto Gat = [&](int i, int bb, int k, int cc) -> double {        // the (3 i + bb, 3 k + cc) entry of the block form, without mu
+        if (!proj) return bb == cc ? G[(size_t)i * M + k] : 0.0;
+        return G[(size_t)qmap[bb][cc] * M * M + (size_t)i * M + k];
+    };
+    // the energy of a delta (M x 3) by the quadratic form: d^T G d - 2 d^T S^T c + tt + mu |d - delta0|^2
+    auto energy = [&](const double *d) {
+        long double e = tt;
+        for (int i = 0; i < M; ++i)
+            for (int bb = 0; bb < 3; ++bb) {
+                long double row = 0.0L;
+                for (int k = 0; k < M; ++k)
+                    for (int cc = 0; cc < 3; ++cc) {
+                        if (!proj && cc != bb) continue;
+                        row += (long double)Gat(i, bb, k, cc) * d[3 * k + cc];
+                    }
+                const long double di = d[3 * i + bb], d0 = delta0 ? (long double)delta0[3 * i + bb] : 0.0L;
+                e += di * row - 2.0L * di * Stc[3 * i + bb] + (long double)mu * (di - d0) * (di - d0);
+            }
+        return (double)e;
+    };
+    std::vector<double> d0v((size_t)M * 3, 0.0);
+    if (delta0) for (size_t i = 0; i < (size_t)M * 3; ++i) d0v[i] = (double)delta0[i];
+    const double E0 = energy(d0v.data());
+    std::vector<double> A((size_t)order * order);
+    if (proj) {
+        for (int i = 0; i < M; ++i)
+            for (int bb = 0; bb < 3; ++bb)
+                for (int k = 0; k < M; ++k)
+                    for (int cc = 0; cc < 3; ++cc)
+                        A[(size_t)(3 * i + bb) * order + 3 * k + cc] = Gat(i, bb, k, cc) + (i == k && bb == cc ? mu : 0.0);
+    } else {
+        for (int i = 0; i < M; ++i)
+            for (int k = 0; k < M; ++k) A[(size_t)i * M + k] = G[(size_t)i * M + k] + (i == k ? mu : 0.0);
+    }
+    const double ms_compose = fit_ms_since(t0);
+    // ---- the solve
+    t0 = std::chrono::steady_clock::now();
+    double pmin = 0.0, pmax = 0.0;
+    const bool ok = order == 0 || fit_cholesky(order, A.data(), pmin, pmax);
+    if (ok && order > 0) {
+        // without projection b is M x 3: three interleaved right-hand sides; with it b is one vector of 3 M in the same memory order
+        fit_cholesky_solve(order, A.data(), proj ? 1 : 3, b.data());
+    }
+    const double ms_solve = fit_ms_since(t0);
+    if (report) {
+        report->order = order;
+        report->E0 = E0;
+        report->E_fit = ok ? energy(b.data()) : E0;
+        report->pivot_min = order > 0 ? pmin : 0.0;
+        report->pivot_max = pmax;
+        report->ms_gram = ms_gram; report->ms_adjoint = ms_adjoint; report->ms_compose = ms_compose; report->ms_solve = ms_solve;
+    }
+    if (!ok) {
+        set_err(ctx, "fd_fit_deltas: the normal matrix is not positive definite (pivot %.3e): control points that no live vertex "
+                     "constrains need mu > 0", pmin);
+        return FD_E_SINGULAR;
+    }
+    for (size_t i = 0; i < (size_t)M * 3; ++i) delta_out[i] = b[i];
+    return FD_OK;
 }
 
 // One launch evaluates every context of the batch on its own vertex arrays (grid y = context)

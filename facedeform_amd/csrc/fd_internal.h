@@ -304,6 +304,18 @@ struct AdjointArgs {
 };
 int adjoint_groups(int64_t N);        // workgroups along the vertices: a function of N alone
 hipError_t launch_adjoint(const DeformArgs &a, const AdjointArgs &g, hipStream_t stream);
+// the Gram operator of the deformation (fd_gram.hip, fd_deform_gram*): `a` as for the adjoint; omega the per-vertex weights
+// (N, or null for 1), H the nq x (M + 4) x (M + 4) result (nq = 6 with projection frames, else 1), T as above, partial a
+// scratch of gram_partial_doubles(N, M, nq) doubles.  Two launches; N = 0 writes zeros.
+struct GramArgs {
+    const float *omega;
+    double *H;
+    double *partial;
+    int T;
+};
+int gram_ranges(int64_t N, int C);    // workgroups along the vertices: a function of N and C alone
+size_t gram_partial_doubles(int64_t N, int C, int nq);
+hipError_t launch_gram(const DeformArgs &a, const GramArgs &g, hipStream_t stream);
 hipError_t launch_deform_batch(const DeformArgs *a, int n, hipStream_t stream);
 // frames that share the mesh and the rest rig (fd_eval.hip, k_deform32_tps_shared): phi once per
 // (vertex, centre), the 3 F-wide weight contraction on the matrix pipe

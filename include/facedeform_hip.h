@@ -395,6 +395,85 @@ int fd_deform_adjoint(fd_ctx *ctx, int64_t N, const float *P_in, const float *G,
  * The gradient for the deltas is then one small product on the caller's side:  grad_delta = S^T . grad_W  (M x 3). */
 int fd_solve_operator(fd_ctx *ctx, double *S);
 
+/* ---- the Gram operator and the fit ------------------------------------------------
+ * The deformation is linear in the weights and the weights are linear in the deltas (W = S delta, fd_solve_operator), so
+ * fitting the deformed mesh to target positions by least squares is ONE linear problem.  Its second-order term is the Gram
+ * matrix of the forward map over the vertices, which fd_deform_gram returns; fd_fit_deltas composes it with the adjoint and S
+ * and solves for the deltas.
+ *
+ * Notation.  For vertex v, Psi_v is the row of length C+4 that multiplies W in fd_get_weights' layout and convention: its
+ *   first C entries are phi_j(x_v) times the factor the records' weights carry, then 1, x, y, z.
+ *   D_v(W) = f_v Pi_v (Psi_v W).
+ * With optional per-vertex fp32 weights omega_v >= 0 (NULL means 1):
+ *   H[q][j][k] = sum_v omega_v f_v^2 (Pi_v^2)[b][c] Psi_vj Psi_vk        q <-> (b,c)
+ * The contract.  For the built model and any W', W'' in fd_get_weights' layout,
+ *   sum_{b,c} sum_{j,k} W'[j][b] H[q(b,c)][j][k] W''[k][c] = sum_v omega_v D_v(W') . D_v(W''),
+ *   D what FD_OUTPUT_DISPLACEMENT defines, evaluated exactly.
+ * Pi is not idempotent: the projection axes a1, a2 are normalised but not orthogonalised, so the weight is Pi_v^2, not Pi_v.
+ *   Pi_v is formed with the forward path's own code and squared in fp64.
+ * Output.  nq x (C+4) x (C+4) fp64 row-major.  Without projection frames nq = 1 (Pi = I; H (x) I_3 is the full operator);
+ *   with projection frames nq = 6, ordered xx, xy, xz, yy, yz, zz.  Both triangles are written, and the lower is the mirror of
+ *   the upper bit for bit.  Multilayer records come out in fd_get_weights' layer-major order.  Rows and columns of polynomial
+ *   terms the model lacks are 0.0.  Only the nq (C+4)^2 entries are written.
+ * Arithmetic.  The adjoint's: everything is fp64 whatever fd_set_eval_precision says, x - c_j in raw coordinates, phi of the
+ *   kind as the inverse forms it; the gate, f and Pi are the forward path's own code.  The products run on the fp64 matrix pipe.
+ * Vertices that contribute nothing.  A gated vertex, a vertex with f = 0 and a vertex with omega = 0 contribute exactly
+ *   nothing whatever P or omega hold there, NaN included (a select, not a product).  A model with terminationtype != 1, or
+ *   N = 0, gives zeros and FD_OK.
+ * Determinism.  No atomics: workgroups write partial blocks that a second launch adds in a fixed order.  The number of vertex
+ *   ranges is a function of N and C alone; the same inputs give the same bits on every call, and the host and device-pointer
+ *   forms agree bit for bit.  The scratch for partial blocks lives in the context and is bounded by lowering the number of
+ *   ranges: at most 256 ranges, and at most 256 MiB with all six components (one range above that; C + 4 <= 2352 stays inside).
+ * Checks and errors.  FD_E_INVALID for a NULL context, a NULL H or N < 0 comes before any device work.  The build-status poll
+ *   and repair, FD_E_NOT_BUILT, the all-or-none rule for tu/tv/nrm and the ordering behind a batched build are fd_deform's.
+ *   fd_set_output has no effect.
+ *
+ * Device pointers, asynchronous on the context's stream (two launches). */
+int fd_deform_gram_dev(fd_ctx *ctx, int64_t N, const float *d_P_in, const float *d_omega, const float *d_dist2,
+                       const float *d_tu, const float *d_tv, const float *d_nrm,
+                       float radius2, float falloffrate, double *d_H);
+/* Same, host arrays, staged through the context's buffers as fd_deform_adjoint's; synchronous. */
+int fd_deform_gram(fd_ctx *ctx, int64_t N, const float *P_in, const float *omega, const float *dist2,
+                   const float *tu, const float *tv, const float *nrm,
+                   float radius2, float falloffrate, double *H);
+
+/* fd_fit_deltas minimises over delta (M x 3)
+ *   E(delta) = sum_v omega_v |D_v(S delta) - (T_v - P_v)|^2 + mu sum_i |delta_i - delta0_i|^2
+ * for the context's rest rig, kernel and term: the mesh arguments of fd_deform (host arrays), targets T (N x 3 fp32), omega
+ * (N fp32 or NULL for 1), mu >= 0, delta0 (M x 3 fp32, or NULL for 0) and S -- what fd_solve_operator returned, which the
+ * caller keeps while the rest rig stands, or NULL to have it computed inside the call.  A host composition, no new kernel:
+ *   right-hand side  S^T . fd_deform_adjoint(g) + mu delta0,  g_v = omega_v (T_v - P_v): the difference and the product by
+ *                    omega_v are formed in fp32 (the cotangent fd_deform_adjoint takes is fp32); everything after is fp64.
+ *   normal matrix    without projection S^T H S + mu I, of order M, solved with three right-hand sides; with projection the
+ *                    3M x 3M block form of S^T H_q S (unknown 3 i + b).  Plain blocked loops and a Cholesky factorisation on
+ *                    the host in fp64.  FD_E_SINGULAR when a pivot is not positive -- not above order . 2^-52 times its
+ *                    diagonal entry, which is where a zero pivot lands in fp64: mu = 0 and control points that no live
+ *                    vertex constrains.
+ * Limits.  FD_E_INVALID, with a message, when C + 4 > FD_FIT_MAX_ROWS (1028) or the order of the system exceeds
+ *   FD_FIT_MAX_ORDER (3072): the host composition is O(order^3) and is not meant for more.
+ * Outputs.  delta_out, M x 3 fp64 (the caller rounds it for fd_set_deltas), and, unless report is NULL, an fd_fit_report.
+ * State.  The context's model, deltas and stored factorisation are left as they were.
+ * Checks and errors.  FD_E_INVALID for a NULL context, NULL T or delta_out, N < 0, mu < 0 or not finite, a report whose
+ *   struct_size is too small, a bad frame triple, or a limit above comes before any device work; then FD_E_NOT_BUILT, and
+ *   whatever fd_solve_operator, fd_deform_gram or fd_deform_adjoint return.  Synchronous. */
+#define FD_FIT_MAX_ROWS 1028
+#define FD_FIT_MAX_ORDER 3072
+typedef struct fd_fit_report {
+    int struct_size;      /* = sizeof(fd_fit_report); smaller is FD_E_INVALID */
+    int order;            /* the order of the system solved: M, or 3 M with projection frames */
+    double E0;            /* E(delta0) */
+    double E_fit;         /* E at the solution, predicted from the quadratic form */
+    double pivot_min;     /* the smallest and the largest Cholesky pivot (before the square root); on FD_E_SINGULAR */
+    double pivot_max;     /*   pivot_min is the pivot that failed */
+    double ms_gram;       /* milliseconds in fd_deform_gram, fd_deform_adjoint (with forming g), the composition of the */
+    double ms_adjoint;    /*   normal system, and the factorisation and solve */
+    double ms_compose;
+    double ms_solve;
+} fd_fit_report;
+int fd_fit_deltas(fd_ctx *ctx, int64_t N, const float *P_in, const float *T, const float *omega, const float *dist2,
+                  const float *tu, const float *tv, const float *nrm, float radius2, float falloffrate,
+                  double mu, const float *delta0, const double *S, double *delta_out, fd_fit_report *report);
+
 /* ---- device-resident mesh (next row N3, engine side) --------------------------
  * In an animated shot the mesh on input 0 -- P, the capture's dist2, the tangent
  * frames -- is the same from cook to cook (Houdini tells by the attributes' data
