@@ -92,7 +92,7 @@ class FdsopShot(C.Structure):
 EXPORTS = [
     "fd_create", "fd_destroy", "fd_last_error", "fd_abi_version", "fd_set_stream", "fd_set_eval_precision", "fd_set_output", "fd_fp32_holds", "fd_set_points",
     "fd_set_points_dev", "fd_set_deltas", "fd_set_deltas_dev", "fd_set_kernel", "fd_set_term", "fd_build", "fd_build_async",
-    "fd_build_result", "fd_deform", "fd_deform_dev", "fd_deform_dev_stream", "fd_deform_vectors", "fd_deform_vectors_dev", "fd_invert", "fd_invert_dev", "fd_deform_adjoint", "fd_deform_adjoint_dev", "fd_solve_operator", "fd_deform_gram", "fd_deform_gram_dev", "fd_fit_deltas", "fd_get_weights", "fd_model_centres", "fd_model_bytes",
+    "fd_build_result", "fd_deform", "fd_deform_dev", "fd_deform_dev_stream", "fd_deform_vectors", "fd_deform_vectors_dev", "fd_invert", "fd_invert_dev", "fd_deform_adjoint", "fd_deform_adjoint_dev", "fd_solve_operator", "fd_deform_gram", "fd_deform_gram_dev", "fd_fit_deltas", "fd_deform_adjoint_shot", "fd_deform_adjoint_shot_dev", "fd_fit_deltas_shot", "fd_get_weights", "fd_model_centres", "fd_model_bytes",
     "fd_export_model", "fd_import_model", "fd_synchronize", "fd_host_alloc", "fd_host_free",
     "fd_mesh_set", "fd_mesh_size", "fd_deform_mesh", "fd_mesh_capture", "fd_mesh_get_dist2",
     "fd_capture_dist2", "fd_capture_dist2_dev", "fd_capture_islands", "fd_capture_islands_dev",
@@ -180,6 +180,12 @@ def load() -> C.CDLL:
     L.fd_deform_gram_dev.restype = i32
     L.fd_fit_deltas.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, C.c_double, vp, vp, vp, vp]
     L.fd_fit_deltas.restype = i32
+    L.fd_deform_adjoint_shot.argtypes = [vp, i64, C.c_int, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, vp]
+    L.fd_deform_adjoint_shot.restype = i32
+    L.fd_deform_adjoint_shot_dev.argtypes = [vp, i64, C.c_int, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, vp]
+    L.fd_deform_adjoint_shot_dev.restype = i32
+    L.fd_fit_deltas_shot.argtypes = [vp, i64, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, C.c_double, vp, vp, vp, vp]
+    L.fd_fit_deltas_shot.restype = i32
     L.fd_get_weights.argtypes = [vp, _f64p, _f64p]; L.fd_get_weights.restype = i32
     L.fd_model_centres.argtypes = [vp]; L.fd_model_centres.restype = i32
     L.fd_model_bytes.argtypes = [vp]; L.fd_model_bytes.restype = sz
@@ -619,6 +625,60 @@ class Engine:
                                          _np_ptr(tv), _np_ptr(nr), float(radius2), float(falloffrate), float(mu), _np_ptr(d0),
                                          _np_ptr(Sm), _np_ptr(out), C.byref(rep)))
         return out, rep
+
+    def deform_adjoint_shot(self, P, G, dist2=None, tangents=None, radius2=1.0, falloffrate=1.0):
+        """fd_deform_adjoint_shot: (F, C + 4, 3) float64, frame f's block being deform_adjoint's result for the cotangent G[f];
+        G is (F, N, 3).  One matrix-pipe launch per 32 frames; frame f's bits do not depend on the other frames."""
+        P = np.ascontiguousarray(P, np.float32).reshape(-1, 3)
+        G = np.ascontiguousarray(G, np.float32)
+        if G.ndim != 3 or G.shape[0] < 1 or G.shape[1:] != P.shape:
+            raise ValueError("G must be (F, N, 3) with F >= 1 and P (N, 3)")
+        d2 = None if dist2 is None else np.ascontiguousarray(dist2, np.float32)
+        tu = tv = nr = None
+        if tangents is not None:
+            tu, tv, nr = (np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in tangents)
+        out = np.empty((G.shape[0], int(self.L.fd_model_centres(self.ctx)) + 4, 3), np.float64)
+        self._check(self.L.fd_deform_adjoint_shot(self.ctx, P.shape[0], G.shape[0], _np_ptr(P), _np_ptr(G), _np_ptr(d2), _np_ptr(tu),
+                                                  _np_ptr(tv), _np_ptr(nr), float(radius2), float(falloffrate), _np_ptr(out)))
+        return out
+
+    def deform_adjoint_shot_dev(self, N: int, F: int, d_P_in: int, d_G: int, d_grad_W: int, d_dist2: int = 0, d_tu: int = 0,
+                                d_tv: int = 0, d_nrm: int = 0, radius2=1.0, falloffrate=1.0):
+        """fd_deform_adjoint_shot_dev: device pointers (ints), asynchronous on the context's stream; d_G is F x N x 3 float32,
+        d_grad_W F x (C + 4) x 3 float64."""
+        vp = C.c_void_p
+        self._check(self.L.fd_deform_adjoint_shot_dev(self.ctx, N, int(F), vp(d_P_in or None), vp(d_G or None), vp(d_dist2 or None),
+                                                      vp(d_tu or None), vp(d_tv or None), vp(d_nrm or None), float(radius2),
+                                                      float(falloffrate), vp(d_grad_W or None)))
+
+    def fit_deltas_shot(self, P, T, omega=None, dist2=None, tangents=None, radius2=1.0, falloffrate=1.0, mu=0.0, delta0=None, S=None):
+        """fd_fit_deltas_shot: (deltas, reports) -- fit_deltas for the F targets T[f] (T is (F, N, 3)) over one mesh, omega and
+        mu, with one Gram launch, one factorisation and the shot adjoint: deltas is (F, M, 3) float64, reports a list of F
+        FdFitReport.  delta0: (F, M, 3) or None.  S: solve_operator()'s result, or None to have it computed inside."""
+        P = np.ascontiguousarray(P, np.float32).reshape(-1, 3)
+        T = np.ascontiguousarray(T, np.float32)
+        if T.ndim != 3 or T.shape[0] < 1 or T.shape[1:] != P.shape:
+            raise ValueError("T must be (F, N, 3) with F >= 1 and P (N, 3)")
+        F = T.shape[0]
+        om = None if omega is None else np.ascontiguousarray(omega, np.float32)
+        d2 = None if dist2 is None else np.ascontiguousarray(dist2, np.float32)
+        tu = tv = nr = None
+        if tangents is not None:
+            tu, tv, nr = (np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in tangents)
+        d0 = None if delta0 is None else np.ascontiguousarray(delta0, np.float32).reshape(F, self.M, 3)
+        Sm = None
+        if S is not None:
+            Sm = np.ascontiguousarray(S, np.float64)
+            if Sm.shape != (int(self.L.fd_model_centres(self.ctx)) + 4, self.M):
+                raise ValueError("S must be solve_operator()'s (C + 4, M) array")
+        out = np.empty((F, self.M, 3), np.float64)
+        reps = (FdFitReport * F)()
+        for r in reps:
+            r.struct_size = C.sizeof(FdFitReport)
+        self._check(self.L.fd_fit_deltas_shot(self.ctx, P.shape[0], F, _np_ptr(P), _np_ptr(T), _np_ptr(om), _np_ptr(d2), _np_ptr(tu),
+                                              _np_ptr(tv), _np_ptr(nr), float(radius2), float(falloffrate), float(mu), _np_ptr(d0),
+                                              _np_ptr(Sm), _np_ptr(out), reps))
+        return out, list(reps)
 
     def get_weights(self):
         n = int(self.L.fd_model_centres(self.ctx))     # M, or M * layers for the multilayer model

@@ -115,6 +115,14 @@ struct fd_ctx {
     // call's omega goes through d_fall
     size_t cap_gram = 0;
     double *d_gram = nullptr;
+    // fd_deform_adjoint_shot*: the ranges' partial blocks of one group of frames and, behind them, the host call's staging of
+    // grad_W (adjoint_shot_reserve); the host call's G goes group by group through d_gshot
+    size_t cap_adjs = 0, cap_gshot = 0;
+    double *d_adjs = nullptr;
+    float *d_gshot = nullptr;
+    // fd_fit_deltas_shot: a group's cotangents g_f = omega (T_f - P) on the host (malloc)
+    size_t cap_hgshot = 0;
+    float *h_gshot = nullptr;
     // fd_mesh_set: the mesh arrays that stay the same from cook to cook live in their own
     // device buffers (the staging above is evaluated in place, so it cannot serve as a cache)
     int64_t mesh_N = 0, mesh_cap = 0;
@@ -466,6 +474,8 @@ static int adjoint_host(fd_ctx *ctx, int64_t N, const float *P_in, const float *
                         const float *nrm, float radius2, float falloffrate, double *grad_W);
 static int gram_host(fd_ctx *ctx, int64_t N, const float *P_in, const float *omega, const float *dist2, const float *tu, const float *tv,
                      const float *nrm, float radius2, float falloffrate, double *H);
+static int adjoint_shot_host(fd_ctx *ctx, int64_t N, int F, const float *P_in, const float *G, const float *dist2, const float *tu,
+                             const float *tv, const float *nrm, float radius2, float falloffrate, double *grad_W, bool mesh_staged);
 
 extern "C" {
 
@@ -538,9 +548,10 @@ void fd_destroy(fd_ctx *ctx)
     if (ctx->stream_ || ctx->own_stream) (void)hipStreamSynchronize(cur_stream(ctx));
     void *bufs[] = {ctx->d_rest, ctx->d_delta, ctx->d_centres, ctx->d_radii, ctx->d_W, ctx->d_A,
                     ctx->d_X, ctx->d_ipiv, ctx->d_moves, ctx->d_rec32, ctx->d_rec64, ctx->d_tiles, ctx->d_tiles16, ctx->d_ns, ctx->d_model, ctx->d_slot,
-                    ctx->d_P, ctx->d_dist2, ctx->d_fall, ctx->d_tu, ctx->d_tv, ctx->d_nrm, ctx->d_vec, ctx->d_vecP, ctx->d_iters, ctx->d_adj, ctx->d_gram,
+                    ctx->d_P, ctx->d_dist2, ctx->d_fall, ctx->d_tu, ctx->d_tv, ctx->d_nrm, ctx->d_vec, ctx->d_vecP, ctx->d_iters, ctx->d_adj, ctx->d_gram, ctx->d_adjs, ctx->d_gshot,
                     ctx->m_P, ctx->m_dist2, ctx->m_tu, ctx->m_tv, ctx->m_nrm, ctx->m_out, ctx->m_fall};
     for (void *p : bufs) if (p) (void)hipFree(p);
+    free(ctx->h_gshot);
     if (ctx->h_model) (void)hipHostFree(ctx->h_model);
     if (ctx->h_header) (void)hipHostFree(ctx->h_header);
     if (ctx->h_status) (void)hipHostFree(ctx->h_status);
@@ -1030,19 +1041,37 @@ static int gram_reserve(fd_ctx *ctx, int64_t N, int C, int nq)
 }
 static double *gram_staging(const fd_ctx *ctx, int64_t N, int C, int nq) { return ctx->d_gram + gram_partial_doubles(N, C, nq); }
 
+// fd_deform_adjoint_shot*: the scratch for N vertices and C records -- adjoint_shot_partial_doubles partial blocks, which the
+// groups of frames use one after the other, and behind them room for `staged` frames' grad_W, where the host call stages its
+// result (adjoint_shot_staging).  Grows on demand and never shrinks: the launch's own reserve (staged = 0) keeps the host call's.
+static int adjoint_shot_reserve(fd_ctx *ctx, int64_t N, int C, int staged)
+{
+    const size_t need = adjoint_shot_partial_doubles(N, C) + (size_t)staged * adjoint_block(C);
+    if (need <= ctx->cap_adjs) return FD_OK;
+    ctx->cap_adjs = 0;
+    const int rc = dev_alloc(ctx, &ctx->d_adjs, need);
+    if (rc) return rc;
+    ctx->cap_adjs = need;
+    return FD_OK;
+}
+static double *adjoint_shot_staging(const fd_ctx *ctx, int64_t N, int C) { return ctx->d_adjs + adjoint_shot_partial_doubles(N, C); }
+
 // fd_deform_dev_stream / fd_deform_vectors_dev / the staged host calls: vec == nullptr is the deformation alone.
 // fd_invert_dev: inv != nullptr -- the same checks, status poll and ordering, then the inverse's one launch in place of the
 // deformation's (d_P_in = the deformed points, d_P_out = the rest-space points; no fall-off output, no vectors).
 // fd_deform_adjoint_dev: adj != nullptr -- likewise, then the adjoint's two launches (no d_P_out; adj names G and grad_W, the
 // partial blocks are the context's).
 // fd_deform_gram_dev: gram != nullptr -- likewise, the Gram operator's two launches (gram names omega and H).
+// fd_deform_adjoint_shot_dev: shot != nullptr -- likewise, the shot adjoint's two launches per group of frames (shot names G,
+// grad_W and F).
 static int deform_dev_common(fd_ctx *ctx, void *hip_stream, int64_t N, const float *d_P_in, float *d_P_out,
                              const float *d_dist2, float *d_falloff_out, const float *d_tu, const float *d_tv,
                              const float *d_nrm, float radius2, float falloffrate, const fd_vectors *vec,
-                             const InvertArgs *inv = nullptr, const AdjointArgs *adj = nullptr, const GramArgs *gram = nullptr)
+                             const InvertArgs *inv = nullptr, const AdjointArgs *adj = nullptr, const GramArgs *gram = nullptr,
+                             const AdjointShotArgs *shot = nullptr)
 {
     hipStream_t launch_stream = hip_stream ? (hipStream_t)hip_stream : cur_stream(ctx);
-    if (N < 0 || (N > 0 && (!d_P_in || (!d_P_out && !adj && !gram)))) { set_err(ctx, "fd_deform: bad N / P pointers"); return FD_E_INVALID; }
+    if (N < 0 || (N > 0 && (!d_P_in || (!d_P_out && !adj && !gram && !shot)))) { set_err(ctx, "fd_deform: bad N / P pointers"); return FD_E_INVALID; }
     if (!frames_ok(d_tu, d_tv, d_nrm)) { set_err(ctx, "fd_deform: tu, tv, nrm must be all set or all NULL"); return FD_E_INVALID; }
     if (!ctx->built && !ctx->build_pending) { set_err(ctx, "fd_deform: no successfully built model"); return FD_E_NOT_BUILT; }
     if (N == 0) return FD_OK;
@@ -1065,6 +1094,12 @@ static int deform_dev_common(fd_ctx *ctx, void *hip_stream, int64_t N, const flo
         if ((rc = gram_reserve(ctx, N, a.M, d_tu ? 6 : 1))) return rc;
         const GramArgs g{gram->omega, gram->H, ctx->d_gram, term_cols(ctx->term)};
         FD_HIP(ctx, launch_gram(a, g, launch_stream));
+        return FD_OK;
+    }
+    if (shot) {
+        if ((rc = adjoint_shot_reserve(ctx, N, a.M, 0))) return rc;
+        const AdjointShotArgs g{shot->G, shot->grad_W, ctx->d_adjs, shot->F, term_cols(ctx->term)};
+        FD_HIP(ctx, launch_adjoint_shot(a, g, launch_stream));
         return FD_OK;
     }
     if (!vec) {
@@ -1206,6 +1241,30 @@ int fd_deform_gram(fd_ctx *ctx, int64_t N, const float *P_in, const float *omega
     if (!ctx) return FD_E_INVALID;
     if (!H || N < 0) { set_err(ctx, "fd_deform_gram: bad N / H pointers"); return FD_E_INVALID; }
     return gram_host(ctx, N, P_in, omega, dist2, tu, tv, nrm, radius2, falloffrate, H);
+}
+
+int fd_deform_adjoint_shot_dev(fd_ctx *ctx, int64_t N, int F, const float *d_P_in, const float *d_G, const float *d_dist2,
+                               const float *d_tu, const float *d_tv, const float *d_nrm, float radius2, float falloffrate,
+                               double *d_grad_W)
+{
+    if (!ctx) return FD_E_INVALID;
+    if (!d_G || !d_grad_W || N < 0 || F < 1) { set_err(ctx, "fd_deform_adjoint_shot: bad N / F / G / grad_W pointers"); return FD_E_INVALID; }
+    const AdjointShotArgs shot{d_G, d_grad_W, nullptr, F, 0};
+    int rc = deform_dev_common(ctx, nullptr, N, d_P_in, nullptr, d_dist2, nullptr, d_tu, d_tv, d_nrm, radius2, falloffrate, nullptr,
+                               nullptr, nullptr, nullptr, &shot);
+    if (rc || N > 0) return rc;
+    // no vertex: no launch, zeros
+    if ((rc = use_device(ctx))) return rc;
+    FD_HIP(ctx, hipMemsetAsync(d_grad_W, 0, sizeof(double) * (size_t)F * adjoint_block(model_centres(ctx)), cur_stream(ctx)));
+    return FD_OK;
+}
+
+int fd_deform_adjoint_shot(fd_ctx *ctx, int64_t N, int F, const float *P_in, const float *G, const float *dist2, const float *tu,
+                           const float *tv, const float *nrm, float radius2, float falloffrate, double *grad_W)
+{
+    if (!ctx) return FD_E_INVALID;
+    if (!G || !grad_W || N < 0 || F < 1) { set_err(ctx, "fd_deform_adjoint_shot: bad N / F / G / grad_W pointers"); return FD_E_INVALID; }
+    return adjoint_shot_host(ctx, N, F, P_in, G, dist2, tu, tv, nrm, radius2, falloffrate, grad_W, false);
 }
 
 }  // extern "C"
@@ -1419,6 +1478,55 @@ static int gram_host(fd_ctx *ctx, int64_t N, const float *P_in, const float *ome
                            tu ? ctx->d_tv : nullptr, tu ? ctx->d_nrm : nullptr, radius2, falloffrate, nullptr, nullptr, nullptr, &gram);
     if (rc) return rc;
     FD_HIP(ctx, hipMemcpyAsync(H, d_out, sizeof(double) * gram_block(C, nq), hipMemcpyDeviceToHost, s));
+    FD_HIP(ctx, hipStreamSynchronize(s));
+    return FD_OK;
+}
+
+// fd_deform_adjoint_shot on host arrays: the mesh staged like adjoint_host (mesh_staged: a host call before this one has left
+// these very arrays in the staging buffers, fd_fit_deltas_shot's gram_host); G goes through d_gshot one group of FD_MAX_BATCH
+// frames at a time, each group's launches behind its copy on the stream; grad_W of all frames is staged behind the partial
+// blocks and comes back in one copy
+static int adjoint_shot_host(fd_ctx *ctx, int64_t N, int F, const float *P_in, const float *G, const float *dist2, const float *tu,
+                             const float *tv, const float *nrm, float radius2, float falloffrate, double *grad_W, bool mesh_staged)
+{
+    if (N > 0 && !P_in) { set_err(ctx, "fd_deform_adjoint_shot: bad N / P pointers"); return FD_E_INVALID; }
+    if (!frames_ok(tu, tv, nrm)) { set_err(ctx, "fd_deform_adjoint_shot: tu, tv, nrm must be all set or all NULL"); return FD_E_INVALID; }
+    if (!ctx->built && !ctx->build_pending) { set_err(ctx, "fd_deform_adjoint_shot: no successfully built model"); return FD_E_NOT_BUILT; }
+    const int C = model_centres(ctx);
+    if (N == 0) { memset(grad_W, 0, sizeof(double) * (size_t)F * adjoint_block(C)); return FD_OK; }
+    int rc = use_device(ctx);
+    if (rc) return rc;
+    if ((rc = ensure_staging(ctx, N, tu != nullptr))) return rc;
+    const int group = F < FD_MAX_BATCH ? F : FD_MAX_BATCH;
+    const size_t frame = (size_t)N * 3;
+    if ((size_t)group * frame > ctx->cap_gshot) {
+        ctx->cap_gshot = 0;
+        if ((rc = dev_alloc(ctx, &ctx->d_gshot, (size_t)group * frame))) return rc;
+        ctx->cap_gshot = (size_t)group * frame;
+    }
+    if ((rc = adjoint_shot_reserve(ctx, N, C, F))) return rc;
+    hipStream_t s = cur_stream(ctx);
+    const size_t b3 = sizeof(float) * frame, b1 = sizeof(float) * (size_t)N;
+    if (!mesh_staged) {
+        FD_HIP(ctx, hipMemcpyAsync(ctx->d_P, P_in, b3, hipMemcpyHostToDevice, s));
+        if (dist2) FD_HIP(ctx, hipMemcpyAsync(ctx->d_dist2, dist2, b1, hipMemcpyHostToDevice, s));
+        if (tu) {
+            FD_HIP(ctx, hipMemcpyAsync(ctx->d_tu, tu, b3, hipMemcpyHostToDevice, s));
+            FD_HIP(ctx, hipMemcpyAsync(ctx->d_tv, tv, b3, hipMemcpyHostToDevice, s));
+            FD_HIP(ctx, hipMemcpyAsync(ctx->d_nrm, nrm, b3, hipMemcpyHostToDevice, s));
+        }
+    }
+    double *d_out = adjoint_shot_staging(ctx, N, C);
+    for (int f0 = 0; f0 < F; f0 += FD_MAX_BATCH) {
+        const int nF = F - f0 < FD_MAX_BATCH ? F - f0 : FD_MAX_BATCH;
+        FD_HIP(ctx, hipMemcpyAsync(ctx->d_gshot, G + (size_t)f0 * frame, b3 * (size_t)nF, hipMemcpyHostToDevice, s));
+        const AdjointShotArgs shot{ctx->d_gshot, d_out + (size_t)f0 * adjoint_block(C), nullptr, nF, 0};
+        rc = deform_dev_common(ctx, nullptr, N, ctx->d_P, nullptr, dist2 ? ctx->d_dist2 : nullptr, nullptr, tu ? ctx->d_tu : nullptr,
+                               tu ? ctx->d_tv : nullptr, tu ? ctx->d_nrm : nullptr, radius2, falloffrate, nullptr, nullptr, nullptr,
+                               nullptr, &shot);
+        if (rc) return rc;
+    }
+    FD_HIP(ctx, hipMemcpyAsync(grad_W, d_out, sizeof(double) * (size_t)F * adjoint_block(C), hipMemcpyDeviceToHost, s));
     FD_HIP(ctx, hipStreamSynchronize(s));
     return FD_OK;
 }
@@ -2294,44 +2402,35 @@ static double fit_ms_since(const std::chrono::steady_clock::time_point &t0)
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
-int fd_fit_deltas(fd_ctx *ctx, int64_t N, const float *P_in, const float *T, const float *omega, const float *dist2, const float *tu,
-                  const float *tv, const float *nrm, float radius2, float falloffrate, double mu, const float *delta0,
-                  const double *S, double *delta_out, fd_fit_report *report)
+// ---- what fd_fit_deltas and fd_fit_deltas_shot share: the checks, the cotangent, the normal matrix and its factor, the
+// per-frame right-hand side, energy and solve
+static int fit_checks(fd_ctx *ctx, const char *who, int64_t N, const float *P_in, const float *T, double mu, const float *tu,
+                      const float *tv, const float *nrm, const double *delta_out, const fd_fit_report *reports, int F)
 {
-    if (!ctx) return FD_E_INVALID;
-    if (!T || !delta_out || N < 0 || (N > 0 && !P_in)) { set_err(ctx, "fd_fit_deltas: bad N / P / T / delta_out pointers"); return FD_E_INVALID; }
-    if (!(mu >= 0.0) || !(mu < INFINITY)) { set_err(ctx, "fd_fit_deltas: mu must be finite and >= 0"); return FD_E_INVALID; }
-    if (report && report->struct_size < (int)sizeof(fd_fit_report)) {
-        set_err(ctx, "fd_fit_deltas: report->struct_size is %d, must be sizeof(fd_fit_report) = %d", report->struct_size,
-                (int)sizeof(fd_fit_report));
-        return FD_E_INVALID;
+    if (!T || !delta_out || N < 0 || (N > 0 && !P_in)) { set_err(ctx, "%s: bad N / P / T / delta_out pointers", who); return FD_E_INVALID; }
+    if (!(mu >= 0.0) || !(mu < INFINITY)) { set_err(ctx, "%s: mu must be finite and >= 0", who); return FD_E_INVALID; }
+    for (int f = 0; reports && f < F; ++f) {
+        if (reports[f].struct_size < (int)sizeof(fd_fit_report)) {
+            set_err(ctx, "%s: report->struct_size is %d, must be sizeof(fd_fit_report) = %d", who, reports[f].struct_size,
+                    (int)sizeof(fd_fit_report));
+            return FD_E_INVALID;
+        }
     }
-    if (!frames_ok(tu, tv, nrm)) { set_err(ctx, "fd_fit_deltas: tu, tv, nrm must be all set or all NULL"); return FD_E_INVALID; }
-    const int M = ctx->M, C = model_centres(ctx), n = C + 4;
-    const bool proj = tu != nullptr;
-    const int nq = proj ? 6 : 1, order = proj ? 3 * M : M;
+    if (!frames_ok(tu, tv, nrm)) { set_err(ctx, "%s: tu, tv, nrm must be all set or all NULL", who); return FD_E_INVALID; }
+    const int M = ctx->M, n = model_centres(ctx) + 4, order = tu ? 3 * M : M;
     if (n > FD_FIT_MAX_ROWS || order > FD_FIT_MAX_ORDER) {
-        set_err(ctx, "fd_fit_deltas: C + 4 = %d (at most %d) or the order of the normal system %d (at most %d) is beyond the host composition",
-                n, FD_FIT_MAX_ROWS, order, FD_FIT_MAX_ORDER);
+        set_err(ctx, "%s: C + 4 = %d (at most %d) or the order of the normal system %d (at most %d) is beyond the host composition",
+                who, n, FD_FIT_MAX_ROWS, order, FD_FIT_MAX_ORDER);
         return FD_E_INVALID;
     }
-    if (!ctx->built && !ctx->build_pending) { set_err(ctx, "fd_fit_deltas: no successfully built model"); return FD_E_NOT_BUILT; }
-    int rc;
-    std::vector<double> S_own;
-    if (!S) {
-        S_own.resize((size_t)n * M);
-        if ((rc = fd_solve_operator(ctx, S_own.data()))) return rc;
-        S = S_own.data();
-    }
-    // ---- the second-order term
-    auto t0 = std::chrono::steady_clock::now();
-    std::vector<double> H((size_t)nq * n * n);
-    if ((rc = gram_host(ctx, N, P_in, omega, dist2, tu, tv, nrm, radius2, falloffrate, H.data()))) return rc;
-    const double ms_gram = fit_ms_since(t0);
-    // ---- the first-order term: the adjoint of g = omega (T - P), the difference and the product in fp32
-    t0 = std::chrono::steady_clock::now();
-    std::vector<float> g((size_t)N * 3);
-    double tt = 0.0;                                   // sum_v omega_v |T_v - P_v|^2
+    if (!ctx->built && !ctx->build_pending) { set_err(ctx, "%s: no successfully built model", who); return FD_E_NOT_BUILT; }
+    return FD_OK;
+}
+
+// g = omega (T - P), the difference and the product in fp32; returns sum_v omega_v |T_v - P_v|^2
+static double fit_cotangent(int64_t N, const float *P_in, const float *T, const float *omega, float *g)
+{
+    double tt = 0.0;
     for (int64_t v = 0; v < N; ++v) {
         const float w = omega ? omega[v] : 1.f;
         double t2 = 0.0;
@@ -2342,83 +2441,244 @@ int fd_fit_deltas(fd_ctx *ctx, int64_t N, const float *P_in, const float *T, con
         }
         if (w != 0.f) tt += (double)w * t2;
     }
-    std::vector<double> c((size_t)n * 3);
-    if ((rc = adjoint_host(ctx, N, P_in, g.data(), dist2, tu, tv, nrm, radius2, falloffrate, c.data()))) return rc;
-    const double ms_adjoint = fit_ms_since(t0);
-    // ---- the normal system in the deltas: unknown 3 i + b with projection (order 3 M), else M with three right-hand sides
-    t0 = std::chrono::steady_clock::now();
-    std::vector<double> G((size_t)nq * M * M, 0.0);     // S^T H_q S
+    return tt;
+}
+
+// the normal system in the deltas: unknown 3 i + b with projection (order 3 M), else M with three right-hand sides.  Nothing
+// in it depends on the target: one FitSystem serves every frame of a shot.
+struct FitSystem {
+    int M, n, nq, order;
+    bool proj;
+    double mu;
+    const double *S;
+    std::vector<double> G;              // S^T H_q S, nq x M x M
+    std::vector<double> A;              // G in block form + mu I; its Cholesky factor after fit_factor
+    double pmin = 0.0, pmax = 0.0;
+    double at(int i, int bb, int k, int cc) const       // the (3 i + bb, 3 k + cc) entry of the block form, without mu
     {
-        std::vector<double> HS((size_t)n * M);
-        for (int q = 0; q < nq; ++q) {
-            std::fill(HS.begin(), HS.end(), 0.0);
-            fit_atb(n, M, n, H.data() + (size_t)q * n * n, S, HS.data());          // H_q is symmetric: H_q^T S
-            fit_atb(M, M, n, S, HS.data(), G.data() + (size_t)q * M * M);
-        }
-    }
-    std::vector<double> b((size_t)M * 3, 0.0);          // S^T c + mu delta0, M x 3
-    fit_atb(M, 3, n, S, c.data(), b.data());
-    std::vector<double> Stc = b;
-    if (delta0) for (size_t i = 0; i < (size_t)M * 3; ++i) b[i] += mu * (double)delta0[i];
-    static const int qmap[3][3] = {{0, 1, 2}, {1, 3, 4}, {2, 4, 5}};
-    auto Gat = [&](int i, int bb, int k, int cc) -> double {        // the (3 i + bb, 3 k + cc) entry of the block form, without mu
+        static const int qmap[3][3] = {{0, 1, 2}, {1, 3, 4}, {2, 4, 5}};
         if (!proj) return bb == cc ? G[(size_t)i * M + k] : 0.0;
         return G[(size_t)qmap[bb][cc] * M * M + (size_t)i * M + k];
-    };
-    // the energy of a delta (M x 3) by the quadratic form: d^T G d - 2 d^T S^T c + tt + mu |d - delta0|^2
-    auto energy = [&](const double *d) {
-        long double e = tt;
-        for (int i = 0; i < M; ++i)
-            for (int bb = 0; bb < 3; ++bb) {
-                long double row = 0.0L;
-                for (int k = 0; k < M; ++k)
-                    for (int cc = 0; cc < 3; ++cc) {
-                        if (!proj && cc != bb) continue;
-                        row += (long double)Gat(i, bb, k, cc) * d[3 * k + cc];
-                    }
-                const long double di = d[3 * i + bb], d0 = delta0 ? (long double)delta0[3 * i + bb] : 0.0L;
-                e += di * row - 2.0L * di * Stc[3 * i + bb] + (long double)mu * (di - d0) * (di - d0);
-            }
-        return (double)e;
-    };
-    std::vector<double> d0v((size_t)M * 3, 0.0);
-    if (delta0) for (size_t i = 0; i < (size_t)M * 3; ++i) d0v[i] = (double)delta0[i];
-    const double E0 = energy(d0v.data());
-    std::vector<double> A((size_t)order * order);
-    if (proj) {
+    }
+};
+
+static void fit_compose_G(FitSystem &sys, const double *H)
+{
+    const int M = sys.M, n = sys.n;
+    sys.G.assign((size_t)sys.nq * M * M, 0.0);
+    std::vector<double> HS((size_t)n * M);
+    for (int q = 0; q < sys.nq; ++q) {
+        std::fill(HS.begin(), HS.end(), 0.0);
+        fit_atb(n, M, n, H + (size_t)q * n * n, sys.S, HS.data());                 // H_q is symmetric: H_q^T S
+        fit_atb(M, M, n, sys.S, HS.data(), sys.G.data() + (size_t)q * M * M);
+    }
+}
+
+static void fit_compose_A(FitSystem &sys)
+{
+    const int M = sys.M, order = sys.order;
+    const double mu = sys.mu;
+    sys.A.resize((size_t)order * order);
+    if (sys.proj) {
         for (int i = 0; i < M; ++i)
             for (int bb = 0; bb < 3; ++bb)
                 for (int k = 0; k < M; ++k)
                     for (int cc = 0; cc < 3; ++cc)
-                        A[(size_t)(3 * i + bb) * order + 3 * k + cc] = Gat(i, bb, k, cc) + (i == k && bb == cc ? mu : 0.0);
+                        sys.A[(size_t)(3 * i + bb) * order + 3 * k + cc] = sys.at(i, bb, k, cc) + (i == k && bb == cc ? mu : 0.0);
     } else {
         for (int i = 0; i < M; ++i)
-            for (int k = 0; k < M; ++k) A[(size_t)i * M + k] = G[(size_t)i * M + k] + (i == k ? mu : 0.0);
+            for (int k = 0; k < M; ++k) sys.A[(size_t)i * M + k] = sys.G[(size_t)i * M + k] + (i == k ? mu : 0.0);
     }
+}
+
+static bool fit_factor(FitSystem &sys) { return sys.order == 0 || fit_cholesky(sys.order, sys.A.data(), sys.pmin, sys.pmax); }
+
+// one frame's right-hand side b = S^T c + mu delta0 (M x 3), with S^T c kept aside for the energy
+static void fit_rhs(const FitSystem &sys, const double *c, const float *delta0, std::vector<double> &b, std::vector<double> &Stc)
+{
+    const int M = sys.M;
+    b.assign((size_t)M * 3, 0.0);
+    fit_atb(M, 3, sys.n, sys.S, c, b.data());
+    Stc = b;
+    if (delta0) for (size_t i = 0; i < (size_t)M * 3; ++i) b[i] += sys.mu * (double)delta0[i];
+}
+
+// the energy of a delta (M x 3) by the quadratic form: d^T G d - 2 d^T S^T c + tt + mu |d - delta0|^2
+static double fit_energy(const FitSystem &sys, const std::vector<double> &Stc, double tt, const float *delta0, const double *d)
+{
+    const int M = sys.M;
+    const bool proj = sys.proj;
+    long double e = tt;
+    for (int i = 0; i < M; ++i)
+        for (int bb = 0; bb < 3; ++bb) {
+            long double row = 0.0L;
+            for (int k = 0; k < M; ++k)
+                for (int cc = 0; cc < 3; ++cc) {
+                    if (!proj && cc != bb) continue;
+                    row += (long double)sys.at(i, bb, k, cc) * d[3 * k + cc];
+                }
+            const long double di = d[3 * i + bb], d0 = delta0 ? (long double)delta0[3 * i + bb] : 0.0L;
+            e += di * row - 2.0L * di * Stc[3 * i + bb] + (long double)sys.mu * (di - d0) * (di - d0);
+        }
+    return (double)e;
+}
+
+static double fit_energy_at_delta0(const FitSystem &sys, const std::vector<double> &Stc, double tt, const float *delta0)
+{
+    std::vector<double> d0v((size_t)sys.M * 3, 0.0);
+    if (delta0) for (size_t i = 0; i < (size_t)sys.M * 3; ++i) d0v[i] = (double)delta0[i];
+    return fit_energy(sys, Stc, tt, delta0, d0v.data());
+}
+
+// one frame's solve against the factor: without projection b is M x 3, three interleaved right-hand sides; with it b is one
+// vector of 3 M in the same memory order
+static void fit_solve(const FitSystem &sys, double *b)
+{
+    if (sys.order > 0) fit_cholesky_solve(sys.order, sys.A.data(), sys.proj ? 1 : 3, b);
+}
+
+static int fit_singular(fd_ctx *ctx, const char *who, double pmin)
+{
+    set_err(ctx, "%s: the normal matrix is not positive definite (pivot %.3e): control points that no live vertex "
+                 "constrains need mu > 0", who, pmin);
+    return FD_E_SINGULAR;
+}
+
+int fd_fit_deltas(fd_ctx *ctx, int64_t N, const float *P_in, const float *T, const float *omega, const float *dist2, const float *tu,
+                  const float *tv, const float *nrm, float radius2, float falloffrate, double mu, const float *delta0,
+                  const double *S, double *delta_out, fd_fit_report *report)
+{
+    if (!ctx) return FD_E_INVALID;
+    int rc;
+    if ((rc = fit_checks(ctx, "fd_fit_deltas", N, P_in, T, mu, tu, tv, nrm, delta_out, report, 1))) return rc;
+    FitSystem sys;
+    sys.M = ctx->M; sys.n = model_centres(ctx) + 4; sys.proj = tu != nullptr;
+    sys.nq = sys.proj ? 6 : 1; sys.order = sys.proj ? 3 * sys.M : sys.M; sys.mu = mu;
+    const int M = sys.M, n = sys.n;
+    std::vector<double> S_own;
+    if (!S) {
+        S_own.resize((size_t)n * M);
+        if ((rc = fd_solve_operator(ctx, S_own.data()))) return rc;
+        S = S_own.data();
+    }
+    sys.S = S;
+    // ---- the second-order term
+    auto t0 = std::chrono::steady_clock::now();
+    std::vector<double> H((size_t)sys.nq * n * n);
+    if ((rc = gram_host(ctx, N, P_in, omega, dist2, tu, tv, nrm, radius2, falloffrate, H.data()))) return rc;
+    const double ms_gram = fit_ms_since(t0);
+    // ---- the first-order term: the adjoint of g = omega (T - P)
+    t0 = std::chrono::steady_clock::now();
+    std::vector<float> g((size_t)N * 3);
+    const double tt = fit_cotangent(N, P_in, T, omega, g.data());
+    std::vector<double> c((size_t)n * 3);
+    if ((rc = adjoint_host(ctx, N, P_in, g.data(), dist2, tu, tv, nrm, radius2, falloffrate, c.data()))) return rc;
+    const double ms_adjoint = fit_ms_since(t0);
+    // ---- the normal system
+    t0 = std::chrono::steady_clock::now();
+    fit_compose_G(sys, H.data());
+    std::vector<double> b, Stc;
+    fit_rhs(sys, c.data(), delta0, b, Stc);
+    const double E0 = fit_energy_at_delta0(sys, Stc, tt, delta0);
+    fit_compose_A(sys);
     const double ms_compose = fit_ms_since(t0);
     // ---- the solve
     t0 = std::chrono::steady_clock::now();
-    double pmin = 0.0, pmax = 0.0;
-    const bool ok = order == 0 || fit_cholesky(order, A.data(), pmin, pmax);
-    if (ok && order > 0) {
-        // without projection b is M x 3: three interleaved right-hand sides; with it b is one vector of 3 M in the same memory order
-        fit_cholesky_solve(order, A.data(), proj ? 1 : 3, b.data());
-    }
+    const bool ok = fit_factor(sys);
+    if (ok) fit_solve(sys, b.data());
     const double ms_solve = fit_ms_since(t0);
     if (report) {
-        report->order = order;
+        report->order = sys.order;
         report->E0 = E0;
-        report->E_fit = ok ? energy(b.data()) : E0;
-        report->pivot_min = order > 0 ? pmin : 0.0;
-        report->pivot_max = pmax;
+        report->E_fit = ok ? fit_energy(sys, Stc, tt, delta0, b.data()) : E0;
+        report->pivot_min = sys.order > 0 ? sys.pmin : 0.0;
+        report->pivot_max = sys.pmax;
         report->ms_gram = ms_gram; report->ms_adjoint = ms_adjoint; report->ms_compose = ms_compose; report->ms_solve = ms_solve;
     }
-    if (!ok) {
-        set_err(ctx, "fd_fit_deltas: the normal matrix is not positive definite (pivot %.3e): control points that no live vertex "
-                     "constrains need mu > 0", pmin);
-        return FD_E_SINGULAR;
-    }
+    if (!ok) return fit_singular(ctx, "fd_fit_deltas", sys.pmin);
     for (size_t i = 0; i < (size_t)M * 3; ++i) delta_out[i] = b[i];
+    return FD_OK;
+}
+
+int fd_fit_deltas_shot(fd_ctx *ctx, int64_t N, int F, const float *P_in, const float *T, const float *omega, const float *dist2,
+                       const float *tu, const float *tv, const float *nrm, float radius2, float falloffrate, double mu,
+                       const float *delta0, const double *S, double *delta_out, fd_fit_report *reports)
+{
+    if (!ctx) return FD_E_INVALID;
+    if (F < 1) { set_err(ctx, "fd_fit_deltas_shot: F < 1"); return FD_E_INVALID; }
+    int rc;
+    if ((rc = fit_checks(ctx, "fd_fit_deltas_shot", N, P_in, T, mu, tu, tv, nrm, delta_out, reports, F))) return rc;
+    FitSystem sys;
+    sys.M = ctx->M; sys.n = model_centres(ctx) + 4; sys.proj = tu != nullptr;
+    sys.nq = sys.proj ? 6 : 1; sys.order = sys.proj ? 3 * sys.M : sys.M; sys.mu = mu;
+    const int M = sys.M, n = sys.n;
+    std::vector<double> S_own;
+    if (!S) {
+        S_own.resize((size_t)n * M);
+        if ((rc = fd_solve_operator(ctx, S_own.data()))) return rc;
+        S = S_own.data();
+    }
+    sys.S = S;
+    // ---- the second-order term, once
+    auto t0 = std::chrono::steady_clock::now();
+    std::vector<double> H((size_t)sys.nq * n * n);
+    if ((rc = gram_host(ctx, N, P_in, omega, dist2, tu, tv, nrm, radius2, falloffrate, H.data()))) return rc;
+    const double ms_gram = fit_ms_since(t0);
+    // ---- the first-order terms: the shot adjoint of g_f = omega (T_f - P), one group of frames at a time; the mesh is where
+    // gram_host staged it
+    t0 = std::chrono::steady_clock::now();
+    const size_t frame = (size_t)N * 3, cblock = (size_t)n * 3, dblock = (size_t)M * 3;
+    std::vector<double> tt((size_t)F), c((size_t)F * cblock);
+    {
+        // the group's cotangents on the host, in a buffer the context keeps: fresh pages for 32 frames of a large mesh cost more
+        // than everything else in this stage
+        const size_t gneed = (size_t)(F < FD_MAX_BATCH ? F : FD_MAX_BATCH) * frame + 1;
+        if (gneed > ctx->cap_hgshot) {
+            free(ctx->h_gshot);
+            ctx->cap_hgshot = 0;
+            ctx->h_gshot = (float *)malloc(gneed * sizeof(float));
+            if (!ctx->h_gshot) { set_err(ctx, "fd_fit_deltas_shot: malloc(%zu bytes) failed", gneed * sizeof(float)); return FD_E_NOMEM; }
+            ctx->cap_hgshot = gneed;
+        }
+        float *const g = ctx->h_gshot;
+        for (int f0 = 0; f0 < F; f0 += FD_MAX_BATCH) {
+            const int nF = F - f0 < FD_MAX_BATCH ? F - f0 : FD_MAX_BATCH;
+            for (int f = 0; f < nF; ++f) tt[f0 + f] = fit_cotangent(N, P_in, T + (size_t)(f0 + f) * frame, omega, g + (size_t)f * frame);
+            if ((rc = adjoint_shot_host(ctx, N, nF, P_in, g, dist2, tu, tv, nrm, radius2, falloffrate,
+                                        c.data() + (size_t)f0 * cblock, true))) return rc;
+        }
+    }
+    const double ms_adjoint = fit_ms_since(t0);
+    // ---- the normal system, once, and every frame's right-hand side
+    t0 = std::chrono::steady_clock::now();
+    fit_compose_G(sys, H.data());
+    std::vector<std::vector<double>> b((size_t)F), Stc((size_t)F);
+    std::vector<double> E0((size_t)F);
+    for (int f = 0; f < F; ++f) {
+        const float *d0 = delta0 ? delta0 + (size_t)f * dblock : nullptr;
+        fit_rhs(sys, c.data() + (size_t)f * cblock, d0, b[f], Stc[f]);
+        E0[f] = fit_energy_at_delta0(sys, Stc[f], tt[f], d0);
+    }
+    fit_compose_A(sys);
+    const double ms_compose = fit_ms_since(t0);
+    // ---- one factorisation, F solves
+    t0 = std::chrono::steady_clock::now();
+    const bool ok = fit_factor(sys);
+    if (ok) for (int f = 0; f < F; ++f) fit_solve(sys, b[f].data());
+    const double ms_solve = fit_ms_since(t0);
+    for (int f = 0; reports && f < F; ++f) {
+        fd_fit_report *report = reports + f;
+        const float *d0 = delta0 ? delta0 + (size_t)f * dblock : nullptr;
+        report->order = sys.order;
+        report->E0 = E0[f];
+        report->E_fit = ok ? fit_energy(sys, Stc[f], tt[f], d0, b[f].data()) : E0[f];
+        report->pivot_min = sys.order > 0 ? sys.pmin : 0.0;
+        report->pivot_max = sys.pmax;
+        report->ms_gram = ms_gram; report->ms_adjoint = ms_adjoint; report->ms_compose = ms_compose; report->ms_solve = ms_solve;
+    }
+    if (!ok) return fit_singular(ctx, "fd_fit_deltas_shot", sys.pmin);
+    for (int f = 0; f < F; ++f)
+        for (size_t i = 0; i < dblock; ++i) delta_out[(size_t)f * dblock + i] = b[f][i];
     return FD_OK;
 }
 

@@ -304,6 +304,18 @@ struct AdjointArgs {
 };
 int adjoint_groups(int64_t N);        // workgroups along the vertices: a function of N alone
 hipError_t launch_adjoint(const DeformArgs &a, const AdjointArgs &g, hipStream_t stream);
+// the adjoint for the F cotangents of a shot (fd_adjoint_shot.hip, fd_deform_adjoint_shot*): `a` as for the adjoint; G is
+// F x N x 3 frame-major, grad_W F x (M + 4) x 3, T as above, partial a scratch of adjoint_shot_partial_doubles(N, M) doubles
+// that the groups of 32 frames use one after the other.  Two launches per group; N = 0 writes zeros.
+struct AdjointShotArgs {
+    const float *G;
+    double *grad_W;
+    double *partial;
+    int F, T;
+};
+int adjoint_shot_ranges(int64_t N, int C);    // workgroups along the vertices: a function of N and C alone, not of F
+size_t adjoint_shot_partial_doubles(int64_t N, int C);
+hipError_t launch_adjoint_shot(const DeformArgs &a, const AdjointShotArgs &g, hipStream_t stream);
 // the Gram operator of the deformation (fd_gram.hip, fd_deform_gram*): `a` as for the adjoint; omega the per-vertex weights
 // (N, or null for 1), H the nq x (M + 4) x (M + 4) result (nq = 6 with projection frames, else 1), T as above, partial a
 // scratch of gram_partial_doubles(N, M, nq) doubles.  Two launches; N = 0 writes zeros.

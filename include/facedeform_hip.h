@@ -474,6 +474,61 @@ int fd_fit_deltas(fd_ctx *ctx, int64_t N, const float *P_in, const float *T, con
                   const float *tu, const float *tv, const float *nrm, float radius2, float falloffrate,
                   double mu, const float *delta0, const double *S, double *delta_out, fd_fit_report *report);
 
+/* ---- the adjoint and the fit for the frames of a shot --------------------------------
+ * F cotangents over one mesh, one built model, one gate and one set of projection frames -- a scan sequence, per-frame
+ * corrective sculpts -- go through the adjoint in one launch per group of FD_MAX_BATCH frames:
+ *   grad_W[f] = Psi^T R_f,   r_{f,v} = f_v Pi_v g_{f,v}
+ * which is fd_deform_adjoint's result for the cotangent G_f.  It is a product with C+4 rows, 3F columns and depth N, and it
+ * runs on the fp64 matrix pipe with phi formed once per (vertex, record) for all frames of a group.
+ * Layout.  G is F x N x 3 fp32, frame-major: frame f's cotangent at vertex v is G[(f N + v) 3 ..].  grad_W is F x (C+4) x 3
+ *   fp64: frame f's block, in fd_get_weights' layout, starts at grad_W[f (C+4) 3].
+ * The contract.  For every frame f, the built model and any W' in fd_get_weights' layout and convention,
+ *   sum_{j,a} grad_W[f][j][a] W'[j][a] = sum_v g_{f,v} . D_v(W'),
+ *   D_v the displacement FD_OUTPUT_DISPLACEMENT defines, evaluated exactly with the weights W'.
+ * Arithmetic.  The adjoint's: everything is fp64 whatever fd_set_eval_precision says, x - c_j in raw coordinates, phi of the
+ *   kind as the inverse forms it; the gate, f and Pi are the forward path's own code; Pi g and the product by f are fp64.
+ * The shot form and fd_deform_adjoint differ in the order of additions and are not bit-equal to each other.  Each stays
+ *   inside the same bound against the exact sum.
+ * Independence of F.  No atomics: workgroups write partial blocks that a second launch adds in a fixed order, and the number
+ *   of vertex ranges is a function of N and C alone, not of F.  The block of frame f has the same bits whether it is computed
+ *   alone (F = 1) or among any number of other frames, whatever those hold, on every call, and in the host and the
+ *   device-pointer forms.
+ * Vertices that contribute nothing.  A gated vertex (dist2 > radius2) and a vertex with f = 0 contribute exactly nothing in
+ *   every frame whatever G holds there, NaN and infinity included (a select before the product).  A NaN or infinity in frame
+ *   f's G at a live vertex reaches frame f's block only.  A model with terminationtype != 1 gives zeros and FD_OK; N = 0 gives
+ *   zeros.  Rows of a polynomial term the model lacks are 0.0.
+ * Scratch.  The partial blocks live in the context and grow on demand: at most 256 ranges, and at most 256 MiB for a group
+ *   of 32 frames at any C + 4 <= 1028 (fewer ranges above that).  The groups use them one after the other.
+ * Checks and errors.  FD_E_INVALID for a NULL context, a NULL G or grad_W, N < 0 or F < 1 comes before any device work; any
+ *   F >= 1 is accepted.  The build-status poll and repair, FD_E_NOT_BUILT, the all-or-none rule for tu/tv/nrm and the
+ *   ordering behind a batched build are fd_deform's.  fd_set_output has no effect.  Only the F (C+4) x 3 entries are written.
+ *
+ * Device pointers, asynchronous on the context's stream: two launches per group of FD_MAX_BATCH frames. */
+int fd_deform_adjoint_shot_dev(fd_ctx *ctx, int64_t N, int F, const float *d_P_in, const float *d_G, const float *d_dist2,
+                               const float *d_tu, const float *d_tv, const float *d_nrm,
+                               float radius2, float falloffrate, double *d_grad_W);
+/* Same, host arrays; synchronous.  G is staged group by group through a buffer the context owns (FD_MAX_BATCH frames of
+ * N x 3 fp32 at most). */
+int fd_deform_adjoint_shot(fd_ctx *ctx, int64_t N, int F, const float *P_in, const float *G, const float *dist2,
+                           const float *tu, const float *tv, const float *nrm,
+                           float radius2, float falloffrate, double *grad_W);
+/* fd_fit_deltas for F targets over the same mesh, rest rig, omega, mu and gate: frame f minimises E with T_f (T is F x N x 3
+ * fp32, frame-major) and delta0_f (delta0 is F x M x 3 fp32, or NULL for 0).  The Gram matrix, S^T H_q S + mu I and its
+ * Cholesky factor hold nothing of the target, so the call runs fd_deform_gram once, composes and factorises once, takes
+ * g_{f,v} = omega_v (T_{f,v} - P_v) (fp32, as fd_fit_deltas forms it) through fd_deform_adjoint_shot in groups of FD_MAX_BATCH
+ * frames -- for every F, F = 1 included -- and solves every frame's right-hand side against the one factor.
+ * Frame f's deltas have the same bits whatever the other frames are and however many there are.  They are not bit-equal to
+ *   fd_fit_deltas' on the same target: the two adjoints add in different orders.
+ * Outputs.  delta_out is F x M x 3 fp64.  reports is NULL or F entries, each with struct_size set: E0 and E_fit are the
+ *   frame's; order, the pivots and the four ms_* are the call's own and the same in every entry (ms_adjoint covers forming
+ *   every g_f and all groups).  On FD_E_SINGULAR nothing is written to delta_out.
+ * Limits, FD_E_SINGULAR, the checks and the state guarantee are fd_fit_deltas'; in addition F < 1 is FD_E_INVALID and every
+ *   entry's struct_size is checked before any device work.  Synchronous. */
+int fd_fit_deltas_shot(fd_ctx *ctx, int64_t N, int F, const float *P_in, const float *T, const float *omega,
+                       const float *dist2, const float *tu, const float *tv, const float *nrm,
+                       float radius2, float falloffrate, double mu, const float *delta0, const double *S,
+                       double *delta_out, fd_fit_report *reports);
+
 /* ---- device-resident mesh (next row N3, engine side) --------------------------
  * In an animated shot the mesh on input 0 -- P, the capture's dist2, the tangent
  * frames -- is the same from cook to cook (Houdini tells by the attributes' data
