@@ -294,6 +294,17 @@ def _np_ptr(a):
     return None if a is None else C.c_void_p(a.ctypes.data)
 
 
+def _mesh_arrays(P, dist2, tangents):
+    """(P, dist2, tu, tv, nrm) as C-contiguous float32 arrays: P is (N, 3), dist2 (N,) or None, tangents = (tu, tv, nrm) three
+    (N, 3) arrays or None, which gives three times None."""
+    P = np.ascontiguousarray(P, np.float32).reshape(-1, 3)
+    d2 = None if dist2 is None else np.ascontiguousarray(dist2, np.float32)
+    tu = tv = nr = None
+    if tangents is not None:
+        tu, tv, nr = (np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in tangents)
+    return P, d2, tu, tv, nr
+
+
 class Engine:
     """Thin object wrapper over fd_ctx.  Host arrays are numpy; device pointers are ints."""
 
@@ -390,14 +401,10 @@ class Engine:
         return rep
 
     def deform(self, P, dist2=None, tangents=None, radius2=1.0, falloffrate=1.0, want_falloff=True):
-        P = np.ascontiguousarray(P, np.float32).reshape(-1, 3)
+        P, d2, tu, tv, nr = _mesh_arrays(P, dist2, tangents)
         N = P.shape[0]
         out = P.copy()
-        d2 = None if dist2 is None else np.ascontiguousarray(dist2, np.float32)
         fall = np.zeros(N, np.float32) if want_falloff else None
-        tu = tv = nr = None
-        if tangents is not None:
-            tu, tv, nr = (np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in tangents)
         self._check(self.L.fd_deform(self.ctx, N, _np_ptr(out), _np_ptr(out), _np_ptr(d2), _np_ptr(fall),
                                      _np_ptr(tu), _np_ptr(tv), _np_ptr(nr), float(radius2),
                                      float(falloffrate)))
@@ -417,11 +424,7 @@ class Engine:
 
     def mesh_set(self, P, dist2=None, tangents=None):
         """Upload the cook-invariant mesh arrays once (fd_mesh_set)."""
-        P = np.ascontiguousarray(P, np.float32).reshape(-1, 3)
-        d2 = None if dist2 is None else np.ascontiguousarray(dist2, np.float32)
-        tu = tv = nr = None
-        if tangents is not None:
-            tu, tv, nr = (np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in tangents)
+        P, d2, tu, tv, nr = _mesh_arrays(P, dist2, tangents)
         self._check(self.L.fd_mesh_set(self.ctx, P.shape[0], _np_ptr(P), _np_ptr(d2), _np_ptr(tu), _np_ptr(tv), _np_ptr(nr)))
 
     def mesh_capture(self, offsets, neighbours, rig, max_edges, triangles, radius2, dofalloff=True, want=True):
@@ -490,14 +493,10 @@ class Engine:
         """fd_deform_vectors: the deformation plus what it does to vectors.  tangents = (tu, tv, nrm) are the projection
         frames; N is transported as a normal, tu / tv as tangents.  Returns (P_out, falloff, N_out, tu_out, tv_out,
         jacobian), None for what was not asked for; jacobian is N x 3 x 3 (row-major A per vertex)."""
-        P = np.ascontiguousarray(P, np.float32).reshape(-1, 3)
+        P, d2, fu, fv, fn = _mesh_arrays(P, dist2, tangents)
         n = P.shape[0]
         out = P.copy()
-        d2 = None if dist2 is None else np.ascontiguousarray(dist2, np.float32)
         fall = np.zeros(n, np.float32)
-        fu = fv = fn = None
-        if tangents is not None:
-            fu, fv, fn = (np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in tangents)
         ins = [None if a is None else np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in (N, tu, tv)]
         outs = [None if a is None else np.empty_like(a) for a in ins]
         jac = np.empty((n, 3, 3), np.float32) if want_jacobian else None
@@ -523,13 +522,9 @@ class Engine:
         dist2 and tangents = (tu, tv, nrm) are the vertices' attributes, as in deform().  Returns (X, residual, iters):
         iters >= 0 steps taken, -1 max_iter reached, -2 broke down (X then holds the best iterate seen); None for an
         output that was not asked for."""
-        Y = np.ascontiguousarray(Y, np.float32).reshape(-1, 3)
+        Y, d2, tu, tv, nr = _mesh_arrays(Y, dist2, tangents)
         n = Y.shape[0]
         X = Y.copy()
-        d2 = None if dist2 is None else np.ascontiguousarray(dist2, np.float32)
-        tu = tv = nr = None
-        if tangents is not None:
-            tu, tv, nr = (np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in tangents)
         res = np.zeros(n, np.float32) if want_residual else None
         its = np.zeros(n, np.int32) if want_iters else None
         opts = FdInvertOpts(C.sizeof(FdInvertOpts), int(max_iter), float(tol), _np_ptr(res), _np_ptr(its))
@@ -549,14 +544,10 @@ class Engine:
         """fd_deform_adjoint: dL/dW, (C + 4, 3) float64 in get_weights' layout, for the sensitivity G = dL/dP' at the deformed
         vertices (N x 3).  dist2 and tangents = (tu, tv, nrm) are the vertices' attributes, as in deform().  The gradient for
         the deltas is solve_operator().T @ deform_adjoint(...)."""
-        P = np.ascontiguousarray(P, np.float32).reshape(-1, 3)
+        P, d2, tu, tv, nr = _mesh_arrays(P, dist2, tangents)
         G = np.ascontiguousarray(G, np.float32).reshape(-1, 3)
         if G.shape != P.shape:
             raise ValueError("P and G must have the same shape")
-        d2 = None if dist2 is None else np.ascontiguousarray(dist2, np.float32)
-        tu = tv = nr = None
-        if tangents is not None:
-            tu, tv, nr = (np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in tangents)
         out = np.empty((int(self.L.fd_model_centres(self.ctx)) + 4, 3), np.float64)
         self._check(self.L.fd_deform_adjoint(self.ctx, P.shape[0], _np_ptr(P), _np_ptr(G), _np_ptr(d2), _np_ptr(tu), _np_ptr(tv),
                                              _np_ptr(nr), float(radius2), float(falloffrate), _np_ptr(out)))
@@ -576,16 +567,21 @@ class Engine:
         self._check(self.L.fd_solve_operator(self.ctx, S.ctypes.data_as(_f64p)))
         return S
 
+    def _solve_operator_arg(self, S):
+        """S as the C-contiguous float64 (C + 4, M) array the fits take, or None"""
+        if S is None:
+            return None
+        Sm = np.ascontiguousarray(S, np.float64)
+        if Sm.shape != (int(self.L.fd_model_centres(self.ctx)) + 4, self.M):
+            raise ValueError("S must be solve_operator()'s (C + 4, M) array")
+        return Sm
+
     def deform_gram(self, P, omega=None, dist2=None, tangents=None, radius2=1.0, falloffrate=1.0):
         """fd_deform_gram: H, (nq, C + 4, C + 4) float64 with H[q] = sum_v omega_v f_v^2 (Pi_v^2)[b][c] Psi_v^T Psi_v in
         get_weights' layout; nq = 1 without tangents = (tu, tv, nrm), else 6 ordered xx, xy, xz, yy, yz, zz.  omega: per-vertex
         weights >= 0 (None: 1)."""
-        P = np.ascontiguousarray(P, np.float32).reshape(-1, 3)
+        P, d2, tu, tv, nr = _mesh_arrays(P, dist2, tangents)
         om = None if omega is None else np.ascontiguousarray(omega, np.float32)
-        d2 = None if dist2 is None else np.ascontiguousarray(dist2, np.float32)
-        tu = tv = nr = None
-        if tangents is not None:
-            tu, tv, nr = (np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in tangents)
         n = int(self.L.fd_model_centres(self.ctx)) + 4
         out = np.empty((1 if tangents is None else 6, n, n), np.float64)
         self._check(self.L.fd_deform_gram(self.ctx, P.shape[0], _np_ptr(P), _np_ptr(om), _np_ptr(d2), _np_ptr(tu), _np_ptr(tv),
@@ -603,21 +599,13 @@ class Engine:
     def fit_deltas(self, P, T, omega=None, dist2=None, tangents=None, radius2=1.0, falloffrate=1.0, mu=0.0, delta0=None, S=None):
         """fd_fit_deltas: (delta, report) -- the (M, 3) float64 deltas that minimise sum_v omega_v |D_v(S delta) - (T_v - P_v)|^2
         + mu |delta - delta0|^2, and the FdFitReport.  S: solve_operator()'s result, or None to have it computed inside."""
-        P = np.ascontiguousarray(P, np.float32).reshape(-1, 3)
+        P, d2, tu, tv, nr = _mesh_arrays(P, dist2, tangents)
         T = np.ascontiguousarray(T, np.float32).reshape(-1, 3)
         if T.shape != P.shape:
             raise ValueError("P and T must have the same shape")
         om = None if omega is None else np.ascontiguousarray(omega, np.float32)
-        d2 = None if dist2 is None else np.ascontiguousarray(dist2, np.float32)
-        tu = tv = nr = None
-        if tangents is not None:
-            tu, tv, nr = (np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in tangents)
         d0 = None if delta0 is None else np.ascontiguousarray(delta0, np.float32).reshape(self.M, 3)
-        Sm = None
-        if S is not None:
-            Sm = np.ascontiguousarray(S, np.float64)
-            if Sm.shape != (int(self.L.fd_model_centres(self.ctx)) + 4, self.M):
-                raise ValueError("S must be solve_operator()'s (C + 4, M) array")
+        Sm = self._solve_operator_arg(S)
         out = np.empty((self.M, 3), np.float64)
         rep = FdFitReport()
         rep.struct_size = C.sizeof(FdFitReport)
@@ -629,14 +617,10 @@ class Engine:
     def deform_adjoint_shot(self, P, G, dist2=None, tangents=None, radius2=1.0, falloffrate=1.0):
         """fd_deform_adjoint_shot: (F, C + 4, 3) float64, frame f's block being deform_adjoint's result for the cotangent G[f];
         G is (F, N, 3).  One matrix-pipe launch per 32 frames; frame f's bits do not depend on the other frames."""
-        P = np.ascontiguousarray(P, np.float32).reshape(-1, 3)
+        P, d2, tu, tv, nr = _mesh_arrays(P, dist2, tangents)
         G = np.ascontiguousarray(G, np.float32)
         if G.ndim != 3 or G.shape[0] < 1 or G.shape[1:] != P.shape:
             raise ValueError("G must be (F, N, 3) with F >= 1 and P (N, 3)")
-        d2 = None if dist2 is None else np.ascontiguousarray(dist2, np.float32)
-        tu = tv = nr = None
-        if tangents is not None:
-            tu, tv, nr = (np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in tangents)
         out = np.empty((G.shape[0], int(self.L.fd_model_centres(self.ctx)) + 4, 3), np.float64)
         self._check(self.L.fd_deform_adjoint_shot(self.ctx, P.shape[0], G.shape[0], _np_ptr(P), _np_ptr(G), _np_ptr(d2), _np_ptr(tu),
                                                   _np_ptr(tv), _np_ptr(nr), float(radius2), float(falloffrate), _np_ptr(out)))
@@ -655,22 +639,14 @@ class Engine:
         """fd_fit_deltas_shot: (deltas, reports) -- fit_deltas for the F targets T[f] (T is (F, N, 3)) over one mesh, omega and
         mu, with one Gram launch, one factorisation and the shot adjoint: deltas is (F, M, 3) float64, reports a list of F
         FdFitReport.  delta0: (F, M, 3) or None.  S: solve_operator()'s result, or None to have it computed inside."""
-        P = np.ascontiguousarray(P, np.float32).reshape(-1, 3)
+        P, d2, tu, tv, nr = _mesh_arrays(P, dist2, tangents)
         T = np.ascontiguousarray(T, np.float32)
         if T.ndim != 3 or T.shape[0] < 1 or T.shape[1:] != P.shape:
             raise ValueError("T must be (F, N, 3) with F >= 1 and P (N, 3)")
         F = T.shape[0]
         om = None if omega is None else np.ascontiguousarray(omega, np.float32)
-        d2 = None if dist2 is None else np.ascontiguousarray(dist2, np.float32)
-        tu = tv = nr = None
-        if tangents is not None:
-            tu, tv, nr = (np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in tangents)
         d0 = None if delta0 is None else np.ascontiguousarray(delta0, np.float32).reshape(F, self.M, 3)
-        Sm = None
-        if S is not None:
-            Sm = np.ascontiguousarray(S, np.float64)
-            if Sm.shape != (int(self.L.fd_model_centres(self.ctx)) + 4, self.M):
-                raise ValueError("S must be solve_operator()'s (C + 4, M) array")
+        Sm = self._solve_operator_arg(S)
         out = np.empty((F, self.M, 3), np.float64)
         reps = (FdFitReport * F)()
         for r in reps:

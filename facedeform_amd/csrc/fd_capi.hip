@@ -12,9 +12,11 @@
 #include <new>
 #include <vector>
 
+#include "fd_fit_host.h"
 #include "fd_internal.h"
 
 using namespace fd;
+using namespace fd_fit;
 
 // what a captured build graph was made for (ensure_graph): another key captures again
 struct GraphKey {
@@ -101,22 +103,23 @@ struct fd_ctx {
     int64_t cap_N = 0;
     float *d_P = nullptr, *d_dist2 = nullptr, *d_fall = nullptr;
     float *d_tu = nullptr, *d_tv = nullptr, *d_nrm = nullptr;
-    // fd_deform_vectors: staging of the transported vectors + Jacobian (N x 18), and P_in set aside when it is overwritten
-    int64_t cap_vec = 0, cap_vecP = 0;
+    // fd_deform_vectors: staging of the transported vectors + Jacobian (N x 18), and P_in set aside when it is overwritten.
+    // The capacities of this and the scratch buffers below count elements (dev_grow).
+    size_t cap_vec = 0, cap_vecP = 0;
     float *d_vec = nullptr, *d_vecP = nullptr;
     // fd_invert: staging of iters_out (residual_out goes through d_fall)
-    int64_t cap_iters = 0;
+    size_t cap_iters = 0;
     int *d_iters = nullptr;
-    // fd_deform_adjoint*: the workgroups' partial blocks and, behind them, the host call's staging of grad_W (adjoint_reserve);
+    // fd_deform_adjoint*: the workgroups' partial blocks and, behind them, the host call's staging of grad_W (adjoint_scratch);
     // the host call's G goes through d_vecP
     size_t cap_adj = 0;
     double *d_adj = nullptr;
-    // fd_deform_gram*: the workgroups' partial blocks and, behind them, the host call's staging of H (gram_reserve); the host
+    // fd_deform_gram*: the workgroups' partial blocks and, behind them, the host call's staging of H (gram_scratch); the host
     // call's omega goes through d_fall
     size_t cap_gram = 0;
     double *d_gram = nullptr;
     // fd_deform_adjoint_shot*: the ranges' partial blocks of one group of frames and, behind them, the host call's staging of
-    // grad_W (adjoint_shot_reserve); the host call's G goes group by group through d_gshot
+    // grad_W (adjoint_shot_scratch); the host call's G goes group by group through d_gshot
     size_t cap_adjs = 0, cap_gshot = 0;
     double *d_adjs = nullptr;
     float *d_gshot = nullptr;
@@ -271,6 +274,19 @@ static int dev_alloc(fd_ctx *ctx, T **p, size_t count)
         set_err(ctx, "hipMalloc(%zu bytes) failed: %s", count * sizeof(T), hipGetErrorString(e));
         return FD_E_NOMEM;
     }
+    return FD_OK;
+}
+
+// A scratch buffer that grows on demand and never shrinks, *cap its size in elements.  *cap is 0 while *p is being replaced, so
+// that a failed allocation leaves no capacity behind for a later, smaller request to trust (hipFree drains the device).
+template <typename T>
+static int dev_grow(fd_ctx *ctx, T **p, size_t *cap, size_t count)
+{
+    if (count <= *cap) return FD_OK;
+    *cap = 0;
+    const int rc = dev_alloc(ctx, p, count);
+    if (rc) return rc;
+    *cap = count;
     return FD_OK;
 }
 
@@ -466,16 +482,6 @@ static bool frames_ok(const void *tu, const void *tv, const void *nrm)
 }
 
 static int poll_status(fd_ctx *ctx);
-static int deform_host(fd_ctx *ctx, int64_t N, const float *P_in, float *P_out, const float *dist2, float *falloff_out,
-                       const float *tu, const float *tv, const float *nrm, float radius2, float falloffrate, const fd_vectors *vec);
-static int invert_host(fd_ctx *ctx, int64_t N, const float *Y, float *X_out, const float *dist2, const float *tu, const float *tv,
-                       const float *nrm, float radius2, float falloffrate, const fd_invert_opts *opts);
-static int adjoint_host(fd_ctx *ctx, int64_t N, const float *P_in, const float *G, const float *dist2, const float *tu, const float *tv,
-                        const float *nrm, float radius2, float falloffrate, double *grad_W);
-static int gram_host(fd_ctx *ctx, int64_t N, const float *P_in, const float *omega, const float *dist2, const float *tu, const float *tv,
-                     const float *nrm, float radius2, float falloffrate, double *H);
-static int adjoint_shot_host(fd_ctx *ctx, int64_t N, int F, const float *P_in, const float *G, const float *dist2, const float *tu,
-                             const float *tv, const float *nrm, float radius2, float falloffrate, double *grad_W, bool mesh_staged);
 
 extern "C" {
 
@@ -963,16 +969,23 @@ static int poll_status(fd_ctx *ctx)
     return ctx->sticky_rc;
 }
 
-// the evaluation of c's model over N vertices
-static DeformArgs deform_args(const fd_ctx *c, int64_t N, const float *P_in, float *P_out, const float *dist2, float *falloff_out,
-                              const float *tu, const float *tv, const float *nrm, float radius2, float falloffrate)
+// The mesh a one-context call works on: N vertices, their optional gate distances and projection frames, and the gate's two
+// parameters.  Host arrays in the host calls, device arrays everywhere else; stage_mesh makes the second of the first.
+struct Mesh {
+    int64_t N;
+    const float *P, *dist2, *tu, *tv, *nrm;
+    float radius2, falloffrate;
+};
+
+// the evaluation of c's model over the mesh m
+static DeformArgs deform_args(const fd_ctx *c, const Mesh &m, float *P_out, float *falloff_out)
 {
     DeformArgs a;
-    a.N = N;
-    a.P_in = P_in; a.P_out = P_out;
-    a.dist2 = dist2; a.falloff_out = falloff_out;
-    a.tu = tu; a.tv = tv; a.nrm = nrm;
-    a.radius2 = radius2; a.falloffrate = falloffrate;
+    a.N = m.N;
+    a.P_in = m.P; a.P_out = P_out;
+    a.dist2 = m.dist2; a.falloff_out = falloff_out;
+    a.tu = m.tu; a.tv = m.tv; a.nrm = m.nrm;
+    a.radius2 = m.radius2; a.falloffrate = m.falloffrate;
     a.M = model_centres(c); a.Mpad = round_up(a.M, kRecPad); a.kind = eval_kind(c); a.layers = record_layers(c);
     a.rec32 = c->d_rec32; a.rec64 = c->d_rec64; a.tiles = c->d_tiles; a.tiles16 = c->d_tiles16;
     a.model = c->d_model;
@@ -1011,97 +1024,53 @@ static bool invert_opts_ok(fd_ctx *ctx, const fd_invert_opts *opts)
     return true;
 }
 
-// fd_deform_adjoint*: the scratch for N vertices and C records -- adjoint_groups(N) partial blocks of (C + 4) x 3 doubles, and one
-// more block behind them where the host call stages grad_W (adjoint_staging).  Grows on demand (hipFree drains the device).
+// The scratch of the adjoint, the Gram operator and the shot adjoint for N vertices and C records: the workgroups' partial blocks
+// and, behind them, room for the result, where the host call stages it (*_staging).  Grown on demand (dev_grow).
+// fd_deform_adjoint*: adjoint_groups(N) partial blocks of (C + 4) x 3 doubles and one more for grad_W
 static size_t adjoint_block(int C) { return (size_t)(C + 4) * 3; }
-static int adjoint_reserve(fd_ctx *ctx, int64_t N, int C)
-{
-    const size_t need = ((size_t)adjoint_groups(N) + 1) * adjoint_block(C);
-    if (need <= ctx->cap_adj) return FD_OK;
-    ctx->cap_adj = 0;
-    const int rc = dev_alloc(ctx, &ctx->d_adj, need);
-    if (rc) return rc;
-    ctx->cap_adj = need;
-    return FD_OK;
-}
+static size_t adjoint_scratch(int64_t N, int C) { return ((size_t)adjoint_groups(N) + 1) * adjoint_block(C); }
 static double *adjoint_staging(const fd_ctx *ctx, int64_t N, int C) { return ctx->d_adj + (size_t)adjoint_groups(N) * adjoint_block(C); }
-
-// fd_deform_gram*: the scratch for N vertices, C records and nq components -- gram_partial_doubles partial blocks and, behind
-// them, room for H, where the host call stages it (gram_staging).  Grows on demand.
+// fd_deform_gram*: gram_partial_doubles partial blocks and H, nq components of (C + 4) x (C + 4)
 static size_t gram_block(int C, int nq) { return (size_t)nq * (size_t)(C + 4) * (size_t)(C + 4); }
-static int gram_reserve(fd_ctx *ctx, int64_t N, int C, int nq)
-{
-    const size_t need = gram_partial_doubles(N, C, nq) + gram_block(C, nq);
-    if (need <= ctx->cap_gram) return FD_OK;
-    ctx->cap_gram = 0;
-    const int rc = dev_alloc(ctx, &ctx->d_gram, need);
-    if (rc) return rc;
-    ctx->cap_gram = need;
-    return FD_OK;
-}
+static size_t gram_scratch(int64_t N, int C, int nq) { return gram_partial_doubles(N, C, nq) + gram_block(C, nq); }
 static double *gram_staging(const fd_ctx *ctx, int64_t N, int C, int nq) { return ctx->d_gram + gram_partial_doubles(N, C, nq); }
-
-// fd_deform_adjoint_shot*: the scratch for N vertices and C records -- adjoint_shot_partial_doubles partial blocks, which the
-// groups of frames use one after the other, and behind them room for `staged` frames' grad_W, where the host call stages its
-// result (adjoint_shot_staging).  Grows on demand and never shrinks: the launch's own reserve (staged = 0) keeps the host call's.
-static int adjoint_shot_reserve(fd_ctx *ctx, int64_t N, int C, int staged)
-{
-    const size_t need = adjoint_shot_partial_doubles(N, C) + (size_t)staged * adjoint_block(C);
-    if (need <= ctx->cap_adjs) return FD_OK;
-    ctx->cap_adjs = 0;
-    const int rc = dev_alloc(ctx, &ctx->d_adjs, need);
-    if (rc) return rc;
-    ctx->cap_adjs = need;
-    return FD_OK;
-}
+// fd_deform_adjoint_shot*: adjoint_shot_partial_doubles partial blocks, which the groups of frames use one after the other, and
+// `staged` frames' grad_W.  The launch's own request (staged = 0) keeps what the host call asked for: the buffer never shrinks.
+static size_t adjoint_shot_scratch(int64_t N, int C, int staged) { return adjoint_shot_partial_doubles(N, C) + (size_t)staged * adjoint_block(C); }
 static double *adjoint_shot_staging(const fd_ctx *ctx, int64_t N, int C) { return ctx->d_adjs + adjoint_shot_partial_doubles(N, C); }
 
-// fd_deform_dev_stream / fd_deform_vectors_dev / the staged host calls: vec == nullptr is the deformation alone.
-// fd_invert_dev: inv != nullptr -- the same checks, status poll and ordering, then the inverse's one launch in place of the
-// deformation's (d_P_in = the deformed points, d_P_out = the rest-space points; no fall-off output, no vectors).
-// fd_deform_adjoint_dev: adj != nullptr -- likewise, then the adjoint's two launches (no d_P_out; adj names G and grad_W, the
-// partial blocks are the context's).
-// fd_deform_gram_dev: gram != nullptr -- likewise, the Gram operator's two launches (gram names omega and H).
-// fd_deform_adjoint_shot_dev: shot != nullptr -- likewise, the shot adjoint's two launches per group of frames (shot names G,
-// grad_W and F).
-static int deform_dev_common(fd_ctx *ctx, void *hip_stream, int64_t N, const float *d_P_in, float *d_P_out,
-                             const float *d_dist2, float *d_falloff_out, const float *d_tu, const float *d_tv,
-                             const float *d_nrm, float radius2, float falloffrate, const fd_vectors *vec,
-                             const InvertArgs *inv = nullptr, const AdjointArgs *adj = nullptr, const GramArgs *gram = nullptr,
-                             const AdjointShotArgs *shot = nullptr)
+// What every one-context call on a mesh checks first, for the entry point `who`; out_ok: the call has the output array it needs
+static int mesh_checks(fd_ctx *ctx, const char *who, const Mesh &m, bool out_ok)
 {
-    hipStream_t launch_stream = hip_stream ? (hipStream_t)hip_stream : cur_stream(ctx);
-    if (N < 0 || (N > 0 && (!d_P_in || (!d_P_out && !adj && !gram && !shot)))) { set_err(ctx, "fd_deform: bad N / P pointers"); return FD_E_INVALID; }
-    if (!frames_ok(d_tu, d_tv, d_nrm)) { set_err(ctx, "fd_deform: tu, tv, nrm must be all set or all NULL"); return FD_E_INVALID; }
-    if (!ctx->built && !ctx->build_pending) { set_err(ctx, "fd_deform: no successfully built model"); return FD_E_NOT_BUILT; }
-    if (N == 0) return FD_OK;
-    int rc = use_device(ctx);
-    if (rc) return rc;
+    if (m.N < 0 || (m.N > 0 && (!m.P || !out_ok))) { set_err(ctx, "%s: bad N / P pointers", who); return FD_E_INVALID; }
+    if (!frames_ok(m.tu, m.tv, m.nrm)) { set_err(ctx, "%s: tu, tv, nrm must be all set or all NULL", who); return FD_E_INVALID; }
+    if (!ctx->built && !ctx->build_pending) { set_err(ctx, "%s: no successfully built model", who); return FD_E_NOT_BUILT; }
+    return FD_OK;
+}
+
+// What every one-context device call does before its launches: the checks; for an empty mesh nothing more (the caller returns
+// on m.N == 0 as it does on an error); else the device, the model's status, the evaluation's arguments and the order behind a
+// batched build.  *s is the stream to launch on: hip_stream, or the context's when that is null.
+static int deform_begin(fd_ctx *ctx, const char *who, void *hip_stream, const Mesh &m, float *d_P_out, float *d_falloff_out,
+                        bool out_ok, DeformArgs *a, hipStream_t *s)
+{
+    *s = hip_stream ? (hipStream_t)hip_stream : cur_stream(ctx);
+    int rc = mesh_checks(ctx, who, m, out_ok);
+    if (rc || m.N == 0) return rc;
+    if ((rc = use_device(ctx))) return rc;
     if ((rc = poll_status(ctx))) return rc;           // a failed asynchronous build: repaired here, or reported
-    const DeformArgs a = deform_args(ctx, N, d_P_in, d_P_out, d_dist2, d_falloff_out, d_tu, d_tv, d_nrm, radius2, falloffrate);
-    if ((rc = order_after_batch(ctx, launch_stream))) return rc;
-    if (inv) {
-        FD_HIP(ctx, launch_invert(a, *inv, launch_stream));
-        return FD_OK;
-    }
-    if (adj) {
-        if ((rc = adjoint_reserve(ctx, N, a.M))) return rc;
-        const AdjointArgs g{adj->G, adj->grad_W, ctx->d_adj, term_cols(ctx->term)};
-        FD_HIP(ctx, launch_adjoint(a, g, launch_stream));
-        return FD_OK;
-    }
-    if (gram) {
-        if ((rc = gram_reserve(ctx, N, a.M, d_tu ? 6 : 1))) return rc;
-        const GramArgs g{gram->omega, gram->H, ctx->d_gram, term_cols(ctx->term)};
-        FD_HIP(ctx, launch_gram(a, g, launch_stream));
-        return FD_OK;
-    }
-    if (shot) {
-        if ((rc = adjoint_shot_reserve(ctx, N, a.M, 0))) return rc;
-        const AdjointShotArgs g{shot->G, shot->grad_W, ctx->d_adjs, shot->F, term_cols(ctx->term)};
-        FD_HIP(ctx, launch_adjoint_shot(a, g, launch_stream));
-        return FD_OK;
-    }
+    *a = deform_args(ctx, m, d_P_out, d_falloff_out);
+    return order_after_batch(ctx, *s);
+}
+
+// fd_deform_dev_stream / fd_deform_vectors_dev / the staged host calls: the deformation's launch, with vec the vectors' as well
+static int deform_dev(fd_ctx *ctx, const char *who, void *hip_stream, const Mesh &m, float *d_P_out, float *d_falloff_out,
+                      const fd_vectors *vec)
+{
+    DeformArgs a;
+    hipStream_t launch_stream;
+    int rc = deform_begin(ctx, who, hip_stream, m, d_P_out, d_falloff_out, d_P_out != nullptr, &a, &launch_stream);
+    if (rc || m.N == 0) return rc;
     if (!vec) {
         FD_HIP(ctx, launch_deform(a, launch_stream));
         return FD_OK;
@@ -1112,19 +1081,16 @@ static int deform_dev_common(fd_ctx *ctx, void *hip_stream, int64_t N, const flo
     const VectorArgs v{vec->N, vec->tu, vec->tv, vec->N_out, vec->tu_out, vec->tv_out, vec->jacobian};
     const float *const outs[3] = {v.N_out, v.tu_out, v.tv_out};
     bool clash = false;
-    for (const float *o : outs) clash |= o && (o == d_tu || o == d_tv || o == d_nrm || o == d_dist2);
+    for (const float *o : outs) clash |= o && (o == m.tu || o == m.tv || o == m.nrm || o == m.dist2);
     if (!clash) {
         FD_HIP(ctx, launch_vectors(a, v, launch_stream));
         FD_HIP(ctx, launch_deform(a, launch_stream));
         return FD_OK;
     }
     DeformArgs av = a;
-    if (d_P_out == d_P_in) {
-        if (N > ctx->cap_vecP) {
-            if ((rc = dev_alloc(ctx, &ctx->d_vecP, (size_t)N * 3))) return rc;
-            ctx->cap_vecP = N;
-        }
-        FD_HIP(ctx, hipMemcpyAsync(ctx->d_vecP, d_P_in, sizeof(float) * 3 * (size_t)N, hipMemcpyDeviceToDevice, launch_stream));
+    if (d_P_out == m.P) {
+        if ((rc = dev_grow(ctx, &ctx->d_vecP, &ctx->cap_vecP, (size_t)m.N * 3))) return rc;
+        FD_HIP(ctx, hipMemcpyAsync(ctx->d_vecP, m.P, sizeof(float) * 3 * (size_t)m.N, hipMemcpyDeviceToDevice, launch_stream));
         av.P_in = ctx->d_vecP;
     }
     FD_HIP(ctx, launch_deform(a, launch_stream));
@@ -1132,158 +1098,72 @@ static int deform_dev_common(fd_ctx *ctx, void *hip_stream, int64_t N, const flo
     return FD_OK;
 }
 
-extern "C" {
-
-int fd_deform_dev(fd_ctx *ctx, int64_t N, const float *d_P_in, float *d_P_out, const float *d_dist2,
-                  float *d_falloff_out, const float *d_tu, const float *d_tv, const float *d_nrm,
-                  float radius2, float falloffrate)
+// fd_invert_dev: the inverse's one launch (m.P = the deformed points, d_X_out = the rest-space points)
+static int invert_dev(fd_ctx *ctx, const Mesh &m, float *d_X_out, const InvertArgs &inv)
 {
-    if (!ctx) return FD_E_INVALID;
-    return fd_deform_dev_stream(ctx, cur_stream(ctx), N, d_P_in, d_P_out, d_dist2, d_falloff_out, d_tu, d_tv,
-                                d_nrm, radius2, falloffrate);
-}
-
-int fd_deform_dev_stream(fd_ctx *ctx, void *hip_stream, int64_t N, const float *d_P_in, float *d_P_out,
-                         const float *d_dist2, float *d_falloff_out, const float *d_tu,
-                         const float *d_tv, const float *d_nrm, float radius2, float falloffrate)
-{
-    if (!ctx) return FD_E_INVALID;
-    return deform_dev_common(ctx, hip_stream, N, d_P_in, d_P_out, d_dist2, d_falloff_out, d_tu, d_tv, d_nrm, radius2,
-                             falloffrate, nullptr);
-}
-
-int fd_deform_vectors_dev(fd_ctx *ctx, int64_t N, const float *d_P_in, float *d_P_out, const float *d_dist2,
-                          float *d_falloff_out, const float *d_tu, const float *d_tv, const float *d_nrm,
-                          float radius2, float falloffrate, const fd_vectors *vec)
-{
-    if (!ctx) return FD_E_INVALID;
-    if (!vectors_ok(ctx, vec)) return FD_E_INVALID;
-    return deform_dev_common(ctx, nullptr, N, d_P_in, d_P_out, d_dist2, d_falloff_out, d_tu, d_tv, d_nrm, radius2,
-                             falloffrate, vectors_wanted(vec) ? vec : nullptr);
-}
-
-int fd_deform(fd_ctx *ctx, int64_t N, const float *P_in, float *P_out, const float *dist2,
-              float *falloff_out, const float *tu, const float *tv, const float *nrm, float radius2,
-              float falloffrate)
-{
-    if (!ctx) return FD_E_INVALID;
-    return deform_host(ctx, N, P_in, P_out, dist2, falloff_out, tu, tv, nrm, radius2, falloffrate, nullptr);
-}
-
-int fd_deform_vectors(fd_ctx *ctx, int64_t N, const float *P_in, float *P_out, const float *dist2,
-                      float *falloff_out, const float *tu, const float *tv, const float *nrm,
-                      float radius2, float falloffrate, const fd_vectors *vec)
-{
-    if (!ctx) return FD_E_INVALID;
-    if (!vectors_ok(ctx, vec)) return FD_E_INVALID;
-    return deform_host(ctx, N, P_in, P_out, dist2, falloff_out, tu, tv, nrm, radius2, falloffrate,
-                       vectors_wanted(vec) ? vec : nullptr);
-}
-
-int fd_invert_dev(fd_ctx *ctx, int64_t N, const float *d_Y, float *d_X_out, const float *d_dist2, const float *d_tu,
-                  const float *d_tv, const float *d_nrm, float radius2, float falloffrate, const fd_invert_opts *opts)
-{
-    if (!ctx) return FD_E_INVALID;
-    if (!invert_opts_ok(ctx, opts)) return FD_E_INVALID;
-    const InvertArgs inv{opts->max_iter, opts->tol, opts->residual_out, opts->iters_out};
-    return deform_dev_common(ctx, nullptr, N, d_Y, d_X_out, d_dist2, nullptr, d_tu, d_tv, d_nrm, radius2, falloffrate, nullptr, &inv);
-}
-
-int fd_invert(fd_ctx *ctx, int64_t N, const float *Y, float *X_out, const float *dist2, const float *tu, const float *tv,
-              const float *nrm, float radius2, float falloffrate, const fd_invert_opts *opts)
-{
-    if (!ctx) return FD_E_INVALID;
-    if (!invert_opts_ok(ctx, opts)) return FD_E_INVALID;
-    return invert_host(ctx, N, Y, X_out, dist2, tu, tv, nrm, radius2, falloffrate, opts);
-}
-
-int fd_deform_adjoint_dev(fd_ctx *ctx, int64_t N, const float *d_P_in, const float *d_G, const float *d_dist2, const float *d_tu,
-                          const float *d_tv, const float *d_nrm, float radius2, float falloffrate, double *d_grad_W)
-{
-    if (!ctx) return FD_E_INVALID;
-    if (!d_G || !d_grad_W || N < 0) { set_err(ctx, "fd_deform_adjoint: bad N / G / grad_W pointers"); return FD_E_INVALID; }
-    const AdjointArgs adj{d_G, d_grad_W, nullptr, 0};
-    int rc = deform_dev_common(ctx, nullptr, N, d_P_in, nullptr, d_dist2, nullptr, d_tu, d_tv, d_nrm, radius2, falloffrate, nullptr,
-                               nullptr, &adj);
-    if (rc || N > 0) return rc;
-    // no vertex: no launch, zeros
-    if ((rc = use_device(ctx))) return rc;
-    FD_HIP(ctx, hipMemsetAsync(d_grad_W, 0, sizeof(double) * adjoint_block(model_centres(ctx)), cur_stream(ctx)));
+    DeformArgs a;
+    hipStream_t s;
+    const int rc = deform_begin(ctx, "fd_invert", nullptr, m, d_X_out, nullptr, d_X_out != nullptr, &a, &s);
+    if (rc || m.N == 0) return rc;
+    FD_HIP(ctx, launch_invert(a, inv, s));
     return FD_OK;
 }
 
-int fd_deform_adjoint(fd_ctx *ctx, int64_t N, const float *P_in, const float *G, const float *dist2, const float *tu, const float *tv,
-                      const float *nrm, float radius2, float falloffrate, double *grad_W)
+// fd_deform_adjoint_dev: the adjoint's two launches.  Like the two below it writes nothing for an empty mesh: the caller zeroes.
+static int adjoint_dev(fd_ctx *ctx, const char *who, const Mesh &m, const float *d_G, double *d_grad_W)
 {
-    if (!ctx) return FD_E_INVALID;
-    if (!G || !grad_W || N < 0) { set_err(ctx, "fd_deform_adjoint: bad N / G / grad_W pointers"); return FD_E_INVALID; }
-    return adjoint_host(ctx, N, P_in, G, dist2, tu, tv, nrm, radius2, falloffrate, grad_W);
-}
-
-int fd_deform_gram_dev(fd_ctx *ctx, int64_t N, const float *d_P_in, const float *d_omega, const float *d_dist2, const float *d_tu,
-                       const float *d_tv, const float *d_nrm, float radius2, float falloffrate, double *d_H)
-{
-    if (!ctx) return FD_E_INVALID;
-    if (!d_H || N < 0) { set_err(ctx, "fd_deform_gram: bad N / H pointers"); return FD_E_INVALID; }
-    const GramArgs gram{d_omega, d_H, nullptr, 0};
-    int rc = deform_dev_common(ctx, nullptr, N, d_P_in, nullptr, d_dist2, nullptr, d_tu, d_tv, d_nrm, radius2, falloffrate, nullptr,
-                               nullptr, nullptr, &gram);
-    if (rc || N > 0) return rc;
-    // no vertex: no launch, zeros
-    if ((rc = use_device(ctx))) return rc;
-    FD_HIP(ctx, hipMemsetAsync(d_H, 0, sizeof(double) * gram_block(model_centres(ctx), d_tu ? 6 : 1), cur_stream(ctx)));
+    DeformArgs a;
+    hipStream_t s;
+    int rc = deform_begin(ctx, who, nullptr, m, nullptr, nullptr, true, &a, &s);
+    if (rc || m.N == 0) return rc;
+    if ((rc = dev_grow(ctx, &ctx->d_adj, &ctx->cap_adj, adjoint_scratch(m.N, a.M)))) return rc;
+    const AdjointArgs g{d_G, d_grad_W, ctx->d_adj, term_cols(ctx->term)};
+    FD_HIP(ctx, launch_adjoint(a, g, s));
     return FD_OK;
 }
 
-int fd_deform_gram(fd_ctx *ctx, int64_t N, const float *P_in, const float *omega, const float *dist2, const float *tu, const float *tv,
-                   const float *nrm, float radius2, float falloffrate, double *H)
+// fd_deform_gram_dev: the Gram operator's two launches
+static int gram_dev(fd_ctx *ctx, const char *who, const Mesh &m, const float *d_omega, double *d_H)
 {
-    if (!ctx) return FD_E_INVALID;
-    if (!H || N < 0) { set_err(ctx, "fd_deform_gram: bad N / H pointers"); return FD_E_INVALID; }
-    return gram_host(ctx, N, P_in, omega, dist2, tu, tv, nrm, radius2, falloffrate, H);
-}
-
-int fd_deform_adjoint_shot_dev(fd_ctx *ctx, int64_t N, int F, const float *d_P_in, const float *d_G, const float *d_dist2,
-                               const float *d_tu, const float *d_tv, const float *d_nrm, float radius2, float falloffrate,
-                               double *d_grad_W)
-{
-    if (!ctx) return FD_E_INVALID;
-    if (!d_G || !d_grad_W || N < 0 || F < 1) { set_err(ctx, "fd_deform_adjoint_shot: bad N / F / G / grad_W pointers"); return FD_E_INVALID; }
-    const AdjointShotArgs shot{d_G, d_grad_W, nullptr, F, 0};
-    int rc = deform_dev_common(ctx, nullptr, N, d_P_in, nullptr, d_dist2, nullptr, d_tu, d_tv, d_nrm, radius2, falloffrate, nullptr,
-                               nullptr, nullptr, nullptr, &shot);
-    if (rc || N > 0) return rc;
-    // no vertex: no launch, zeros
-    if ((rc = use_device(ctx))) return rc;
-    FD_HIP(ctx, hipMemsetAsync(d_grad_W, 0, sizeof(double) * (size_t)F * adjoint_block(model_centres(ctx)), cur_stream(ctx)));
+    DeformArgs a;
+    hipStream_t s;
+    int rc = deform_begin(ctx, who, nullptr, m, nullptr, nullptr, true, &a, &s);
+    if (rc || m.N == 0) return rc;
+    if ((rc = dev_grow(ctx, &ctx->d_gram, &ctx->cap_gram, gram_scratch(m.N, a.M, m.tu ? 6 : 1)))) return rc;
+    const GramArgs g{d_omega, d_H, ctx->d_gram, term_cols(ctx->term)};
+    FD_HIP(ctx, launch_gram(a, g, s));
     return FD_OK;
 }
 
-int fd_deform_adjoint_shot(fd_ctx *ctx, int64_t N, int F, const float *P_in, const float *G, const float *dist2, const float *tu,
-                           const float *tv, const float *nrm, float radius2, float falloffrate, double *grad_W)
+// fd_deform_adjoint_shot_dev: the shot adjoint's two launches per group of frames
+static int adjoint_shot_dev(fd_ctx *ctx, const char *who, const Mesh &m, int F, const float *d_G, double *d_grad_W)
 {
-    if (!ctx) return FD_E_INVALID;
-    if (!G || !grad_W || N < 0 || F < 1) { set_err(ctx, "fd_deform_adjoint_shot: bad N / F / G / grad_W pointers"); return FD_E_INVALID; }
-    return adjoint_shot_host(ctx, N, F, P_in, G, dist2, tu, tv, nrm, radius2, falloffrate, grad_W, false);
+    DeformArgs a;
+    hipStream_t s;
+    int rc = deform_begin(ctx, who, nullptr, m, nullptr, nullptr, true, &a, &s);
+    if (rc || m.N == 0) return rc;
+    if ((rc = dev_grow(ctx, &ctx->d_adjs, &ctx->cap_adjs, adjoint_shot_scratch(m.N, a.M, 0)))) return rc;
+    const AdjointShotArgs g{d_G, d_grad_W, ctx->d_adjs, F, term_cols(ctx->term)};
+    FD_HIP(ctx, launch_adjoint_shot(a, g, s));
+    return FD_OK;
 }
 
-}  // extern "C"
-
-// the staging arrays of the host calls for N vertices: d_P, d_dist2, d_fall; the frames' on first use
+// the staging arrays of the host calls for N vertices: d_P, d_dist2, d_fall; the frames' on first use.  cap_N is 0 while the
+// first three are being replaced, and d_nrm, which comes last, is set only when all three frames are.
 static int ensure_staging(fd_ctx *ctx, int64_t N, bool frames)
 {
     int rc;
     if (N > ctx->cap_N) {
+        ctx->cap_N = 0;                 // one capacity for three buffers: dev_grow's rule, spelled out
         if ((rc = dev_alloc(ctx, &ctx->d_P, (size_t)N * 3))) return rc;
         if ((rc = dev_alloc(ctx, &ctx->d_dist2, (size_t)N))) return rc;
         if ((rc = dev_alloc(ctx, &ctx->d_fall, (size_t)N))) return rc;
         // tangent frames are optional and 3x as large: allocate on first use
-        if (ctx->d_tu) { (void)hipFree(ctx->d_tu); ctx->d_tu = nullptr; }
-        if (ctx->d_tv) { (void)hipFree(ctx->d_tv); ctx->d_tv = nullptr; }
-        if (ctx->d_nrm) { (void)hipFree(ctx->d_nrm); ctx->d_nrm = nullptr; }
+        for (float **p : {&ctx->d_tu, &ctx->d_tv, &ctx->d_nrm})
+            if (*p) { (void)hipFree(*p); *p = nullptr; }
         ctx->cap_N = N;
     }
-    if (frames && !ctx->d_tu) {
+    if (frames && !ctx->d_nrm) {
         if ((rc = dev_alloc(ctx, &ctx->d_tu, (size_t)ctx->cap_N * 3))) return rc;
         if ((rc = dev_alloc(ctx, &ctx->d_tv, (size_t)ctx->cap_N * 3))) return rc;
         if ((rc = dev_alloc(ctx, &ctx->d_nrm, (size_t)ctx->cap_N * 3))) return rc;
@@ -1291,17 +1171,45 @@ static int ensure_staging(fd_ctx *ctx, int64_t N, bool frames)
     return FD_OK;
 }
 
-// fd_deform / fd_deform_vectors on host arrays: staged through the context's device buffers, or -- page-locked arrays and
-// no vectors -- read and written in place
-static int deform_host(fd_ctx *ctx, int64_t N, const float *P_in, float *P_out, const float *dist2, float *falloff_out,
-                       const float *tu, const float *tv, const float *nrm, float radius2, float falloffrate, const fd_vectors *vec)
+// one more host array of `floats` per vertex that goes up among the mesh's, into the staging buffer *dst (read once
+// ensure_staging has run, which may replace it); src == nullptr: none
+struct Upload { float *const *dst; const float *src; int floats; };
+
+// The host mesh h on the device, for the host calls: the staging buffers grown for it, the uploads enqueued on s -- P, after_P's,
+// dist2, after_dist2's, the three frames -- and *d the same mesh in the staging buffers, null where h has null.  An empty
+// mesh touches no device and is handed back as it came: whether it has frames still says how large a result is.
+static int stage_mesh(fd_ctx *ctx, const Mesh &h, hipStream_t s, Mesh *d, Upload after_P = {}, Upload after_dist2 = {})
 {
-    if (N < 0 || (N > 0 && (!P_in || !P_out))) { set_err(ctx, "fd_deform: bad N / P pointers"); return FD_E_INVALID; }
-    if (!frames_ok(tu, tv, nrm)) { set_err(ctx, "fd_deform: tu, tv, nrm must be all set or all NULL"); return FD_E_INVALID; }
-    if (!ctx->built && !ctx->build_pending) { set_err(ctx, "fd_deform: no successfully built model"); return FD_E_NOT_BUILT; }
-    if (N == 0) return FD_OK;
+    *d = h;
+    if (h.N == 0) return FD_OK;
     int rc = use_device(ctx);
     if (rc) return rc;
+    if ((rc = ensure_staging(ctx, h.N, h.tu != nullptr))) return rc;
+    const size_t b1 = sizeof(float) * (size_t)h.N, b3 = 3 * b1;
+    FD_HIP(ctx, hipMemcpyAsync(ctx->d_P, h.P, b3, hipMemcpyHostToDevice, s));
+    if (after_P.src) FD_HIP(ctx, hipMemcpyAsync(*after_P.dst, after_P.src, b1 * (size_t)after_P.floats, hipMemcpyHostToDevice, s));
+    if (h.dist2) FD_HIP(ctx, hipMemcpyAsync(ctx->d_dist2, h.dist2, b1, hipMemcpyHostToDevice, s));
+    if (after_dist2.src) FD_HIP(ctx, hipMemcpyAsync(*after_dist2.dst, after_dist2.src, b1 * (size_t)after_dist2.floats, hipMemcpyHostToDevice, s));
+    d->P = ctx->d_P;
+    d->dist2 = h.dist2 ? ctx->d_dist2 : nullptr;
+    if (h.tu) {
+        FD_HIP(ctx, hipMemcpyAsync(ctx->d_tu, h.tu, b3, hipMemcpyHostToDevice, s));
+        FD_HIP(ctx, hipMemcpyAsync(ctx->d_tv, h.tv, b3, hipMemcpyHostToDevice, s));
+        FD_HIP(ctx, hipMemcpyAsync(ctx->d_nrm, h.nrm, b3, hipMemcpyHostToDevice, s));
+        d->tu = ctx->d_tu; d->tv = ctx->d_tv; d->nrm = ctx->d_nrm;
+    }
+    return FD_OK;
+}
+
+// fd_deform / fd_deform_vectors on host arrays: staged through the context's device buffers, or -- page-locked arrays and
+// no vectors -- read and written in place
+static int deform_host(fd_ctx *ctx, const char *who, const Mesh &m, float *P_out, float *falloff_out, const fd_vectors *vec)
+{
+    const int64_t N = m.N;
+    const float *const P_in = m.P, *const dist2 = m.dist2, *const tu = m.tu, *const tv = m.tv, *const nrm = m.nrm;
+    int rc = mesh_checks(ctx, who, m, P_out != nullptr);
+    if (rc || N == 0) return rc;
+    if ((rc = use_device(ctx))) return rc;
     // Page-locked caller arrays (fd_host_alloc, hipHostMalloc, hipHostRegister): the kernel reads
     // and writes them in place over the host link -- reads and writes travel in both directions
     // at once and nothing is staged.  Measured at C2: 0.44 ms against 0.62 ms for upload +
@@ -1322,33 +1230,23 @@ static int deform_host(fd_ctx *ctx, int64_t N, const float *P_in, float *P_out, 
         float *zO = (float *)dp(P_out), *zF = (float *)dp(falloff_out);
         if (ok) {
             hipStream_t s = cur_stream(ctx);
-            rc = fd_deform_dev_stream(ctx, s, N, zP, zO, zD, zF, zU, zV, zN, radius2, falloffrate);
+            rc = fd_deform_dev_stream(ctx, s, N, zP, zO, zD, zF, zU, zV, zN, m.radius2, m.falloffrate);
             if (rc) return rc;
             FD_HIP(ctx, hipStreamSynchronize(s));
             return FD_OK;
         }
     }
-    if ((rc = ensure_staging(ctx, N, tu != nullptr))) return rc;
     // A vertex whose gate fails keeps the caller's fd_falloff entry, so that array goes up as
     // well -- unless no vertex can be gated (no dist2 and a non-negative radius^2).
-    const bool fall_up = falloff_out && (dist2 || radius2 < 0.f);
+    const bool fall_up = falloff_out && (dist2 || m.radius2 < 0.f);
     hipStream_t s = cur_stream(ctx);
+    Mesh d;
+    if ((rc = stage_mesh(ctx, m, s, &d, {}, Upload{&ctx->d_fall, fall_up ? falloff_out : nullptr, 1}))) return rc;
     const size_t b3 = sizeof(float) * 3 * (size_t)N, b1 = sizeof(float) * (size_t)N;
-    FD_HIP(ctx, hipMemcpyAsync(ctx->d_P, P_in, b3, hipMemcpyHostToDevice, s));
-    if (dist2) FD_HIP(ctx, hipMemcpyAsync(ctx->d_dist2, dist2, b1, hipMemcpyHostToDevice, s));
-    if (fall_up) FD_HIP(ctx, hipMemcpyAsync(ctx->d_fall, falloff_out, b1, hipMemcpyHostToDevice, s));
-    if (tu) {
-        FD_HIP(ctx, hipMemcpyAsync(ctx->d_tu, tu, b3, hipMemcpyHostToDevice, s));
-        FD_HIP(ctx, hipMemcpyAsync(ctx->d_tv, tv, b3, hipMemcpyHostToDevice, s));
-        FD_HIP(ctx, hipMemcpyAsync(ctx->d_nrm, nrm, b3, hipMemcpyHostToDevice, s));
-    }
     // the vectors: each staged in its own device array and transported in place there
     fd_vectors dv{};
     if (vec) {
-        if (N > ctx->cap_vec) {
-            if ((rc = dev_alloc(ctx, &ctx->d_vec, (size_t)N * 18))) return rc;
-            ctx->cap_vec = N;
-        }
+        if ((rc = dev_grow(ctx, &ctx->d_vec, &ctx->cap_vec, (size_t)N * 18))) return rc;
         float *const slot[4] = {ctx->d_vec, ctx->d_vec + 3 * N, ctx->d_vec + 6 * N, ctx->d_vec + 9 * N};
         const float *const in[3] = {vec->N, vec->tu, vec->tv};
         for (int k = 0; k < 3; ++k)
@@ -1359,10 +1257,7 @@ static int deform_host(fd_ctx *ctx, int64_t N, const float *P_in, float *P_out, 
         if (vec->tv) { dv.tv = slot[2]; dv.tv_out = slot[2]; }
         if (vec->jacobian) dv.jacobian = slot[3];
     }
-    rc = deform_dev_common(ctx, nullptr, N, ctx->d_P, ctx->d_P, dist2 ? ctx->d_dist2 : nullptr,
-                           falloff_out ? ctx->d_fall : nullptr, tu ? ctx->d_tu : nullptr,
-                           tu ? ctx->d_tv : nullptr, tu ? ctx->d_nrm : nullptr, radius2, falloffrate, vec ? &dv : nullptr);
-    if (rc) return rc;
+    if ((rc = deform_dev(ctx, who, nullptr, d, ctx->d_P, falloff_out ? ctx->d_fall : nullptr, vec ? &dv : nullptr))) return rc;
     FD_HIP(ctx, hipMemcpyAsync(P_out, ctx->d_P, b3, hipMemcpyDeviceToHost, s));
     if (falloff_out) FD_HIP(ctx, hipMemcpyAsync(falloff_out, ctx->d_fall, b1, hipMemcpyDeviceToHost, s));
     if (vec) {
@@ -1375,161 +1270,239 @@ static int deform_host(fd_ctx *ctx, int64_t N, const float *P_in, float *P_out, 
     return FD_OK;
 }
 
-// fd_invert on host arrays: staged through the context's device buffers like deform_host with vectors (no zero-copy form);
-// solved in place in d_P, residual_out through d_fall, iters_out through d_iters
-static int invert_host(fd_ctx *ctx, int64_t N, const float *Y, float *X_out, const float *dist2, const float *tu, const float *tv,
-                       const float *nrm, float radius2, float falloffrate, const fd_invert_opts *opts)
+// fd_invert on host arrays: staged like deform_host with vectors (no zero-copy form); solved in place in d_P, residual_out
+// through d_fall, iters_out through d_iters
+static int invert_host(fd_ctx *ctx, const Mesh &m, float *X_out, const fd_invert_opts *opts)
 {
-    if (N < 0 || (N > 0 && (!Y || !X_out))) { set_err(ctx, "fd_invert: bad N / Y / X_out pointers"); return FD_E_INVALID; }
-    if (!frames_ok(tu, tv, nrm)) { set_err(ctx, "fd_invert: tu, tv, nrm must be all set or all NULL"); return FD_E_INVALID; }
-    if (!ctx->built && !ctx->build_pending) { set_err(ctx, "fd_invert: no successfully built model"); return FD_E_NOT_BUILT; }
-    if (N == 0) return FD_OK;
-    int rc = use_device(ctx);
-    if (rc) return rc;
-    if ((rc = ensure_staging(ctx, N, tu != nullptr))) return rc;
-    if (opts->iters_out && N > ctx->cap_iters) {
-        if ((rc = dev_alloc(ctx, &ctx->d_iters, (size_t)N))) return rc;
-        ctx->cap_iters = N;
-    }
+    int rc = mesh_checks(ctx, "fd_invert", m, X_out != nullptr);
+    if (rc || m.N == 0) return rc;
+    if ((rc = use_device(ctx))) return rc;
+    if (opts->iters_out && (rc = dev_grow(ctx, &ctx->d_iters, &ctx->cap_iters, (size_t)m.N))) return rc;
     hipStream_t s = cur_stream(ctx);
-    const size_t b3 = sizeof(float) * 3 * (size_t)N, b1 = sizeof(float) * (size_t)N;
-    FD_HIP(ctx, hipMemcpyAsync(ctx->d_P, Y, b3, hipMemcpyHostToDevice, s));
-    if (dist2) FD_HIP(ctx, hipMemcpyAsync(ctx->d_dist2, dist2, b1, hipMemcpyHostToDevice, s));
-    if (tu) {
-        FD_HIP(ctx, hipMemcpyAsync(ctx->d_tu, tu, b3, hipMemcpyHostToDevice, s));
-        FD_HIP(ctx, hipMemcpyAsync(ctx->d_tv, tv, b3, hipMemcpyHostToDevice, s));
-        FD_HIP(ctx, hipMemcpyAsync(ctx->d_nrm, nrm, b3, hipMemcpyHostToDevice, s));
-    }
+    Mesh d;
+    if ((rc = stage_mesh(ctx, m, s, &d))) return rc;
     const InvertArgs inv{opts->max_iter, opts->tol, opts->residual_out ? ctx->d_fall : nullptr, opts->iters_out ? ctx->d_iters : nullptr};
-    rc = deform_dev_common(ctx, nullptr, N, ctx->d_P, ctx->d_P, dist2 ? ctx->d_dist2 : nullptr, nullptr, tu ? ctx->d_tu : nullptr,
-                           tu ? ctx->d_tv : nullptr, tu ? ctx->d_nrm : nullptr, radius2, falloffrate, nullptr, &inv);
-    if (rc) return rc;
-    FD_HIP(ctx, hipMemcpyAsync(X_out, ctx->d_P, b3, hipMemcpyDeviceToHost, s));
+    if ((rc = invert_dev(ctx, d, ctx->d_P, inv))) return rc;
+    const size_t b1 = sizeof(float) * (size_t)m.N;
+    FD_HIP(ctx, hipMemcpyAsync(X_out, ctx->d_P, 3 * b1, hipMemcpyDeviceToHost, s));
     if (opts->residual_out) FD_HIP(ctx, hipMemcpyAsync(opts->residual_out, ctx->d_fall, b1, hipMemcpyDeviceToHost, s));
-    if (opts->iters_out) FD_HIP(ctx, hipMemcpyAsync(opts->iters_out, ctx->d_iters, sizeof(int) * (size_t)N, hipMemcpyDeviceToHost, s));
+    if (opts->iters_out) FD_HIP(ctx, hipMemcpyAsync(opts->iters_out, ctx->d_iters, sizeof(int) * (size_t)m.N, hipMemcpyDeviceToHost, s));
     FD_HIP(ctx, hipStreamSynchronize(s));
     return FD_OK;
 }
 
-// fd_deform_adjoint on host arrays: staged through the context's device buffers like invert_host; G through d_vecP, grad_W
-// through the block behind the partial sums
-static int adjoint_host(fd_ctx *ctx, int64_t N, const float *P_in, const float *G, const float *dist2, const float *tu, const float *tv,
-                        const float *nrm, float radius2, float falloffrate, double *grad_W)
+// fd_deform_adjoint on host arrays: staged like invert_host; G through d_vecP, grad_W through the block behind the partial sums
+static int adjoint_host(fd_ctx *ctx, const char *who, const Mesh &m, const float *G, double *grad_W)
 {
-    if (N > 0 && !P_in) { set_err(ctx, "fd_deform_adjoint: bad N / P pointers"); return FD_E_INVALID; }
-    if (!frames_ok(tu, tv, nrm)) { set_err(ctx, "fd_deform_adjoint: tu, tv, nrm must be all set or all NULL"); return FD_E_INVALID; }
-    if (!ctx->built && !ctx->build_pending) { set_err(ctx, "fd_deform_adjoint: no successfully built model"); return FD_E_NOT_BUILT; }
+    int rc = mesh_checks(ctx, who, m, true);
+    if (rc) return rc;
     const int C = model_centres(ctx);
-    if (N == 0) { memset(grad_W, 0, sizeof(double) * adjoint_block(C)); return FD_OK; }
-    int rc = use_device(ctx);
-    if (rc) return rc;
-    if ((rc = ensure_staging(ctx, N, tu != nullptr))) return rc;
-    if (N > ctx->cap_vecP) {
-        if ((rc = dev_alloc(ctx, &ctx->d_vecP, (size_t)N * 3))) return rc;
-        ctx->cap_vecP = N;
-    }
-    if ((rc = adjoint_reserve(ctx, N, C))) return rc;
+    if (m.N == 0) { memset(grad_W, 0, sizeof(double) * adjoint_block(C)); return FD_OK; }
+    if ((rc = use_device(ctx))) return rc;
+    if ((rc = dev_grow(ctx, &ctx->d_vecP, &ctx->cap_vecP, (size_t)m.N * 3))) return rc;
+    if ((rc = dev_grow(ctx, &ctx->d_adj, &ctx->cap_adj, adjoint_scratch(m.N, C)))) return rc;
     hipStream_t s = cur_stream(ctx);
-    const size_t b3 = sizeof(float) * 3 * (size_t)N, b1 = sizeof(float) * (size_t)N;
-    FD_HIP(ctx, hipMemcpyAsync(ctx->d_P, P_in, b3, hipMemcpyHostToDevice, s));
-    FD_HIP(ctx, hipMemcpyAsync(ctx->d_vecP, G, b3, hipMemcpyHostToDevice, s));
-    if (dist2) FD_HIP(ctx, hipMemcpyAsync(ctx->d_dist2, dist2, b1, hipMemcpyHostToDevice, s));
-    if (tu) {
-        FD_HIP(ctx, hipMemcpyAsync(ctx->d_tu, tu, b3, hipMemcpyHostToDevice, s));
-        FD_HIP(ctx, hipMemcpyAsync(ctx->d_tv, tv, b3, hipMemcpyHostToDevice, s));
-        FD_HIP(ctx, hipMemcpyAsync(ctx->d_nrm, nrm, b3, hipMemcpyHostToDevice, s));
-    }
-    double *d_out = adjoint_staging(ctx, N, C);
-    const AdjointArgs adj{ctx->d_vecP, d_out, nullptr, 0};
-    rc = deform_dev_common(ctx, nullptr, N, ctx->d_P, nullptr, dist2 ? ctx->d_dist2 : nullptr, nullptr, tu ? ctx->d_tu : nullptr,
-                           tu ? ctx->d_tv : nullptr, tu ? ctx->d_nrm : nullptr, radius2, falloffrate, nullptr, nullptr, &adj);
-    if (rc) return rc;
+    Mesh d;
+    if ((rc = stage_mesh(ctx, m, s, &d, Upload{&ctx->d_vecP, G, 3}))) return rc;
+    double *d_out = adjoint_staging(ctx, m.N, C);
+    if ((rc = adjoint_dev(ctx, who, d, ctx->d_vecP, d_out))) return rc;
     FD_HIP(ctx, hipMemcpyAsync(grad_W, d_out, sizeof(double) * adjoint_block(C), hipMemcpyDeviceToHost, s));
     FD_HIP(ctx, hipStreamSynchronize(s));
     return FD_OK;
 }
 
-// fd_deform_gram on host arrays: staged like adjoint_host; omega through d_fall, H through the block behind the partial blocks
-static int gram_host(fd_ctx *ctx, int64_t N, const float *P_in, const float *omega, const float *dist2, const float *tu, const float *tv,
-                     const float *nrm, float radius2, float falloffrate, double *H)
+// The Gram operator of a mesh that stage_mesh has put on the device (d_omega: where its omega went, or null), H to the host: H
+// is staged in the block behind the partial blocks.  An empty mesh gives zeros and touches no device.
+static int gram_staged(fd_ctx *ctx, const char *who, const Mesh &d, const float *d_omega, double *H)
 {
-    if (N > 0 && !P_in) { set_err(ctx, "fd_deform_gram: bad N / P pointers"); return FD_E_INVALID; }
-    if (!frames_ok(tu, tv, nrm)) { set_err(ctx, "fd_deform_gram: tu, tv, nrm must be all set or all NULL"); return FD_E_INVALID; }
-    if (!ctx->built && !ctx->build_pending) { set_err(ctx, "fd_deform_gram: no successfully built model"); return FD_E_NOT_BUILT; }
-    const int C = model_centres(ctx), nq = tu ? 6 : 1;
-    if (N == 0) { memset(H, 0, sizeof(double) * gram_block(C, nq)); return FD_OK; }
-    int rc = use_device(ctx);
+    const int C = model_centres(ctx), nq = d.tu ? 6 : 1;
+    if (d.N == 0) { memset(H, 0, sizeof(double) * gram_block(C, nq)); return FD_OK; }
+    int rc = dev_grow(ctx, &ctx->d_gram, &ctx->cap_gram, gram_scratch(d.N, C, nq));
     if (rc) return rc;
-    if ((rc = ensure_staging(ctx, N, tu != nullptr))) return rc;
-    if ((rc = gram_reserve(ctx, N, C, nq))) return rc;
     hipStream_t s = cur_stream(ctx);
-    const size_t b3 = sizeof(float) * 3 * (size_t)N, b1 = sizeof(float) * (size_t)N;
-    FD_HIP(ctx, hipMemcpyAsync(ctx->d_P, P_in, b3, hipMemcpyHostToDevice, s));
-    if (omega) FD_HIP(ctx, hipMemcpyAsync(ctx->d_fall, omega, b1, hipMemcpyHostToDevice, s));
-    if (dist2) FD_HIP(ctx, hipMemcpyAsync(ctx->d_dist2, dist2, b1, hipMemcpyHostToDevice, s));
-    if (tu) {
-        FD_HIP(ctx, hipMemcpyAsync(ctx->d_tu, tu, b3, hipMemcpyHostToDevice, s));
-        FD_HIP(ctx, hipMemcpyAsync(ctx->d_tv, tv, b3, hipMemcpyHostToDevice, s));
-        FD_HIP(ctx, hipMemcpyAsync(ctx->d_nrm, nrm, b3, hipMemcpyHostToDevice, s));
-    }
-    double *d_out = gram_staging(ctx, N, C, nq);
-    const GramArgs gram{omega ? ctx->d_fall : nullptr, d_out, nullptr, 0};
-    rc = deform_dev_common(ctx, nullptr, N, ctx->d_P, nullptr, dist2 ? ctx->d_dist2 : nullptr, nullptr, tu ? ctx->d_tu : nullptr,
-                           tu ? ctx->d_tv : nullptr, tu ? ctx->d_nrm : nullptr, radius2, falloffrate, nullptr, nullptr, nullptr, &gram);
-    if (rc) return rc;
+    double *d_out = gram_staging(ctx, d.N, C, nq);
+    if ((rc = gram_dev(ctx, who, d, d_omega, d_out))) return rc;
     FD_HIP(ctx, hipMemcpyAsync(H, d_out, sizeof(double) * gram_block(C, nq), hipMemcpyDeviceToHost, s));
     FD_HIP(ctx, hipStreamSynchronize(s));
     return FD_OK;
 }
 
-// fd_deform_adjoint_shot on host arrays: the mesh staged like adjoint_host (mesh_staged: a host call before this one has left
-// these very arrays in the staging buffers, fd_fit_deltas_shot's gram_host); G goes through d_gshot one group of FD_MAX_BATCH
-// frames at a time, each group's launches behind its copy on the stream; grad_W of all frames is staged behind the partial
-// blocks and comes back in one copy
-static int adjoint_shot_host(fd_ctx *ctx, int64_t N, int F, const float *P_in, const float *G, const float *dist2, const float *tu,
-                             const float *tv, const float *nrm, float radius2, float falloffrate, double *grad_W, bool mesh_staged)
+// fd_deform_gram on host arrays: omega goes up through d_fall
+static int gram_host(fd_ctx *ctx, const char *who, const Mesh &m, const float *omega, double *H)
 {
-    if (N > 0 && !P_in) { set_err(ctx, "fd_deform_adjoint_shot: bad N / P pointers"); return FD_E_INVALID; }
-    if (!frames_ok(tu, tv, nrm)) { set_err(ctx, "fd_deform_adjoint_shot: tu, tv, nrm must be all set or all NULL"); return FD_E_INVALID; }
-    if (!ctx->built && !ctx->build_pending) { set_err(ctx, "fd_deform_adjoint_shot: no successfully built model"); return FD_E_NOT_BUILT; }
-    const int C = model_centres(ctx);
-    if (N == 0) { memset(grad_W, 0, sizeof(double) * (size_t)F * adjoint_block(C)); return FD_OK; }
-    int rc = use_device(ctx);
+    int rc = mesh_checks(ctx, who, m, true);
     if (rc) return rc;
-    if ((rc = ensure_staging(ctx, N, tu != nullptr))) return rc;
+    Mesh d;
+    if ((rc = stage_mesh(ctx, m, cur_stream(ctx), &d, Upload{&ctx->d_fall, omega, 1}))) return rc;
+    return gram_staged(ctx, who, d, omega ? ctx->d_fall : nullptr, H);
+}
+
+// The shot adjoint of a mesh that stage_mesh has put on the device, for F cotangents G on the host: G goes through d_gshot
+// one group of FD_MAX_BATCH frames at a time, each group's launches behind its copy on the stream; grad_W of all frames is staged
+// behind the partial blocks and comes back in one copy.  An empty mesh gives zeros and touches no device.
+static int adjoint_shot_staged(fd_ctx *ctx, const char *who, const Mesh &d, int F, const float *G, double *grad_W)
+{
+    const int C = model_centres(ctx);
+    if (d.N == 0) { memset(grad_W, 0, sizeof(double) * (size_t)F * adjoint_block(C)); return FD_OK; }
     const int group = F < FD_MAX_BATCH ? F : FD_MAX_BATCH;
-    const size_t frame = (size_t)N * 3;
-    if ((size_t)group * frame > ctx->cap_gshot) {
-        ctx->cap_gshot = 0;
-        if ((rc = dev_alloc(ctx, &ctx->d_gshot, (size_t)group * frame))) return rc;
-        ctx->cap_gshot = (size_t)group * frame;
-    }
-    if ((rc = adjoint_shot_reserve(ctx, N, C, F))) return rc;
+    const size_t frame = (size_t)d.N * 3;
+    int rc;
+    if ((rc = dev_grow(ctx, &ctx->d_gshot, &ctx->cap_gshot, (size_t)group * frame))) return rc;
+    if ((rc = dev_grow(ctx, &ctx->d_adjs, &ctx->cap_adjs, adjoint_shot_scratch(d.N, C, F)))) return rc;
     hipStream_t s = cur_stream(ctx);
-    const size_t b3 = sizeof(float) * frame, b1 = sizeof(float) * (size_t)N;
-    if (!mesh_staged) {
-        FD_HIP(ctx, hipMemcpyAsync(ctx->d_P, P_in, b3, hipMemcpyHostToDevice, s));
-        if (dist2) FD_HIP(ctx, hipMemcpyAsync(ctx->d_dist2, dist2, b1, hipMemcpyHostToDevice, s));
-        if (tu) {
-            FD_HIP(ctx, hipMemcpyAsync(ctx->d_tu, tu, b3, hipMemcpyHostToDevice, s));
-            FD_HIP(ctx, hipMemcpyAsync(ctx->d_tv, tv, b3, hipMemcpyHostToDevice, s));
-            FD_HIP(ctx, hipMemcpyAsync(ctx->d_nrm, nrm, b3, hipMemcpyHostToDevice, s));
-        }
-    }
-    double *d_out = adjoint_shot_staging(ctx, N, C);
+    double *d_out = adjoint_shot_staging(ctx, d.N, C);
     for (int f0 = 0; f0 < F; f0 += FD_MAX_BATCH) {
         const int nF = F - f0 < FD_MAX_BATCH ? F - f0 : FD_MAX_BATCH;
-        FD_HIP(ctx, hipMemcpyAsync(ctx->d_gshot, G + (size_t)f0 * frame, b3 * (size_t)nF, hipMemcpyHostToDevice, s));
-        const AdjointShotArgs shot{ctx->d_gshot, d_out + (size_t)f0 * adjoint_block(C), nullptr, nF, 0};
-        rc = deform_dev_common(ctx, nullptr, N, ctx->d_P, nullptr, dist2 ? ctx->d_dist2 : nullptr, nullptr, tu ? ctx->d_tu : nullptr,
-                               tu ? ctx->d_tv : nullptr, tu ? ctx->d_nrm : nullptr, radius2, falloffrate, nullptr, nullptr, nullptr,
-                               nullptr, &shot);
-        if (rc) return rc;
+        FD_HIP(ctx, hipMemcpyAsync(ctx->d_gshot, G + (size_t)f0 * frame, sizeof(float) * frame * (size_t)nF, hipMemcpyHostToDevice, s));
+        if ((rc = adjoint_shot_dev(ctx, who, d, nF, ctx->d_gshot, d_out + (size_t)f0 * adjoint_block(C)))) return rc;
     }
     FD_HIP(ctx, hipMemcpyAsync(grad_W, d_out, sizeof(double) * (size_t)F * adjoint_block(C), hipMemcpyDeviceToHost, s));
     FD_HIP(ctx, hipStreamSynchronize(s));
     return FD_OK;
 }
+
+// fd_deform_adjoint_shot on host arrays
+static int adjoint_shot_host(fd_ctx *ctx, const char *who, const Mesh &m, int F, const float *G, double *grad_W)
+{
+    int rc = mesh_checks(ctx, who, m, true);
+    if (rc) return rc;
+    Mesh d;
+    if ((rc = stage_mesh(ctx, m, cur_stream(ctx), &d))) return rc;
+    return adjoint_shot_staged(ctx, who, d, F, G, grad_W);
+}
+
+extern "C" {
+
+int fd_deform_dev(fd_ctx *ctx, int64_t N, const float *d_P_in, float *d_P_out, const float *d_dist2,
+                  float *d_falloff_out, const float *d_tu, const float *d_tv, const float *d_nrm,
+                  float radius2, float falloffrate)
+{
+    if (!ctx) return FD_E_INVALID;
+    return fd_deform_dev_stream(ctx, cur_stream(ctx), N, d_P_in, d_P_out, d_dist2, d_falloff_out, d_tu, d_tv,
+                                d_nrm, radius2, falloffrate);
+}
+
+int fd_deform_dev_stream(fd_ctx *ctx, void *hip_stream, int64_t N, const float *d_P_in, float *d_P_out,
+                         const float *d_dist2, float *d_falloff_out, const float *d_tu,
+                         const float *d_tv, const float *d_nrm, float radius2, float falloffrate)
+{
+    if (!ctx) return FD_E_INVALID;
+    return deform_dev(ctx, "fd_deform", hip_stream, Mesh{N, d_P_in, d_dist2, d_tu, d_tv, d_nrm, radius2, falloffrate}, d_P_out,
+                      d_falloff_out, nullptr);
+}
+
+int fd_deform_vectors_dev(fd_ctx *ctx, int64_t N, const float *d_P_in, float *d_P_out, const float *d_dist2,
+                          float *d_falloff_out, const float *d_tu, const float *d_tv, const float *d_nrm,
+                          float radius2, float falloffrate, const fd_vectors *vec)
+{
+    if (!ctx) return FD_E_INVALID;
+    if (!vectors_ok(ctx, vec)) return FD_E_INVALID;
+    return deform_dev(ctx, "fd_deform_vectors", nullptr, Mesh{N, d_P_in, d_dist2, d_tu, d_tv, d_nrm, radius2, falloffrate}, d_P_out,
+                      d_falloff_out, vectors_wanted(vec) ? vec : nullptr);
+}
+
+int fd_deform(fd_ctx *ctx, int64_t N, const float *P_in, float *P_out, const float *dist2,
+              float *falloff_out, const float *tu, const float *tv, const float *nrm, float radius2,
+              float falloffrate)
+{
+    if (!ctx) return FD_E_INVALID;
+    return deform_host(ctx, "fd_deform", Mesh{N, P_in, dist2, tu, tv, nrm, radius2, falloffrate}, P_out, falloff_out, nullptr);
+}
+
+int fd_deform_vectors(fd_ctx *ctx, int64_t N, const float *P_in, float *P_out, const float *dist2,
+                      float *falloff_out, const float *tu, const float *tv, const float *nrm,
+                      float radius2, float falloffrate, const fd_vectors *vec)
+{
+    if (!ctx) return FD_E_INVALID;
+    if (!vectors_ok(ctx, vec)) return FD_E_INVALID;
+    return deform_host(ctx, "fd_deform_vectors", Mesh{N, P_in, dist2, tu, tv, nrm, radius2, falloffrate}, P_out, falloff_out,
+                       vectors_wanted(vec) ? vec : nullptr);
+}
+
+int fd_invert_dev(fd_ctx *ctx, int64_t N, const float *d_Y, float *d_X_out, const float *d_dist2, const float *d_tu,
+                  const float *d_tv, const float *d_nrm, float radius2, float falloffrate, const fd_invert_opts *opts)
+{
+    if (!ctx) return FD_E_INVALID;
+    if (!invert_opts_ok(ctx, opts)) return FD_E_INVALID;
+    const InvertArgs inv{opts->max_iter, opts->tol, opts->residual_out, opts->iters_out};
+    return invert_dev(ctx, Mesh{N, d_Y, d_dist2, d_tu, d_tv, d_nrm, radius2, falloffrate}, d_X_out, inv);
+}
+
+int fd_invert(fd_ctx *ctx, int64_t N, const float *Y, float *X_out, const float *dist2, const float *tu, const float *tv,
+              const float *nrm, float radius2, float falloffrate, const fd_invert_opts *opts)
+{
+    if (!ctx) return FD_E_INVALID;
+    if (!invert_opts_ok(ctx, opts)) return FD_E_INVALID;
+    if (N < 0 || (N > 0 && (!Y || !X_out))) { set_err(ctx, "fd_invert: bad N / Y / X_out pointers"); return FD_E_INVALID; }
+    return invert_host(ctx, Mesh{N, Y, dist2, tu, tv, nrm, radius2, falloffrate}, X_out, opts);
+}
+
+int fd_deform_adjoint_dev(fd_ctx *ctx, int64_t N, const float *d_P_in, const float *d_G, const float *d_dist2, const float *d_tu,
+                          const float *d_tv, const float *d_nrm, float radius2, float falloffrate, double *d_grad_W)
+{
+    if (!ctx) return FD_E_INVALID;
+    if (!d_G || !d_grad_W || N < 0) { set_err(ctx, "fd_deform_adjoint: bad N / G / grad_W pointers"); return FD_E_INVALID; }
+    int rc = adjoint_dev(ctx, "fd_deform_adjoint", Mesh{N, d_P_in, d_dist2, d_tu, d_tv, d_nrm, radius2, falloffrate}, d_G, d_grad_W);
+    if (rc || N > 0) return rc;
+    // no vertex: no launch, zeros
+    if ((rc = use_device(ctx))) return rc;
+    FD_HIP(ctx, hipMemsetAsync(d_grad_W, 0, sizeof(double) * adjoint_block(model_centres(ctx)), cur_stream(ctx)));
+    return FD_OK;
+}
+
+int fd_deform_adjoint(fd_ctx *ctx, int64_t N, const float *P_in, const float *G, const float *dist2, const float *tu, const float *tv,
+                      const float *nrm, float radius2, float falloffrate, double *grad_W)
+{
+    if (!ctx) return FD_E_INVALID;
+    if (!G || !grad_W || N < 0) { set_err(ctx, "fd_deform_adjoint: bad N / G / grad_W pointers"); return FD_E_INVALID; }
+    return adjoint_host(ctx, "fd_deform_adjoint", Mesh{N, P_in, dist2, tu, tv, nrm, radius2, falloffrate}, G, grad_W);
+}
+
+int fd_deform_gram_dev(fd_ctx *ctx, int64_t N, const float *d_P_in, const float *d_omega, const float *d_dist2, const float *d_tu,
+                       const float *d_tv, const float *d_nrm, float radius2, float falloffrate, double *d_H)
+{
+    if (!ctx) return FD_E_INVALID;
+    if (!d_H || N < 0) { set_err(ctx, "fd_deform_gram: bad N / H pointers"); return FD_E_INVALID; }
+    int rc = gram_dev(ctx, "fd_deform_gram", Mesh{N, d_P_in, d_dist2, d_tu, d_tv, d_nrm, radius2, falloffrate}, d_omega, d_H);
+    if (rc || N > 0) return rc;
+    // no vertex: no launch, zeros
+    if ((rc = use_device(ctx))) return rc;
+    FD_HIP(ctx, hipMemsetAsync(d_H, 0, sizeof(double) * gram_block(model_centres(ctx), d_tu ? 6 : 1), cur_stream(ctx)));
+    return FD_OK;
+}
+
+int fd_deform_gram(fd_ctx *ctx, int64_t N, const float *P_in, const float *omega, const float *dist2, const float *tu, const float *tv,
+                   const float *nrm, float radius2, float falloffrate, double *H)
+{
+    if (!ctx) return FD_E_INVALID;
+    if (!H || N < 0) { set_err(ctx, "fd_deform_gram: bad N / H pointers"); return FD_E_INVALID; }
+    return gram_host(ctx, "fd_deform_gram", Mesh{N, P_in, dist2, tu, tv, nrm, radius2, falloffrate}, omega, H);
+}
+
+int fd_deform_adjoint_shot_dev(fd_ctx *ctx, int64_t N, int F, const float *d_P_in, const float *d_G, const float *d_dist2,
+                               const float *d_tu, const float *d_tv, const float *d_nrm, float radius2, float falloffrate,
+                               double *d_grad_W)
+{
+    if (!ctx) return FD_E_INVALID;
+    if (!d_G || !d_grad_W || N < 0 || F < 1) { set_err(ctx, "fd_deform_adjoint_shot: bad N / F / G / grad_W pointers"); return FD_E_INVALID; }
+    int rc = adjoint_shot_dev(ctx, "fd_deform_adjoint_shot", Mesh{N, d_P_in, d_dist2, d_tu, d_tv, d_nrm, radius2, falloffrate}, F, d_G,
+                              d_grad_W);
+    if (rc || N > 0) return rc;
+    // no vertex: no launch, zeros
+    if ((rc = use_device(ctx))) return rc;
+    FD_HIP(ctx, hipMemsetAsync(d_grad_W, 0, sizeof(double) * (size_t)F * adjoint_block(model_centres(ctx)), cur_stream(ctx)));
+    return FD_OK;
+}
+
+int fd_deform_adjoint_shot(fd_ctx *ctx, int64_t N, int F, const float *P_in, const float *G, const float *dist2, const float *tu,
+                           const float *tv, const float *nrm, float radius2, float falloffrate, double *grad_W)
+{
+    if (!ctx) return FD_E_INVALID;
+    if (!G || !grad_W || N < 0 || F < 1) { set_err(ctx, "fd_deform_adjoint_shot: bad N / F / G / grad_W pointers"); return FD_E_INVALID; }
+    return adjoint_shot_host(ctx, "fd_deform_adjoint_shot", Mesh{N, P_in, dist2, tu, tv, nrm, radius2, falloffrate}, F, G, grad_W);
+}
+
+}  // extern "C"
 
 // ---- fillers of the shot launches' argument structs (fd_batch_deform_*shared*_dev below; templates, so outside the C linkage block) ----
 // the mesh part of a launch's arguments (SharedDeformArgs, SharedEvalCommon and SharedVectorCommon name these fields alike)
@@ -2328,82 +2301,13 @@ int fd_solve_operator(fd_ctx *ctx, double *S)
     return done(FD_OK);
 }
 
-// ---- fd_fit_deltas: the host composition on top of the Gram operator, the adjoint and the solve operator ----
-// C (m x p) += A^T B for row-major A (k x m), B (k x p): rows of B and C are walked contiguously, k in blocks that stay in cache
-static void fit_atb(int m, int p, int k, const double *A, const double *B, double *Cm)
-{
-    constexpr int kb = 64;
-    for (int k0 = 0; k0 < k; k0 += kb) {
-        const int k1 = k0 + kb < k ? k0 + kb : k;
-        for (int i = 0; i < m; ++i) {
-            double *c = Cm + (size_t)i * p;
-            for (int kk = k0; kk < k1; ++kk) {
-                const double a = A[(size_t)kk * m + i];
-                const double *b = B + (size_t)kk * p;
-                for (int j = 0; j < p; ++j) c[j] += a * b[j];
-            }
-        }
-    }
-}
-
-// a . b with four running sums (a dependent chain of n additions would set the pace of the factorisation)
-static double fit_dot(const double *a, const double *b, int n)
-{
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-    int k = 0;
-    for (; k + 4 <= n; k += 4) { s0 += a[k] * b[k]; s1 += a[k + 1] * b[k + 1]; s2 += a[k + 2] * b[k + 2]; s3 += a[k + 3] * b[k + 3]; }
-    for (; k < n; ++k) s0 += a[k] * b[k];
-    return (s0 + s1) + (s2 + s3);
-}
-
-// A = L L^T in place on the lower triangle of the row-major A (order n); the pivots' extremes; false when a pivot is not
-// above n 2^-52 times its diagonal entry, which is where a zero pivot lands in fp64
-static bool fit_cholesky(int n, double *A, double &pmin, double &pmax)
-{
-    pmin = INFINITY; pmax = 0.0;
-    for (int j = 0; j < n; ++j) {
-        double *rj = A + (size_t)j * n;
-        const double ajj = rj[j];
-        const double d = ajj - fit_dot(rj, rj, j);
-        if (!(d > (double)n * 0x1p-52 * ajj) || !(d > 0.0) || !(d < INFINITY)) { pmin = d < pmin || d != d ? d : pmin; return false; }
-        pmin = d < pmin ? d : pmin; pmax = d > pmax ? d : pmax;
-        const double l = sqrt(d), inv = 1.0 / l;
-        rj[j] = l;
-        for (int i = j + 1; i < n; ++i) {
-            double *ri = A + (size_t)i * n;
-            ri[j] = (ri[j] - fit_dot(ri, rj, j)) * inv;
-        }
-    }
-    return true;
-}
-
-// L L^T x = b for nrhs interleaved right-hand sides (b is n x nrhs row-major, overwritten with x)
-static void fit_cholesky_solve(int n, const double *L, int nrhs, double *b)
-{
-    for (int i = 0; i < n; ++i) {
-        const double *ri = L + (size_t)i * n;
-        for (int a = 0; a < nrhs; ++a) {
-            double s = b[(size_t)i * nrhs + a];
-            for (int k = 0; k < i; ++k) s -= ri[k] * b[(size_t)k * nrhs + a];
-            b[(size_t)i * nrhs + a] = s / ri[i];
-        }
-    }
-    for (int i = n - 1; i >= 0; --i) {
-        for (int a = 0; a < nrhs; ++a) {
-            double s = b[(size_t)i * nrhs + a];
-            for (int k = i + 1; k < n; ++k) s -= L[(size_t)k * n + i] * b[(size_t)k * nrhs + a];
-            b[(size_t)i * nrhs + a] = s / L[(size_t)i * n + i];
-        }
-    }
-}
-
+// ---- fd_fit_deltas, fd_fit_deltas_shot: the host composition on top of the Gram operator, the adjoint and the solve operator;
+// its dense algebra is fd_fit_host.h's ----
 static double fit_ms_since(const std::chrono::steady_clock::time_point &t0)
 {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
-// ---- what fd_fit_deltas and fd_fit_deltas_shot share: the checks, the cotangent, the normal matrix and its factor, the
-// per-frame right-hand side, energy and solve
 static int fit_checks(fd_ctx *ctx, const char *who, int64_t N, const float *P_in, const float *T, double mu, const float *tu,
                       const float *tv, const float *nrm, const double *delta_out, const fd_fit_report *reports, int F)
 {
@@ -2427,116 +2331,6 @@ static int fit_checks(fd_ctx *ctx, const char *who, int64_t N, const float *P_in
     return FD_OK;
 }
 
-// g = omega (T - P), the difference and the product in fp32; returns sum_v omega_v |T_v - P_v|^2
-static double fit_cotangent(int64_t N, const float *P_in, const float *T, const float *omega, float *g)
-{
-    double tt = 0.0;
-    for (int64_t v = 0; v < N; ++v) {
-        const float w = omega ? omega[v] : 1.f;
-        double t2 = 0.0;
-        for (int a = 0; a < 3; ++a) {
-            const float d = T[3 * v + a] - P_in[3 * v + a];
-            g[3 * v + a] = w * d;
-            t2 += (double)d * (double)d;
-        }
-        if (w != 0.f) tt += (double)w * t2;
-    }
-    return tt;
-}
-
-// the normal system in the deltas: unknown 3 i + b with projection (order 3 M), else M with three right-hand sides.  Nothing
-// in it depends on the target: one FitSystem serves every frame of a shot.
-struct FitSystem {
-    int M, n, nq, order;
-    bool proj;
-    double mu;
-    const double *S;
-    std::vector<double> G;              // S^T H_q S, nq x M x M
-    std::vector<double> A;              // G in block form + mu I; its Cholesky factor after fit_factor
-    double pmin = 0.0, pmax = 0.0;
-    double at(int i, int bb, int k, int cc) const       // the (3 i + bb, 3 k + cc) entry of the block form, without mu
-    {
-        static const int qmap[3][3] = {{0, 1, 2}, {1, 3, 4}, {2, 4, 5}};
-        if (!proj) return bb == cc ? G[(size_t)i * M + k] : 0.0;
-        return G[(size_t)qmap[bb][cc] * M * M + (size_t)i * M + k];
-    }
-};
-
-static void fit_compose_G(FitSystem &sys, const double *H)
-{
-    const int M = sys.M, n = sys.n;
-    sys.G.assign((size_t)sys.nq * M * M, 0.0);
-    std::vector<double> HS((size_t)n * M);
-    for (int q = 0; q < sys.nq; ++q) {
-        std::fill(HS.begin(), HS.end(), 0.0);
-        fit_atb(n, M, n, H + (size_t)q * n * n, sys.S, HS.data());                 // H_q is symmetric: H_q^T S
-        fit_atb(M, M, n, sys.S, HS.data(), sys.G.data() + (size_t)q * M * M);
-    }
-}
-
-static void fit_compose_A(FitSystem &sys)
-{
-    const int M = sys.M, order = sys.order;
-    const double mu = sys.mu;
-    sys.A.resize((size_t)order * order);
-    if (sys.proj) {
-        for (int i = 0; i < M; ++i)
-            for (int bb = 0; bb < 3; ++bb)
-                for (int k = 0; k < M; ++k)
-                    for (int cc = 0; cc < 3; ++cc)
-                        sys.A[(size_t)(3 * i + bb) * order + 3 * k + cc] = sys.at(i, bb, k, cc) + (i == k && bb == cc ? mu : 0.0);
-    } else {
-        for (int i = 0; i < M; ++i)
-            for (int k = 0; k < M; ++k) sys.A[(size_t)i * M + k] = sys.G[(size_t)i * M + k] + (i == k ? mu : 0.0);
-    }
-}
-
-static bool fit_factor(FitSystem &sys) { return sys.order == 0 || fit_cholesky(sys.order, sys.A.data(), sys.pmin, sys.pmax); }
-
-// one frame's right-hand side b = S^T c + mu delta0 (M x 3), with S^T c kept aside for the energy
-static void fit_rhs(const FitSystem &sys, const double *c, const float *delta0, std::vector<double> &b, std::vector<double> &Stc)
-{
-    const int M = sys.M;
-    b.assign((size_t)M * 3, 0.0);
-    fit_atb(M, 3, sys.n, sys.S, c, b.data());
-    Stc = b;
-    if (delta0) for (size_t i = 0; i < (size_t)M * 3; ++i) b[i] += sys.mu * (double)delta0[i];
-}
-
-// the energy of a delta (M x 3) by the quadratic form: d^T G d - 2 d^T S^T c + tt + mu |d - delta0|^2
-static double fit_energy(const FitSystem &sys, const std::vector<double> &Stc, double tt, const float *delta0, const double *d)
-{
-    const int M = sys.M;
-    const bool proj = sys.proj;
-    long double e = tt;
-    for (int i = 0; i < M; ++i)
-        for (int bb = 0; bb < 3; ++bb) {
-            long double row = 0.0L;
-            for (int k = 0; k < M; ++k)
-                for (int cc = 0; cc < 3; ++cc) {
-                    if (!proj && cc != bb) continue;
-                    row += (long double)sys.at(i, bb, k, cc) * d[3 * k + cc];
-                }
-            const long double di = d[3 * i + bb], d0 = delta0 ? (long double)delta0[3 * i + bb] : 0.0L;
-            e += di * row - 2.0L * di * Stc[3 * i + bb] + (long double)sys.mu * (di - d0) * (di - d0);
-        }
-    return (double)e;
-}
-
-static double fit_energy_at_delta0(const FitSystem &sys, const std::vector<double> &Stc, double tt, const float *delta0)
-{
-    std::vector<double> d0v((size_t)sys.M * 3, 0.0);
-    if (delta0) for (size_t i = 0; i < (size_t)sys.M * 3; ++i) d0v[i] = (double)delta0[i];
-    return fit_energy(sys, Stc, tt, delta0, d0v.data());
-}
-
-// one frame's solve against the factor: without projection b is M x 3, three interleaved right-hand sides; with it b is one
-// vector of 3 M in the same memory order
-static void fit_solve(const FitSystem &sys, double *b)
-{
-    if (sys.order > 0) fit_cholesky_solve(sys.order, sys.A.data(), sys.proj ? 1 : 3, b);
-}
-
 static int fit_singular(fd_ctx *ctx, const char *who, double pmin)
 {
     set_err(ctx, "%s: the normal matrix is not positive definite (pivot %.3e): control points that no live vertex "
@@ -2544,15 +2338,16 @@ static int fit_singular(fd_ctx *ctx, const char *who, double pmin)
     return FD_E_SINGULAR;
 }
 
-int fd_fit_deltas(fd_ctx *ctx, int64_t N, const float *P_in, const float *T, const float *omega, const float *dist2, const float *tu,
-                  const float *tv, const float *nrm, float radius2, float falloffrate, double mu, const float *delta0,
-                  const double *S, double *delta_out, fd_fit_report *report)
+// fd_fit_deltas (shot = false, F = 1) and fd_fit_deltas_shot: the fit of F targets T (F x N x 3) over one mesh, omega and mu;
+// delta0 and delta_out are F x M x 3, reports F structs.  One Gram launch, one normal matrix and one factor serve all frames.  The
+// two calls differ in the first-order stage alone: the adjoint's launch there, the shot adjoint's here, even for one frame.
+static int fit_frames(fd_ctx *ctx, const char *who, bool shot, const Mesh &m, int F, const float *T, const float *omega, double mu,
+                      const float *delta0, const double *S, double *delta_out, fd_fit_report *reports)
 {
-    if (!ctx) return FD_E_INVALID;
     int rc;
-    if ((rc = fit_checks(ctx, "fd_fit_deltas", N, P_in, T, mu, tu, tv, nrm, delta_out, report, 1))) return rc;
+    if ((rc = fit_checks(ctx, who, m.N, m.P, T, mu, m.tu, m.tv, m.nrm, delta_out, reports, F))) return rc;
     FitSystem sys;
-    sys.M = ctx->M; sys.n = model_centres(ctx) + 4; sys.proj = tu != nullptr;
+    sys.M = ctx->M; sys.n = model_centres(ctx) + 4; sys.proj = m.tu != nullptr;
     sys.nq = sys.proj ? 6 : 1; sys.order = sys.proj ? 3 * sys.M : sys.M; sys.mu = mu;
     const int M = sys.M, n = sys.n;
     std::vector<double> S_own;
@@ -2562,90 +2357,37 @@ int fd_fit_deltas(fd_ctx *ctx, int64_t N, const float *P_in, const float *T, con
         S = S_own.data();
     }
     sys.S = S;
-    // ---- the second-order term
+    // ---- the second-order term, once; the mesh stays staged for the shot adjoint
     auto t0 = std::chrono::steady_clock::now();
     std::vector<double> H((size_t)sys.nq * n * n);
-    if ((rc = gram_host(ctx, N, P_in, omega, dist2, tu, tv, nrm, radius2, falloffrate, H.data()))) return rc;
+    Mesh d;
+    if ((rc = stage_mesh(ctx, m, cur_stream(ctx), &d, Upload{&ctx->d_fall, omega, 1}))) return rc;
+    if ((rc = gram_staged(ctx, who, d, omega ? ctx->d_fall : nullptr, H.data()))) return rc;
     const double ms_gram = fit_ms_since(t0);
-    // ---- the first-order term: the adjoint of g = omega (T - P)
+    // ---- the first-order terms: the adjoint of g_f = omega (T_f - P)
     t0 = std::chrono::steady_clock::now();
-    std::vector<float> g((size_t)N * 3);
-    const double tt = fit_cotangent(N, P_in, T, omega, g.data());
-    std::vector<double> c((size_t)n * 3);
-    if ((rc = adjoint_host(ctx, N, P_in, g.data(), dist2, tu, tv, nrm, radius2, falloffrate, c.data()))) return rc;
-    const double ms_adjoint = fit_ms_since(t0);
-    // ---- the normal system
-    t0 = std::chrono::steady_clock::now();
-    fit_compose_G(sys, H.data());
-    std::vector<double> b, Stc;
-    fit_rhs(sys, c.data(), delta0, b, Stc);
-    const double E0 = fit_energy_at_delta0(sys, Stc, tt, delta0);
-    fit_compose_A(sys);
-    const double ms_compose = fit_ms_since(t0);
-    // ---- the solve
-    t0 = std::chrono::steady_clock::now();
-    const bool ok = fit_factor(sys);
-    if (ok) fit_solve(sys, b.data());
-    const double ms_solve = fit_ms_since(t0);
-    if (report) {
-        report->order = sys.order;
-        report->E0 = E0;
-        report->E_fit = ok ? fit_energy(sys, Stc, tt, delta0, b.data()) : E0;
-        report->pivot_min = sys.order > 0 ? sys.pmin : 0.0;
-        report->pivot_max = sys.pmax;
-        report->ms_gram = ms_gram; report->ms_adjoint = ms_adjoint; report->ms_compose = ms_compose; report->ms_solve = ms_solve;
-    }
-    if (!ok) return fit_singular(ctx, "fd_fit_deltas", sys.pmin);
-    for (size_t i = 0; i < (size_t)M * 3; ++i) delta_out[i] = b[i];
-    return FD_OK;
-}
-
-int fd_fit_deltas_shot(fd_ctx *ctx, int64_t N, int F, const float *P_in, const float *T, const float *omega, const float *dist2,
-                       const float *tu, const float *tv, const float *nrm, float radius2, float falloffrate, double mu,
-                       const float *delta0, const double *S, double *delta_out, fd_fit_report *reports)
-{
-    if (!ctx) return FD_E_INVALID;
-    if (F < 1) { set_err(ctx, "fd_fit_deltas_shot: F < 1"); return FD_E_INVALID; }
-    int rc;
-    if ((rc = fit_checks(ctx, "fd_fit_deltas_shot", N, P_in, T, mu, tu, tv, nrm, delta_out, reports, F))) return rc;
-    FitSystem sys;
-    sys.M = ctx->M; sys.n = model_centres(ctx) + 4; sys.proj = tu != nullptr;
-    sys.nq = sys.proj ? 6 : 1; sys.order = sys.proj ? 3 * sys.M : sys.M; sys.mu = mu;
-    const int M = sys.M, n = sys.n;
-    std::vector<double> S_own;
-    if (!S) {
-        S_own.resize((size_t)n * M);
-        if ((rc = fd_solve_operator(ctx, S_own.data()))) return rc;
-        S = S_own.data();
-    }
-    sys.S = S;
-    // ---- the second-order term, once
-    auto t0 = std::chrono::steady_clock::now();
-    std::vector<double> H((size_t)sys.nq * n * n);
-    if ((rc = gram_host(ctx, N, P_in, omega, dist2, tu, tv, nrm, radius2, falloffrate, H.data()))) return rc;
-    const double ms_gram = fit_ms_since(t0);
-    // ---- the first-order terms: the shot adjoint of g_f = omega (T_f - P), one group of frames at a time; the mesh is where
-    // gram_host staged it
-    t0 = std::chrono::steady_clock::now();
-    const size_t frame = (size_t)N * 3, cblock = (size_t)n * 3, dblock = (size_t)M * 3;
+    const size_t frame = (size_t)m.N * 3, cblock = (size_t)n * 3, dblock = (size_t)M * 3;
     std::vector<double> tt((size_t)F), c((size_t)F * cblock);
-    {
-        // the group's cotangents on the host, in a buffer the context keeps: fresh pages for 32 frames of a large mesh cost more
-        // than everything else in this stage
+    if (!shot) {
+        std::vector<float> g(frame);
+        tt[0] = fit_cotangent(m.N, m.P, T, omega, g.data());
+        if ((rc = adjoint_host(ctx, who, m, g.data(), c.data()))) return rc;
+    } else {
+        // one group of frames at a time, its cotangents on the host in a buffer the context keeps: fresh pages for 32 frames of
+        // a large mesh cost more than everything else in this stage
         const size_t gneed = (size_t)(F < FD_MAX_BATCH ? F : FD_MAX_BATCH) * frame + 1;
         if (gneed > ctx->cap_hgshot) {
             free(ctx->h_gshot);
             ctx->cap_hgshot = 0;
             ctx->h_gshot = (float *)malloc(gneed * sizeof(float));
-            if (!ctx->h_gshot) { set_err(ctx, "fd_fit_deltas_shot: malloc(%zu bytes) failed", gneed * sizeof(float)); return FD_E_NOMEM; }
+            if (!ctx->h_gshot) { set_err(ctx, "%s: malloc(%zu bytes) failed", who, gneed * sizeof(float)); return FD_E_NOMEM; }
             ctx->cap_hgshot = gneed;
         }
         float *const g = ctx->h_gshot;
         for (int f0 = 0; f0 < F; f0 += FD_MAX_BATCH) {
             const int nF = F - f0 < FD_MAX_BATCH ? F - f0 : FD_MAX_BATCH;
-            for (int f = 0; f < nF; ++f) tt[f0 + f] = fit_cotangent(N, P_in, T + (size_t)(f0 + f) * frame, omega, g + (size_t)f * frame);
-            if ((rc = adjoint_shot_host(ctx, N, nF, P_in, g, dist2, tu, tv, nrm, radius2, falloffrate,
-                                        c.data() + (size_t)f0 * cblock, true))) return rc;
+            for (int f = 0; f < nF; ++f) tt[f0 + f] = fit_cotangent(m.N, m.P, T + (size_t)(f0 + f) * frame, omega, g + (size_t)f * frame);
+            if ((rc = adjoint_shot_staged(ctx, who, d, nF, g, c.data() + (size_t)f0 * cblock))) return rc;
         }
     }
     const double ms_adjoint = fit_ms_since(t0);
@@ -2676,10 +2418,29 @@ int fd_fit_deltas_shot(fd_ctx *ctx, int64_t N, int F, const float *P_in, const f
         report->pivot_max = sys.pmax;
         report->ms_gram = ms_gram; report->ms_adjoint = ms_adjoint; report->ms_compose = ms_compose; report->ms_solve = ms_solve;
     }
-    if (!ok) return fit_singular(ctx, "fd_fit_deltas_shot", sys.pmin);
+    if (!ok) return fit_singular(ctx, who, sys.pmin);
     for (int f = 0; f < F; ++f)
         for (size_t i = 0; i < dblock; ++i) delta_out[(size_t)f * dblock + i] = b[f][i];
     return FD_OK;
+}
+
+int fd_fit_deltas(fd_ctx *ctx, int64_t N, const float *P_in, const float *T, const float *omega, const float *dist2, const float *tu,
+                  const float *tv, const float *nrm, float radius2, float falloffrate, double mu, const float *delta0,
+                  const double *S, double *delta_out, fd_fit_report *report)
+{
+    if (!ctx) return FD_E_INVALID;
+    return fit_frames(ctx, "fd_fit_deltas", false, Mesh{N, P_in, dist2, tu, tv, nrm, radius2, falloffrate}, 1, T, omega, mu, delta0, S,
+                      delta_out, report);
+}
+
+int fd_fit_deltas_shot(fd_ctx *ctx, int64_t N, int F, const float *P_in, const float *T, const float *omega, const float *dist2,
+                       const float *tu, const float *tv, const float *nrm, float radius2, float falloffrate, double mu,
+                       const float *delta0, const double *S, double *delta_out, fd_fit_report *reports)
+{
+    if (!ctx) return FD_E_INVALID;
+    if (F < 1) { set_err(ctx, "fd_fit_deltas_shot: F < 1"); return FD_E_INVALID; }
+    return fit_frames(ctx, "fd_fit_deltas_shot", true, Mesh{N, P_in, dist2, tu, tv, nrm, radius2, falloffrate}, F, T, omega, mu, delta0, S,
+                      delta_out, reports);
 }
 
 // One launch evaluates every context of the batch on its own vertex arrays (grid y = context)
@@ -2705,8 +2466,8 @@ int fd_batch_deform_dev(fd_batch *b, void *hip_stream, int64_t N, const float *c
         if (!c->built && !c->build_pending) { batch_err(b, "fd_batch_deform_dev: context %d has no built model", i); return FD_E_NOT_BUILT; }
         const float *tu = d_tu ? d_tu[i] : nullptr, *tv = d_tv ? d_tv[i] : nullptr, *nr = d_nrm ? d_nrm[i] : nullptr;
         if (!frames_ok(tu, tv, nr)) { batch_err(b, "fd_batch_deform_dev: context %d: tu, tv, nrm must be all set or all NULL", i); return FD_E_INVALID; }
-        args[i] = deform_args(c, N, d_P_in[i], d_P_out[i], d_dist2 ? d_dist2[i] : nullptr, d_falloff_out ? d_falloff_out[i] : nullptr,
-                              tu, tv, nr, radius2, falloffrate);
+        args[i] = deform_args(c, Mesh{N, d_P_in[i], d_dist2 ? d_dist2[i] : nullptr, tu, tv, nr, radius2, falloffrate}, d_P_out[i],
+                              d_falloff_out ? d_falloff_out[i] : nullptr);
         if (c->output != c0->output) { batch_err(b, "fd_batch_deform_dev: context %d has another fd_set_output setting than context 0", i); return FD_E_INVALID; }
     }
     // statuses first: a model the poll had to rebuild (on its context's stream) is then ordered like any other build
@@ -2886,8 +2647,8 @@ static int vectors_per_context(fd_batch *b, hipStream_t stream, int precision, h
                                const float *d_tv, const float *d_nrm, float radius2, float falloffrate, const fd_batch_vectors *vec)
 {
     for (int i = 0; i < b->n; ++i) {
-        DeformArgs a = deform_args(b->ctxs[i], N, d_P_in, d_P_out[i], d_dist2, d_falloff_out ? d_falloff_out[i] : nullptr, d_tu, d_tv,
-                                   d_nrm, radius2, falloffrate);
+        DeformArgs a = deform_args(b->ctxs[i], Mesh{N, d_P_in, d_dist2, d_tu, d_tv, d_nrm, radius2, falloffrate}, d_P_out[i],
+                                   d_falloff_out ? d_falloff_out[i] : nullptr);
         a.precision = precision;
         const VectorArgs v{vec->N, vec->tu, vec->tv, vec->N ? vec->N_out[i] : nullptr, vec->tu ? vec->tu_out[i] : nullptr,
                            vec->tv ? vec->tv_out[i] : nullptr, vec->jacobian ? vec->jacobian[i] : nullptr};
@@ -3084,8 +2845,8 @@ int fd_batch_deform_vectors_shared_dev(fd_batch *b, void *hip_stream, int64_t N,
             fd_ctx *c = b->ctxs[i];
             const fd_vectors v{(int)sizeof(fd_vectors), vec->N, vec->N ? vec->N_out[i] : nullptr, vec->tu, vec->tu ? vec->tu_out[i] : nullptr,
                                vec->tv, vec->tv ? vec->tv_out[i] : nullptr, vec->jacobian ? vec->jacobian[i] : nullptr};
-            rc = deform_dev_common(c, stream, N, d_P_in, d_P_out[i], d_dist2, d_falloff_out ? d_falloff_out[i] : nullptr, d_tu, d_tv, d_nrm,
-                                   radius2, falloffrate, &v);
+            rc = deform_dev(c, "fd_deform", stream, Mesh{N, d_P_in, d_dist2, d_tu, d_tv, d_nrm, radius2, falloffrate}, d_P_out[i],
+                            d_falloff_out ? d_falloff_out[i] : nullptr, &v);
             if (rc) { batch_err(b, "context %d: %s", i, c->err); return rc; }
         }
         // these launches read the models to their end: fd_batch_wait_consumed waits for all of them
@@ -3169,8 +2930,8 @@ int fd_batch_deform_shared_fp64_dev(fd_batch *b, void *hip_stream, int64_t N, co
     if (!fast) {
         // the multilayer model, an eval_variant override: per context, the launch of an FD_EVAL_FP64 context on the shared arrays
         for (int i = 0; i < b->n; ++i) {
-            DeformArgs a = deform_args(b->ctxs[i], N, d_P_in, d_P_out[i], d_dist2, d_falloff_out ? d_falloff_out[i] : nullptr, d_tu, d_tv,
-                                       d_nrm, radius2, falloffrate);
+            DeformArgs a = deform_args(b->ctxs[i], Mesh{N, d_P_in, d_dist2, d_tu, d_tv, d_nrm, radius2, falloffrate}, d_P_out[i],
+                                       d_falloff_out ? d_falloff_out[i] : nullptr);
             a.precision = FD_EVAL_FP64;
             hipError_t e = launch_deform(a, stream);
             if (e != hipSuccess) { batch_err(b, "launch_deform failed: %s", hipGetErrorString(e)); return FD_E_DEVICE; }
@@ -3831,8 +3592,8 @@ int fd_shot_dev_eval_fp64_over(fd_shot_dev *sd, fd_ctx *ctx, int set, int slot, 
     if (sd->v_in[2]) { vec.tv = sd->v_in[2]; vec.tv_out = vo[2]; }
     const int before = ctx->eval_precision;
     ctx->eval_precision = FD_EVAL_FP64;
-    const int rc = deform_dev_common(ctx, sd->work, m.N, m.P, shot_slice_P(sd, set, slot), m.d2, shot_slice_fall(sd, set, slot), m.tu, m.tv,
-                                     m.nr, radius2, falloffrate, which > 0 ? &vec : nullptr);
+    const int rc = deform_dev(ctx, "fd_deform", sd->work, Mesh{m.N, m.P, m.d2, m.tu, m.tv, m.nr, radius2, falloffrate},
+                              shot_slice_P(sd, set, slot), shot_slice_fall(sd, set, slot), which > 0 ? &vec : nullptr);
     ctx->eval_precision = before;
     if (rc) { shot_err(sd, "%s", ctx->err); return rc; }
     FD_SHIP(sd, hipEventRecord(sd->sets[set].eval_ev, sd->work));
@@ -3884,7 +3645,8 @@ int fd_shot_dev_vectors_engine(fd_shot_dev *sd, float radius2, float falloffrate
     if (sd->v_in[2]) { vec.tv = sd->v_in[2]; vec.tv_out = vo[2]; }
     hipStream_t s = cur_stream(e);
     if (sd->set_fall && (m.d2 || radius2 < 0.f)) FD_SHIP(sd, hipMemsetAsync(shot_slice_fall(sd, 0, 0), 0, sizeof(float) * (size_t)sd->set_Np, s));
-    rc = deform_dev_common(e, s, m.N, m.P, shot_slice_P(sd, 0, 0), m.d2, shot_slice_fall(sd, 0, 0), m.tu, m.tv, m.nr, radius2, falloffrate, &vec);
+    rc = deform_dev(e, "fd_deform", s, Mesh{m.N, m.P, m.d2, m.tu, m.tv, m.nr, radius2, falloffrate}, shot_slice_P(sd, 0, 0),
+                    shot_slice_fall(sd, 0, 0), &vec);
     if (rc) { shot_err(sd, "%s", e->err); return rc; }
     float *const host[3] = {N_out, tu_out, tv_out};
     const size_t b3 = sizeof(float) * 3 * (size_t)m.N;

@@ -1,0 +1,212 @@
+"""One SHA-256 per case over the outputs of the one-context operators, to compare two builds of the library bit for bit:
+
+    python tests/tools/operators_digest.py > listing.txt          # in each of the two trees; the listings must be equal
+
+Fixed seed.  Models: thin-plate, QNN and a three-layer multilayer model, linear term, M in {5, 60, 253} control points (253:
+C + 4 = 257, a third Gram panel and a 17th tile).  Meshes: the first N in {0, 1, 255, 257, 1000} vertices of a head mesh -- an
+empty call, a lone vertex, both sides of a 256-vertex tile -- without and with dist2 (uniform on [0, radius2 / 0.9): about a
+tenth of the vertices gated) and without and with projection frames.  Per mesh and model, one line for each of
+  deform        fd_deform and fd_deform_dev: P_out, fd_falloff
+  vectors       fd_deform_vectors and fd_deform_vectors_dev, all outputs and the Jacobian; with projection frames the device
+                call once more with P_out = P_in and N_out = nrm in place, which sets P_in aside
+  invert        fd_invert and fd_invert_dev on the deformed points: X, residual, iters
+  adjoint       fd_deform_adjoint and fd_deform_adjoint_dev
+  gram          fd_deform_gram and fd_deform_gram_dev, omega given and not
+  adjoint_shot  fd_deform_adjoint_shot and fd_deform_adjoint_shot_dev at F in {1, 3, 33} (33: across the 32-frame group)
+  fit           fd_fit_deltas, omega given and not, S given and not: the deltas, and the report's order, E0, E_fit and pivots
+  fit_shot      fd_fit_deltas_shot at F in {1, 3, 33}, the same per frame
+(the two fits at M in {5, 60} alone), and one adjoint line at M = 520, a second 512-centre span.  The report's timings are in
+no digest.  A tool, not a test."""
+import hashlib
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+from facedeform_amd import capi, synth   # noqa: E402
+
+RADIUS2, RATE = 0.36, 1.7
+SIZES = (0, 1, 255, 257, 1000)
+CENTRES = (5, 60, 253)
+FIT_CENTRES = (5, 60)
+FRAMES = (1, 3, 33)
+MODELS = [("thin_plate", capi.KERNEL_THIN_PLATE, []), ("qnn", capi.KERNEL_GAUSSIAN_QNN, [1.0, 5.0]),
+          ("multilayer3", capi.KERNEL_GAUSSIAN_ML, [0.7, 3, 0.1])]
+DEV = None
+
+
+def digest(arrays):
+    h = hashlib.sha256()
+    for a in arrays:
+        if a is None:
+            h.update(b"-")
+            continue
+        if isinstance(a, torch.Tensor):
+            a = a.cpu().numpy()
+        h.update(np.ascontiguousarray(a).tobytes())
+    return h.hexdigest()
+
+
+def up(a):
+    """a on the device; an empty array becomes a few zeros, so that the pointer is not null"""
+    a = np.ascontiguousarray(a)
+    t = torch.from_numpy(a).to(DEV) if a.size else torch.zeros(4, dtype=torch.from_numpy(a).dtype, device=DEV)
+    torch.cuda.synchronize()        # the library works on a stream of its own, which does not wait for torch's
+    return t
+
+
+def fresh(shape, dtype=torch.float32):
+    """an output array filled with a value no call writes; an empty one becomes a few of them, so that the pointer is not null"""
+    n = int(np.prod(shape))
+    t = torch.full((max(n, 4),), -7, dtype=dtype, device=DEV)
+    torch.cuda.synchronize()        # the fill must have landed before a call on the library's own stream writes
+    return t[:n].reshape(shape) if n else t
+
+
+def ptr(t):
+    return 0 if t is None else t.data_ptr()
+
+
+def report(r):
+    return np.array([r.order, r.E0, r.E_fit, r.pivot_min, r.pivot_max], np.float64)
+
+
+def engine(kind, params, M):
+    e = capi.Engine(device=0)
+    rest = synth.control_points(M)
+    e.set_points(rest, synth.rig_deltas(rest, 0)); e.set_kernel(kind, params); e.set_term(capi.TERM_LINEAR)
+    assert e.build().terminationtype == 1
+    return e
+
+
+def mesh_cases():
+    full = synth.head_mesh(20_000)[::20][:1000].copy()
+    ftu, ftv, fnr = synth.tangent_frames(full)
+    rng = np.random.default_rng(5)
+    fd2 = (rng.random(1000) * RADIUS2 / 0.9).astype(np.float32)
+    fom = np.random.default_rng(19).choice(np.array([0, 0.5, 1, 2], np.float32), 1000)
+    fG = np.random.default_rng(11).standard_normal((max(FRAMES), 1000, 3)).astype(np.float32)
+    fV = np.random.default_rng(12).standard_normal((3, 1000, 3)).astype(np.float32)
+    for N in SIZES:
+        for with_d2 in (False, True):
+            for proj in (False, True):
+                yield dict(N=N, P=full[:N], d2=fd2[:N] if with_d2 else None, frames=(ftu[:N], ftv[:N], fnr[:N]) if proj else None,
+                           omega=fom[:N], G=np.ascontiguousarray(fG[:, :N]), V=fV[:, :N],
+                           label="N=%-4d dist2=%d proj=%d" % (N, with_d2, proj))
+
+
+def run_case(e, c, n, with_fits, S):
+    """the lines of one mesh on one engine: (operator, digest) pairs; n = C + 4"""
+    N, P, d2, frames, omega, G, V = c["N"], c["P"], c["d2"], c["frames"], c["omega"], c["G"], c["V"]
+    kw = dict(radius2=RADIUS2, falloffrate=RATE)
+    hkw = dict(dist2=d2, tangents=frames, **kw)
+    d_P, d_d2 = up(P), None if d2 is None else up(d2)
+    d_fr = [None] * 3 if frames is None else [up(a) for a in frames]
+    dkw = dict(d_dist2=ptr(d_d2), d_tu=ptr(d_fr[0]), d_tv=ptr(d_fr[1]), d_nrm=ptr(d_fr[2]), **kw)
+    sync = torch.cuda.synchronize
+    out = []
+
+    # deform
+    res = list(e.deform(P, **hkw))
+    o_P, o_f = fresh((N, 3)), fresh((N,))
+    e.deform_dev(N, ptr(d_P), ptr(o_P), d_falloff=ptr(o_f), **dkw); sync()
+    out.append(("deform", digest(res + [o_P, o_f])))
+    Y = res[0]
+
+    # vectors
+    res = list(e.deform_vectors(P, N=V[0], tu=V[1], tv=V[2], want_jacobian=True, **hkw))
+    d_V = [up(V[k]) for k in range(3)]
+    o_P, o_f, o_V, o_J = fresh((N, 3)), fresh((N,)), [fresh((N, 3)) for _ in range(3)], fresh((N, 9))
+    e.deform_vectors_dev(N, ptr(d_P), ptr(o_P), d_falloff=ptr(o_f), d_N=ptr(d_V[0]), d_N_out=ptr(o_V[0]), d_vtu=ptr(d_V[1]),
+                         d_vtu_out=ptr(o_V[1]), d_vtv=ptr(d_V[2]), d_vtv_out=ptr(o_V[2]), d_jacobian=ptr(o_J), **dkw); sync()
+    res += [o_P, o_f, o_J] + o_V
+    if frames is not None:          # N transported in place over the projection normal, P in place: P_in is set aside
+        c_P, c_nr, o_f = d_P.clone(), d_fr[2].clone(), fresh((N,))     # fresh() synchronises last
+        ckw = dict(dkw, d_nrm=ptr(c_nr))
+        e.deform_vectors_dev(N, ptr(c_P), ptr(c_P), d_falloff=ptr(o_f), d_N=ptr(c_nr), d_N_out=ptr(c_nr), **ckw); sync()
+        res += [c_P, c_nr, o_f]
+    out.append(("vectors", digest(res)))
+
+    # invert, on the deformed points
+    res = list(e.invert(Y, **hkw))
+    d_Y, o_X, o_r, o_i = up(Y), fresh((N, 3)), fresh((N,)), fresh((N,), torch.int32)
+    e.invert_dev(N, ptr(d_Y), ptr(o_X), d_residual=ptr(o_r), d_iters=ptr(o_i), **dkw); sync()
+    out.append(("invert", digest(res + [o_X, o_r, o_i])))
+
+    # adjoint
+    res = [e.deform_adjoint(P, G[0], **hkw)]
+    d_G, o_W = up(G), fresh((n, 3), torch.float64)
+    e.deform_adjoint_dev(N, ptr(d_P), ptr(d_G), ptr(o_W), **dkw); sync()
+    out.append(("adjoint", digest(res + [o_W])))
+
+    # gram
+    res = []
+    for om in (None, omega):
+        res.append(e.deform_gram(P, omega=om, **hkw))
+        d_om, o_H = None if om is None else up(om), fresh((6 if frames is not None else 1, n, n), torch.float64)
+        e.deform_gram_dev(N, ptr(d_P), ptr(o_H), d_omega=ptr(d_om), **dkw); sync()
+        res.append(o_H)
+    out.append(("gram", digest(res)))
+
+    # adjoint_shot
+    res = []
+    for F in FRAMES:
+        res.append(e.deform_adjoint_shot(P, G[:F], **hkw))
+        o_W = fresh((F, n, 3), torch.float64)
+        e.deform_adjoint_shot_dev(N, F, ptr(d_P), ptr(d_G), ptr(o_W), **dkw); sync()
+        res.append(o_W)
+    out.append(("adjoint_shot", digest(res)))
+
+    if with_fits:
+        M = e.M
+        T = (P[None] + np.float32(0.01) * G).astype(np.float32)
+        delta0 = (np.float32(0.01) * np.random.default_rng(13).standard_normal((max(FRAMES), M, 3))).astype(np.float32)
+        mu = 1e-3 * max(N, 1)
+        res = []
+        for om in (None, omega):
+            for Sm in (S, None):
+                d, r = e.fit_deltas(P, T[0], omega=om, mu=mu, delta0=delta0[0], S=Sm, **hkw)
+                res += [d, report(r)]
+        out.append(("fit", digest(res)))
+        res = []
+        for F in FRAMES:
+            d, reps = e.fit_deltas_shot(P, T[:F], omega=omega, mu=mu, delta0=delta0[:F], S=S, **hkw)
+            res += [d] + [report(r) for r in reps]
+        d, reps = e.fit_deltas_shot(P, T[:3], mu=mu, S=None, **hkw)
+        out.append(("fit_shot", digest(res + [d] + [report(r) for r in reps])))
+    return out
+
+
+def main():
+    global DEV
+    if not torch.cuda.is_available():
+        sys.exit("no GPU")
+    DEV = torch.device("cuda", 0)
+    cases = list(mesh_cases())
+    for name, kind, params in MODELS:
+        for M in CENTRES:
+            e = engine(kind, params, M)
+            n = int(e.L.fd_model_centres(e.ctx)) + 4
+            with_fits = M in FIT_CENTRES
+            S = e.solve_operator() if with_fits else None
+            for c in cases:
+                for op, h in run_case(e, c, n, with_fits, S):
+                    print("%-11s M=%-3d %s %-12s %s" % (name, M, c["label"], op, h), flush=True)
+            e.close()
+    # the adjoint over a second 512-centre span
+    e = engine(capi.KERNEL_THIN_PLATE, [], 520)
+    c = [c for c in cases if c["N"] == 1000][-1]
+    d_P, d_G, o_W = up(c["P"]), up(c["G"]), fresh((524, 3), torch.float64)
+    d_d2, d_fr = up(c["d2"]), [up(a) for a in c["frames"]]
+    host = e.deform_adjoint(c["P"], c["G"][0], dist2=c["d2"], tangents=c["frames"], radius2=RADIUS2, falloffrate=RATE)
+    e.deform_adjoint_dev(1000, ptr(d_P), ptr(d_G), ptr(o_W), d_dist2=ptr(d_d2), d_tu=ptr(d_fr[0]), d_tv=ptr(d_fr[1]), d_nrm=ptr(d_fr[2]),
+                         radius2=RADIUS2, falloffrate=RATE)
+    torch.cuda.synchronize()
+    print("%-11s M=%-3d %s %-12s %s" % ("thin_plate", 520, c["label"], "adjoint", digest([host, o_W])), flush=True)
+    e.close()
+
+
+if __name__ == "__main__":
+    main()
