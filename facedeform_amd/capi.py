@@ -60,6 +60,11 @@ class FdInvertOpts(C.Structure):
                 ("iters_out", C.c_void_p)]
 
 
+class FdAdjointPointsOpts(C.Structure):
+    """fd_adjoint_points_opts: the optional grad_f output (N float64) of fd_deform_adjoint_points*."""
+    _fields_ = [("struct_size", C.c_int), ("reserved", C.c_int), ("grad_f", C.c_void_p)]
+
+
 class FdBatchVectors(C.Structure):
     """fd_batch_vectors: ONE input array per vector (the shared mesh's, N x 3) with a table of one output pointer per
     context, and a table of Jacobian outputs (N x 9 each) or NULL."""
@@ -92,7 +97,7 @@ class FdsopShot(C.Structure):
 EXPORTS = [
     "fd_create", "fd_destroy", "fd_last_error", "fd_abi_version", "fd_set_stream", "fd_set_eval_precision", "fd_set_output", "fd_fp32_holds", "fd_set_points",
     "fd_set_points_dev", "fd_set_deltas", "fd_set_deltas_dev", "fd_set_kernel", "fd_set_term", "fd_build", "fd_build_async",
-    "fd_build_result", "fd_deform", "fd_deform_dev", "fd_deform_dev_stream", "fd_deform_vectors", "fd_deform_vectors_dev", "fd_invert", "fd_invert_dev", "fd_deform_adjoint", "fd_deform_adjoint_dev", "fd_solve_operator", "fd_deform_gram", "fd_deform_gram_dev", "fd_fit_deltas", "fd_deform_adjoint_shot", "fd_deform_adjoint_shot_dev", "fd_fit_deltas_shot", "fd_get_weights", "fd_model_centres", "fd_model_bytes",
+    "fd_build_result", "fd_deform", "fd_deform_dev", "fd_deform_dev_stream", "fd_deform_vectors", "fd_deform_vectors_dev", "fd_invert", "fd_invert_dev", "fd_deform_adjoint", "fd_deform_adjoint_dev", "fd_deform_adjoint_points", "fd_deform_adjoint_points_dev", "fd_solve_operator", "fd_deform_gram", "fd_deform_gram_dev", "fd_fit_deltas", "fd_deform_adjoint_shot", "fd_deform_adjoint_shot_dev", "fd_fit_deltas_shot", "fd_get_weights", "fd_model_centres", "fd_model_bytes",
     "fd_export_model", "fd_import_model", "fd_synchronize", "fd_host_alloc", "fd_host_free",
     "fd_mesh_set", "fd_mesh_size", "fd_deform_mesh", "fd_mesh_capture", "fd_mesh_get_dist2",
     "fd_capture_dist2", "fd_capture_dist2_dev", "fd_capture_islands", "fd_capture_islands_dev",
@@ -173,6 +178,10 @@ def load() -> C.CDLL:
     L.fd_deform_adjoint.restype = i32
     L.fd_deform_adjoint_dev.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, vp]
     L.fd_deform_adjoint_dev.restype = i32
+    L.fd_deform_adjoint_points.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, vp, C.POINTER(FdAdjointPointsOpts)]
+    L.fd_deform_adjoint_points.restype = i32
+    L.fd_deform_adjoint_points_dev.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, vp, C.POINTER(FdAdjointPointsOpts)]
+    L.fd_deform_adjoint_points_dev.restype = i32
     L.fd_solve_operator.argtypes = [vp, _f64p]; L.fd_solve_operator.restype = i32
     L.fd_deform_gram.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, vp]
     L.fd_deform_gram.restype = i32
@@ -560,6 +569,33 @@ class Engine:
         self._check(self.L.fd_deform_adjoint_dev(self.ctx, N, vp(d_P_in or None), vp(d_G or None), vp(d_dist2 or None),
                                                  vp(d_tu or None), vp(d_tv or None), vp(d_nrm or None), float(radius2),
                                                  float(falloffrate), vp(d_grad_W or None)))
+
+    def deform_adjoint_points(self, P, G, dist2=None, tangents=None, radius2=1.0, falloffrate=1.0, want_grad_f=False):
+        """fd_deform_adjoint_points: dL/dP_in = A^T g, (N, 3) float64, for the sensitivity G = dL/dP' at the deformed vertices
+        (N x 3): the cotangent of the POSITION output (for the displacement output subtract G).  dist2 and tangents =
+        (tu, tv, nrm) are the vertices' attributes, as in deform(); they are not differentiated.  want_grad_f: returns
+        (grad_P, grad_f), grad_f (N,) float64 the sensitivity g . Pi d(x) for each vertex's fall-off value."""
+        P, d2, tu, tv, nr = _mesh_arrays(P, dist2, tangents)
+        G = np.ascontiguousarray(G, np.float32).reshape(-1, 3)
+        if G.shape != P.shape:
+            raise ValueError("P and G must have the same shape")
+        n = P.shape[0]
+        out = np.empty((n, 3), np.float64)
+        gf = np.empty(n, np.float64) if want_grad_f else None
+        opts = FdAdjointPointsOpts(C.sizeof(FdAdjointPointsOpts), 0, _np_ptr(gf))
+        self._check(self.L.fd_deform_adjoint_points(self.ctx, n, _np_ptr(P), _np_ptr(G), _np_ptr(d2), _np_ptr(tu), _np_ptr(tv),
+                                                    _np_ptr(nr), float(radius2), float(falloffrate), _np_ptr(out), C.byref(opts)))
+        return (out, gf) if want_grad_f else out
+
+    def deform_adjoint_points_dev(self, N: int, d_P_in: int, d_G: int, d_grad_P: int, d_grad_f: int = 0, d_dist2: int = 0,
+                                  d_tu: int = 0, d_tv: int = 0, d_nrm: int = 0, radius2=1.0, falloffrate=1.0):
+        """fd_deform_adjoint_points_dev: device pointers (ints), one launch, asynchronous on the context's stream; d_grad_P is
+        N x 3 float64, d_grad_f N float64 or 0."""
+        vp = C.c_void_p
+        opts = FdAdjointPointsOpts(C.sizeof(FdAdjointPointsOpts), 0, vp(d_grad_f or None))
+        self._check(self.L.fd_deform_adjoint_points_dev(self.ctx, N, vp(d_P_in or None), vp(d_G or None), vp(d_dist2 or None),
+                                                        vp(d_tu or None), vp(d_tv or None), vp(d_nrm or None), float(radius2),
+                                                        float(falloffrate), vp(d_grad_P or None), C.byref(opts)))
 
     def solve_operator(self):
         """fd_solve_operator: S, (C + 4, M) float64 with W[:, a] = S @ delta[:, a] for the context's rest rig, kernel and term."""

@@ -114,6 +114,9 @@ struct fd_ctx {
     // the host call's G goes through d_vecP
     size_t cap_adj = 0;
     double *d_adj = nullptr;
+    // fd_deform_adjoint_points: the host call's staging of grad_P (N x 3) and, behind it, grad_f (N); its G goes through d_vecP
+    size_t cap_adjp = 0;
+    double *d_adjp = nullptr;
     // fd_deform_gram*: the workgroups' partial blocks and, behind them, the host call's staging of H (gram_scratch); the host
     // call's omega goes through d_fall
     size_t cap_gram = 0;
@@ -554,7 +557,7 @@ void fd_destroy(fd_ctx *ctx)
     if (ctx->stream_ || ctx->own_stream) (void)hipStreamSynchronize(cur_stream(ctx));
     void *bufs[] = {ctx->d_rest, ctx->d_delta, ctx->d_centres, ctx->d_radii, ctx->d_W, ctx->d_A,
                     ctx->d_X, ctx->d_ipiv, ctx->d_moves, ctx->d_rec32, ctx->d_rec64, ctx->d_tiles, ctx->d_tiles16, ctx->d_ns, ctx->d_model, ctx->d_slot,
-                    ctx->d_P, ctx->d_dist2, ctx->d_fall, ctx->d_tu, ctx->d_tv, ctx->d_nrm, ctx->d_vec, ctx->d_vecP, ctx->d_iters, ctx->d_adj, ctx->d_gram, ctx->d_adjs, ctx->d_gshot,
+                    ctx->d_P, ctx->d_dist2, ctx->d_fall, ctx->d_tu, ctx->d_tv, ctx->d_nrm, ctx->d_vec, ctx->d_vecP, ctx->d_iters, ctx->d_adj, ctx->d_adjp, ctx->d_gram, ctx->d_adjs, ctx->d_gshot,
                     ctx->m_P, ctx->m_dist2, ctx->m_tu, ctx->m_tv, ctx->m_nrm, ctx->m_out, ctx->m_fall};
     for (void *p : bufs) if (p) (void)hipFree(p);
     free(ctx->h_gshot);
@@ -1024,6 +1027,17 @@ static bool invert_opts_ok(fd_ctx *ctx, const fd_invert_opts *opts)
     return true;
 }
 
+// fd_deform_adjoint_points*: NULL opts (no grad_f), or a struct of at least this ABI's size
+static bool adjoint_points_opts_ok(fd_ctx *ctx, const fd_adjoint_points_opts *opts)
+{
+    if (opts && opts->struct_size < (int)sizeof(fd_adjoint_points_opts)) {
+        set_err(ctx, "fd_deform_adjoint_points: opts->struct_size is %d, must be sizeof(fd_adjoint_points_opts) = %d",
+                opts->struct_size, (int)sizeof(fd_adjoint_points_opts));
+        return false;
+    }
+    return true;
+}
+
 // The scratch of the adjoint, the Gram operator and the shot adjoint for N vertices and C records: the workgroups' partial blocks
 // and, behind them, room for the result, where the host call stages it (*_staging).  Grown on demand (dev_grow).
 // fd_deform_adjoint*: adjoint_groups(N) partial blocks of (C + 4) x 3 doubles and one more for grad_W
@@ -1119,6 +1133,17 @@ static int adjoint_dev(fd_ctx *ctx, const char *who, const Mesh &m, const float 
     if ((rc = dev_grow(ctx, &ctx->d_adj, &ctx->cap_adj, adjoint_scratch(m.N, a.M)))) return rc;
     const AdjointArgs g{d_G, d_grad_W, ctx->d_adj, term_cols(ctx->term)};
     FD_HIP(ctx, launch_adjoint(a, g, s));
+    return FD_OK;
+}
+
+// fd_deform_adjoint_points_dev: the one launch (d_grad_f: null for none); nothing is written for an empty mesh
+static int adjoint_points_dev(fd_ctx *ctx, const char *who, const Mesh &m, const float *d_G, double *d_grad_P, double *d_grad_f)
+{
+    DeformArgs a;
+    hipStream_t s;
+    const int rc = deform_begin(ctx, who, nullptr, m, nullptr, nullptr, true, &a, &s);
+    if (rc || m.N == 0) return rc;
+    FD_HIP(ctx, launch_adjoint_points(a, AdjointPointsArgs{d_G, d_grad_P, d_grad_f}, s));
     return FD_OK;
 }
 
@@ -1311,6 +1336,27 @@ static int adjoint_host(fd_ctx *ctx, const char *who, const Mesh &m, const float
     return FD_OK;
 }
 
+// fd_deform_adjoint_points on host arrays: staged like adjoint_host, G through d_vecP behind P; grad_P and, behind it, grad_f
+// come back from d_adjp
+static int adjoint_points_host(fd_ctx *ctx, const char *who, const Mesh &m, const float *G, double *grad_P, double *grad_f)
+{
+    int rc = mesh_checks(ctx, who, m, true);
+    if (rc || m.N == 0) return rc;
+    if ((rc = use_device(ctx))) return rc;
+    const size_t n = (size_t)m.N;
+    if ((rc = dev_grow(ctx, &ctx->d_vecP, &ctx->cap_vecP, n * 3))) return rc;
+    if ((rc = dev_grow(ctx, &ctx->d_adjp, &ctx->cap_adjp, n * 4))) return rc;
+    hipStream_t s = cur_stream(ctx);
+    Mesh d;
+    if ((rc = stage_mesh(ctx, m, s, &d, Upload{&ctx->d_vecP, G, 3}))) return rc;
+    double *d_f = grad_f ? ctx->d_adjp + n * 3 : nullptr;
+    if ((rc = adjoint_points_dev(ctx, who, d, ctx->d_vecP, ctx->d_adjp, d_f))) return rc;
+    FD_HIP(ctx, hipMemcpyAsync(grad_P, ctx->d_adjp, sizeof(double) * n * 3, hipMemcpyDeviceToHost, s));
+    if (grad_f) FD_HIP(ctx, hipMemcpyAsync(grad_f, d_f, sizeof(double) * n, hipMemcpyDeviceToHost, s));
+    FD_HIP(ctx, hipStreamSynchronize(s));
+    return FD_OK;
+}
+
 // The Gram operator of a mesh that stage_mesh has put on the device (d_omega: where its omega went, or null), H to the host: H
 // is staged in the block behind the partial blocks.  An empty mesh gives zeros and touches no device.
 static int gram_staged(fd_ctx *ctx, const char *who, const Mesh &d, const float *d_omega, double *H)
@@ -1456,6 +1502,28 @@ int fd_deform_adjoint(fd_ctx *ctx, int64_t N, const float *P_in, const float *G,
     if (!ctx) return FD_E_INVALID;
     if (!G || !grad_W || N < 0) { set_err(ctx, "fd_deform_adjoint: bad N / G / grad_W pointers"); return FD_E_INVALID; }
     return adjoint_host(ctx, "fd_deform_adjoint", Mesh{N, P_in, dist2, tu, tv, nrm, radius2, falloffrate}, G, grad_W);
+}
+
+int fd_deform_adjoint_points_dev(fd_ctx *ctx, int64_t N, const float *d_P_in, const float *d_G, const float *d_dist2,
+                                 const float *d_tu, const float *d_tv, const float *d_nrm, float radius2, float falloffrate,
+                                 double *d_grad_P, const fd_adjoint_points_opts *opts)
+{
+    if (!ctx) return FD_E_INVALID;
+    if (!d_G || !d_grad_P || N < 0) { set_err(ctx, "fd_deform_adjoint_points: bad N / G / grad_P pointers"); return FD_E_INVALID; }
+    if (!adjoint_points_opts_ok(ctx, opts)) return FD_E_INVALID;
+    return adjoint_points_dev(ctx, "fd_deform_adjoint_points", Mesh{N, d_P_in, d_dist2, d_tu, d_tv, d_nrm, radius2, falloffrate}, d_G,
+                              d_grad_P, opts ? opts->grad_f : nullptr);
+}
+
+int fd_deform_adjoint_points(fd_ctx *ctx, int64_t N, const float *P_in, const float *G, const float *dist2, const float *tu,
+                             const float *tv, const float *nrm, float radius2, float falloffrate, double *grad_P,
+                             const fd_adjoint_points_opts *opts)
+{
+    if (!ctx) return FD_E_INVALID;
+    if (!G || !grad_P || N < 0) { set_err(ctx, "fd_deform_adjoint_points: bad N / G / grad_P pointers"); return FD_E_INVALID; }
+    if (!adjoint_points_opts_ok(ctx, opts)) return FD_E_INVALID;
+    return adjoint_points_host(ctx, "fd_deform_adjoint_points", Mesh{N, P_in, dist2, tu, tv, nrm, radius2, falloffrate}, G, grad_P,
+                               opts ? opts->grad_f : nullptr);
 }
 
 int fd_deform_gram_dev(fd_ctx *ctx, int64_t N, const float *d_P_in, const float *d_omega, const float *d_dist2, const float *d_tu,

@@ -304,6 +304,15 @@ struct AdjointArgs {
 };
 int adjoint_groups(int64_t N);        // workgroups along the vertices: a function of N alone
 hipError_t launch_adjoint(const DeformArgs &a, const AdjointArgs &g, hipStream_t stream);
+// the adjoint in the vertex positions (fd_adjoint_points.hip, fd_deform_adjoint_points*): `a` as for the adjoint; G is the
+// cotangent at the deformed vertices (N x 3), grad_P the N x 3 result A^T g, grad_f the N values g . Pi d(x) or null.  One
+// launch, no scratch; N = 0 launches nothing.
+struct AdjointPointsArgs {
+    const float *G;
+    double *grad_P;
+    double *grad_f;
+};
+hipError_t launch_adjoint_points(const DeformArgs &a, const AdjointPointsArgs &g, hipStream_t stream);
 // the adjoint for the F cotangents of a shot (fd_adjoint_shot.hip, fd_deform_adjoint_shot*): `a` as for the adjoint; G is
 // F x N x 3 frame-major, grad_W F x (M + 4) x 3, T as above, partial a scratch of adjoint_shot_partial_doubles(N, M) doubles
 // that the groups of 32 frames use one after the other.  Two launches per group; N = 0 writes zeros.

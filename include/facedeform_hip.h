@@ -375,7 +375,7 @@ int fd_invert_dev(fd_ctx *ctx, int64_t N, const float *d_Y, float *d_X_out, cons
  * Checks and errors.  The build-status poll and repair, FD_E_NOT_BUILT, the all-or-none rule for tu/tv/nrm and the ordering
  *   behind a batched build are fd_deform's.  FD_E_INVALID for a NULL context, a NULL G or grad_W or N < 0 comes before any
  *   device work.  fd_set_output has no effect.  Only the (C+4) x 3 entries are written.
- * The sensitivity with respect to P_in is not part of this: it is A^T g with the A fd_deform_vectors writes.
+ * The sensitivity with respect to P_in is not part of this: it is A^T g, which fd_deform_adjoint_points returns (below).
  *
  * Device pointers, asynchronous on the context's stream (two launches; the partial sums live in the context). */
 int fd_deform_adjoint_dev(fd_ctx *ctx, int64_t N, const float *d_P_in, const float *d_G, const float *d_dist2,
@@ -394,6 +394,49 @@ int fd_deform_adjoint(fd_ctx *ctx, int64_t N, const float *P_in, const float *G,
  * stands.  FD_E_NOT_BUILT before fd_set_points; a helper build's own error if one fails.
  * The gradient for the deltas is then one small product on the caller's side:  grad_delta = S^T . grad_W  (M x 3). */
 int fd_solve_operator(fd_ctx *ctx, double *S);
+
+/* ---- the adjoint of the deformation in the vertex positions ---------------------------
+ * Given the same sensitivity g_v = dL/dP'_v, fd_deform_adjoint_points returns dL/dP_in: the reverse-mode derivative of
+ * P' = x + f . Pi . d(x) in the positions, dual to the forward-mode transport t' = A t of fd_deform_vectors.  With d, Pi, f, J, L
+ * and A = I + f Pi J as above and r_v = f_v Pi_v g_v:
+ *   grad_P[v] = A_v^T g_v = g_v + J(x_v)^T r_v,   J(x)^T r = sum_j (w_j . r) grad phi_j(x - c_j) + L^T r
+ *   grad_f[v] = g_v . Pi_v d(x_v)                 (d including its polynomial term; the sensitivity for the fall-off value f_v,
+ *                                                  what a caller needs to tune radius, falloffrate or the capture distances)
+ * grad_P is N x 3 fp64, grad_f N fp64.  dist2 and the frames are per-point attributes: they are not differentiated.
+ *
+ * The contract.  For any tangent field t (N x 3),
+ *   sum_v grad_P[v] . t_v = sum_v g_v . (A_v t_v),
+ *   A_v t_v what fd_deform_vectors writes as tu_out for tu = t, evaluated exactly.  This fixes every factor as the adjoint's
+ *   identity fixes the weights' factors.
+ * Arithmetic.  Everything is fp64 whatever fd_set_eval_precision says: the fp32 positions and g widened, x - c_j in raw
+ *   coordinates, phi and g of grad phi of the kind from one shared transcendental as the inverse forms them; the gate, f and Pi
+ *   are the forward path's own code.  r is formed as a1 (a1 . g) + a2 (a2 . g), then times f.
+ * Vertices where A = I.  A gated vertex (dist2 > radius2), a model with terminationtype != 1 (FD_OK, as fd_deform passes such a
+ *   model through) and a vertex with f = 0: grad_P[v] is g_v widened, bit for bit, NaN and infinity included (a select, not a
+ *   product): fd_deform_vectors' "A = I exactly".  grad_f[v] is 0.0 for the gated vertex and for the model that is not built;
+ *   for f = 0 it is the formula's value: the map still depends on f there.
+ * Determinism.  A vertex's result depends on nothing but its own inputs and the model: the same bits for any N, at any place in
+ *   the launch, on every call, in the host and the device-pointer form.  No atomics and no sums across vertices.
+ * fd_set_output has no effect: the result is the cotangent of the POSITION output.  For FD_OUTPUT_DISPLACEMENT the caller
+ *   subtracts g.
+ * Aliasing.  None allowed.
+ * Checks and errors.  FD_E_INVALID for a NULL context, a NULL G or grad_P (G even with N = 0, as the adjoint's), N < 0 or an opts
+ *   whose struct_size is too small comes before any device work.  The build-status poll and repair, FD_E_NOT_BUILT, the
+ *   all-or-none rule for tu/tv/nrm and the ordering behind a batched build are fd_deform's.  N = 0 writes nothing. */
+typedef struct fd_adjoint_points_opts {
+    int struct_size;     /* = sizeof(fd_adjoint_points_opts); smaller is FD_E_INVALID */
+    int reserved;
+    double *grad_f;      /* N, or NULL */
+} fd_adjoint_points_opts;
+
+/* Device pointers (grad_f in `opts` too), asynchronous on the context's stream: one launch.  opts == NULL: no grad_f. */
+int fd_deform_adjoint_points_dev(fd_ctx *ctx, int64_t N, const float *d_P_in, const float *d_G, const float *d_dist2,
+                                 const float *d_tu, const float *d_tv, const float *d_nrm,
+                                 float radius2, float falloffrate, double *d_grad_P, const fd_adjoint_points_opts *opts);
+/* Same, host arrays (grad_f in `opts` too), staged through the context's buffers as fd_deform_adjoint's; synchronous. */
+int fd_deform_adjoint_points(fd_ctx *ctx, int64_t N, const float *P_in, const float *G, const float *dist2,
+                             const float *tu, const float *tv, const float *nrm,
+                             float radius2, float falloffrate, double *grad_P, const fd_adjoint_points_opts *opts);
 
 /* ---- the Gram operator and the fit ------------------------------------------------
  * The deformation is linear in the weights and the weights are linear in the deltas (W = S delta, fd_solve_operator), so
