@@ -14,6 +14,7 @@
 
 #include "fd_fit_host.h"
 #include "fd_internal.h"
+#include "fd_shared_plan.h"
 
 using namespace fd;
 using namespace fd_fit;
@@ -2747,12 +2748,9 @@ static int shared_pack(fd_batch *b, hipStream_t stream, int ek, float *const *d_
     }
     // "one rest rig" by content is what the pack kernel checks (an address does not identify contents); contexts that ONE batched
     // build read from one array are equal by construction, and the comparison -- the pack kernel's longest chain -- is skipped
-    {
-        bool one_build = c0->rig_build_id != 0;
-        for (int i = 1; i < b->n && one_build; ++i) one_build = b->ctxs[i]->rig_build_id == c0->rig_build_id;
-        if (one_build) for (int i = 1; i < b->n; ++i) a.centres[i] = a.centres[0];
-    }
-    const size_t wb = shared_wtile_bytes(a.Mpad, a.nF), fb = shared_frame_bytes(a.nF);
+    if (one_build(b)) for (int i = 1; i < b->n; ++i) a.centres[i] = a.centres[0];
+    const SharedPlan pl = shared_plan(a.Mpad, a.nF, a.kind);
+    const size_t wb = pl.wtile_bytes, fb = pl.frame_bytes;
     if (wb > st.cap_wtiles || fb > st.cap_frames) {
         // (hipFree drains the device: no launch still reads the old scratch)
         if (st.d_wtiles) (void)hipFree(st.d_wtiles);
@@ -3396,7 +3394,7 @@ const char *fd_shared_kernel_name(int M, int frames, int kind)
 {
     const bool takes = (kind == FD_KERNEL_THIN_PLATE || kind == FD_KERNEL_GAUSSIAN || kind == FD_KERNEL_GAUSSIAN_QNN) && M > 0 && round_up(M, kRecPad) >= 32 &&
                        frames >= 1 && frames <= kMaxBatch;
-    return takes ? shared_kernel_name(round_up(M, kRecPad), frames, kind) : "";
+    return takes ? shared_plan(round_up(M, kRecPad), frames, kind).kernel : "";
 }
 
 }  // extern "C"

@@ -16,6 +16,7 @@
 
 #include "fd_eval_common.h"
 #include "fd_shared_common.h"
+#include "fd_shared_plan.h"
 
 namespace fd {
 
@@ -43,21 +44,8 @@ namespace {
 // x 16 vertices with rows = 4 frames x (x, y, z, unused): lane group g' of the accumulator then holds
 // all three components of frame 4 T + g' for its vertex and writes them as 12 contiguous bytes.
 
-constexpr int kSharedThreads = 512;
-constexpr int kWideWaves = 8;      // waves per workgroup of the two-tile 32-row kernel: two per SIMD, up to 256 registers each
-
-// Two row layouts of the output tiles (16 rows x 16 vertices each):
-//   padded (up to 12 frames): tile T holds frames 4 T .. 4 T + 3, row = 4 (frame - 4 T) + component, one row in
-//     four unused -- ceil(F / 4) tiles;
-//   dense (13 frames and more): frames come in blocks of 16 and a block is three tiles, one per component:
-//     tile 3 B + c holds component c of frames 16 B .. 16 B + 15, row = frame - 16 B -- 3 ceil(F / 16) tiles, no
-//     unused rows at F = 16, 32 (6 tiles instead of 8 at 32 frames: a quarter fewer matrix instructions).
-// Either way the 4 x 4 transpose across lane groups in the epilogue leaves every lane with all rows of
-// every tile for ONE vertex.
-constexpr bool shared_dense(int nF) { return nF > 12; }
-constexpr int shared_tiles(int nF) { return shared_dense(nF) ? 3 * ((nF + 15) / 16) : (nF + 3) / 4; }
-constexpr int shared_slots(int nT, bool dense) { return dense ? nT / 3 * 16 : nT * 4; }     // frame records
-
+// The tile shapes, the row layouts, the scratch offsets and the LDS sizes of the four kernel forms: fd_shared_plan.h.
+static_assert(sizeof(MfmaTileH) == kMfmaTileHBytes && sizeof(SharedFrame) == kSharedFrameBytes, "fd_shared_plan.h is sized by these");
 
 struct SharedOut {                // per-frame outputs (kernel argument)
     float *P_out[kMaxBatch];
@@ -126,39 +114,35 @@ __device__ __forceinline__ bool rig_matches(const SharedSlots &slots, int f, int
 // same matrix product as five more "centres" whose phi are (1, x', y', z', |x'|^2): one K = 32
 // instruction per output tile and vertex tile holds all three split products -- lane group 0
 // pairs hi x hi, group 1 lo(vertex) x hi(coefficient), group 2 hi(vertex) x lo(coefficient).
+// poly_at, copy_at, norm_at: SharedPlan's, 16-byte words into wtiles.
 __global__ __launch_bounds__(256) void k_pack_shared(const SharedSlots slots, const SharedOut out, int nF, int Mpad, int dense,
-                                                      uint4 *wtiles, SharedFrame *frames, const MfmaTileH *ctiles, int gauss)
+                                                      uint4 *wtiles, SharedFrame *frames, const MfmaTileH *ctiles, int gauss,
+                                                      size_t poly_at, size_t copy_at, size_t norm_at)
 {
-    const int kb = blockIdx.x, T = blockIdx.y, nT = gridDim.y, nkb = gridDim.x;
+    const int kb = blockIdx.x, T = blockIdx.y, nT = gridDim.y;
+    constexpr int per = (int)(sizeof(MfmaTileH) / 16);
+    uint4 *copy = wtiles + copy_at;
     if (T == 0 && gauss) {
         // Gaussian kinds: the slot of a K block's two centre tiles holds its 32 centre records instead
         // ({c'x, c'y, c'z, -log2(e) s^2 / R_j^2}: the first half of Rec32), read by direct differences
-        constexpr int per = (int)(sizeof(MfmaTileH) / 16);
-        uint4 *dst = wtiles + (size_t)nkb * nT * 128 + (size_t)nT * 64;
         if (threadIdx.x < 32) {
             const int centre = 32 * kb + (int)threadIdx.x;
-            dst[(size_t)2 * kb * per + threadIdx.x] =
+            copy[(size_t)2 * kb * per + threadIdx.x] =
                 centre < Mpad ? *reinterpret_cast<const uint4 *>(&slots.rec32[0][centre]) : make_uint4(0u, 0u, 0u, 0u);
-        }
-        if (kb == 0 && threadIdx.x == 255) {
-            const float *nn = slots.model[0]->norm32;
-            dst[(size_t)2 * nkb * per] = make_uint4(__float_as_uint(nn[0]), __float_as_uint(nn[1]), __float_as_uint(nn[2]), __float_as_uint(nn[3]));
         }
     } else if (T == 0) {
         // everything else the evaluation reads of the contexts: the rest rig's centre tiles and normalisation.  With
         // these in the batch's scratch the contexts are free for their next build as soon as THIS kernel has run.
-        constexpr int per = (int)(sizeof(MfmaTileH) / 16);
-        uint4 *dst = wtiles + (size_t)nkb * nT * 128 + (size_t)nT * 64;
         const int ntiles = Mpad / 16;
         if ((int)threadIdx.x < 2 * per) {
             const int tile = 2 * kb + (int)threadIdx.x / per;
-            dst[(size_t)2 * kb * per + threadIdx.x] =
+            copy[(size_t)2 * kb * per + threadIdx.x] =
                 tile < ntiles ? reinterpret_cast<const uint4 *>(ctiles + tile)[threadIdx.x % per] : make_uint4(0u, 0u, 0u, 0u);
         }
-        if (kb == 0 && threadIdx.x == 255) {
-            const float *nn = slots.model[0]->norm32;
-            dst[(size_t)2 * nkb * per] = make_uint4(__float_as_uint(nn[0]), __float_as_uint(nn[1]), __float_as_uint(nn[2]), __float_as_uint(nn[3]));
-        }
+    }
+    if (T == 0 && kb == 0 && threadIdx.x == 255) {
+        const float *nn = slots.model[0]->norm32;
+        wtiles[norm_at] = make_uint4(__float_as_uint(nn[0]), __float_as_uint(nn[1]), __float_as_uint(nn[2]), __float_as_uint(nn[3]));
     }
     const int lane = threadIdx.x & 63, g = lane >> 4, rho = lane & 15;
     // row rho of tile T: frame f0 + fi, component c
@@ -223,7 +207,7 @@ __global__ __launch_bounds__(256) void k_pack_shared(const SharedSlots slots, co
             const _Float16 h = (_Float16)w;
             pt[sidx] = g == 2 ? (_Float16)(w - (float)h) : h;
         }
-        wtiles[(size_t)nkb * nT * 128 + (size_t)T * 64 + lane] = __builtin_bit_cast(uint4, pt);
+        wtiles[poly_at + (size_t)T * 64 + lane] = __builtin_bit_cast(uint4, pt);
     }
 }
 
@@ -699,18 +683,7 @@ void k_deform32_tps_shared(const SharedParams p, int ngroups)
 // r of lane half h -- which after the logarithm ARE the lane's B operands of the two K = 16 steps (registers 0..7 and
 // 8..15): the weight tiles are packed to that centre order.  The epilogue needs one v_permlane32_swap per register pair.
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-constexpr bool shared_wide(int nF, int kind) { (void)kind; return nF > 16; }      // thin-plate and the Gaussian kinds alike
-constexpr int kWideSlots = 32;                      // frame records
-// Rows of the output tiles are packed densely: row 3 f + c of the stack of 32-row tiles is component c of frame slot f, so
-// 17..20 frames are TWO tiles (60 rows of 64) where one tile per component would be three (r2: 96 rows whatever the frame
-// count) -- a third fewer matrix instructions for the driver's 20-frame launch.  After the epilogue's lane-half swap a lane
-// holds every row of every tile for its own vertex, so any row <-> (frame, component) map costs nothing there.
-// Frame slots come in fours (the fall-off rows leave four frames per store): a launch of nF frames runs
-// NSLOT = 4 ceil(nF / 4) slots, and slots nF .. NSLOT - 1 are DUPLICATES of frame nF - 1 (same weights, scale and output
-// pointers: the same bits stored twice to the same address) -- so every frame count takes the straight-line epilogue.
-constexpr int wide_slots(int nF) { return (nF + 3) / 4 * 4; }
-constexpr int wide_tiles(int nslot) { return (3 * nslot + 31) / 32; }               // 2 up to 20 slots (21 frames would fit, 24 slots do not), else 3
-constexpr int wide_w16(int nt) { return nt * 2 * 2 * 64; }                          // 16-byte words of weight tiles per K block: [tile][K step][hi, lo][lane]
+// The row packing, the frame slots in fours and the tile counts: wide_slots / wide_tiles / wide_w16 in fd_shared_plan.h.
 
 // grid (nkb, NT row tiles), 256 threads.  Output regions: weight tiles [kb][tile][K step][hi, lo][lane], NT x 64 words of
 // polynomial tiles, then the d2 operands of the centres ([kb][2 instructions][64 lanes] x 8 B) and the normalisation.
@@ -720,11 +693,11 @@ constexpr int wide_w16(int nt) { return nt * 2 * 2 * 64; }                      
 // register r = 4 (rho / 8) + rho % 4 of half hh = (rho / 4) % 2, flat index k = 16 T + r of that half = component k % 3 of the
 // half's local frame k / 3, which is frame slot 2 (k / 3) + hh.
 __global__ __launch_bounds__(256) void k_pack_shared_wide(const SharedSlots slots, const SharedOut out, int nF, int nslot, int Mpad,
-                                                           uint4 *wtiles, SharedFrame *frames, const MfmaTileH *ctiles, int gauss, int layout)
+                                                           uint4 *wtiles, SharedFrame *frames, const MfmaTileH *ctiles, int gauss, int layout,
+                                                           size_t poly_at, size_t copy_at, size_t norm_at)
 {
-    const int kb = blockIdx.x, T = blockIdx.y, nkb = gridDim.x, NT = gridDim.y;
+    const int kb = blockIdx.x, T = blockIdx.y, NT = gridDim.y;
     const int w16 = wide_w16(NT);
-    const size_t poly_at = (size_t)nkb * w16, copy_at = poly_at + (size_t)NT * 64;
     if (T == 0) {
         // lane (h, r) of instruction i: k-slots 4 h .. 4 h + 3 of centre r = coordinate group 2 i + h of the 16-row tile
         uint2 *dst = reinterpret_cast<uint2 *>(wtiles + copy_at) + (size_t)kb * 128;
@@ -756,7 +729,7 @@ __global__ __launch_bounds__(256) void k_pack_shared_wide(const SharedSlots slot
         }
         if (kb == 0 && threadIdx.x == 255) {
             const float *nn = slots.model[0]->norm32;
-            wtiles[copy_at + (size_t)nkb * 64] = make_uint4(__float_as_uint(nn[0]), __float_as_uint(nn[1]), __float_as_uint(nn[2]), __float_as_uint(nn[3]));
+            wtiles[norm_at] = make_uint4(__float_as_uint(nn[0]), __float_as_uint(nn[1]), __float_as_uint(nn[2]), __float_as_uint(nn[3]));
         }
     }
     // scale of each frame slot: largest |weight| or |polynomial coefficient| to [2^13, 2^14); 8 lanes per slot
@@ -1316,10 +1289,6 @@ void k_deform32_tps_shared_wide(const SharedParams p, int ngroups)
 // the K-slot <-> centre map and the polynomial tile are round 3's.  The K loop is plain double buffering, unrolled by two so
 // that no operand is copied: phi of block k + 1 (16 logarithms, 16 multiplies, the fp16 split) goes under the 18 matrix
 // instructions of block k.
-constexpr int kW1Waves = 12;                      // three per SIMD
-constexpr int kW1Unit = 32;                       // vertices per wave and unit
-constexpr size_t w1_fixed_lds(int nt) { return sizeof(SharedFrame) * (size_t)kWideSlots + 32 * 16 + (size_t)nt * 64 * 16 + 256 * sizeof(uint64_t) + 16; }
-
 // The whole model must be resident in LDS (p.nkb <= p.kchunk: M = 256 at 32 frames): no staging and no barrier inside the unit
 // loop.  Models that are staged in chunks keep the two-tile kernel: its 512-vertex groups re-stage the model a quarter less often
 // (C3, M = 2048: 1.04 against 1.15 ms per 32 frames; C5's ranges, M = 512: 0.40 against 0.44 ms, same process).
@@ -1722,6 +1691,96 @@ void k_deform32_shared_w1(const SharedParams p, int ngroups)
 #endif
 #undef FD_W1STAMP
 }
+
+// ---- host side: every shape-dependent number is SharedPlan's (fd_shared_plan.h) ----
+
+// One kernel instantiation: its LDS attribute once per device, then the launch (as launch_shot<> of fd_shot_launch.h, with the
+// plan's block size: the three forms run 8, 8 and 12 waves).
+template <auto Kernel>
+hipError_t launch_form(const SharedPlan &pl, unsigned grid, hipStream_t stream, const SharedParams &p, int ngroups)
+{
+    static LdsAttrOnce once;          // one per kernel instantiation
+    hipError_t e = once.ensure((const void *)Kernel, 160 * 1024);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(Kernel, dim3(grid), dim3(pl.threads), pl.lds_fixed + pl.lds_per_kb * (size_t)p.kchunk, stream, p, ngroups);
+    return hipGetLastError();
+}
+
+// variant, row tiles and frame slots -> the kernel's template arguments
+template <bool GAUSS>
+hipError_t launch_variant(const SharedPlan &pl, unsigned grid, hipStream_t stream, const SharedParams &p, int ngroups)
+{
+    switch (pl.variant) {
+    case 0:
+        if (pl.ntiles == 1) return launch_form<k_deform32_tps_shared<1, false, GAUSS>>(pl, grid, stream, p, ngroups);
+        if (pl.ntiles == 2) return launch_form<k_deform32_tps_shared<2, false, GAUSS>>(pl, grid, stream, p, ngroups);
+        if (pl.ntiles == 3) return launch_form<k_deform32_tps_shared<3, false, GAUSS>>(pl, grid, stream, p, ngroups);
+        break;
+    case 1:
+        if (pl.ntiles == 3) return launch_form<k_deform32_tps_shared<3, true, GAUSS>>(pl, grid, stream, p, ngroups);
+        break;
+    case 2:
+        if (pl.nslot == 20) return launch_form<k_deform32_tps_shared_wide<GAUSS, 2, 20>>(pl, grid, stream, p, ngroups);
+        if (pl.nslot == 24) return launch_form<k_deform32_tps_shared_wide<GAUSS, 3, 24>>(pl, grid, stream, p, ngroups);
+        if (pl.nslot == 28) return launch_form<k_deform32_tps_shared_wide<GAUSS, 3, 28>>(pl, grid, stream, p, ngroups);
+        if (pl.nslot == 32) return launch_form<k_deform32_tps_shared_wide<GAUSS, 3, 32>>(pl, grid, stream, p, ngroups);
+        break;
+    case 3:
+        if (pl.nslot == 20) return launch_form<k_deform32_shared_w1<GAUSS, 2, 20>>(pl, grid, stream, p, ngroups);
+        if (pl.nslot == 24) return launch_form<k_deform32_shared_w1<GAUSS, 3, 24>>(pl, grid, stream, p, ngroups);
+        if (pl.nslot == 28) return launch_form<k_deform32_shared_w1<GAUSS, 3, 28>>(pl, grid, stream, p, ngroups);
+        if (pl.nslot == 32) return launch_form<k_deform32_shared_w1<GAUSS, 3, 32>>(pl, grid, stream, p, ngroups);
+        break;
+    }
+    return hipErrorInvalidValue;
+}
+
+#ifdef FD_TUNING
+// diagnostics, compiled in only for tuning builds (-DFD_TUNING): in-kernel clock stamps, printed per launch (FD_SHARED_STAMPS)
+constexpr size_t kStampWords = 64 + (size_t)kMaxCUs * 8 * 2;
+
+// the stamp words, zeroed on `stream` for the launch to come; null where stamps are not asked for
+unsigned long long *stamps_begin(hipStream_t stream)
+{
+    static unsigned long long *d_stamps = nullptr;
+    static const bool want_stamps = tuning_env("FD_SHARED_STAMPS") != nullptr;
+    if (want_stamps && !d_stamps) (void)hipMalloc((void **)&d_stamps, kStampWords * sizeof(unsigned long long));
+    if (want_stamps && d_stamps) (void)hipMemsetAsync(d_stamps, 0, kStampWords * sizeof(unsigned long long), stream);
+    return want_stamps ? d_stamps : nullptr;
+}
+
+void stamps_print(const SharedPlan &pl, unsigned grid, const unsigned long long *d_stamps, hipStream_t stream)
+{
+    static unsigned long long h[kStampWords];
+    const bool w1 = pl.variant == 3, wide = pl.variant == 2;
+    (void)hipStreamSynchronize(stream);         // (a non-blocking stream: the copy below does not wait for it by itself)
+    if (hipMemcpy(h, d_stamps, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return;
+    if (w1) {
+        fprintf(stderr, "[w1 stamps, shader cycles per wave of workgroup 0: load+poly | K loop | epilogue | units | whole (counts, 100 MHz ticks)]\n");
+        for (int w = 0; w < kW1Waves; ++w)
+            fprintf(stderr, "   wave %2d: %8llu %8llu %8llu  units %llu  whole %llu counts in %llu ticks = %.3f GHz\n", w, h[w * 8], h[w * 8 + 1], h[w * 8 + 2], h[w * 8 + 3],
+                    h[w * 8 + 4], h[w * 8 + 5], h[w * 8 + 5] ? (double)h[w * 8 + 4] / (double)h[w * 8 + 5] * 0.1 : 0.0);
+        return;
+    }
+    if (wide) {
+        // first tick anywhere to every workgroup's first and last tick: who starts late, who finishes late (10 ns units)
+        unsigned long long t0 = ~0ull, t1 = 0;
+        const unsigned sgrid = grid < kMaxCUs ? grid : kMaxCUs;
+        for (unsigned b = 0; b < sgrid * 8; ++b) if (h[64 + 2 * b]) { t0 = h[64 + 2 * b] < t0 ? h[64 + 2 * b] : t0; t1 = h[65 + 2 * b] > t1 ? h[65 + 2 * b] : t1; }
+        fprintf(stderr, "[shared stamps: %u workgroups, first entry to last exit %.1f us; per workgroup (entry, exit) in us after the first entry:]\n", grid, (t1 - t0) * 0.01);
+        for (unsigned b = 0; b < sgrid; ++b) {
+            unsigned long long a = ~0ull, z = 0;
+            for (int w = 0; w < 8; ++w) if (h[64 + 2 * (b * 8 + w)]) { a = h[64 + 2 * (b * 8 + w)] < a ? h[64 + 2 * (b * 8 + w)] : a; z = h[65 + 2 * (b * 8 + w)] > z ? h[65 + 2 * (b * 8 + w)] : z; }
+            fprintf(stderr, "%s%5.1f-%5.1f", b % 8 ? "  " : "\n   ", (a - t0) * 0.01, (z - t0) * 0.01);
+        }
+        fprintf(stderr, "\n");
+    }
+    fprintf(stderr, "[shared stamps, shader cycles per wave of workgroup 0: load+poly | K loop | transposes | per-vertex + frames]\n");
+    for (int w = 0; w < 8; ++w)
+        fprintf(stderr, "   wave %d: %8llu %8llu %8llu %8llu   (whole: %llu counts in %llu reference ticks)\n", w, h[w * 8], h[w * 8 + 1], h[w * 8 + 2], h[w * 8 + 3],
+                h[w * 8 + 4], h[w * 8 + 5]);
+}
+#endif
 }  // namespace
 
 // Frames of one mesh and one rest rig (SharedDeformArgs): pack the weight tiles, then one launch.
@@ -1729,34 +1788,28 @@ hipError_t launch_deform_shared(const SharedDeformArgs &a, hipStream_t stream)
 {
     if (a.N <= 0 || a.nF <= 0) return hipSuccess;
     if (a.nF > kMaxBatch || a.Mpad % 16 != 0) return hipErrorInvalidValue;
-    const int ntiles = a.Mpad / 16, nkb = (ntiles + 1) / 2;
+    const SharedPlan pl = shared_plan(a.Mpad, a.nF, a.kind);
+    if (pl.kchunk < 1) return hipErrorInvalidValue;
     const bool gauss = a.kind != FD_KERNEL_THIN_PLATE;       // FD_KERNEL_GAUSSIAN / _QNN: per-record scale, direct differences
-    // 17..32 frames: 32-row tiles (r2 kept the 16-row kernel selectable for them, at six tiles: 201 against 175 us at C2 x 32)
-    const bool wide = shared_wide(a.nF, a.kind);
-    const bool dense = shared_dense(a.nF);
-    const int nT = shared_tiles(a.nF);                       // 16-row tiles (also what the scratch is sized by)
-    const int wslot = wide_slots(a.nF), wNT = wide_tiles(wslot);
-    // Frame slots beyond nF are duplicates of the LAST frame: same weights, same scale, same output pointers, so their
-    // stores repeat that frame's bits at the same addresses and the straight-line epilogue needs no "unused slot" case.
-    const int nslot = wide ? wslot : shared_slots(nT, dense);
-    SharedSlots slots{};
-    SharedOut out{};
-    for (int f = 0; f < kMaxBatch; ++f) {
-        const int q = f < a.nF ? f : a.nF - 1;
-        slots.rec32[f] = a.rec32[q]; slots.model[f] = a.model[q]; slots.centres[f] = a.centres[q];
-        out.P_out[f] = a.P_out[q]; out.falloff_out[f] = a.falloff_out ? a.falloff_out[q] : nullptr;
-    }
-    slots.M = a.M; slots.nreal = a.nF; slots.mismatch = a.mismatch;
-    // 17..32 frames: one vertex tile per wave, three waves per SIMD (k_deform32_shared_w1) where the whole model is resident in
-    // LDS (M = 256 at 32 frames, 384 at 20); models staged in chunks keep the two-tile kernel
-    const bool w1 = wide && (kSharedLdsBudget - w1_fixed_lds(wNT)) / ((size_t)1024 + (size_t)wide_w16(wNT) * 16) >= (size_t)nkb;
+    uint4 *wtiles = (uint4 *)a.wtiles;
     if (a.mode != 2) {
-        if (wide)
-            hipLaunchKernelGGL(k_pack_shared_wide, dim3(nkb, wNT), dim3(256), 0, stream, slots, out, a.nF, wslot, a.Mpad, (uint4 *)a.wtiles,
-                               (SharedFrame *)a.frames, a.ctiles, gauss ? 1 : 0, w1 ? 1 : 0);
+        // Frame slots beyond nF are duplicates of the LAST frame: same weights, same scale, same output pointers, so their
+        // stores repeat that frame's bits at the same addresses and the straight-line epilogue needs no "unused slot" case.
+        SharedSlots slots{};
+        SharedOut out{};
+        for (int f = 0; f < kMaxBatch; ++f) {
+            const int q = f < a.nF ? f : a.nF - 1;
+            slots.rec32[f] = a.rec32[q]; slots.model[f] = a.model[q]; slots.centres[f] = a.centres[q];
+            out.P_out[f] = a.P_out[q]; out.falloff_out[f] = a.falloff_out ? a.falloff_out[q] : nullptr;
+        }
+        slots.M = a.M; slots.nreal = a.nF; slots.mismatch = a.mismatch;
+        const dim3 pgrid(pl.nkb, pl.ntiles);
+        if (pl.variant >= 2)
+            hipLaunchKernelGGL(k_pack_shared_wide, pgrid, dim3(256), 0, stream, slots, out, a.nF, pl.nslot, a.Mpad, wtiles, (SharedFrame *)a.frames,
+                               a.ctiles, gauss ? 1 : 0, pl.variant == 3 ? 1 : 0, pl.poly_at, pl.copy_at, pl.norm_at);
         else
-            hipLaunchKernelGGL(k_pack_shared, dim3(nkb, nT), dim3(256), 0, stream, slots, out, nslot, a.Mpad, dense ? 1 : 0, (uint4 *)a.wtiles,
-                               (SharedFrame *)a.frames, a.ctiles, gauss ? 1 : 0);
+            hipLaunchKernelGGL(k_pack_shared, pgrid, dim3(256), 0, stream, slots, out, pl.nslot, a.Mpad, pl.variant, wtiles, (SharedFrame *)a.frames,
+                               a.ctiles, gauss ? 1 : 0, pl.poly_at, pl.copy_at, pl.norm_at);
         if (a.packed_ev) {
             hipError_t e = hipEventRecord(a.packed_ev, stream);
             if (e != hipSuccess) return e;
@@ -1766,49 +1819,26 @@ hipError_t launch_deform_shared(const SharedDeformArgs &a, hipStream_t stream)
     SharedParams p{};
     p.N = a.N; p.P_in = a.P_in; p.dist2 = a.dist2; p.tu = a.tu; p.tv = a.tv; p.nrm = a.nrm;
     p.radius2 = a.radius2; p.falloffrate = a.falloffrate; p.delta = a.delta_out;
-    p.ntiles = ntiles; p.nkb = nkb; p.nF = a.nF; p.nT = nT;
-    if (wide) {
-        const uint4 *copy = (const uint4 *)a.wtiles + (size_t)nkb * wide_w16(wNT) + (size_t)wNT * 64;
-        p.ctiles = reinterpret_cast<const MfmaTileH *>(copy);
-        p.norm = reinterpret_cast<const float *>(copy + (size_t)nkb * 64);
-    } else {
-        const uint4 *copy = (const uint4 *)a.wtiles + (size_t)nkb * nT * 128 + (size_t)nT * 64;
-        p.ctiles = reinterpret_cast<const MfmaTileH *>(copy);
-        p.norm = reinterpret_cast<const float *>(copy + (size_t)2 * nkb * (sizeof(MfmaTileH) / 16));
-    }
-    p.wtiles = (const uint4 *)a.wtiles; p.frames = (const SharedFrame *)a.frames;
+    p.ntiles = a.Mpad / 16; p.nkb = pl.nkb; p.nF = a.nF; p.nT = pl.ntiles; p.kchunk = pl.kchunk;
+    p.ctiles = reinterpret_cast<const MfmaTileH *>(wtiles + pl.copy_at);
+    p.norm = reinterpret_cast<const float *>(wtiles + pl.norm_at);
+    p.wtiles = wtiles; p.frames = (const SharedFrame *)a.frames;
     {
         // no gate, no fall-off input, no tangent frames, fd_falloff wanted for every frame: the straight-line epilogue.
         // Any frame count: the slots a launch runs beyond nF repeat the last frame (above).
         // (repeated slots cost stores: worth it up to a quarter of the frames -- 17..32 frames always qualify)
         bool fast = !a.delta_out && a.dist2 == nullptr && a.tu == nullptr && a.radius2 > 0.f && a.falloff_out != nullptr &&
-                    a.N < ((int64_t)1 << 28) && 4 * (nslot - a.nF) <= a.nF;
+                    a.N < ((int64_t)1 << 28) && 4 * (pl.nslot - a.nF) <= a.nF;
         // (the straight-line epilogues store fd_falloff 8 and 16 bytes at a time: 16-byte aligned arrays, or the general path)
         for (int f = 0; fast && f < a.nF; ++f) fast = a.falloff_out[f] != nullptr && a.P_out[f] != nullptr && ((uintptr_t)a.falloff_out[f] & 15) == 0;
         p.fast = fast ? 1 : 0;
     }
 #ifdef FD_TUNING
-    // diagnostics, compiled in only for tuning builds (-DFD_TUNING): in-kernel clock stamps, printed per launch
-    static unsigned long long *d_stamps = nullptr;
-    static const bool want_stamps = tuning_env("FD_SHARED_STAMPS") != nullptr;
-    constexpr size_t kStampWords = 64 + (size_t)kMaxCUs * 8 * 2;
-    if (want_stamps && !d_stamps) (void)hipMalloc((void **)&d_stamps, kStampWords * sizeof(unsigned long long));
-    if (want_stamps && d_stamps) (void)hipMemsetAsync(d_stamps, 0, kStampWords * sizeof(unsigned long long), stream);
-    p.stamps = want_stamps ? d_stamps : nullptr;
+    p.stamps = stamps_begin(stream);
 #else
     p.stamps = nullptr;
 #endif
-    const size_t fixed = w1 ? w1_fixed_lds(wNT) :
-                         wide ? sizeof(SharedFrame) * (size_t)kWideSlots + (size_t)wNT * 64 * 16 + 512 * sizeof(uint64_t) + 16
-                              : sizeof(SharedFrame) * (size_t)shared_slots(nT, dense) + (size_t)nT * 64 * 16;
-    const size_t per_kb = wide ? (size_t)1024 + (size_t)wide_w16(wNT) * 16 : 2 * sizeof(MfmaTileH) + (size_t)nT * 128 * 16;
-    int kchunk = (int)((kSharedLdsBudget - fixed) / per_kb);
-    if (kchunk < 1) return hipErrorInvalidValue;
-    if (kchunk > nkb) kchunk = nkb;
-    p.kchunk = kchunk;
-    const size_t lds = fixed + per_kb * (size_t)kchunk;
-    const int64_t per = w1 ? kW1Unit * kW1Waves : wide ? 64 * kWideWaves : kSharedThreads / 64 * 64;          // vertices per workgroup and group
-    const int64_t ngroups = (a.N + per - 1) / per;
+    const int64_t ngroups = (a.N + pl.group_vertices - 1) / pl.group_vertices;
     // One persistent workgroup per CU (150 KiB of LDS, two 240-register waves per SIMD: nothing else fits beside it).
     // a.max_wgs < 256 (fd_batch_set_eval_cus) leaves the other CUs to whatever runs on other streams -- the builds of the
     // next frames in a pipeline (bench.py).
@@ -1816,130 +1846,11 @@ hipError_t launch_deform_shared(const SharedDeformArgs &a, hipStream_t stream)
     // wait for a CU a build holds delays the launch by less.
     const int64_t max_wgs = a.max_wgs > 0 ? (a.max_wgs < 4096 ? a.max_wgs : 4096) : (int64_t)device_cus();
     const unsigned grid = (unsigned)(ngroups < max_wgs ? ngroups : max_wgs);
-#define FD_SHARED_CASE(NTV, DNS, GSS)                                                                                \
-    {                                                                                                                \
-        static LdsAttrOnce once;                                                                                     \
-        hipError_t e = once.ensure((const void *)k_deform32_tps_shared<NTV, DNS, GSS>, 160 * 1024);                  \
-        if (e != hipSuccess) return e;                                                                               \
-        hipLaunchKernelGGL((k_deform32_tps_shared<NTV, DNS, GSS>), dim3(grid), dim3(kSharedThreads), lds, stream, p, (int)ngroups); \
-    }
-#define FD_SHARED_KIND(NTV, DNS) { if (gauss) FD_SHARED_CASE(NTV, DNS, true) else FD_SHARED_CASE(NTV, DNS, false) }
-#define FD_WIDE_CASE(GSS, NTW, NSL)                                                                                  \
-    {                                                                                                                \
-        static LdsAttrOnce once;                                                                                     \
-        hipError_t e = once.ensure((const void *)k_deform32_tps_shared_wide<GSS, NTW, NSL>, 160 * 1024); \
-        if (e != hipSuccess) return e;                                                                               \
-        hipLaunchKernelGGL((k_deform32_tps_shared_wide<GSS, NTW, NSL>), dim3(grid), dim3(64 * kWideWaves), lds, stream, p, (int)ngroups); \
-    }
-#define FD_WIDE_KIND(NTW, NSL) { if (gauss) FD_WIDE_CASE(true, NTW, NSL) else FD_WIDE_CASE(false, NTW, NSL) }
-#define FD_W1_CASE(GSS, NTW, NSL)                                                                                    \
-    {                                                                                                                \
-        static LdsAttrOnce once;                                                                                     \
-        hipError_t e = once.ensure((const void *)k_deform32_shared_w1<GSS, NTW, NSL>, 160 * 1024);                   \
-        if (e != hipSuccess) return e;                                                                               \
-        hipLaunchKernelGGL((k_deform32_shared_w1<GSS, NTW, NSL>), dim3(grid), dim3(64 * kW1Waves), lds, stream, p, (int)ngroups); \
-    }
-#define FD_W1_KIND(NTW, NSL) { if (gauss) FD_W1_CASE(true, NTW, NSL) else FD_W1_CASE(false, NTW, NSL) }
-    if (w1) {
-        if (wslot == 20) FD_W1_KIND(2, 20)
-        else if (wslot == 24) FD_W1_KIND(3, 24)
-        else if (wslot == 28) FD_W1_KIND(3, 28)
-        else if (wslot == 32) FD_W1_KIND(3, 32)
-        else return hipErrorInvalidValue;
-    } else if (wide) {
-        if (wslot == 20) FD_WIDE_KIND(2, 20)
-        else if (wslot == 24) FD_WIDE_KIND(3, 24)
-        else if (wslot == 28) FD_WIDE_KIND(3, 28)
-        else if (wslot == 32) FD_WIDE_KIND(3, 32)
-        else return hipErrorInvalidValue;
-    } else if (dense) {
-        if (nT == 3) FD_SHARED_KIND(3, true)
-        else return hipErrorInvalidValue;
-    } else {
-        if (nT == 1) FD_SHARED_KIND(1, false)
-        else if (nT == 2) FD_SHARED_KIND(2, false)
-        else if (nT == 3) FD_SHARED_KIND(3, false)
-        else return hipErrorInvalidValue;
-    }
-#undef FD_SHARED_KIND
-#undef FD_SHARED_CASE
-#undef FD_WIDE_CASE
-#undef FD_WIDE_KIND
-#undef FD_W1_CASE
-#undef FD_W1_KIND
+    const hipError_t e = gauss ? launch_variant<true>(pl, grid, stream, p, (int)ngroups) : launch_variant<false>(pl, grid, stream, p, (int)ngroups);
 #ifdef FD_TUNING
-    if (want_stamps && d_stamps) {
-        static unsigned long long h[kStampWords];
-        (void)hipStreamSynchronize(stream);         // (a non-blocking stream: the copy below does not wait for it by itself)
-        if (hipMemcpy(h, d_stamps, sizeof(h), hipMemcpyDeviceToHost) == hipSuccess) {
-            if (w1) {
-                fprintf(stderr, "[w1 stamps, shader cycles per wave of workgroup 0: load+poly | K loop | epilogue | units | whole (counts, 100 MHz ticks)]\n");
-                for (int w = 0; w < kW1Waves; ++w)
-                    fprintf(stderr, "   wave %2d: %8llu %8llu %8llu  units %llu  whole %llu counts in %llu ticks = %.3f GHz\n", w, h[w * 8], h[w * 8 + 1], h[w * 8 + 2], h[w * 8 + 3],
-                            h[w * 8 + 4], h[w * 8 + 5], h[w * 8 + 5] ? (double)h[w * 8 + 4] / (double)h[w * 8 + 5] * 0.1 : 0.0);
-            } else if (wide) {
-                // first tick anywhere to every workgroup's first and last tick: who starts late, who finishes late (10 ns units)
-                unsigned long long t0 = ~0ull, t1 = 0;
-                const unsigned sgrid = grid < kMaxCUs ? grid : kMaxCUs;
-                for (unsigned b = 0; b < sgrid * 8; ++b) if (h[64 + 2 * b]) { t0 = h[64 + 2 * b] < t0 ? h[64 + 2 * b] : t0; t1 = h[65 + 2 * b] > t1 ? h[65 + 2 * b] : t1; }
-                fprintf(stderr, "[shared stamps: %u workgroups, first entry to last exit %.1f us; per workgroup (entry, exit) in us after the first entry:]\n", grid, (t1 - t0) * 0.01);
-                for (unsigned b = 0; b < sgrid; ++b) {
-                    unsigned long long a = ~0ull, z = 0;
-                    for (int w = 0; w < 8; ++w) if (h[64 + 2 * (b * 8 + w)]) { a = h[64 + 2 * (b * 8 + w)] < a ? h[64 + 2 * (b * 8 + w)] : a; z = h[65 + 2 * (b * 8 + w)] > z ? h[65 + 2 * (b * 8 + w)] : z; }
-                    fprintf(stderr, "%s%5.1f-%5.1f", b % 8 ? "  " : "\n   ", (a - t0) * 0.01, (z - t0) * 0.01);
-                }
-                fprintf(stderr, "\n");
-            }
-            if (!w1) fprintf(stderr, "[shared stamps, shader cycles per wave of workgroup 0: load+poly | K loop | transposes | per-vertex + frames]\n");
-            for (int w = 0; w < 8 && !w1; ++w)
-                fprintf(stderr, "   wave %d: %8llu %8llu %8llu %8llu   (whole: %llu counts in %llu reference ticks)\n", w, h[w * 8], h[w * 8 + 1], h[w * 8 + 2], h[w * 8 + 3],
-                        h[w * 8 + 4], h[w * 8 + 5]);
-        }
-    }
+    if (e == hipSuccess && p.stamps) stamps_print(pl, grid, p.stamps, stream);
 #endif
-    return hipGetLastError();
-}
-
-size_t shared_wtile_bytes(int Mpad, int nF)
-{
-    const int nkb = (Mpad / 16 + 1) / 2, nT = shared_tiles(nF);
-    // weight tiles + polynomial tiles + the rest rig's centre tiles (2 nkb) and normalisation (16 B)
-    return (size_t)nkb * nT * 128 * 16 + (size_t)nT * 64 * 16 + (size_t)2 * nkb * sizeof(MfmaTileH) + 16;
-}
-// the kernel launch_deform_shared picks (same decisions as above)
-const char *shared_kernel_name(int Mpad, int nF, int kind)
-{
-    if (!shared_wide(nF, kind)) return "k_deform32_tps_shared";
-    const int nkb = (Mpad / 16 + 1) / 2, wNT = wide_tiles(wide_slots(nF));
-    const bool w1 = (kSharedLdsBudget - w1_fixed_lds(wNT)) / ((size_t)1024 + (size_t)wide_w16(wNT) * 16) >= (size_t)nkb;
-    return w1 ? "k_deform32_shared_w1" : "k_deform32_tps_shared_wide";
-}
-// where launch_deform_shared's pack kernel leaves what the shared-rig vector launch (fd_vectors_shared.hip) reads
-SharedPacking shared_packing(int Mpad, int nF)
-{
-    SharedPacking q{};
-    const int nkb = (Mpad / 16 + 1) / 2;
-    if (!shared_wide(nF, 0)) {
-        const int nT = shared_tiles(nF);
-        q.layout = shared_dense(nF) ? 1 : 0;
-        q.ntiles = nT;
-        q.poly_at = (size_t)nkb * nT * 128;
-        q.copy_at = q.poly_at + (size_t)nT * 64;
-        q.norm_at = q.copy_at + (size_t)2 * nkb * (sizeof(MfmaTileH) / 16);
-    } else {
-        const int wNT = wide_tiles(wide_slots(nF));
-        const bool w1 = (kSharedLdsBudget - w1_fixed_lds(wNT)) / ((size_t)1024 + (size_t)wide_w16(wNT) * 16) >= (size_t)nkb;
-        q.layout = w1 ? 3 : 2;
-        q.ntiles = wNT;
-        q.poly_at = (size_t)nkb * wide_w16(wNT);
-        q.copy_at = q.poly_at + (size_t)wNT * 64;
-        q.norm_at = q.copy_at + (size_t)nkb * 64;
-    }
-    return q;
-}
-size_t shared_frame_bytes(int nF)
-{
-    return sizeof(SharedFrame) * (size_t)shared_slots(shared_tiles(nF), shared_dense(nF));
+    return e;
 }
 
 }  // namespace fd

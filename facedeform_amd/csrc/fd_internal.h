@@ -353,7 +353,7 @@ struct SharedDeformArgs {
     const DevModel *model[kMaxBatch];
     float *P_out[kMaxBatch];
     float *const *falloff_out;            // nF entries or nullptr
-    void *wtiles, *frames;                // scratch of shared_wtile_bytes / shared_frame_bytes
+    void *wtiles, *frames;                // scratch of SharedPlan::wtile_bytes / frame_bytes
     hipEvent_t packed_ev;                 // recorded once the pack kernel has read the models (may be null): from then on the
                                           // launch reads nothing of the contexts -- their next build may start
     int mode;                             // 0: pack kernel + evaluation; 1: pack kernel only (fd_batch_prepare_shared);
@@ -366,18 +366,8 @@ struct SharedDeformArgs {
     int M;
     int *mismatch;
 };
+// (scratch sizes, the kernel's name and where its pack kernel leaves what in the scratch: shared_plan, fd_shared_plan.h)
 hipError_t launch_deform_shared(const SharedDeformArgs &a, hipStream_t stream);
-size_t shared_wtile_bytes(int Mpad, int nF);
-size_t shared_frame_bytes(int nF);
-const char *shared_kernel_name(int Mpad, int nF, int kind);
-// What the pack kernel of launch_deform_shared left in the scratch, for the shared-rig vector launch: the weight tiles' row
-// layout (0: 16-row padded, 1: 16-row dense, 2: 32-row rows 3 f + c, 3: 32-row per lane half -- fd_eval_shared.hip), their
-// row tiles, and the 16-byte word offsets of the polynomial tiles, the rest rig's centre copy and its normalisation.
-struct SharedPacking {
-    int layout, ntiles;
-    size_t poly_at, copy_at, norm_at;
-};
-SharedPacking shared_packing(int Mpad, int nF);
 // What the arguments of the four shot vector launches have in common (fd_vectors_shot.h fills the kernels' arguments from it):
 // the mesh, the vectors to carry and the per-frame outputs.
 struct SharedVectorCommon {

@@ -5,16 +5,13 @@
 #include <hip/hip_runtime.h>
 
 #include "fd_eval_common.h"
+#include "fd_shared_plan.h"       // kSharedLdsBudget, kGaussShift
 
 namespace fd {
 namespace {
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-
-constexpr size_t kSharedLdsBudget = 158 * 1024;   // of 160 KiB (one workgroup per CU)
-
-constexpr int kGaussShift = 10;      // Gaussian kinds: phi (<= 1) enters the matrix pipe as 2^10 phi, clear of the fp16 subnormals
 
 struct SharedFrame {              // one per frame slot (nT * 4), written by k_pack_shared
     float inv_scale;              // 2^-k: undoes the scaling of the frame's weights and polynomial

@@ -22,6 +22,7 @@
 
 #include "fd_eval_common.h"
 #include "fd_pack.h"
+#include "fd_shared_plan.h"
 #include "fd_vectors_shot.h"
 
 namespace fd {
@@ -41,11 +42,10 @@ constexpr size_t kVsLdsBudget = 158 * 1024;
 //   Gaussian kinds 2^8: |g (x - c)| <= 0.52 sqrt(|s_j|) (s_j = -log2(e) / R_j'^2), finite for R_j' above ~0.0024 rig radii
 //     (include/facedeform_hip.h states it); lo pieces exact down to 2^-11.
 constexpr int grad_shift(bool gauss) { return gauss ? 8 : 4; }
-constexpr int kPackGaussShift = 10;                // fd_eval_shared.hip's kGaussShift, carried by the Gaussian frame records
 
 struct VsParams : ShotMesh {
     int nF, nkb, kchunk;
-    int layout, srcNT;                   // SharedPacking
+    int layout, srcNT;                   // SharedPlan::variant, ntiles
     unsigned poly_at, copy_at, norm_at;
     const uint4 *wtiles;
     const unsigned *frames;              // the pack kernel's frame records, 8 words each: {inv_scale, built, ...}
@@ -93,7 +93,7 @@ __device__ __forceinline__ void vectors_shared_body(const VsParams &p, int ngrou
     if (tid < p.nF) {
         const int f = tid;
         const float inv = __uint_as_float(p.frames[8 * f]);
-        const float unscale = GAUSS ? inv * (float)(1 << kPackGaussShift) : inv;         // 2^-k
+        const float unscale = GAUSS ? inv * (float)(1 << kGaussShift) : inv;         // 2^-k
         float *fc = s_fc + kFrameWords * f;
         fc[0] = unscale * (1.f / (float)(1 << grad_shift(GAUSS)));
         fc[1] = p.frames[8 * f + 1] != 0u ? 1.f : 0.f;
@@ -321,14 +321,14 @@ hipError_t launch_vectors_shared(const SharedVectorArgs &a, hipStream_t stream)
 {
     if (a.N <= 0 || a.nF <= 0) return hipSuccess;
     if (a.nF > kMaxBatch || a.Mpad % 16 != 0) return hipErrorInvalidValue;
-    const SharedPacking pk = shared_packing(a.Mpad, a.nF);
-    const int nkb = (a.Mpad / 16 + 1) / 2;
+    const SharedPlan pk = shared_plan(a.Mpad, a.nF, a.kind);      // of the position launch that packed the scratch
+    const int nkb = pk.nkb;
     const int NT = shot_tiles(a.nF);
     VsParams p{};
     ShotOut out{};
     fill_shot(p, out, a);
     p.nF = a.nF; p.nkb = nkb;
-    p.layout = pk.layout; p.srcNT = pk.ntiles;
+    p.layout = pk.variant; p.srcNT = pk.ntiles;
     p.poly_at = (unsigned)pk.poly_at; p.copy_at = (unsigned)pk.copy_at; p.norm_at = (unsigned)pk.norm_at;
     p.wtiles = (const uint4 *)a.wtiles; p.frames = (const unsigned *)a.frames;
     const size_t fixed = sizeof(float) * kFrameWords * kMaxBatch + sizeof(float *) * 4 * kMaxBatch;

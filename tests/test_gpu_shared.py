@@ -533,3 +533,53 @@ def test_the_workgroup_budget_changes_the_schedule_not_the_bits(hip_lib, F, kind
         else:
             assert torch.equal(got, ref), cus
     _close(engines, batch)
+
+
+def _boundary_shapes():
+    """(Mpad, F, kernel) at the two residency boundaries the recorded plan table shows (tests/golden/shared_plan_table.txt: the
+    last model of 32 and of 20 frames that is resident in LDS and the first that is staged), and at 256 centres on either side of
+    the 12 | 13 (padded | dense rows) and 16 | 17 (16-row | 32-row tiles) frame counts"""
+    from test_shared_plan import THIN_PLATE, boundary, golden
+    rows = golden()
+    shapes = [(M, F) for F in (32, 20) for M in boundary(rows, F)] + [(256, F) for F in (12, 13, 16, 17)]
+    return [(M, F, rows[(M, F, THIN_PLATE)]["kernel"]) for M, F in shapes]
+
+
+@pytest.mark.parametrize("M,F,kernel", _boundary_shapes())
+def test_variant_boundaries_match_the_oracle(hip_lib, oracle, M, F, kernel):
+    """Every frame against the oracle on both sides of each decision of the launch's plan (csrc/fd_shared_plan.h), at the bar of
+    test_shared_frames_match_oracle; N = 1025 is full vertex groups and a partial one in every variant (groups of 512 and 384).
+    Plain: the straight-line epilogue and the general one for the tail; then with a gate.  The kernel the library names for the
+    shape is the table's."""
+    N = 1025
+    assert capi.fd_shared_kernel_name(M, F, capi.KERNEL_THIN_PLATE) == kernel
+    dev, P, rest, deltas, d_P, keep, engines, batch = _setup(M, N, F)
+    outs = [torch.empty_like(d_P) for _ in range(F)]
+    falls = [torch.full((N,), 7.0, device=dev) for _ in range(F)]
+    dist2 = (np.random.default_rng(M + F).random(N) * 0.6).astype(np.float32)
+    d_d2 = torch.from_numpy(dist2).to(dev)
+    r2 = np.float32(0.49)
+    refs = {}
+    for gate in (False, True):
+        kw = dict(d_dist2=d_d2.data_ptr(), radius2=r2, falloffrate=1.5) if gate else {}
+        okw = dict(dist2=dist2, radius2=r2, falloffrate=1.5) if gate else {}
+        for fl in falls:
+            fl.fill_(7.0)
+        batch.deform_shared_dev(N, d_P.data_ptr(), [o.data_ptr() for o in outs], d_falloff=[f.data_ptr() for f in falls], **kw)
+        torch.cuda.synchronize()
+        for f in range(F):
+            if f not in refs:
+                table = oracle.control_table(rest, (rest + deltas[f]).astype(np.float32))
+                rc, tt, W, radii = oracle.build(table, fo.KERNEL_THIN_PLATE, [], 0)
+                refs[f] = (table, W, radii)
+            table, W, radii = refs[f]
+            ref, ref_fall = oracle.deform(table, fo.KERNEL_THIN_PLATE, radii, W, P, **okw)
+            out = outs[f].cpu().numpy()
+            assert parity_ratio(out, ref, P, TOL) <= 1.0, (gate, f, parity_ratio(out, ref, P, TOL))
+            if not gate:
+                assert l2_parity_ulp(out, ref, P, TOL) <= 1.0, (f, l2_parity_ulp(out, ref, P, TOL), l2_parity(out, ref, P))
+            fall = falls[f].cpu().numpy()
+            gated = dist2 > r2 if gate else np.zeros(N, bool)
+            assert np.array_equal(out[gated], P[gated]) and np.all(fall[gated] == 7.0)      # B2: untouched
+            assert np.allclose(fall[~gated], ref_fall[~gated], rtol=2e-6, atol=1e-7)
+    _close(engines, batch)
