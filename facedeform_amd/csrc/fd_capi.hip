@@ -14,6 +14,7 @@
 
 #include "fd_fit_host.h"
 #include "fd_internal.h"
+#include "fd_owned.h"
 #include "fd_shared_plan.h"
 
 using namespace fd;
@@ -29,8 +30,9 @@ struct GraphKey {
 struct fd_batch;
 struct fd_ctx {
     int device = 0;
-    hipStream_t own_stream = nullptr;   // created on first use when the caller sets no stream
-    hipStream_t stream_ = nullptr;          // fd_set_stream; nullptr: own_stream
+    Stream own_stream;                  // created on first use when the caller sets no stream; the first member: it outlives
+                                        // everything that was enqueued on it
+    hipStream_t stream_ = nullptr;          // fd_set_stream (borrowed); nullptr: own_stream
     int eval_precision = FD_EVAL_FP32;
     int eval_variant = 0;
     int output = FD_OUTPUT_POSITION;    // fd_set_output
@@ -38,7 +40,7 @@ struct fd_ctx {
     int imported_layers = 0;         // a multilayer model that came in through fd_import_model
     uint64_t rig_build_id = 0;       // nonzero: the id of the ONE batched build that read this context's rest rig, in place, from the same array as
                                      // its batch mates (their centres are equal by construction); 0: built on its own / from its own copy
-    const float *rest_src = nullptr; // caller's device array the rest points were last read from in place (fd_batch_set_points_dev), else null
+    const float *rest_src = nullptr; // (borrowed) caller's device array the rest points were last read from in place (fd_batch_set_points_dev), else null
     bool prefer_lu = false;          // the Cholesky path lost definiteness on this rig: LU until kernel, term or M change
     unsigned long long model_gen = 0; // counts the models this context has held (every enqueued build, every import): what a
                                      // batch's packed copy of the weights is checked against before it is reused
@@ -60,73 +62,68 @@ struct fd_ctx {
     bool have_factor = false;
     bool factor_grouped = false;   // the factorisation in d_A was built with grouped panels (a batched build)
     bool deltas_only = false;
-    hipGraphExec_t resolve_exec = nullptr;
+    GraphExec resolve_exec;
 
     // device buffers (grow-only)
     int cap_M = 0;                // capacity in centres
     int cap_npad = 0;
     int cap_records = 0;             // centres / radii / weights / records: M, or M * layers for the multilayer model
-    float *d_rest = nullptr, *d_delta = nullptr;
-    double *d_centres = nullptr, *d_radii = nullptr, *d_W = nullptr;
-    double *d_A = nullptr, *d_X = nullptr;
-    int *d_ipiv = nullptr, *d_moves = nullptr;
-    Rec32 *d_rec32 = nullptr;
-    Rec64 *d_rec64 = nullptr;
-    MfmaTile *d_tiles = nullptr;
-    MfmaTileH *d_tiles16 = nullptr;
-    double *d_ns = nullptr;          // null-space solver state (fd_nullspace.hip)
-    DevModel *d_model = nullptr;
-    DevModel *h_model = nullptr;  // pinned mirror
+    DevBuf<float> d_rest, d_delta;
+    DevBuf<double> d_centres, d_radii, d_W;
+    DevBuf<double> d_A, d_X;
+    DevBuf<int> d_ipiv, d_moves;
+    DevBuf<Rec32> d_rec32;
+    DevBuf<Rec64> d_rec64;
+    DevBuf<MfmaTile> d_tiles;
+    DevBuf<MfmaTileH> d_tiles16;
+    DevBuf<double> d_ns;             // null-space solver state (fd_nullspace.hip)
+    DevBuf<DevModel> d_model;
+    Pinned<DevModel> h_model;     // pinned mirror
     // where the build kernels find the buffers above: a one-entry device table (a single build
     // is a batch of one); re-uploaded whenever a buffer is reallocated
-    BatchSlot *d_slot = nullptr;
+    DevBuf<BatchSlot> d_slot;
     BatchSlot h_slot{};
     uint64_t alloc_gen = 0;
     // set while the model comes from a batched build on another stream (fd_batch_build_async)
+    // (borrowed: the batch's event, the stream the batch built on)
     hipEvent_t wait_event = nullptr;
     hipStream_t wait_stream = nullptr;
     struct fd_batch *wait_batch = nullptr;
-    hipEvent_t tev0 = nullptr, tev_mid = nullptr, tev1 = nullptr;   // events the report's timings come from
-    ModelHeader *h_header = nullptr;  // pinned, for device-side export
+    hipEvent_t tev0 = nullptr, tev_mid = nullptr, tev1 = nullptr;   // events the report's timings come from (borrowed: ev0 / ev_mid / ev1, or the batch's)
+    Pinned<ModelHeader> h_header;     // pinned, for device-side export
     // Asynchronous status: after every enqueued build a one-thread kernel drops the model's
     // terminationtype into this page-locked word and status_ev is recorded behind it.  Every later
     // call on the context polls the event (no wait): a Cholesky that lost definiteness is then
     // rebuilt with the LU right away, on the stream, before whatever the call enqueues; a failure
     // the LU confirms becomes a sticky error that fd_deform* returns until the next set-up call.
-    int *h_status = nullptr;
-    int *d_status_alias = nullptr;      // the same word as the device sees it (looked up once: hipHostGetDevicePointer costs a runtime call per build)
-    hipEvent_t status_ev = nullptr;
-    hipEvent_t status_poll = nullptr;   // the event that says h_status is in: status_ev, or the one of the batch that built the model
+    Pinned<int> h_status;
+    int *d_status_alias = nullptr;      // (borrowed) the same word as the device sees it (looked up once: hipHostGetDevicePointer costs a runtime call per build)
+    Event status_ev;
+    hipEvent_t status_poll = nullptr;   // (borrowed) the event that says h_status is in: status_ev, or the one of the batch that built the model
     bool status_inflight = false;
     int sticky_rc = FD_OK;
 
     // staging for the host-pointer deform
     int64_t cap_N = 0;
-    float *d_P = nullptr, *d_dist2 = nullptr, *d_fall = nullptr;
-    float *d_tu = nullptr, *d_tv = nullptr, *d_nrm = nullptr;
+    DevBuf<float> d_P, d_dist2, d_fall;
+    DevBuf<float> d_tu, d_tv, d_nrm;
     // fd_deform_vectors: staging of the transported vectors + Jacobian (N x 18), and P_in set aside when it is overwritten.
-    // The capacities of this and the scratch buffers below count elements (dev_grow).
-    size_t cap_vec = 0, cap_vecP = 0;
-    float *d_vec = nullptr, *d_vecP = nullptr;
+    // This and the scratch buffers below grow by need (DevBuf::grow).
+    DevBuf<float> d_vec, d_vecP;
     // fd_invert: staging of iters_out (residual_out goes through d_fall)
-    size_t cap_iters = 0;
-    int *d_iters = nullptr;
+    DevBuf<int> d_iters;
     // fd_deform_adjoint*: the workgroups' partial blocks and, behind them, the host call's staging of grad_W (adjoint_scratch);
     // the host call's G goes through d_vecP
-    size_t cap_adj = 0;
-    double *d_adj = nullptr;
+    DevBuf<double> d_adj;
     // fd_deform_adjoint_points: the host call's staging of grad_P (N x 3) and, behind it, grad_f (N); its G goes through d_vecP
-    size_t cap_adjp = 0;
-    double *d_adjp = nullptr;
+    DevBuf<double> d_adjp;
     // fd_deform_gram*: the workgroups' partial blocks and, behind them, the host call's staging of H (gram_scratch); the host
     // call's omega goes through d_fall
-    size_t cap_gram = 0;
-    double *d_gram = nullptr;
+    DevBuf<double> d_gram;
     // fd_deform_adjoint_shot*: the ranges' partial blocks of one group of frames and, behind them, the host call's staging of
     // grad_W (adjoint_shot_scratch); the host call's G goes group by group through d_gshot
-    size_t cap_adjs = 0, cap_gshot = 0;
-    double *d_adjs = nullptr;
-    float *d_gshot = nullptr;
+    DevBuf<double> d_adjs;
+    DevBuf<float> d_gshot;
     // fd_fit_deltas_shot: a group's cotangents g_f = omega (T_f - P) on the host (malloc)
     size_t cap_hgshot = 0;
     float *h_gshot = nullptr;
@@ -134,14 +131,14 @@ struct fd_ctx {
     // device buffers (the staging above is evaluated in place, so it cannot serve as a cache)
     int64_t mesh_N = 0, mesh_cap = 0;
     bool mesh_has_dist2 = false, mesh_has_frames = false;
-    float *m_P = nullptr, *m_dist2 = nullptr, *m_tu = nullptr, *m_tv = nullptr, *m_nrm = nullptr;
-    float *m_out = nullptr, *m_fall = nullptr;      // result staging for pageable outputs
+    DevBuf<float> m_P, m_dist2, m_tu, m_tv, m_nrm;
+    DevBuf<float> m_out, m_fall;                    // result staging for pageable outputs
 
-    hipEvent_t ev0 = nullptr, ev_mid = nullptr, ev1 = nullptr;
+    Event ev0, ev_mid, ev1;
 
     // The build is ~25 dependent launches whose arguments depend only on the configuration
     // and on buffer addresses: captured once into a hipGraph, replayed on every later build.
-    hipGraphExec_t build_exec = nullptr;
+    GraphExec build_exec;
     bool use_graph = true;
     GraphKey graph_key{}, resolve_key{};
     char err[512] = {0};
@@ -150,11 +147,10 @@ struct fd_ctx {
 // Scratch of a one-launch shot call that keeps its own (fd_batch_deform_shared_fp64_dev, _ml_dev, _ml_fp64_dev; the vector call
 // that goes with each reads it too), and the two events that order the contexts' models and the scratch around its launches.
 struct ShotScratch {
-    void *d = nullptr;                   // what the call's pack kernel writes and its evaluation reads
-    size_t cap = 0;
-    hipEvent_t consumed_ev = nullptr;    // behind the last read of the contexts' models by that call (its pack kernel, or its per-context launches)
+    DevBuf<void> d;                      // what the call's pack kernel writes and its evaluation reads
+    Event consumed_ev;                   // behind the last read of the contexts' models by that call (its pack kernel, or its per-context launches)
     bool consumed = false;               // ... and recorded: fd_batch_wait_consumed waits for it too
-    hipEvent_t eval_ev = nullptr;        // behind its last evaluation: the next pack kernel rewrites the scratch that one reads
+    Event eval_ev;                       // behind its last evaluation: the next pack kernel rewrites the scratch that one reads
     bool eval_pending = false;
 };
 
@@ -163,42 +159,39 @@ struct fd_batch {
     int device = 0;
     fd_ctx *ctxs[kMaxBatch] = {};
     uint64_t gens[kMaxBatch] = {};
-    BatchSlot *d_slots = nullptr;
+    DevBuf<BatchSlot> d_slots;
     PointSrc src{};
     bool have_src = false;
-    hipEvent_t ev0 = nullptr, ev_mid = nullptr, ev1 = nullptr;
-    hipGraphExec_t exec = nullptr;
+    Event ev0, ev_mid, ev1;
+    GraphExec exec;
     bool use_graph = true;
     GraphKey key{};
     // a stream that already waits for the current build (set by the first evaluation that
     // needed it): the other contexts' evaluations on that stream need no wait of their own
-    hipStream_t waited_stream = nullptr;
-    hipEvent_t status_ev = nullptr;     // behind the kernel that posts every context's status after a batched build
+    hipStream_t waited_stream = nullptr;    // (borrowed)
+    Event status_ev;                    // behind the kernel that posts every context's status after a batched build
     // scratch of the shared-rig evaluation (fd_batch_deform_shared_dev): weight tiles + frame records
     // Two sets: the set a launch reads must not be rewritten by the pack kernel of the NEXT models before that launch
     // has finished -- with fd_batch_prepare_shared the next pack runs on the build stream, under the previous evaluation.
     struct SharedSet {
-        void *d_wtiles = nullptr, *d_frames = nullptr;
-        size_t cap_wtiles = 0, cap_frames = 0;
-        hipEvent_t packed_ev = nullptr;  // behind the pack kernel that filled the set
-        hipEvent_t eval_ev = nullptr;    // behind the last evaluation that read it
-        hipEvent_t eval_done = nullptr;  // the event that says so: eval_ev, or -- a lean group call -- the batch's ev1, recorded right behind
+        DevBuf<void> d_wtiles, d_frames;
+        Event packed_ev;                 // behind the pack kernel that filled the set
+        Event eval_ev;                   // behind the last evaluation that read it
+        hipEvent_t eval_done = nullptr;  // (borrowed) the event that says so: eval_ev, or -- a lean group call -- the batch's ev1, recorded right behind
         bool eval_pending = false;
     } sets[2];
     // "One rest rig" is decided on the host by the address the rest points were read from; an address does not identify
     // its contents (the array may have been rewritten, or freed and allocated again, between the set-ups of two contexts:
     // ADVICE r2), so the pack kernel compares every context's centres with context 0's ON THE DEVICE, passes a frame that
     // differs through like a failed build and posts 1 + its index here (page-locked); the next call on the batch reports it.
-    int *h_mismatch = nullptr;
+    Pinned<int> h_mismatch;
     int eval_cus = 0;                    // fd_batch_set_eval_cus: CUs a shared-rig evaluation may occupy (0: all)
     int shared_factor = 0;               // fd_batch_set_shared_factor: one factorisation per build where the contexts share the rest rig
-    double *d_fac = nullptr;             // ... and its scratch (reg_factor_doubles())
+    DevBuf<double> d_fac;                // ... and its scratch (reg_factor_doubles())
     int last_shared_factor = 0;          // the last build took that path
-    void *d_mlfac = nullptr;             // multilayer batches: the L layer factors' scratch (ml_shared_scratch_bytes), allocated at the first such build
-    size_t cap_mlfac = 0;
+    DevBuf<void> d_mlfac;                // multilayer batches: the L layer factors' scratch (ml_shared_scratch_bytes), allocated at the first such build
     int shared_lu = 0;                   // fd_batch_set_shared_lu: QNN batches, one LU of the rest rig's kernel block per build
-    void *d_qnnfac = nullptr;            // ... and its scratch (qnn_shared_scratch_bytes), allocated at the first such build, grown by need
-    size_t cap_qnnfac = 0;
+    DevBuf<void> d_qnnfac;               // ... and its scratch (qnn_shared_scratch_bytes), allocated at the first such build, grown by need
     bool qnn_slot_ready = false;         // the last shared build went out whole: its solve kernel left the scratch slot filled and reset
     int qnn_slot_M = 0, qnn_slot_npad = 0;   // ... for a system of these sizes (they decide where the slot's pieces lie in the scratch)
     int cur_set = 0;                     // the set packed last
@@ -208,19 +201,19 @@ struct fd_batch {
     float *prep_P_out[kMaxBatch] = {nullptr};
     float *prep_fall[kMaxBatch] = {nullptr};
     bool prep_has_fall = false;
-    hipEvent_t fallback_ev = nullptr;    // behind the per-frame launches when the shared launch does not apply
+    Event fallback_ev;                   // behind the per-frame launches when the shared launch does not apply
     // the other one-launch shot calls: a scratch of their own each (the two fp32 sets, packed_valid, cur_set and prepared are not
     // their business)
     ShotScratch s64;                     // fd_batch_deform_shared_fp64_dev
     ShotScratch sml;                     // fd_batch_deform_shared_ml_dev, for the multilayer shot launch
     ShotScratch sml64;                   // fd_batch_deform_shared_ml_fp64_dev, for the fp64 multilayer shot launch
-    hipEvent_t group_ev = nullptr;       // fd_batch_cook_group: behind the group's builds, for the evaluation stream
+    Event group_ev;                      // fd_batch_cook_group: behind the group's builds, for the evaluation stream
     // fd_batch_cook_group with the evaluation on the build stream itself (one unpipelined group): stream order does what the
     // events between build, packing and evaluation do across streams, and every event record is a barrier packet that keeps the
     // queue idle for ~4 us.  `lean`: the build's end (ev1) and the packing's are not recorded where they happen; ev1 goes behind
     // the evaluation (later than needed, never earlier), and "the models are consumed" is the evaluation's own event.
     bool lean = false;
-    hipEvent_t consumed_override = nullptr;
+    hipEvent_t consumed_override = nullptr;     // (borrowed: ev1)
     char err[512] = {0};
 };
 
@@ -243,10 +236,7 @@ static void set_err(fd_ctx *ctx, const char *fmt, ...)
 static hipStream_t cur_stream(fd_ctx *ctx)
 {
     if (ctx->stream_) return ctx->stream_;
-    if (!ctx->own_stream && hipStreamCreateWithFlags(&ctx->own_stream, hipStreamNonBlocking) != hipSuccess) {
-        (void)hipGetLastError();
-        ctx->own_stream = nullptr;     // falls back to the null stream
-    }
+    if (!ctx->own_stream && ctx->own_stream.create() != hipSuccess) (void)hipGetLastError();      // falls back to the null stream
     return ctx->own_stream;
 }
 
@@ -267,31 +257,15 @@ static int use_device(fd_ctx *ctx)
     return FD_OK;
 }
 
+// DevBuf's alloc -- with kGrow its grow: a scratch that grows on demand and never shrinks -- and the context's error text
+constexpr bool kGrow = true;
 template <typename T>
-static int dev_alloc(fd_ctx *ctx, T **p, size_t count)
+static int dev_alloc(fd_ctx *ctx, DevBuf<T> &b, size_t count, bool grow = false)
 {
-    if (*p) { (void)hipFree(*p); *p = nullptr; }
-    if (count == 0) count = 1;
-    hipError_t e = hipMalloc((void **)p, count * sizeof(T));
-    if (e != hipSuccess) {
-        *p = nullptr;
-        set_err(ctx, "hipMalloc(%zu bytes) failed: %s", count * sizeof(T), hipGetErrorString(e));
-        return FD_E_NOMEM;
-    }
-    return FD_OK;
-}
-
-// A scratch buffer that grows on demand and never shrinks, *cap its size in elements.  *cap is 0 while *p is being replaced, so
-// that a failed allocation leaves no capacity behind for a later, smaller request to trust (hipFree drains the device).
-template <typename T>
-static int dev_grow(fd_ctx *ctx, T **p, size_t *cap, size_t count)
-{
-    if (count <= *cap) return FD_OK;
-    *cap = 0;
-    const int rc = dev_alloc(ctx, p, count);
-    if (rc) return rc;
-    *cap = count;
-    return FD_OK;
+    const hipError_t e = grow ? b.grow(count) : b.alloc(count);
+    if (e == hipSuccess) return FD_OK;
+    set_err(ctx, "hipMalloc(%zu bytes) failed: %s", (count ? count : 1) * sizeof(T), hipGetErrorString(e));
+    return FD_E_NOMEM;
 }
 
 static int order_of(const fd_ctx *ctx) { return ctx->M + term_cols(ctx->term); }
@@ -309,13 +283,13 @@ static int ensure_records_capacity(fd_ctx *ctx, int n)
     int rc;
     if (n > ctx->cap_records) {
         const int npad = round_up(n, kRecPad);
-        if ((rc = dev_alloc(ctx, &ctx->d_centres, (size_t)n * 3))) return rc;
-        if ((rc = dev_alloc(ctx, &ctx->d_radii, (size_t)n))) return rc;
-        if ((rc = dev_alloc(ctx, &ctx->d_W, (size_t)(n + 4) * 3))) return rc;
-        if ((rc = dev_alloc(ctx, &ctx->d_rec32, (size_t)npad))) return rc;
-        if ((rc = dev_alloc(ctx, &ctx->d_rec64, (size_t)npad))) return rc;
-        if ((rc = dev_alloc(ctx, &ctx->d_tiles, (size_t)npad / 16))) return rc;
-        if ((rc = dev_alloc(ctx, &ctx->d_tiles16, (size_t)npad / 16))) return rc;
+        if ((rc = dev_alloc(ctx, ctx->d_centres, (size_t)n * 3))) return rc;
+        if ((rc = dev_alloc(ctx, ctx->d_radii, (size_t)n))) return rc;
+        if ((rc = dev_alloc(ctx, ctx->d_W, (size_t)(n + 4) * 3))) return rc;
+        if ((rc = dev_alloc(ctx, ctx->d_rec32, (size_t)npad))) return rc;
+        if ((rc = dev_alloc(ctx, ctx->d_rec64, (size_t)npad))) return rc;
+        if ((rc = dev_alloc(ctx, ctx->d_tiles, (size_t)npad / 16))) return rc;
+        if ((rc = dev_alloc(ctx, ctx->d_tiles16, (size_t)npad / 16))) return rc;
         ctx->cap_records = n;
     }
     return FD_OK;
@@ -325,9 +299,9 @@ static int ensure_model_capacity(fd_ctx *ctx, int M)
 {
     int rc;
     if (M > ctx->cap_M) {
-        if ((rc = dev_alloc(ctx, &ctx->d_rest, (size_t)M * 3))) return rc;
-        if ((rc = dev_alloc(ctx, &ctx->d_delta, (size_t)M * 3))) return rc;
-        if ((rc = dev_alloc(ctx, &ctx->d_ns, ns_doubles(M)))) return rc;
+        if ((rc = dev_alloc(ctx, ctx->d_rest, (size_t)M * 3))) return rc;
+        if ((rc = dev_alloc(ctx, ctx->d_delta, (size_t)M * 3))) return rc;
+        if ((rc = dev_alloc(ctx, ctx->d_ns, ns_doubles(M)))) return rc;
         ctx->cap_M = M;
     }
     return ensure_records_capacity(ctx, M);
@@ -338,10 +312,10 @@ static int ensure_solver_capacity(fd_ctx *ctx, int npad)
     int rc;
     if (npad > ctx->cap_npad) {
         const size_t cols = (size_t)npad + kRhsCols + 16;  // + 16 zero columns (block overrun)
-        if ((rc = dev_alloc(ctx, &ctx->d_A, (size_t)npad * cols))) return rc;
-        if ((rc = dev_alloc(ctx, &ctx->d_X, (size_t)npad * 3))) return rc;
-        if ((rc = dev_alloc(ctx, &ctx->d_ipiv, (size_t)npad))) return rc;
-        if ((rc = dev_alloc(ctx, &ctx->d_moves, (size_t)kMovesStride * (size_t)lu_step_capacity(npad)))) return rc;
+        if ((rc = dev_alloc(ctx, ctx->d_A, (size_t)npad * cols))) return rc;
+        if ((rc = dev_alloc(ctx, ctx->d_X, (size_t)npad * 3))) return rc;
+        if ((rc = dev_alloc(ctx, ctx->d_ipiv, (size_t)npad))) return rc;
+        if ((rc = dev_alloc(ctx, ctx->d_moves, (size_t)kMovesStride * (size_t)lu_step_capacity(npad)))) return rc;
         ctx->cap_npad = npad;
     }
     return FD_OK;
@@ -359,7 +333,7 @@ static int sync_slot(fd_ctx *ctx)
     t.ns = ctx->d_ns;
     t.host_status = ctx->d_status_alias;
     if (ctx->alloc_gen != 0 && memcmp(&t, &ctx->h_slot, sizeof(t)) == 0) return FD_OK;
-    // a buffer moved: hipFree in dev_alloc has drained the device, nothing reads the old table
+    // a buffer moved: hipFree in DevBuf::alloc has drained the device, nothing reads the old table
     FD_HIP(ctx, hipMemcpy(ctx->d_slot, &t, sizeof(t), hipMemcpyHostToDevice));
     ctx->h_slot = t;
     ++ctx->alloc_gen;
@@ -443,10 +417,11 @@ static void note_build_enqueued(fd_ctx *c, hipEvent_t done, hipStream_t s, fd_ba
 // The graph for `key` in *exec, captured from what `launch()` enqueues on `s` unless *exec was made for this key already.  On
 // failure *exec is null: the caller launches directly.
 template <typename Launch>
-static hipError_t ensure_graph(hipStream_t s, hipGraphExec_t *exec, GraphKey *exec_key, const GraphKey &key, Launch launch)
+static hipError_t ensure_graph(hipStream_t s, GraphExec *owner, GraphKey *exec_key, const GraphKey &key, Launch launch)
 {
+    hipGraphExec_t *exec = &owner->exec;
     if (*exec && memcmp(&key, exec_key, sizeof(key)) == 0) return hipSuccess;
-    if (*exec) { (void)hipGraphExecDestroy(*exec); *exec = nullptr; }
+    owner->reset();
     hipGraph_t graph = nullptr;
     hipError_t e = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
     if (e == hipSuccess) {
@@ -531,20 +506,20 @@ fd_ctx *fd_create(const fd_config *cfg)
         return nullptr;
     }
     bool ok = true;
-    ok = ok && hipEventCreate(&ctx->ev0) == hipSuccess && hipEventCreate(&ctx->ev_mid) == hipSuccess &&
-         hipEventCreate(&ctx->ev1) == hipSuccess;
-    ok = ok && hipMalloc((void **)&ctx->d_model, sizeof(DevModel)) == hipSuccess;
-    ok = ok && hipMalloc((void **)&ctx->d_slot, sizeof(BatchSlot)) == hipSuccess;
-    ok = ok && hipHostMalloc((void **)&ctx->h_model, sizeof(DevModel), hipHostMallocDefault) == hipSuccess;
-    ok = ok && hipHostMalloc((void **)&ctx->h_header, sizeof(ModelHeader), hipHostMallocDefault) == hipSuccess;
-    ok = ok && hipHostMalloc((void **)&ctx->h_status, sizeof(int), hipHostMallocDefault) == hipSuccess;
-    if (ok && hipHostGetDevicePointer((void **)&ctx->d_status_alias, ctx->h_status, 0) != hipSuccess) { (void)hipGetLastError(); ctx->d_status_alias = nullptr; }
-    ok = ok && hipEventCreateWithFlags(&ctx->status_ev, hipEventDisableTiming) == hipSuccess;
+    ok = ok && ctx->ev0.create(hipEventDefault) == hipSuccess && ctx->ev_mid.create(hipEventDefault) == hipSuccess &&
+         ctx->ev1.create(hipEventDefault) == hipSuccess;
+    ok = ok && ctx->d_model.alloc(1) == hipSuccess;
+    ok = ok && ctx->d_slot.alloc(1) == hipSuccess;
+    ok = ok && ctx->h_model.alloc(1, hipHostMallocDefault) == hipSuccess;
+    ok = ok && ctx->h_header.alloc(1, hipHostMallocDefault) == hipSuccess;
+    ok = ok && ctx->h_status.alloc(1, hipHostMallocDefault) == hipSuccess;
+    if (ok && hipHostGetDevicePointer((void **)&ctx->d_status_alias, ctx->h_status.p, 0) != hipSuccess) { (void)hipGetLastError(); ctx->d_status_alias = nullptr; }
+    ok = ok && ctx->status_ev.create(hipEventDisableTiming) == hipSuccess;
     if (ok) ok = hipMemset(ctx->d_model, 0, sizeof(DevModel)) == hipSuccess;
     if (!ok) {
         set_err(nullptr, "fd_create: device resource allocation failed: %s",
                 hipGetErrorString(hipGetLastError()));
-        fd_destroy(ctx);
+        fd_destroy(ctx);        // releases what has been created
         return nullptr;
     }
     ctx->tev0 = ctx->ev0; ctx->tev_mid = ctx->ev_mid; ctx->tev1 = ctx->ev1;
@@ -556,23 +531,8 @@ void fd_destroy(fd_ctx *ctx)
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     if (ctx->stream_ || ctx->own_stream) (void)hipStreamSynchronize(cur_stream(ctx));
-    void *bufs[] = {ctx->d_rest, ctx->d_delta, ctx->d_centres, ctx->d_radii, ctx->d_W, ctx->d_A,
-                    ctx->d_X, ctx->d_ipiv, ctx->d_moves, ctx->d_rec32, ctx->d_rec64, ctx->d_tiles, ctx->d_tiles16, ctx->d_ns, ctx->d_model, ctx->d_slot,
-                    ctx->d_P, ctx->d_dist2, ctx->d_fall, ctx->d_tu, ctx->d_tv, ctx->d_nrm, ctx->d_vec, ctx->d_vecP, ctx->d_iters, ctx->d_adj, ctx->d_adjp, ctx->d_gram, ctx->d_adjs, ctx->d_gshot,
-                    ctx->m_P, ctx->m_dist2, ctx->m_tu, ctx->m_tv, ctx->m_nrm, ctx->m_out, ctx->m_fall};
-    for (void *p : bufs) if (p) (void)hipFree(p);
     free(ctx->h_gshot);
-    if (ctx->h_model) (void)hipHostFree(ctx->h_model);
-    if (ctx->h_header) (void)hipHostFree(ctx->h_header);
-    if (ctx->h_status) (void)hipHostFree(ctx->h_status);
-    if (ctx->status_ev) (void)hipEventDestroy(ctx->status_ev);
-    if (ctx->build_exec) (void)hipGraphExecDestroy(ctx->build_exec);
-    if (ctx->resolve_exec) (void)hipGraphExecDestroy(ctx->resolve_exec);
-    if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
-    if (ctx->ev_mid) (void)hipEventDestroy(ctx->ev_mid);
-    if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
-    if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
-    delete ctx;
+    delete ctx;                 // the members release what they own, own_stream last
 }
 
 int fd_set_stream(fd_ctx *ctx, void *hip_stream)
@@ -1040,7 +1000,7 @@ static bool adjoint_points_opts_ok(fd_ctx *ctx, const fd_adjoint_points_opts *op
 }
 
 // The scratch of the adjoint, the Gram operator and the shot adjoint for N vertices and C records: the workgroups' partial blocks
-// and, behind them, room for the result, where the host call stages it (*_staging).  Grown on demand (dev_grow).
+// and, behind them, room for the result, where the host call stages it (*_staging).  Grown on demand (DevBuf::grow).
 // fd_deform_adjoint*: adjoint_groups(N) partial blocks of (C + 4) x 3 doubles and one more for grad_W
 static size_t adjoint_block(int C) { return (size_t)(C + 4) * 3; }
 static size_t adjoint_scratch(int64_t N, int C) { return ((size_t)adjoint_groups(N) + 1) * adjoint_block(C); }
@@ -1104,7 +1064,7 @@ static int deform_dev(fd_ctx *ctx, const char *who, void *hip_stream, const Mesh
     }
     DeformArgs av = a;
     if (d_P_out == m.P) {
-        if ((rc = dev_grow(ctx, &ctx->d_vecP, &ctx->cap_vecP, (size_t)m.N * 3))) return rc;
+        if ((rc = dev_alloc(ctx, ctx->d_vecP, (size_t)m.N * 3, kGrow))) return rc;
         FD_HIP(ctx, hipMemcpyAsync(ctx->d_vecP, m.P, sizeof(float) * 3 * (size_t)m.N, hipMemcpyDeviceToDevice, launch_stream));
         av.P_in = ctx->d_vecP;
     }
@@ -1131,7 +1091,7 @@ static int adjoint_dev(fd_ctx *ctx, const char *who, const Mesh &m, const float 
     hipStream_t s;
     int rc = deform_begin(ctx, who, nullptr, m, nullptr, nullptr, true, &a, &s);
     if (rc || m.N == 0) return rc;
-    if ((rc = dev_grow(ctx, &ctx->d_adj, &ctx->cap_adj, adjoint_scratch(m.N, a.M)))) return rc;
+    if ((rc = dev_alloc(ctx, ctx->d_adj, adjoint_scratch(m.N, a.M), kGrow))) return rc;
     const AdjointArgs g{d_G, d_grad_W, ctx->d_adj, term_cols(ctx->term)};
     FD_HIP(ctx, launch_adjoint(a, g, s));
     return FD_OK;
@@ -1155,7 +1115,7 @@ static int gram_dev(fd_ctx *ctx, const char *who, const Mesh &m, const float *d_
     hipStream_t s;
     int rc = deform_begin(ctx, who, nullptr, m, nullptr, nullptr, true, &a, &s);
     if (rc || m.N == 0) return rc;
-    if ((rc = dev_grow(ctx, &ctx->d_gram, &ctx->cap_gram, gram_scratch(m.N, a.M, m.tu ? 6 : 1)))) return rc;
+    if ((rc = dev_alloc(ctx, ctx->d_gram, gram_scratch(m.N, a.M, m.tu ? 6 : 1), kGrow))) return rc;
     const GramArgs g{d_omega, d_H, ctx->d_gram, term_cols(ctx->term)};
     FD_HIP(ctx, launch_gram(a, g, s));
     return FD_OK;
@@ -1168,7 +1128,7 @@ static int adjoint_shot_dev(fd_ctx *ctx, const char *who, const Mesh &m, int F, 
     hipStream_t s;
     int rc = deform_begin(ctx, who, nullptr, m, nullptr, nullptr, true, &a, &s);
     if (rc || m.N == 0) return rc;
-    if ((rc = dev_grow(ctx, &ctx->d_adjs, &ctx->cap_adjs, adjoint_shot_scratch(m.N, a.M, 0)))) return rc;
+    if ((rc = dev_alloc(ctx, ctx->d_adjs, adjoint_shot_scratch(m.N, a.M, 0), kGrow))) return rc;
     const AdjointShotArgs g{d_G, d_grad_W, ctx->d_adjs, F, term_cols(ctx->term)};
     FD_HIP(ctx, launch_adjoint_shot(a, g, s));
     return FD_OK;
@@ -1180,19 +1140,18 @@ static int ensure_staging(fd_ctx *ctx, int64_t N, bool frames)
 {
     int rc;
     if (N > ctx->cap_N) {
-        ctx->cap_N = 0;                 // one capacity for three buffers: dev_grow's rule, spelled out
-        if ((rc = dev_alloc(ctx, &ctx->d_P, (size_t)N * 3))) return rc;
-        if ((rc = dev_alloc(ctx, &ctx->d_dist2, (size_t)N))) return rc;
-        if ((rc = dev_alloc(ctx, &ctx->d_fall, (size_t)N))) return rc;
+        ctx->cap_N = 0;                 // one capacity for three buffers: DevBuf::grow's rule for them together
+        if ((rc = dev_alloc(ctx, ctx->d_P, (size_t)N * 3))) return rc;
+        if ((rc = dev_alloc(ctx, ctx->d_dist2, (size_t)N))) return rc;
+        if ((rc = dev_alloc(ctx, ctx->d_fall, (size_t)N))) return rc;
         // tangent frames are optional and 3x as large: allocate on first use
-        for (float **p : {&ctx->d_tu, &ctx->d_tv, &ctx->d_nrm})
-            if (*p) { (void)hipFree(*p); *p = nullptr; }
+        for (DevBuf<float> *b : {&ctx->d_tu, &ctx->d_tv, &ctx->d_nrm}) b->reset();
         ctx->cap_N = N;
     }
     if (frames && !ctx->d_nrm) {
-        if ((rc = dev_alloc(ctx, &ctx->d_tu, (size_t)ctx->cap_N * 3))) return rc;
-        if ((rc = dev_alloc(ctx, &ctx->d_tv, (size_t)ctx->cap_N * 3))) return rc;
-        if ((rc = dev_alloc(ctx, &ctx->d_nrm, (size_t)ctx->cap_N * 3))) return rc;
+        if ((rc = dev_alloc(ctx, ctx->d_tu, (size_t)ctx->cap_N * 3))) return rc;
+        if ((rc = dev_alloc(ctx, ctx->d_tv, (size_t)ctx->cap_N * 3))) return rc;
+        if ((rc = dev_alloc(ctx, ctx->d_nrm, (size_t)ctx->cap_N * 3))) return rc;
     }
     return FD_OK;
 }
@@ -1267,12 +1226,12 @@ static int deform_host(fd_ctx *ctx, const char *who, const Mesh &m, float *P_out
     const bool fall_up = falloff_out && (dist2 || m.radius2 < 0.f);
     hipStream_t s = cur_stream(ctx);
     Mesh d;
-    if ((rc = stage_mesh(ctx, m, s, &d, {}, Upload{&ctx->d_fall, fall_up ? falloff_out : nullptr, 1}))) return rc;
+    if ((rc = stage_mesh(ctx, m, s, &d, {}, Upload{&ctx->d_fall.p, fall_up ? falloff_out : nullptr, 1}))) return rc;
     const size_t b3 = sizeof(float) * 3 * (size_t)N, b1 = sizeof(float) * (size_t)N;
     // the vectors: each staged in its own device array and transported in place there
     fd_vectors dv{};
     if (vec) {
-        if ((rc = dev_grow(ctx, &ctx->d_vec, &ctx->cap_vec, (size_t)N * 18))) return rc;
+        if ((rc = dev_alloc(ctx, ctx->d_vec, (size_t)N * 18, kGrow))) return rc;
         float *const slot[4] = {ctx->d_vec, ctx->d_vec + 3 * N, ctx->d_vec + 6 * N, ctx->d_vec + 9 * N};
         const float *const in[3] = {vec->N, vec->tu, vec->tv};
         for (int k = 0; k < 3; ++k)
@@ -1303,7 +1262,7 @@ static int invert_host(fd_ctx *ctx, const Mesh &m, float *X_out, const fd_invert
     int rc = mesh_checks(ctx, "fd_invert", m, X_out != nullptr);
     if (rc || m.N == 0) return rc;
     if ((rc = use_device(ctx))) return rc;
-    if (opts->iters_out && (rc = dev_grow(ctx, &ctx->d_iters, &ctx->cap_iters, (size_t)m.N))) return rc;
+    if (opts->iters_out && (rc = dev_alloc(ctx, ctx->d_iters, (size_t)m.N, kGrow))) return rc;
     hipStream_t s = cur_stream(ctx);
     Mesh d;
     if ((rc = stage_mesh(ctx, m, s, &d))) return rc;
@@ -1325,11 +1284,11 @@ static int adjoint_host(fd_ctx *ctx, const char *who, const Mesh &m, const float
     const int C = model_centres(ctx);
     if (m.N == 0) { memset(grad_W, 0, sizeof(double) * adjoint_block(C)); return FD_OK; }
     if ((rc = use_device(ctx))) return rc;
-    if ((rc = dev_grow(ctx, &ctx->d_vecP, &ctx->cap_vecP, (size_t)m.N * 3))) return rc;
-    if ((rc = dev_grow(ctx, &ctx->d_adj, &ctx->cap_adj, adjoint_scratch(m.N, C)))) return rc;
+    if ((rc = dev_alloc(ctx, ctx->d_vecP, (size_t)m.N * 3, kGrow))) return rc;
+    if ((rc = dev_alloc(ctx, ctx->d_adj, adjoint_scratch(m.N, C), kGrow))) return rc;
     hipStream_t s = cur_stream(ctx);
     Mesh d;
-    if ((rc = stage_mesh(ctx, m, s, &d, Upload{&ctx->d_vecP, G, 3}))) return rc;
+    if ((rc = stage_mesh(ctx, m, s, &d, Upload{&ctx->d_vecP.p, G, 3}))) return rc;
     double *d_out = adjoint_staging(ctx, m.N, C);
     if ((rc = adjoint_dev(ctx, who, d, ctx->d_vecP, d_out))) return rc;
     FD_HIP(ctx, hipMemcpyAsync(grad_W, d_out, sizeof(double) * adjoint_block(C), hipMemcpyDeviceToHost, s));
@@ -1345,11 +1304,11 @@ static int adjoint_points_host(fd_ctx *ctx, const char *who, const Mesh &m, cons
     if (rc || m.N == 0) return rc;
     if ((rc = use_device(ctx))) return rc;
     const size_t n = (size_t)m.N;
-    if ((rc = dev_grow(ctx, &ctx->d_vecP, &ctx->cap_vecP, n * 3))) return rc;
-    if ((rc = dev_grow(ctx, &ctx->d_adjp, &ctx->cap_adjp, n * 4))) return rc;
+    if ((rc = dev_alloc(ctx, ctx->d_vecP, n * 3, kGrow))) return rc;
+    if ((rc = dev_alloc(ctx, ctx->d_adjp, n * 4, kGrow))) return rc;
     hipStream_t s = cur_stream(ctx);
     Mesh d;
-    if ((rc = stage_mesh(ctx, m, s, &d, Upload{&ctx->d_vecP, G, 3}))) return rc;
+    if ((rc = stage_mesh(ctx, m, s, &d, Upload{&ctx->d_vecP.p, G, 3}))) return rc;
     double *d_f = grad_f ? ctx->d_adjp + n * 3 : nullptr;
     if ((rc = adjoint_points_dev(ctx, who, d, ctx->d_vecP, ctx->d_adjp, d_f))) return rc;
     FD_HIP(ctx, hipMemcpyAsync(grad_P, ctx->d_adjp, sizeof(double) * n * 3, hipMemcpyDeviceToHost, s));
@@ -1364,7 +1323,7 @@ static int gram_staged(fd_ctx *ctx, const char *who, const Mesh &d, const float 
 {
     const int C = model_centres(ctx), nq = d.tu ? 6 : 1;
     if (d.N == 0) { memset(H, 0, sizeof(double) * gram_block(C, nq)); return FD_OK; }
-    int rc = dev_grow(ctx, &ctx->d_gram, &ctx->cap_gram, gram_scratch(d.N, C, nq));
+    int rc = dev_alloc(ctx, ctx->d_gram, gram_scratch(d.N, C, nq), kGrow);
     if (rc) return rc;
     hipStream_t s = cur_stream(ctx);
     double *d_out = gram_staging(ctx, d.N, C, nq);
@@ -1380,7 +1339,7 @@ static int gram_host(fd_ctx *ctx, const char *who, const Mesh &m, const float *o
     int rc = mesh_checks(ctx, who, m, true);
     if (rc) return rc;
     Mesh d;
-    if ((rc = stage_mesh(ctx, m, cur_stream(ctx), &d, Upload{&ctx->d_fall, omega, 1}))) return rc;
+    if ((rc = stage_mesh(ctx, m, cur_stream(ctx), &d, Upload{&ctx->d_fall.p, omega, 1}))) return rc;
     return gram_staged(ctx, who, d, omega ? ctx->d_fall : nullptr, H);
 }
 
@@ -1394,8 +1353,8 @@ static int adjoint_shot_staged(fd_ctx *ctx, const char *who, const Mesh &d, int 
     const int group = F < FD_MAX_BATCH ? F : FD_MAX_BATCH;
     const size_t frame = (size_t)d.N * 3;
     int rc;
-    if ((rc = dev_grow(ctx, &ctx->d_gshot, &ctx->cap_gshot, (size_t)group * frame))) return rc;
-    if ((rc = dev_grow(ctx, &ctx->d_adjs, &ctx->cap_adjs, adjoint_shot_scratch(d.N, C, F)))) return rc;
+    if ((rc = dev_alloc(ctx, ctx->d_gshot, (size_t)group * frame, kGrow))) return rc;
+    if ((rc = dev_alloc(ctx, ctx->d_adjs, adjoint_shot_scratch(d.N, C, F), kGrow))) return rc;
     hipStream_t s = cur_stream(ctx);
     double *d_out = adjoint_shot_staging(ctx, d.N, C);
     for (int f0 = 0; f0 < F; f0 += FD_MAX_BATCH) {
@@ -1641,25 +1600,18 @@ int fd_capture_dist2(fd_ctx *ctx, int64_t N, const float *P, const unsigned char
     int rc = use_device(ctx);
     if (rc) return rc;
     hipStream_t s = cur_stream(ctx);
-    float *d_P = nullptr, *d_tri = nullptr, *d_out = nullptr;
-    unsigned char *d_mask = nullptr;
-    auto cleanup = [&]() {
-        if (d_P) (void)hipFree(d_P);
-        if (d_tri) (void)hipFree(d_tri);
-        if (d_out) (void)hipFree(d_out);
-        if (d_mask) (void)hipFree(d_mask);
-    };
-    hipError_t e = hipMalloc((void **)&d_P, sizeof(float) * 3 * (size_t)N);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_out, sizeof(float) * (size_t)N);
-    if (e == hipSuccess && T > 0) e = hipMalloc((void **)&d_tri, sizeof(float) * 9 * (size_t)T);
-    if (e == hipSuccess && mask) e = hipMalloc((void **)&d_mask, (size_t)N);
+    DevBuf<float> d_P, d_tri, d_out;         // released on the way out
+    DevBuf<unsigned char> d_mask;
+    hipError_t e = d_P.alloc(3 * (size_t)N);
+    if (e == hipSuccess) e = d_out.alloc((size_t)N);
+    if (e == hipSuccess && T > 0) e = d_tri.alloc(9 * (size_t)T);
+    if (e == hipSuccess && mask) e = d_mask.alloc((size_t)N);
     if (e == hipSuccess) e = hipMemcpyAsync(d_P, P, sizeof(float) * 3 * (size_t)N, hipMemcpyHostToDevice, s);
     if (e == hipSuccess && T > 0) e = hipMemcpyAsync(d_tri, tri_xyz, sizeof(float) * 9 * (size_t)T, hipMemcpyHostToDevice, s);
     if (e == hipSuccess && mask) e = hipMemcpyAsync(d_mask, mask, (size_t)N, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = launch_capture_dist2(d_P, N, d_mask, d_tri, T, radius2, dofalloff, d_out, s);
     if (e == hipSuccess) e = hipMemcpyAsync(dist2, d_out, sizeof(float) * (size_t)N, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    cleanup();
     if (e != hipSuccess) { set_err(ctx, "fd_capture_dist2 failed: %s", hipGetErrorString(e)); return FD_E_DEVICE; }
     return FD_OK;
 }
@@ -1692,15 +1644,15 @@ int fd_capture_islands(fd_ctx *ctx, int64_t N, const float *P, const int64_t *of
     int rc = use_device(ctx);
     if (rc) return rc;
     hipStream_t s = cur_stream(ctx);
-    float *d_P = nullptr, *d_rig = nullptr;
-    int64_t *d_off = nullptr;
-    int *d_nb = nullptr;
-    unsigned char *d_mask = nullptr;
-    hipError_t e = hipMalloc((void **)&d_P, sizeof(float) * 3 * (size_t)N);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_off, sizeof(int64_t) * (size_t)(N + 1));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_nb, sizeof(int) * (size_t)(E > 0 ? E : 1));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_mask, (size_t)N);
-    if (e == hipSuccess && M > 0) e = hipMalloc((void **)&d_rig, sizeof(float) * 3 * (size_t)M);
+    DevBuf<float> d_P, d_rig;                // released on the way out
+    DevBuf<int64_t> d_off;
+    DevBuf<int> d_nb;
+    DevBuf<unsigned char> d_mask;
+    hipError_t e = d_P.alloc(3 * (size_t)N);
+    if (e == hipSuccess) e = d_off.alloc((size_t)(N + 1));
+    if (e == hipSuccess) e = d_nb.alloc((size_t)(E > 0 ? E : 1));
+    if (e == hipSuccess) e = d_mask.alloc((size_t)N);
+    if (e == hipSuccess && M > 0) e = d_rig.alloc(3 * (size_t)M);
     if (e == hipSuccess) e = hipMemcpyAsync(d_P, P, sizeof(float) * 3 * (size_t)N, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(d_off, offsets, sizeof(int64_t) * (size_t)(N + 1), hipMemcpyHostToDevice, s);
     if (e == hipSuccess && E > 0) e = hipMemcpyAsync(d_nb, neighbours, sizeof(int) * (size_t)E, hipMemcpyHostToDevice, s);
@@ -1708,24 +1660,24 @@ int fd_capture_islands(fd_ctx *ctx, int64_t N, const float *P, const int64_t *of
     if (e == hipSuccess) e = launch_capture_islands(d_P, N, d_off, d_nb, d_rig, M, max_edges, d_mask, s);
     if (e == hipSuccess) e = hipMemcpyAsync(mask, d_mask, (size_t)N, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    for (void *p : {(void *)d_P, (void *)d_off, (void *)d_nb, (void *)d_mask, (void *)d_rig}) if (p) (void)hipFree(p);
     if (e != hipSuccess) { set_err(ctx, "fd_capture_islands failed: %s", hipGetErrorString(e)); return FD_E_DEVICE; }
     return FD_OK;
 }
 
 void *fd_host_alloc(size_t bytes)
 {
-    void *p = nullptr;
-    if (hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocDefault) != hipSuccess) {
+    Pinned<void> h;
+    if (h.alloc(bytes, hipHostMallocDefault) != hipSuccess) {
         set_err(nullptr, "fd_host_alloc(%zu) failed: %s", bytes, hipGetErrorString(hipGetLastError()));
         return nullptr;
     }
-    return p;
+    return h.release();         // the caller's, until fd_host_free
 }
 
 void fd_host_free(void *p)
 {
-    if (p) (void)hipHostFree(p);
+    Pinned<void> h;
+    h.adopt(p);                 // released on the way out
 }
 
 // ---- device-resident mesh (next row N3, engine side) ----------------------------------------
@@ -1739,20 +1691,15 @@ int fd_mesh_set(fd_ctx *ctx, int64_t N, const float *P, const float *dist2, cons
     if (rc) return rc;
     ctx->mesh_N = 0;
     if (N > ctx->mesh_cap) {
-        if ((rc = dev_alloc(ctx, &ctx->m_P, (size_t)N * 3))) return rc;
-        if (ctx->m_dist2) { (void)hipFree(ctx->m_dist2); ctx->m_dist2 = nullptr; }
-        if (ctx->m_tu) { (void)hipFree(ctx->m_tu); ctx->m_tu = nullptr; }
-        if (ctx->m_tv) { (void)hipFree(ctx->m_tv); ctx->m_tv = nullptr; }
-        if (ctx->m_nrm) { (void)hipFree(ctx->m_nrm); ctx->m_nrm = nullptr; }
-        if (ctx->m_out) { (void)hipFree(ctx->m_out); ctx->m_out = nullptr; }
-        if (ctx->m_fall) { (void)hipFree(ctx->m_fall); ctx->m_fall = nullptr; }
+        if ((rc = dev_alloc(ctx, ctx->m_P, (size_t)N * 3))) return rc;
+        for (DevBuf<float> *b : {&ctx->m_dist2, &ctx->m_tu, &ctx->m_tv, &ctx->m_nrm, &ctx->m_out, &ctx->m_fall}) b->reset();
         ctx->mesh_cap = N;
     }
-    if (dist2 && !ctx->m_dist2 && (rc = dev_alloc(ctx, &ctx->m_dist2, (size_t)ctx->mesh_cap))) return rc;
+    if (dist2 && !ctx->m_dist2 && (rc = dev_alloc(ctx, ctx->m_dist2, (size_t)ctx->mesh_cap))) return rc;
     if (tu && !ctx->m_tu) {
-        if ((rc = dev_alloc(ctx, &ctx->m_tu, (size_t)ctx->mesh_cap * 3))) return rc;
-        if ((rc = dev_alloc(ctx, &ctx->m_tv, (size_t)ctx->mesh_cap * 3))) return rc;
-        if ((rc = dev_alloc(ctx, &ctx->m_nrm, (size_t)ctx->mesh_cap * 3))) return rc;
+        if ((rc = dev_alloc(ctx, ctx->m_tu, (size_t)ctx->mesh_cap * 3))) return rc;
+        if ((rc = dev_alloc(ctx, ctx->m_tv, (size_t)ctx->mesh_cap * 3))) return rc;
+        if ((rc = dev_alloc(ctx, ctx->m_nrm, (size_t)ctx->mesh_cap * 3))) return rc;
     }
     hipStream_t s = cur_stream(ctx);
     const size_t b3 = sizeof(float) * 3 * (size_t)N, b1 = sizeof(float) * (size_t)N;
@@ -1799,8 +1746,8 @@ int fd_deform_mesh(fd_ctx *ctx, float *P_out, float *falloff_out, float radius2,
         }
         (void)hipGetLastError();
     }
-    if (!ctx->m_out && (rc = dev_alloc(ctx, &ctx->m_out, (size_t)ctx->mesh_cap * 3))) return rc;
-    if (falloff_out && !ctx->m_fall && (rc = dev_alloc(ctx, &ctx->m_fall, (size_t)ctx->mesh_cap))) return rc;
+    if (!ctx->m_out && (rc = dev_alloc(ctx, ctx->m_out, (size_t)ctx->mesh_cap * 3))) return rc;
+    if (falloff_out && !ctx->m_fall && (rc = dev_alloc(ctx, ctx->m_fall, (size_t)ctx->mesh_cap))) return rc;
     const size_t b3 = sizeof(float) * 3 * (size_t)N, b1 = sizeof(float) * (size_t)N;
     // a gated vertex keeps the caller's fd_falloff entry (see fd_deform)
     if (falloff_out && (d2 || radius2 < 0.f)) FD_HIP(ctx, hipMemcpyAsync(ctx->m_fall, falloff_out, b1, hipMemcpyHostToDevice, s));
@@ -1828,17 +1775,17 @@ int fd_mesh_capture(fd_ctx *ctx, const int64_t *offsets, const int *neighbours, 
     if (offsets[0] != 0 || E < 0 || (E > 0 && !neighbours)) { set_err(ctx, "fd_mesh_capture: bad adjacency"); return FD_E_INVALID; }
     int rc = use_device(ctx);
     if (rc) return rc;
-    if (!ctx->m_dist2 && (rc = dev_alloc(ctx, &ctx->m_dist2, (size_t)ctx->mesh_cap))) return rc;
+    if (!ctx->m_dist2 && (rc = dev_alloc(ctx, ctx->m_dist2, (size_t)ctx->mesh_cap))) return rc;
     hipStream_t s = cur_stream(ctx);
-    float *d_rig = nullptr, *d_tri = nullptr;
-    int64_t *d_off = nullptr;
-    int *d_nb = nullptr;
-    unsigned char *d_mask = nullptr;
-    hipError_t e = hipMalloc((void **)&d_off, sizeof(int64_t) * (size_t)(N + 1));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_nb, sizeof(int) * (size_t)(E > 0 ? E : 1));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_mask, (size_t)N);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_rig, sizeof(float) * 3 * (size_t)(M > 0 ? M : 1));
-    if (e == hipSuccess) e = hipMalloc((void **)&d_tri, sizeof(float) * 9 * (size_t)(T > 0 ? T : 1));
+    DevBuf<float> d_rig, d_tri;              // released on the way out
+    DevBuf<int64_t> d_off;
+    DevBuf<int> d_nb;
+    DevBuf<unsigned char> d_mask;
+    hipError_t e = d_off.alloc((size_t)(N + 1));
+    if (e == hipSuccess) e = d_nb.alloc((size_t)(E > 0 ? E : 1));
+    if (e == hipSuccess) e = d_mask.alloc((size_t)N);
+    if (e == hipSuccess) e = d_rig.alloc(3 * (size_t)(M > 0 ? M : 1));
+    if (e == hipSuccess) e = d_tri.alloc(9 * (size_t)(T > 0 ? T : 1));
     if (e == hipSuccess) e = hipMemcpyAsync(d_off, offsets, sizeof(int64_t) * (size_t)(N + 1), hipMemcpyHostToDevice, s);
     if (e == hipSuccess && E > 0) e = hipMemcpyAsync(d_nb, neighbours, sizeof(int) * (size_t)E, hipMemcpyHostToDevice, s);
     if (e == hipSuccess && M > 0) e = hipMemcpyAsync(d_rig, rig_xyz, sizeof(float) * 3 * (size_t)M, hipMemcpyHostToDevice, s);
@@ -1847,7 +1794,6 @@ int fd_mesh_capture(fd_ctx *ctx, const int64_t *offsets, const int *neighbours, 
     if (e == hipSuccess) e = launch_capture_dist2(ctx->m_P, N, d_mask, d_tri, T, radius2, dofalloff, ctx->m_dist2, s);
     if (e == hipSuccess && dist2_out) e = hipMemcpyAsync(dist2_out, ctx->m_dist2, sizeof(float) * (size_t)N, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    for (void *p : {(void *)d_off, (void *)d_nb, (void *)d_mask, (void *)d_rig, (void *)d_tri}) if (p) (void)hipFree(p);
     if (e != hipSuccess) { (void)hipGetLastError(); set_err(ctx, "fd_mesh_capture failed: %s", hipGetErrorString(e)); return FD_E_DEVICE; }
     ctx->mesh_has_dist2 = true;
     return FD_OK;
@@ -2014,11 +1960,11 @@ fd_batch *fd_batch_create(fd_ctx *const *ctxs, int n)
     b->device = ctxs[0]->device;
     for (int i = 0; i < n; ++i) b->ctxs[i] = ctxs[i];
     bool ok = hipSetDevice(b->device) == hipSuccess;
-    ok = ok && hipMalloc((void **)&b->d_slots, sizeof(BatchSlot) * (size_t)n) == hipSuccess;
-    ok = ok && hipEventCreate(&b->ev0) == hipSuccess && hipEventCreate(&b->ev_mid) == hipSuccess &&
-         hipEventCreate(&b->ev1) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&b->status_ev, hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipHostMalloc((void **)&b->h_mismatch, sizeof(int), hipHostMallocMapped) == hipSuccess;
+    ok = ok && b->d_slots.alloc((size_t)n) == hipSuccess;
+    ok = ok && b->ev0.create(hipEventDefault) == hipSuccess && b->ev_mid.create(hipEventDefault) == hipSuccess &&
+         b->ev1.create(hipEventDefault) == hipSuccess;
+    ok = ok && b->status_ev.create(hipEventDisableTiming) == hipSuccess;
+    ok = ok && b->h_mismatch.alloc(1, hipHostMallocMapped) == hipSuccess;
     if (ok) *b->h_mismatch = 0;
     if (!ok) {
         set_err(nullptr, "fd_batch_create: device resource allocation failed: %s", hipGetErrorString(hipGetLastError()));
@@ -2026,13 +1972,6 @@ fd_batch *fd_batch_create(fd_ctx *const *ctxs, int n)
         return nullptr;
     }
     return b;
-}
-
-static void shot_free(ShotScratch &sc)
-{
-    if (sc.d) (void)hipFree(sc.d);
-    if (sc.consumed_ev) (void)hipEventDestroy(sc.consumed_ev);
-    if (sc.eval_ev) (void)hipEventDestroy(sc.eval_ev);
 }
 
 void fd_batch_destroy(fd_batch *b)
@@ -2048,26 +1987,7 @@ void fd_batch_destroy(fd_batch *b)
         if (c && c->tev0 == b->ev0) { c->tev0 = c->ev0; c->tev_mid = c->ev_mid; c->tev1 = c->ev1; }
         if (c && (c->status_poll == b->status_ev || c->status_poll == b->ev1)) { c->status_poll = c->status_ev; c->status_inflight = false; }
     }
-    if (b->status_ev) (void)hipEventDestroy(b->status_ev);
-    if (b->exec) (void)hipGraphExecDestroy(b->exec);
-    if (b->d_slots) (void)hipFree(b->d_slots);
-    for (auto &st : b->sets) {
-        if (st.d_wtiles) (void)hipFree(st.d_wtiles);
-        if (st.d_frames) (void)hipFree(st.d_frames);
-        if (st.packed_ev) (void)hipEventDestroy(st.packed_ev);
-        if (st.eval_ev) (void)hipEventDestroy(st.eval_ev);
-    }
-    if (b->d_fac) (void)hipFree(b->d_fac);
-    if (b->d_mlfac) (void)hipFree(b->d_mlfac);
-    if (b->d_qnnfac) (void)hipFree(b->d_qnnfac);
-    if (b->fallback_ev) (void)hipEventDestroy(b->fallback_ev);
-    for (ShotScratch *sc : {&b->s64, &b->sml, &b->sml64}) shot_free(*sc);
-    if (b->group_ev) (void)hipEventDestroy(b->group_ev);
-    if (b->h_mismatch) (void)hipHostFree(b->h_mismatch);
-    if (b->ev0) (void)hipEventDestroy(b->ev0);
-    if (b->ev_mid) (void)hipEventDestroy(b->ev_mid);
-    if (b->ev1) (void)hipEventDestroy(b->ev1);
-    delete b;
+    delete b;                   // the members release what they own
 }
 
 const char *fd_batch_last_error(const fd_batch *b) { return b ? b->err : g_err; }
@@ -2168,12 +2088,8 @@ int fd_batch_build_async(fd_batch *b, void *hip_stream)
     // one context, more than 1024 points, no scratch -- builds every model on its own as ever.
     bool shared_ml = b->shared_factor != 0 && bb.ml_layers > 0 && same_rest_launch && ml_shared_applies(bb.M, bb.ml_layers, b->n);
     if (shared_ml && ml_shared_init() != hipSuccess) { (void)hipGetLastError(); shared_ml = false; }
-    if (shared_ml && ml_shared_scratch_bytes(bb) > b->cap_mlfac) {
-        if (b->d_mlfac) (void)hipFree(b->d_mlfac);          // (hipFree drains the device: nobody reads the old scratch)
-        b->d_mlfac = nullptr; b->cap_mlfac = 0;
-        if (hipMalloc(&b->d_mlfac, ml_shared_scratch_bytes(bb)) != hipSuccess) { (void)hipGetLastError(); b->d_mlfac = nullptr; shared_ml = false; }
-        else b->cap_mlfac = ml_shared_scratch_bytes(bb);
-    }
+    // (a scratch that grows: hipFree drains the device, nobody reads the old one)
+    if (shared_ml && b->d_mlfac.grow(ml_shared_scratch_bytes(bb)) != hipSuccess) { (void)hipGetLastError(); shared_ml = false; }
     // A shot of QNN models (fd_batch_set_shared_lu): radii per frame, then reflectors, kernel block and its LU without pivot
     // search once for the group, every frame's right-hand sides through that factor in one launch (launch_build_qnn_shared).
     // Anything it does not take -- other rest arrays, too few contexts, a context that fell back to the pivoted LU, fewer points
@@ -2182,11 +2098,9 @@ int fd_batch_build_async(fd_batch *b, void *hip_stream)
                       bb.npad <= 1024 && bb.M >= bb.T && same_rest_launch && qnn_shared_applies(bb.M, b->n);
     for (int i = 0; i < b->n && shared_qnn; ++i) shared_qnn = b->ctxs[i]->solver == FD_SOLVER_AUTO;
     if (shared_qnn && qnn_shared_init() != hipSuccess) { (void)hipGetLastError(); shared_qnn = false; }
-    if (shared_qnn && qnn_shared_scratch_bytes(bb) > b->cap_qnnfac) {
-        if (b->d_qnnfac) (void)hipFree(b->d_qnnfac);        // (hipFree drains the device: nobody reads the old scratch)
-        b->d_qnnfac = nullptr; b->cap_qnnfac = 0; b->qnn_slot_ready = false;
-        if (hipMalloc(&b->d_qnnfac, qnn_shared_scratch_bytes(bb)) != hipSuccess) { (void)hipGetLastError(); b->d_qnnfac = nullptr; shared_qnn = false; }
-        else b->cap_qnnfac = qnn_shared_scratch_bytes(bb);
+    if (shared_qnn && qnn_shared_scratch_bytes(bb) > b->d_qnnfac.cap) {
+        b->qnn_slot_ready = false;                          // (the slot goes with the old scratch; hipFree drains the device)
+        if (b->d_qnnfac.grow(qnn_shared_scratch_bytes(bb)) != hipSuccess) { (void)hipGetLastError(); shared_qnn = false; }
     }
 
     const GraphKey key = graph_key(c0, (bb.spd << 9) | (bb.small << 10) | (bb.reg << 11) | (bb.nopivot << 12), false);
@@ -2203,8 +2117,8 @@ int fd_batch_build_async(fd_batch *b, void *hip_stream)
     // every model on its own as ever.
     const bool shared_fac_ok = same_rest_launch;
     bool shared_fac = b->shared_factor != 0 && bb.reg && shared_fac_ok && b->n > 1;
-    if (shared_fac && !b->d_fac && hipMalloc((void **)&b->d_fac, sizeof(double) * reg_factor_doubles()) != hipSuccess) {
-        (void)hipGetLastError(); b->d_fac = nullptr; shared_fac = false;
+    if (shared_fac && !b->d_fac && b->d_fac.alloc(reg_factor_doubles()) != hipSuccess) {
+        (void)hipGetLastError(); shared_fac = false;
     }
     b->last_shared_factor = (shared_fac || shared_ml || shared_qnn) ? 1 : 0;
     if (!b->lean) FD_BHIP(hipEventRecord(b->ev0, stream));      // (lean: the group's first packet is its first kernel; the reports carry no phase times)
@@ -2307,12 +2221,12 @@ int fd_solve_operator(fd_ctx *ctx, double *S)
     const int builds = (M + 2) / 3;
     const int nh = builds < kMaxBatch ? builds : kMaxBatch;
     fd_ctx *helpers[kMaxBatch] = {};
-    float *d_unit = nullptr;
+    DevBuf<float> d_unit;
     fd_batch *batch = nullptr;
     auto done = [&](int code) {
         if (batch) fd_batch_destroy(batch);
         for (fd_ctx *h : helpers) if (h) fd_destroy(h);
-        if (d_unit) (void)hipFree(d_unit);
+        d_unit.reset();
         return code;
     };
     fd_config cfg{};
@@ -2329,7 +2243,7 @@ int fd_solve_operator(fd_ctx *ctx, double *S)
         h->stream_ = cur_stream(ctx);       // one stream for all: no hardware queue per helper
     }
     const size_t per = (size_t)M * 3;
-    if (hipMalloc((void **)&d_unit, sizeof(float) * per * (size_t)nh) != hipSuccess) {
+    if (d_unit.alloc(per * (size_t)nh) != hipSuccess) {
         (void)hipGetLastError();
         set_err(ctx, "fd_solve_operator: hipMalloc(%zu bytes) failed", sizeof(float) * per * (size_t)nh);
         return done(FD_E_NOMEM);
@@ -2430,7 +2344,7 @@ static int fit_frames(fd_ctx *ctx, const char *who, bool shot, const Mesh &m, in
     auto t0 = std::chrono::steady_clock::now();
     std::vector<double> H((size_t)sys.nq * n * n);
     Mesh d;
-    if ((rc = stage_mesh(ctx, m, cur_stream(ctx), &d, Upload{&ctx->d_fall, omega, 1}))) return rc;
+    if ((rc = stage_mesh(ctx, m, cur_stream(ctx), &d, Upload{&ctx->d_fall.p, omega, 1}))) return rc;
     if ((rc = gram_staged(ctx, who, d, omega ? ctx->d_fall : nullptr, H.data()))) return rc;
     const double ms_gram = fit_ms_since(t0);
     // ---- the first-order terms: the adjoint of g_f = omega (T_f - P)
@@ -2574,13 +2488,6 @@ static int shared_applies(fd_batch *b, const char *who, float *const *d_P_out, i
     return fast ? 1 : 0;
 }
 
-static bool make_event(hipEvent_t *ev)
-{
-    if (*ev) return true;
-    if (hipEventCreateWithFlags(ev, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); *ev = nullptr; return false; }
-    return true;
-}
-
 // ---- what the eight shot calls share on the host: argument checks, the ShotScratch protocol, the per-context vector launches
 // (fill_mesh and fill_vector_tables, being templates, are in front of this linkage block) ----
 static int shot_check_mesh(fd_batch *b, const char *who, int64_t N, const float *d_P_in, const float *d_tu, const float *d_tv,
@@ -2653,41 +2560,52 @@ static int shot_begin(fd_batch *b, const char *who, ShotScratch &sc, hipStream_t
     if (!b->lean && (rc = batch_poll(b))) return rc;           // before the ordering: a repaired model's rebuild is ordered with the rest
     for (int i = 0; i < b->n; ++i)
         if ((rc = order_after_batch(b->ctxs[i], stream))) { batch_err(b, "context %d: %s", i, b->ctxs[i]->err); return rc; }
-    if (!make_event(&sc.consumed_ev)) { batch_err(b, "%s: hipEventCreate failed", who); return FD_E_DEVICE; }
+    if (!sc.consumed_ev.make()) { batch_err(b, "%s: hipEventCreate failed", who); return FD_E_DEVICE; }
     return FD_OK;
+}
+
+// Before the pack kernel about to be enqueued on `stream` rewrites a scratch: the evaluation that last read it (`done` is recorded
+// behind it while *pending) must be through with it
+static int wait_last_eval(fd_batch *b, const char *who, hipStream_t stream, bool *pending, hipEvent_t done)
+{
+    if (*pending && done && hipStreamWaitEvent(stream, done, 0) != hipSuccess) {
+        batch_err(b, "%s: hipStreamWaitEvent failed: %s", who, hipGetErrorString(hipGetLastError()));
+        return FD_E_DEVICE;
+    }
+    *pending = false;
+    return FD_OK;
+}
+
+// Behind an evaluation on `stream` that read a scratch: `ev` recorded there, for wait_last_eval.  False: there is no event to order
+// the next pack kernel by, and the stream has been waited for instead
+static bool record_eval(Event &ev, hipStream_t stream)
+{
+    if (ev.make() && hipEventRecord(ev, stream) == hipSuccess) return true;
+    (void)hipGetLastError();
+    (void)hipStreamSynchronize(stream);
+    return false;
 }
 
 // `bytes` of scratch for the pack kernel about to be enqueued on `stream`
 static int shot_reserve(fd_batch *b, const char *who, ShotScratch &sc, size_t bytes, hipStream_t stream)
 {
-    if (bytes > sc.cap) {
+    if (bytes > sc.d.cap) {
         // (hipFree drains the device: no launch still reads the old scratch)
-        if (sc.d) (void)hipFree(sc.d);
-        sc.d = nullptr; sc.cap = 0; sc.eval_pending = false;
-        if (hipMalloc(&sc.d, bytes) != hipSuccess) {
+        sc.eval_pending = false;
+        if (sc.d.grow(bytes) != hipSuccess) {
             (void)hipGetLastError();
             batch_err(b, "%s: scratch allocation (%zu bytes) failed", who, bytes);
             return FD_E_NOMEM;
         }
-        sc.cap = bytes;
     }
-    // the evaluation that last read the scratch must be through with it
-    if (sc.eval_pending && hipStreamWaitEvent(stream, sc.eval_ev, 0) != hipSuccess) {
-        batch_err(b, "%s: hipStreamWaitEvent failed: %s", who, hipGetErrorString(hipGetLastError()));
-        return FD_E_DEVICE;
-    }
-    sc.eval_pending = false;
-    return FD_OK;
+    return wait_last_eval(b, who, stream, &sc.eval_pending, sc.eval_ev);
 }
 
 // behind the position launch (pack kernel and evaluation; the launch itself records sc.consumed_ev behind the pack kernel)
 static void shot_evaluated(ShotScratch &sc, hipStream_t stream)
 {
     sc.consumed = true;
-    if (make_event(&sc.eval_ev) && hipEventRecord(sc.eval_ev, stream) == hipSuccess) { sc.eval_pending = true; return; }
-    // no event to order the next pack kernel by: be safe
-    (void)hipGetLastError();
-    (void)hipStreamSynchronize(stream);
+    sc.eval_pending = record_eval(sc.eval_ev, stream);
 }
 
 // behind the vector launch on the same scratch
@@ -2751,26 +2669,18 @@ static int shared_pack(fd_batch *b, hipStream_t stream, int ek, float *const *d_
     if (one_build(b)) for (int i = 1; i < b->n; ++i) a.centres[i] = a.centres[0];
     const SharedPlan pl = shared_plan(a.Mpad, a.nF, a.kind);
     const size_t wb = pl.wtile_bytes, fb = pl.frame_bytes;
-    if (wb > st.cap_wtiles || fb > st.cap_frames) {
-        // (hipFree drains the device: no launch still reads the old scratch)
-        if (st.d_wtiles) (void)hipFree(st.d_wtiles);
-        if (st.d_frames) (void)hipFree(st.d_frames);
-        st.d_wtiles = st.d_frames = nullptr; st.cap_wtiles = st.cap_frames = 0; st.eval_pending = false;
-        if (hipMalloc(&st.d_wtiles, wb) != hipSuccess || hipMalloc(&st.d_frames, fb) != hipSuccess) {
+    if (wb > st.d_wtiles.cap || fb > st.d_frames.cap) {
+        // the two go together (hipFree drains the device: no launch still reads the old scratch)
+        st.d_wtiles.reset(); st.d_frames.reset(); st.eval_pending = false;
+        if (st.d_wtiles.grow(wb) != hipSuccess || st.d_frames.grow(fb) != hipSuccess) {
             (void)hipGetLastError();
             batch_err(b, "shared-rig evaluation: scratch allocation (%zu bytes) failed", wb + fb);
             return FD_E_NOMEM;
         }
-        st.cap_wtiles = wb; st.cap_frames = fb;
     }
-    // the evaluation that last read this set must be through with it
-    if (st.eval_pending && st.eval_done && hipStreamWaitEvent(stream, st.eval_done, 0) != hipSuccess) {
-        batch_err(b, "shared-rig evaluation: hipStreamWaitEvent failed: %s", hipGetErrorString(hipGetLastError()));
-        return FD_E_DEVICE;
-    }
-    st.eval_pending = false;
+    if ((rc = wait_last_eval(b, "shared-rig evaluation", stream, &st.eval_pending, st.eval_done))) return rc;
     a.wtiles = st.d_wtiles; a.frames = st.d_frames;
-    a.packed_ev = b->lean ? nullptr : (make_event(&st.packed_ev) ? st.packed_ev : nullptr);
+    a.packed_ev = b->lean ? nullptr : (st.packed_ev.make() ? st.packed_ev : nullptr);
     b->consumed_override = nullptr;
     a.mode = 1;
     a.M = c0->M;
@@ -2824,7 +2734,7 @@ int fd_batch_deform_shared_dev(fd_batch *b, void *hip_stream, int64_t N, const f
         rc = fd_batch_deform_dev(b, hip_stream, N, pin, d_P_out, d_dist2 ? pd2 : nullptr, d_falloff_out, d_tu ? ptu : nullptr,
                                  d_tu ? ptv : nullptr, d_tu ? pnr : nullptr, radius2, falloffrate);
         // these launches read the models to their end: fd_batch_wait_consumed waits for all of them
-        if (rc == FD_OK && make_event(&b->fallback_ev)) {
+        if (rc == FD_OK && b->fallback_ev.make()) {
             if (hipEventRecord(b->fallback_ev, stream) != hipSuccess) { (void)hipGetLastError(); rc = FD_E_DEVICE; }
             b->packed_valid = false;
             b->consumed_override = nullptr;
@@ -2873,13 +2783,9 @@ int fd_batch_deform_shared_dev(fd_batch *b, void *hip_stream, int64_t N, const f
         //  a build that was itself ordered behind this evaluation by fd_batch_wait_consumed: waiting for it still implies this.)
         st.eval_done = b->ev1;
         st.eval_pending = true;
-    } else if (make_event(&st.eval_ev)) {
-        st.eval_done = st.eval_ev;
-        if (hipEventRecord(st.eval_ev, stream) != hipSuccess) { (void)hipGetLastError(); st.eval_pending = false; }
-        else st.eval_pending = true;
     } else {
-        // no event to order the next pack of this set by: be safe
-        (void)hipStreamSynchronize(stream);
+        st.eval_pending = record_eval(st.eval_ev, stream);
+        st.eval_done = st.eval_ev;
     }
     return FD_OK;
 }
@@ -2916,7 +2822,7 @@ int fd_batch_deform_vectors_shared_dev(fd_batch *b, void *hip_stream, int64_t N,
             if (rc) { batch_err(b, "context %d: %s", i, c->err); return rc; }
         }
         // these launches read the models to their end: fd_batch_wait_consumed waits for all of them
-        if (make_event(&b->fallback_ev)) {
+        if (b->fallback_ev.make()) {
             if (hipEventRecord(b->fallback_ev, stream) != hipSuccess) { (void)hipGetLastError(); return FD_E_DEVICE; }
             b->packed_valid = false;
             b->consumed_override = nullptr;
@@ -3348,7 +3254,7 @@ int fd_batch_cook_group(fd_batch *b, void *build_stream, void *eval_stream, cons
     if (es != bs) {
         // (the evaluation waits for the pack kernel's event inside fd_batch_deform_shared_dev when the set was prepared; the
         // per-frame fallback -- other kernels -- needs the builds themselves)
-        if (!make_event(&b->group_ev) || hipEventRecord(b->group_ev, bs) != hipSuccess || hipStreamWaitEvent(es, b->group_ev, 0) != hipSuccess) {
+        if (!b->group_ev.make() || hipEventRecord(b->group_ev, bs) != hipSuccess || hipStreamWaitEvent(es, b->group_ev, 0) != hipSuccess) {
             batch_err(b, "fd_batch_cook_group: ordering the evaluation stream failed: %s", hipGetErrorString(hipGetLastError()));
             return FD_E_DEVICE;
         }
@@ -3404,17 +3310,14 @@ const char *fd_shared_kernel_name(int M, int frames, int kind)
 
 struct fd_shot_dev {
     fd_ctx *engine = nullptr;
-    hipStream_t work = nullptr, copy = nullptr;
-    float *d_rig = nullptr;             // rest (M x 3), then F x M x 3 deltas
-    size_t cap_rig = 0;
+    Stream work, copy;                  // in front of what is enqueued on them: they outlive it
+    DevBuf<float> d_rig;                // rest (M x 3), then F x M x 3 deltas
     int M = 0, F = 0;
-    float *d_vecs = nullptr;            // the mesh's N, tu, tv as uploaded by fd_shot_dev_set_vectors (a slice each)
-    int64_t cap_vecs = 0;
+    DevBuf<float> d_vecs;               // the mesh's N, tu, tv as uploaded by fd_shot_dev_set_vectors (a slice each), cap / 9 vertices each
     const float *v_in[3] = {nullptr, nullptr, nullptr};   // N, tu, tv inputs, or null
     struct Set {
-        float *d = nullptr;
-        size_t bytes = 0;
-        hipEvent_t eval_ev = nullptr, delivered_ev = nullptr;
+        DevBuf<float> d;
+        Event eval_ev, delivered_ev;
         bool delivering = false;
     } sets[2];
     int set_frames = 0;                 // what the two sets were laid out for
@@ -3432,14 +3335,18 @@ static void shot_err(fd_shot_dev *sd, const char *fmt, ...)
     va_end(ap);
 }
 
+// a runtime call that failed, as the shot calls report it
+static int shot_failed(fd_shot_dev *sd, const char *call, hipError_t e)
+{
+    (void)hipGetLastError();
+    shot_err(sd, "%s failed: %s", call, hipGetErrorString(e));
+    return e == hipErrorOutOfMemory ? FD_E_NOMEM : FD_E_DEVICE;
+}
+
 #define FD_SHIP(sd, call)                                                                          \
     do {                                                                                           \
         hipError_t e_ = (call);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            (void)hipGetLastError();                                                               \
-            shot_err(sd, "%s failed: %s", #call, hipGetErrorString(e_));                          \
-            return e_ == hipErrorOutOfMemory ? FD_E_NOMEM : FD_E_DEVICE;                           \
-        }                                                                                          \
+        if (e_ != hipSuccess) return shot_failed(sd, #call, e_);                                   \
     } while (0)
 
 // slices of a staging set: positions of every frame, then the fall-off of every frame, then the vectors
@@ -3462,11 +3369,9 @@ fd_shot_dev *fd_shot_dev_create(fd_ctx *engine)
     fd_shot_dev *sd = new (std::nothrow) fd_shot_dev();
     if (!sd) return nullptr;
     sd->engine = engine;
-    bool ok = hipStreamCreateWithFlags(&sd->work, hipStreamNonBlocking) == hipSuccess &&
-              hipStreamCreateWithFlags(&sd->copy, hipStreamNonBlocking) == hipSuccess;
+    bool ok = sd->work.create() == hipSuccess && sd->copy.create() == hipSuccess;
     for (auto &st : sd->sets)
-        ok = ok && hipEventCreateWithFlags(&st.eval_ev, hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&st.delivered_ev, hipEventDisableTiming) == hipSuccess;
+        ok = ok && st.eval_ev.create(hipEventDisableTiming) == hipSuccess && st.delivered_ev.create(hipEventDisableTiming) == hipSuccess;
     if (!ok) {
         set_err(nullptr, "fd_shot_dev_create: device resource allocation failed: %s", hipGetErrorString(hipGetLastError()));
         fd_shot_dev_destroy(sd);
@@ -3481,16 +3386,7 @@ void fd_shot_dev_destroy(fd_shot_dev *sd)
     (void)hipSetDevice(sd->engine->device);
     if (sd->work) { (void)hipStreamSynchronize(sd->work); }
     if (sd->copy) { (void)hipStreamSynchronize(sd->copy); }
-    for (auto &st : sd->sets) {
-        if (st.d) (void)hipFree(st.d);
-        if (st.eval_ev) (void)hipEventDestroy(st.eval_ev);
-        if (st.delivered_ev) (void)hipEventDestroy(st.delivered_ev);
-    }
-    if (sd->d_rig) (void)hipFree(sd->d_rig);
-    if (sd->d_vecs) (void)hipFree(sd->d_vecs);
-    if (sd->work) (void)hipStreamDestroy(sd->work);
-    if (sd->copy) (void)hipStreamDestroy(sd->copy);
-    delete sd;
+    delete sd;                  // the members release what they own, the two streams last
 }
 
 const char *fd_shot_dev_error(const fd_shot_dev *sd) { return sd ? sd->err : g_err; }
@@ -3502,12 +3398,11 @@ int fd_shot_dev_set_rig(fd_shot_dev *sd, const float *rest, const float *deltas,
     int rc = use_device(sd->engine);
     if (rc) { shot_err(sd, "%s", sd->engine->err); return rc; }
     const size_t floats = (size_t)(F + 1) * (size_t)M * 3;
-    if (floats > sd->cap_rig) {
+    if (floats > sd->d_rig.cap) {
         // (the batches read the old block in place: nothing of them may still be in flight)
         FD_SHIP(sd, hipStreamSynchronize(sd->work));
-        if (sd->d_rig) { (void)hipFree(sd->d_rig); sd->d_rig = nullptr; sd->cap_rig = 0; }
-        FD_SHIP(sd, hipMalloc((void **)&sd->d_rig, sizeof(float) * floats));
-        sd->cap_rig = floats;
+        const hipError_t e = sd->d_rig.grow(floats);
+        if (e != hipSuccess) return shot_failed(sd, "hipMalloc((void **)&sd->d_rig, sizeof(float) * floats)", e);
     }
     sd->M = M; sd->F = F;
     const size_t rb = sizeof(float) * 3 * (size_t)M;
@@ -3533,16 +3428,15 @@ int fd_shot_dev_set_vectors(fd_shot_dev *sd, const float *N, const float *tu, co
     int rc = use_device(sd->engine);
     if (rc) { shot_err(sd, "%s", sd->engine->err); return rc; }
     const int64_t Np = shot_pad(n);
-    if (Np > sd->cap_vecs) {
+    if (9 * (size_t)Np > sd->d_vecs.cap) {
         FD_SHIP(sd, hipStreamSynchronize(sd->work));
-        if (sd->d_vecs) { (void)hipFree(sd->d_vecs); sd->d_vecs = nullptr; sd->cap_vecs = 0; }
-        FD_SHIP(sd, hipMalloc((void **)&sd->d_vecs, sizeof(float) * 9 * (size_t)Np));
-        sd->cap_vecs = Np;
+        const hipError_t e = sd->d_vecs.grow(9 * (size_t)Np);
+        if (e != hipSuccess) return shot_failed(sd, "hipMalloc((void **)&sd->d_vecs, sizeof(float) * 9 * (size_t)Np)", e);
     }
     const float *src[3] = {N, tu, tv};
     for (int i = 0; i < 3; ++i) {
         if (!src[i]) continue;
-        float *dst = sd->d_vecs + (size_t)i * 3 * (size_t)sd->cap_vecs;
+        float *dst = sd->d_vecs + (size_t)i * (sd->d_vecs.cap / 3);
         FD_SHIP(sd, hipMemcpyAsync(dst, src[i], sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, sd->work));
         sd->v_in[i] = dst;
     }
@@ -3563,19 +3457,18 @@ int fd_shot_dev_reserve(fd_shot_dev *sd, int frames, int want_falloff)
     // another layout: the old sets go (nothing reads them once both streams have drained)
     (void)hipStreamSynchronize(sd->work);
     (void)hipStreamSynchronize(sd->copy);
-    for (auto &st : sd->sets) { if (st.d) (void)hipFree(st.d); st.d = nullptr; st.bytes = 0; st.delivering = false; }
+    for (auto &st : sd->sets) { st.d.reset(); st.delivering = false; }
     sd->set_frames = 0;
     for (int f = frames; f >= 1; f = f / 2) {
-        const size_t bytes = sizeof(float) * (size_t)f * (size_t)Np * (size_t)(3 + (fall ? 1 : 0) + 3 * nvec);
+        const size_t floats = (size_t)f * (size_t)Np * (size_t)(3 + (fall ? 1 : 0) + 3 * nvec);
         bool ok = true;
-        for (auto &st : sd->sets) ok = ok && hipMalloc((void **)&st.d, bytes) == hipSuccess;
+        for (auto &st : sd->sets) ok = ok && st.d.grow(floats) == hipSuccess;
         if (ok) {
-            for (auto &st : sd->sets) st.bytes = bytes;
             sd->set_frames = f; sd->set_Np = Np; sd->set_fall = fall; sd->set_nvec = nvec;
             return f;
         }
         (void)hipGetLastError();
-        for (auto &st : sd->sets) { if (st.d) (void)hipFree(st.d); st.d = nullptr; }
+        for (auto &st : sd->sets) st.d.reset();
     }
     shot_err(sd, "hipMalloc of the shot's staging sets failed: %s", hipGetErrorString(hipErrorOutOfMemory));
     return 0;

@@ -23,6 +23,7 @@
 #include <new>
 
 #include "facedeform_hip.h"
+#include "fd_owned.h"
 #include "fd_tuning.h"
 
 namespace {
@@ -829,29 +830,30 @@ thread_local char g_merr[512] = {0};
 
 }  // namespace
 
+using fd::DevBuf;
+using fd::Event;
+using fd::Stream;
+
 struct fd_morph {
     int device = 0;
     int64_t N = 0;
     int S = 0;
     bool initialised = false, computed = false;
-    hipStream_t stream = nullptr;
-    float *d_rest = nullptr, *d_S32 = nullptr, *d_stage = nullptr, *d_P = nullptr;
+    Stream stream;                // in front of what is enqueued on it: it outlives the buffers and events below
+    DevBuf<float> d_rest, d_S32, d_stage, d_P;
     // the `rest` point attribute the cook passes use (SOP_FaceDeform.cpp:178-184,445); NULL: the
     // init rest pose (they differ only when input 0 carries its own rest attribute)
-    float *d_rest_attr = nullptr;
+    DevBuf<float> d_rest_attr;
     bool use_rest_attr = false;
-    double *d_QR = nullptr, *d_tau = nullptr, *d_w = nullptr, *d_partial = nullptr, *d_hh = nullptr, *d_tmp = nullptr;
-    double *d_bpartial = nullptr, *d_bpartial2 = nullptr, *d_Y = nullptr;   // blocked factorisation
-    size_t cap_bpartial = 0;
+    DevBuf<double> d_QR, d_tau, d_w, d_partial, d_hh, d_tmp;
+    DevBuf<double> d_bpartial, d_bpartial2, d_Y;    // blocked factorisation
     size_t cap_entries = 0;       // 3N * S capacity of d_QR / d_S32
     int64_t cap_N = 0;
     int cap_S = 0;
-    size_t cap_partial = 0;
     // a group of frames (fd_morph_*_batch*): weights F x S and the row partitions' sums, apart from d_w / computed
-    double *d_bw = nullptr, *d_bwpartial = nullptr;
-    size_t cap_bw = 0, cap_bwpartial = 0;
+    DevBuf<double> d_bw, d_bwpartial;
     int batch_F = 0;              // frames of the last batched compute; 0: none since fd_morph_init
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    Event ev0, ev1;
     float last_init_ms = 0.f;
     char err[512] = {0};
 };
@@ -874,16 +876,14 @@ static void merr(fd_morph *m, const char *fmt, ...)
         }                                                                                    \
     } while (0)
 
+// DevBuf's alloc -- with kGrow its grow: a scratch that grows on demand and never shrinks -- and the handle's error text
+constexpr bool kGrow = true;
 template <typename T>
-static int mrealloc(fd_morph *m, T **p, size_t count)
+static int mrealloc(fd_morph *m, DevBuf<T> &b, size_t count, bool grow = false)
 {
-    if (*p) { (void)hipFree(*p); *p = nullptr; }
-    if (hipMalloc((void **)p, (count ? count : 1) * sizeof(T)) != hipSuccess) {
-        *p = nullptr;
-        merr(m, "hipMalloc(%zu bytes) failed: %s", count * sizeof(T), hipGetErrorString(hipGetLastError()));
-        return FD_E_NOMEM;
-    }
-    return FD_OK;
+    if ((grow ? b.grow(count) : b.alloc(count)) == hipSuccess) return FD_OK;
+    merr(m, "hipMalloc(%zu bytes) failed: %s", count * sizeof(T), hipGetErrorString(hipGetLastError()));
+    return FD_E_NOMEM;
 }
 
 // row length of the per-workgroup sums the block-reflector pass leaves: kNB per trailing column + V^T V
@@ -895,32 +895,26 @@ static int morph_reserve(fd_morph *m, int64_t N, int S)
     const size_t rows = 3 * (size_t)N;
     const size_t nwg = (rows + kWRows - 1) / kWRows;        // the finer of the two row partitions
     if (N > m->cap_N) {
-        if ((rc = mrealloc(m, &m->d_rest, rows)) || (rc = mrealloc(m, &m->d_stage, rows)) ||
-            (rc = mrealloc(m, &m->d_P, rows))) return rc;
-        if (m->d_rest_attr) { (void)hipFree(m->d_rest_attr); m->d_rest_attr = nullptr; }
+        if ((rc = mrealloc(m, m->d_rest, rows)) || (rc = mrealloc(m, m->d_stage, rows)) ||
+            (rc = mrealloc(m, m->d_P, rows))) return rc;
+        m->d_rest_attr.reset();
         m->cap_N = N;
     }
     if (rows * (size_t)S > m->cap_entries) {
-        if ((rc = mrealloc(m, &m->d_QR, rows * (size_t)S)) || (rc = mrealloc(m, &m->d_S32, rows * (size_t)S))) return rc;
+        if ((rc = mrealloc(m, m->d_QR, rows * (size_t)S)) || (rc = mrealloc(m, m->d_S32, rows * (size_t)S))) return rc;
         m->cap_entries = rows * (size_t)S;
     }
     if (S > m->cap_S) {
-        if ((rc = mrealloc(m, &m->d_tau, (size_t)S)) || (rc = mrealloc(m, &m->d_w, (size_t)S)) ||
-            (rc = mrealloc(m, &m->d_tmp, (size_t)S)) || (rc = mrealloc(m, &m->d_Y, (size_t)kNB * (size_t)S)) ||
-            (rc = mrealloc(m, &m->d_bpartial2, (size_t)kSlices * wy_ld(S)))) return rc;
+        if ((rc = mrealloc(m, m->d_tau, (size_t)S)) || (rc = mrealloc(m, m->d_w, (size_t)S)) ||
+            (rc = mrealloc(m, m->d_tmp, (size_t)S)) || (rc = mrealloc(m, m->d_Y, (size_t)kNB * (size_t)S)) ||
+            (rc = mrealloc(m, m->d_bpartial2, (size_t)kSlices * wy_ld(S)))) return rc;
         m->cap_S = S;
     }
     {   // blocked factorisation: per-workgroup sums of V^T C and V^T V, their slices, Y
         const size_t nwg_b = (rows + kBRows - 1) / kBRows, ld = wy_ld(S);
-        if (nwg_b * ld > m->cap_bpartial) {
-            if ((rc = mrealloc(m, &m->d_bpartial, nwg_b * ld))) return rc;
-            m->cap_bpartial = nwg_b * ld;
-        }
+        if ((rc = mrealloc(m, m->d_bpartial, nwg_b * ld, kGrow))) return rc;
     }
-    if (nwg * (size_t)(S ? S : 1) > m->cap_partial) {
-        if ((rc = mrealloc(m, &m->d_partial, nwg * (size_t)(S ? S : 1)))) return rc;
-        m->cap_partial = nwg * (size_t)(S ? S : 1);
-    }
+    if ((rc = mrealloc(m, m->d_partial, nwg * (size_t)(S ? S : 1), kGrow))) return rc;
     return FD_OK;
 }
 
@@ -933,22 +927,22 @@ static int morph_factor_blocked(fd_morph *m)
     double *A = m->d_QR;
     for (int k0 = 0; k0 < S; k0 += kNB) {
         const int nb = S - k0 < kNB ? S - k0 : kNB, pend = k0 + nb, ntrail = S - pend;
-        if (k0 == 0) hipLaunchKernelGGL(k_qr_gram, dim3(nwg), dim3(kT), 0, st, A, rows, 0, nb, m->d_bpartial);
+        if (k0 == 0) hipLaunchKernelGGL(k_qr_gram, dim3(nwg), dim3(kT), 0, st, A, rows, 0, nb, m->d_bpartial.p);
         for (int k = k0; k < pend; ++k) {
-            hipLaunchKernelGGL(k_qr_col_setup, dim3(1), dim3(kSetupT), 0, st, A, rows, k, pend - k, m->d_bpartial, (int)nwg, m->d_hh,
-                               m->d_tau, m->d_tmp);
-            hipLaunchKernelGGL(k_qr_panel_apply, dim3(nwg), dim3(kT), 0, st, A, rows, k, pend, m->d_hh, m->d_tmp, m->d_bpartial);
+            hipLaunchKernelGGL(k_qr_col_setup, dim3(1), dim3(kSetupT), 0, st, A, rows, k, pend - k, m->d_bpartial.p, (int)nwg, m->d_hh.p,
+                               m->d_tau.p, m->d_tmp.p);
+            hipLaunchKernelGGL(k_qr_panel_apply, dim3(nwg), dim3(kT), 0, st, A, rows, k, pend, m->d_hh.p, m->d_tmp.p, m->d_bpartial.p);
         }
         if (ntrail > 0) {
             const int ld = ntrail * kNB + 32, nvals = ntrail * kNB + kNB * (kNB - 1) / 2;
             hipLaunchKernelGGL(k_qr_wy_dots, dim3(nwg), dim3(kT), sizeof(double) * 4 * (size_t)ld, st, A, rows, k0, nb, S,
-                               m->d_bpartial, ld);
-            hipLaunchKernelGGL(k_qr_wy_reduce, dim3((nvals + 31) / 32, kSlices), dim3(kT), 0, st, m->d_bpartial, (int)nwg, ld,
-                               nvals, m->d_bpartial2);
-            hipLaunchKernelGGL(k_qr_wy_T, dim3(1), dim3(kT), sizeof(double) * ((size_t)ld + kNB * kNB), st, m->d_bpartial2, ld, k0,
-                               nb, ntrail, m->d_tau, m->d_Y);
+                               m->d_bpartial.p, ld);
+            hipLaunchKernelGGL(k_qr_wy_reduce, dim3((nvals + 31) / 32, kSlices), dim3(kT), 0, st, m->d_bpartial.p, (int)nwg, ld,
+                               nvals, m->d_bpartial2.p);
+            hipLaunchKernelGGL(k_qr_wy_T, dim3(1), dim3(kT), sizeof(double) * ((size_t)ld + kNB * kNB), st, m->d_bpartial2.p, ld, k0,
+                               nb, ntrail, m->d_tau.p, m->d_Y.p);
             hipLaunchKernelGGL(k_qr_wy_apply, dim3(nwg), dim3(kT), sizeof(double) * ((size_t)kNB * ntrail + 4 * kNB), st, A, rows,
-                               k0, nb, S, m->d_Y, ntrail < kNB ? ntrail : kNB, m->d_bpartial);
+                               k0, nb, S, m->d_Y.p, ntrail < kNB ? ntrail : kNB, m->d_bpartial.p);
         }
     }
     FDM_HIP(m, hipGetLastError());
@@ -966,19 +960,19 @@ static int morph_factor(fd_morph *m)
     hipStream_t st = m->stream;
     for (int k = 0; k < S; ++k) {
         double *x = m->d_QR + (size_t)k * rows;
-        hipLaunchKernelGGL(k_qr_tail_norm, dim3(nwg), dim3(kT), 0, st, x, rows, k, m->d_partial);
-        hipLaunchKernelGGL(k_qr_reflector, dim3(1), dim3(kT), 0, st, x, k, m->d_partial, (int)nwg, m->d_hh, m->d_tau);
+        hipLaunchKernelGGL(k_qr_tail_norm, dim3(nwg), dim3(kT), 0, st, x, rows, k, m->d_partial.p);
+        hipLaunchKernelGGL(k_qr_reflector, dim3(1), dim3(kT), 0, st, x, k, m->d_partial.p, (int)nwg, m->d_hh.p, m->d_tau.p);
         if (k + 1 < S) {
             const int nt = S - k - 1;
-            hipLaunchKernelGGL(k_qr_dots, dim3(nwg), dim3(kT), sizeof(double) * 4 * (size_t)nt, st, m->d_QR, rows, S, k,
-                               m->d_hh, m->d_partial, nt);
-            hipLaunchKernelGGL(k_qr_dots_reduce, dim3(nt), dim3(kT), 0, st, m->d_QR, rows, k, m->d_hh, m->d_partial,
-                               (int)nwg, nt, m->d_tmp);
-            hipLaunchKernelGGL(k_qr_apply, dim3(nwg), dim3(kT), 0, st, m->d_QR, rows, S, k, m->d_hh, m->d_tmp);
+            hipLaunchKernelGGL(k_qr_dots, dim3(nwg), dim3(kT), sizeof(double) * 4 * (size_t)nt, st, m->d_QR.p, rows, S, k,
+                               m->d_hh.p, m->d_partial.p, nt);
+            hipLaunchKernelGGL(k_qr_dots_reduce, dim3(nt), dim3(kT), 0, st, m->d_QR.p, rows, k, m->d_hh.p, m->d_partial.p,
+                               (int)nwg, nt, m->d_tmp.p);
+            hipLaunchKernelGGL(k_qr_apply, dim3(nwg), dim3(kT), 0, st, m->d_QR.p, rows, S, k, m->d_hh.p, m->d_tmp.p);
         } else {
             // last column: only its own tail is scaled
-            hipLaunchKernelGGL(k_qr_dots, dim3(nwg), dim3(kT), sizeof(double) * 4, st, m->d_QR, rows, S, k, m->d_hh,
-                               m->d_partial, 1);
+            hipLaunchKernelGGL(k_qr_dots, dim3(nwg), dim3(kT), sizeof(double) * 4, st, m->d_QR.p, rows, S, k, m->d_hh.p,
+                               m->d_partial.p, 1);
         }
     }
     FDM_HIP(m, hipGetLastError());
@@ -1012,9 +1006,9 @@ fd_morph *fd_morph_create(const fd_config *cfg)
         return nullptr;
     }
     m->device = dev;
-    bool ok = hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) == hipSuccess;
-    ok = ok && hipEventCreate(&m->ev0) == hipSuccess && hipEventCreate(&m->ev1) == hipSuccess;
-    ok = ok && hipMalloc((void **)&m->d_hh, 4 * sizeof(double)) == hipSuccess;
+    bool ok = m->stream.create() == hipSuccess;
+    ok = ok && m->ev0.create(hipEventDefault) == hipSuccess && m->ev1.create(hipEventDefault) == hipSuccess;
+    ok = ok && m->d_hh.alloc(4) == hipSuccess;
     if (!ok) {
         merr(nullptr, "fd_morph_create: device resource allocation failed: %s", hipGetErrorString(hipGetLastError()));
         fd_morph_destroy(m);
@@ -1028,13 +1022,7 @@ void fd_morph_destroy(fd_morph *m)
     if (!m) return;
     (void)hipSetDevice(m->device);
     if (m->stream) (void)hipStreamSynchronize(m->stream);
-    void *bufs[] = {m->d_rest_attr, m->d_rest, m->d_S32, m->d_stage, m->d_P, m->d_QR, m->d_tau, m->d_w, m->d_partial, m->d_hh, m->d_tmp,
-                    m->d_bpartial, m->d_bpartial2, m->d_Y, m->d_bw, m->d_bwpartial};
-    for (void *p : bufs) if (p) (void)hipFree(p);
-    if (m->ev0) (void)hipEventDestroy(m->ev0);
-    if (m->ev1) (void)hipEventDestroy(m->ev1);
-    if (m->stream) (void)hipStreamDestroy(m->stream);
-    delete m;
+    delete m;                   // the members release what they own, the stream last
 }
 
 static int morph_init_common(fd_morph *m, int64_t N, int S, const float *rest, const float *const *shapes, bool on_device)
@@ -1070,8 +1058,8 @@ static int morph_init_common(fd_morph *m, int64_t N, int S, const float *rest, c
             FDM_HIP(m, hipMemcpyAsync(m->d_stage, shapes[s], bytes, hipMemcpyHostToDevice, st));
             src = m->d_stage;
         }
-        hipLaunchKernelGGL(k_shape_column, dim3(g), dim3(kT), 0, st, m->d_rest, src, (int64_t)rows,
-                           m->d_QR + (size_t)s * rows, m->d_S32 + (size_t)s * rows);
+        hipLaunchKernelGGL(k_shape_column, dim3(g), dim3(kT), 0, st, m->d_rest.p, src, (int64_t)rows,
+                           m->d_QR.p + (size_t)s * rows, m->d_S32.p + (size_t)s * rows);
     }
     if ((rc = morph_factor(m))) return rc;
     FDM_HIP(m, hipEventRecord(m->ev1, st));
@@ -1099,7 +1087,7 @@ int fd_morph_set_rest(fd_morph *m, const float *rest_xyz, int on_device)
     FDM_HIP(m, hipSetDevice(m->device));
     const size_t rows = 3 * (size_t)m->N;
     if (!m->d_rest_attr) {
-        int rc = mrealloc(m, &m->d_rest_attr, 3 * (size_t)m->cap_N);
+        int rc = mrealloc(m, m->d_rest_attr, 3 * (size_t)m->cap_N);
         if (rc) return rc;
     }
     FDM_HIP(m, hipMemcpyAsync(m->d_rest_attr, rest_xyz, rows * sizeof(float),
@@ -1123,9 +1111,9 @@ int fd_morph_compute_weights_dev(fd_morph *m, const float *d_P_xyz, void *hip_st
     const int64_t rows = 3 * m->N;
     const unsigned nwg = (unsigned)((rows + kWRows - 1) / kWRows);
     if (m->S > 0) {
-        hipLaunchKernelGGL(k_morph_weights, dim3(nwg), dim3(kT), sizeof(double) * 4 * (size_t)m->S, st, m->d_QR, rows, m->S,
-                           d_P_xyz, m->use_rest_attr ? m->d_rest_attr : m->d_rest, m->d_partial);
-        hipLaunchKernelGGL(k_morph_weights_reduce, dim3(m->S), dim3(kT), 0, st, m->d_partial, (int)nwg, m->S, m->d_w);
+        hipLaunchKernelGGL(k_morph_weights, dim3(nwg), dim3(kT), sizeof(double) * 4 * (size_t)m->S, st, m->d_QR.p, rows, m->S,
+                           d_P_xyz, m->use_rest_attr ? m->d_rest_attr.p : m->d_rest.p, m->d_partial.p);
+        hipLaunchKernelGGL(k_morph_weights_reduce, dim3(m->S), dim3(kT), 0, st, m->d_partial.p, (int)nwg, m->S, m->d_w.p);
     }
     FDM_HIP(m, hipGetLastError());
     m->computed = true;
@@ -1140,9 +1128,9 @@ int fd_morph_displace_dev(fd_morph *m, float *d_P_xyz, const float *clamp_lo_hi,
     FDM_HIP(m, hipSetDevice(m->device));
     hipStream_t st = hip_stream ? (hipStream_t)hip_stream : m->stream;
     const unsigned g = (unsigned)((m->N + kT - 1) / kT);
-    hipLaunchKernelGGL(k_morph_displace, dim3(g), dim3(kT), sizeof(float) * (size_t)(m->S ? m->S : 1), st, m->d_S32, m->N,
-                       m->S, m->d_w, clamp_lo_hi ? clamp_lo_hi[0] : 0.f, clamp_lo_hi ? clamp_lo_hi[1] : 0.f,
-                       clamp_lo_hi ? 1 : 0, add_delta ? 1 : 0, falloffradius, m->use_rest_attr ? m->d_rest_attr : m->d_rest,
+    hipLaunchKernelGGL(k_morph_displace, dim3(g), dim3(kT), sizeof(float) * (size_t)(m->S ? m->S : 1), st, m->d_S32.p, m->N,
+                       m->S, m->d_w.p, clamp_lo_hi ? clamp_lo_hi[0] : 0.f, clamp_lo_hi ? clamp_lo_hi[1] : 0.f,
+                       clamp_lo_hi ? 1 : 0, add_delta ? 1 : 0, falloffradius, m->use_rest_attr ? m->d_rest_attr.p : m->d_rest.p,
                        d_P_xyz);
     FDM_HIP(m, hipGetLastError());
     return FD_OK;
@@ -1184,22 +1172,13 @@ int fd_morph_compute_weights_batch_dev(fd_morph *m, int F, const float *const *d
     const int S = m->S, ngroups = (S + kBCols - 1) / kBCols, ldp = ngroups * kBCols;
     const int cpw = (int)((nchunks + kBMaxWg - 1) / kBMaxWg), nwg = (int)((nchunks + cpw - 1) / cpw);
     const size_t need_w = (size_t)FD_MAX_BATCH * (size_t)(S ? S : 1), need_p = (size_t)nwg * FD_MAX_BATCH * (size_t)(ldp ? ldp : 1);
-    if (need_w > m->cap_bw) {
-        m->cap_bw = 0;
-        if ((rc = mrealloc(m, &m->d_bw, need_w))) return rc;
-        m->cap_bw = need_w;
-    }
-    if (need_p > m->cap_bwpartial) {
-        m->cap_bwpartial = 0;
-        if ((rc = mrealloc(m, &m->d_bwpartial, need_p))) return rc;
-        m->cap_bwpartial = need_p;
-    }
+    if ((rc = mrealloc(m, m->d_bw, need_w, kGrow)) || (rc = mrealloc(m, m->d_bwpartial, need_p, kGrow))) return rc;
     if (S > 0) {
         MorphFrames fr = {};
         for (int f = 0; f < F; ++f) fr.p[f] = d_P_xyz[f];
-        hipLaunchKernelGGL(k_morph_weights_batch, dim3(nwg, ngroups), dim3(kT), 0, st, m->d_QR, rows, S, F, fr,
-                           m->use_rest_attr ? m->d_rest_attr : m->d_rest, cpw, m->d_bwpartial, ldp);
-        hipLaunchKernelGGL(k_morph_weights_batch_reduce, dim3(ngroups, F), dim3(kT), 0, st, m->d_bwpartial, nwg, S, F, ldp, m->d_bw);
+        hipLaunchKernelGGL(k_morph_weights_batch, dim3(nwg, ngroups), dim3(kT), 0, st, m->d_QR.p, rows, S, F, fr,
+                           m->use_rest_attr ? m->d_rest_attr.p : m->d_rest.p, cpw, m->d_bwpartial.p, ldp);
+        hipLaunchKernelGGL(k_morph_weights_batch_reduce, dim3(ngroups, F), dim3(kT), 0, st, m->d_bwpartial.p, nwg, S, F, ldp, m->d_bw.p);
     }
     FDM_HIP(m, hipGetLastError());
     m->batch_F = F;
@@ -1225,9 +1204,9 @@ int fd_morph_displace_batch_dev(fd_morph *m, int F, float *const *d_P_xyz, const
     for (int f = 0; f < F; ++f) fr.p[f] = d_P_xyz[f];
     const unsigned g = (unsigned)((m->N + kT - 1) / kT);
     const float lo = clamp_lo_hi ? clamp_lo_hi[0] : 0.f, hi = clamp_lo_hi ? clamp_lo_hi[1] : 0.f;
-    const float *rest = m->use_rest_attr ? m->d_rest_attr : m->d_rest;
+    const float *rest = m->use_rest_attr ? m->d_rest_attr.p : m->d_rest.p;
 #define FD_MORPH_DISPLACE_BATCH(FT)                                                                                      \
-    hipLaunchKernelGGL(k_morph_displace_batch<FT>, dim3(g), dim3(kT), 0, st, m->d_S32, m->N, m->S, F, m->d_bw, lo, hi, \
+    hipLaunchKernelGGL(k_morph_displace_batch<FT>, dim3(g), dim3(kT), 0, st, m->d_S32.p, m->N, m->S, F, m->d_bw.p, lo, hi, \
                        clamp_lo_hi ? 1 : 0, add_delta ? 1 : 0, falloffradius, rest, fr)
     if (F <= 8) FD_MORPH_DISPLACE_BATCH(8);
     else if (F <= 16) FD_MORPH_DISPLACE_BATCH(16);
