@@ -30,7 +30,7 @@ EXTRA_FLAGS = {"fd_eval.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
                # and here: hoisted, the exp constants of the Gaussian instantiation that also returns grad_f cost four SGPR
                # spills
                "fd_adjoint_points.hip": ["-mllvm", "-disable-machine-licm"]}
-HEADERS = [os.path.join(CSRC, "fd_internal.h"), os.path.join(CSRC, "fd_tuning.h"), os.path.join(CSRC, "fd_pack.h"), os.path.join(CSRC, "fd_eval_common.h"), os.path.join(CSRC, "fd_transport.h"), os.path.join(CSRC, "fd_eval_point.h"), os.path.join(CSRC, "fd_shot_launch.h"), os.path.join(CSRC, "fd_vectors_shot.h"), os.path.join(CSRC, "fd_shared64.h"), os.path.join(CSRC, "fd_shared_ml64.h"), os.path.join(CSRC, "fd_shared_ml.h"), os.path.join(CSRC, "fd_shared_common.h"), os.path.join(CSRC, "fd_shared_plan.h"), os.path.join(CSRC, "fd_shared_solve.h"), os.path.join(CSRC, "fd_shot_dev.h"), os.path.join(CSRC, "fd_fit_host.h"), os.path.join(CSRC, "fd_owned.h"), os.path.join(_ROOT, "include", "facedeform_hip.h")]
+HEADERS = [os.path.join(CSRC, "fd_internal.h"), os.path.join(CSRC, "fd_tuning.h"), os.path.join(CSRC, "fd_pack.h"), os.path.join(CSRC, "fd_eval_common.h"), os.path.join(CSRC, "fd_transport.h"), os.path.join(CSRC, "fd_eval_point.h"), os.path.join(CSRC, "fd_shot_launch.h"), os.path.join(CSRC, "fd_vectors_shot.h"), os.path.join(CSRC, "fd_shared64.h"), os.path.join(CSRC, "fd_shared_ml64.h"), os.path.join(CSRC, "fd_shared_ml.h"), os.path.join(CSRC, "fd_shared_common.h"), os.path.join(CSRC, "fd_shared_plan.h"), os.path.join(CSRC, "fd_shared_solve.h"), os.path.join(CSRC, "fd_shot_dev.h"), os.path.join(CSRC, "fd_fit_host.h"), os.path.join(CSRC, "fd_owned.h"), os.path.join(CSRC, "fd_operator.h"), os.path.join(_ROOT, "include", "facedeform_hip.h")]
 
 
 def hipcc_path() -> str:

@@ -3,7 +3,7 @@
 //
 // The pair work of an evaluation with the reduction turned round: over the vertices, not the centres.  Mapping to the hardware:
 // a CENTRE per lane.  A 256-thread workgroup takes tiles of 256 vertices; each thread forms x_v and r_v of one vertex once -- the
-// gate, transport::falloff and transport::axes of the forward path, r = 0 by a select where the vertex is out -- and writes them
+// gate, fall-off and axes of the forward path (fd_operator.h), r = 0 by a select where the vertex is out -- and writes them
 // to LDS as fp64 (48 B per vertex, 12 KB per tile).  After the barrier every lane walks the tile: all lanes of a wave read the
 // same LDS address (a broadcast), x - c in raw coordinates against the lane's own Rec64 centre, phi of the kind (fd_pack.h
 // phi_grad64, the inverse's), three fma into the lane's three sums; the next vertex's values are requested from LDS before the
@@ -15,8 +15,7 @@
 // multilayer records' centre-major order and writes exactly 0.0 for the rows the term lacks.  No atomics: the workgroups and
 // their tile ranges are a function of N alone, so the same inputs give the same bits.  Everything is fp64; built with
 // -ffp-contract=off like fd_invert.hip: every fused multiply-add is written out.
-#include "fd_pack.h"
-#include "fd_transport.h"
+#include "fd_operator.h"
 
 namespace fd {
 
@@ -29,11 +28,8 @@ constexpr int kMaxGroups = 1024;             // workgroups along the vertices at
 
 using packing::phi_grad64;
 
-struct AdjParams {
-    int64_t N;
-    const float *P, *G, *dist2;
-    const float *tu, *tv, *nrm;          // projection frames (all or none)
-    float radius2, falloffrate;
+struct AdjParams : op::Mesh {
+    const float *G;
     int C;                               // records (fd_model_centres)
     int tiles_per;                       // 256-vertex tiles per workgroup
     const Rec64 *rec64;
@@ -68,20 +64,14 @@ __device__ __forceinline__ void adjoint64_body(const AdjParams &p)
     for (int64_t t = t0; t < t1; ++t) {
         const int64_t i = t * kBlock + tid;
         const int64_t ic = i < p.N ? i : p.N - 1;
-        double x[3] = {(double)p.P[3 * ic], (double)p.P[3 * ic + 1], (double)p.P[3 * ic + 2]};
+        double x[3], f;
         double r[3] = {(double)p.G[3 * ic], (double)p.G[3 * ic + 1], (double)p.G[3 * ic + 2]};
-        const float d2f = p.dist2 ? p.dist2[ic] : 0.f;
-        const double f = (double)transport::falloff(p.dist2 != nullptr, p.radius2, p.falloffrate, d2f);
-        // what the forward map moves: in range, not gated, model built, f != 0 (f = 0: the displacement is 0 whatever d is)
-        const bool live = (i < p.N) && !(d2f > p.radius2) && built && f != 0.0;
+        // what the forward map moves, and f != 0 (f = 0: the displacement is 0 whatever d is)
+        const bool live = op::vertex(p, i, ic, p.N, built, x, f) && f != 0.0;
         if (proj) {
-            // Pi = a1 a1^T + a2 a2^T is symmetric: Pi g, formed as the forward path forms Pi d
             double a1[3], a2[3];
             transport::axes<double>(p.tu, p.tv, p.nrm, ic, a1, a2);
-            const double p1 = a1[0] * r[0] + a1[1] * r[1] + a1[2] * r[2];
-            const double p2 = a2[0] * r[0] + a2[1] * r[1] + a2[2] * r[2];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) r[c] = a1[c] * p1 + a2[c] * p2;
+            op::project(a1, a2, r);
         }
         // a select, not a product: a vertex that is out contributes exactly nothing whatever G (or P) holds there
 #pragma unroll
@@ -139,21 +129,13 @@ __device__ __forceinline__ void adjoint64_body(const AdjParams &p)
     }
 }
 
-// stable names for profiles: k_adjoint64_<kind>
-#define FD_ADJ_KERNEL(NAME, KIND) \
-    __global__ __launch_bounds__(kBlock) void k_adjoint64_##NAME(const AdjParams p) { adjoint64_body<KIND>(p); }
-FD_ADJ_KERNEL(gaussian, FD_KERNEL_GAUSSIAN)
-FD_ADJ_KERNEL(thin_plate, FD_KERNEL_THIN_PLATE)
-FD_ADJ_KERNEL(biharmonic, FD_KERNEL_BIHARMONIC)
-FD_ADJ_KERNEL(cubic, FD_KERNEL_CUBIC)
-#undef FD_ADJ_KERNEL
+// k_adjoint64_<kind> and k_adjoint64_launch
+FD_OP_KERNELS(k_adjoint64_, , (kBlock), AdjParams, adjoint64_body<KIND>(p))
 
 // The blocks' sums in a fixed order, the same for every call with this N.  A workgroup takes kEnt entries of the (C + 4) x 3
 // result; kParts threads per entry each add a contiguous range of the blocks in the blocks' order (the loads of eight blocks in
 // flight at a time: one thread per entry over all the blocks would be a chain of a thousand dependent round trips to memory),
-// then the parts are added in their order.  Record position `row` of a multilayer model (centre-major, fd_pack.h) goes back to
-// its row of W (layer-major); `wscale` is the factor between W and the records' weights; + 0.0 keeps an empty sum at +0 under a
-// negative factor.
+// then the parts are added in their order and stored by fd_operator.h's row rule.
 constexpr int kParts = 16, kEnt = kBlock / kParts;
 __global__ __launch_bounds__(kBlock) void k_adjoint64_reduce(const double *partial, int nblocks, int C, int layers, int T,
                                                              double wscale, double *grad_W)
@@ -176,13 +158,7 @@ __global__ __launch_bounds__(kBlock) void k_adjoint64_reduce(const double *parti
 #pragma unroll
     for (int q = 1; q < kParts; ++q) sum += s_p[q][le];
     const int row = e / 3, a = e % 3;
-    if (row < C) {
-        int j = row;
-        if (layers > 1) { const int Mc = C / layers; j = (row % layers) * Mc + row / layers; }
-        grad_W[3 * j + a] = wscale * sum + 0.0;
-    } else {
-        grad_W[e] = row - C < T ? sum : 0.0;
-    }
+    op::store_row(grad_W, row, a, C, layers, T, wscale, sum);
 }
 
 }  // namespace
@@ -199,26 +175,15 @@ hipError_t launch_adjoint(const DeformArgs &a, const AdjointArgs &g, hipStream_t
 {
     const int groups = adjoint_groups(a.N);
     if (groups > 0) {
-        AdjParams p;
-        p.N = a.N;
-        p.P = a.P_in; p.G = g.G; p.dist2 = a.dist2;
-        p.tu = a.tu; p.tv = a.tv; p.nrm = a.nrm;
-        p.radius2 = a.radius2; p.falloffrate = a.falloffrate;
+        AdjParams p = op::params_of<AdjParams>(a);
+        p.G = g.G;
         p.C = a.M;
         const int64_t ntiles = (a.N + kBlock - 1) / kBlock;
         p.tiles_per = (int)((ntiles + groups - 1) / groups);
         p.rec64 = a.rec64; p.model = a.model;
         p.partial = g.partial;
         const dim3 grid((unsigned)groups, (unsigned)((a.M + kSpan - 1) / kSpan));
-        switch (a.kind) {
-        case FD_KERNEL_GAUSSIAN:
-        case FD_KERNEL_GAUSSIAN_QNN: hipLaunchKernelGGL(k_adjoint64_gaussian, grid, dim3(kBlock), 0, stream, p); break;
-        case FD_KERNEL_THIN_PLATE: hipLaunchKernelGGL(k_adjoint64_thin_plate, grid, dim3(kBlock), 0, stream, p); break;
-        case FD_KERNEL_BIHARMONIC: hipLaunchKernelGGL(k_adjoint64_biharmonic, grid, dim3(kBlock), 0, stream, p); break;
-        case FD_KERNEL_CUBIC: hipLaunchKernelGGL(k_adjoint64_cubic, grid, dim3(kBlock), 0, stream, p); break;
-        default: return hipErrorInvalidValue;
-        }
-        const hipError_t e = hipGetLastError();
+        const hipError_t e = k_adjoint64_launch(a.kind, grid, stream, p);
         if (e != hipSuccess) return e;
     }
     const int n = (a.M + 4) * 3;

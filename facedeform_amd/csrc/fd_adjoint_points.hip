@@ -11,8 +11,7 @@
 // vertex where A = I (gated, model not built, f = 0) gets g widened by a select.  A wave none of whose lanes needs the sums
 // skips the records (wave-uniform; a lane's own result is the same either way).  No LDS, no atomics, no cross-vertex sums.
 // Built with -ffp-contract=off like fd_invert.hip: every fused multiply-add is written out.
-#include "fd_pack.h"
-#include "fd_transport.h"
+#include "fd_operator.h"
 
 namespace fd {
 
@@ -130,15 +129,9 @@ __device__ __forceinline__ void adjoint_points64_body(const AdjPointsParams &p)
     }
 }
 
-// stable names for profiles: k_adjoint_points64_<kind>, _f with grad_f
-#define FD_ADJP_KERNEL(NAME, KIND)                                                                                                     \
-    __global__ __launch_bounds__(kBlock) void k_adjoint_points64_##NAME(const AdjPointsParams p) { adjoint_points64_body<KIND, false>(p); } \
-    __global__ __launch_bounds__(kBlock) void k_adjoint_points64_##NAME##_f(const AdjPointsParams p) { adjoint_points64_body<KIND, true>(p); }
-FD_ADJP_KERNEL(gaussian, FD_KERNEL_GAUSSIAN)
-FD_ADJP_KERNEL(thin_plate, FD_KERNEL_THIN_PLATE)
-FD_ADJP_KERNEL(biharmonic, FD_KERNEL_BIHARMONIC)
-FD_ADJP_KERNEL(cubic, FD_KERNEL_CUBIC)
-#undef FD_ADJP_KERNEL
+// k_adjoint_points64_<kind>, _f with grad_f, and their k_adjoint_points64_launch, _f
+FD_OP_KERNELS(k_adjoint_points64_, , (kBlock), AdjPointsParams, adjoint_points64_body<KIND, false>(p))
+FD_OP_KERNELS(k_adjoint_points64_, _f, (kBlock), AdjPointsParams, adjoint_points64_body<KIND, true>(p))
 
 }  // namespace
 
@@ -146,31 +139,14 @@ hipError_t launch_adjoint_points(const DeformArgs &a, const AdjointPointsArgs &g
 {
     if (a.N <= 0) return hipSuccess;
     AdjPointsParams p;
-    p.N = a.N;
-    p.P = a.P_in; p.G = g.G; p.dist2 = a.dist2;
-    p.tu = a.tu; p.tv = a.tv; p.nrm = a.nrm;
-    p.radius2 = a.radius2; p.falloffrate = a.falloffrate;
+    op::fill_mesh(p, a);
+    p.P = a.P_in; p.G = g.G;
     p.Mpad = a.Mpad;
     p.rec64 = a.rec64; p.model = a.model;
     p.grad_P = g.grad_P; p.grad_f = g.grad_f;
     const int64_t per = (int64_t)kBlock * kV;
     const dim3 grid((unsigned)((a.N + per - 1) / per));
-    const bool wf = g.grad_f != nullptr;
-#define FD_ADJP_LAUNCH(NAME)                                                                             \
-    do {                                                                                                 \
-        if (wf) hipLaunchKernelGGL(k_adjoint_points64_##NAME##_f, grid, dim3(kBlock), 0, stream, p);     \
-        else hipLaunchKernelGGL(k_adjoint_points64_##NAME, grid, dim3(kBlock), 0, stream, p);            \
-    } while (0)
-    switch (a.kind) {
-    case FD_KERNEL_GAUSSIAN:
-    case FD_KERNEL_GAUSSIAN_QNN: FD_ADJP_LAUNCH(gaussian); break;
-    case FD_KERNEL_THIN_PLATE: FD_ADJP_LAUNCH(thin_plate); break;
-    case FD_KERNEL_BIHARMONIC: FD_ADJP_LAUNCH(biharmonic); break;
-    case FD_KERNEL_CUBIC: FD_ADJP_LAUNCH(cubic); break;
-    default: return hipErrorInvalidValue;
-    }
-#undef FD_ADJP_LAUNCH
-    return hipGetLastError();
+    return g.grad_f ? k_adjoint_points64_launch_f(a.kind, grid, stream, p) : k_adjoint_points64_launch(a.kind, grid, stream, p);
 }
 
 }  // namespace fd

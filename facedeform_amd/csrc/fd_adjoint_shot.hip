@@ -10,7 +10,8 @@
 // accumulator registers).  It walks its range in super-tiles of 128 vertices:
 //   prepare   threads 0..127 form x_v and f_v of one vertex each, threads 128..255 the projection axes of the same vertices
 //             -- the gate, transport::falloff and transport::axes of the forward path, f = 0 and x = 0 by a select where the
-//             vertex is out (the expressions of fd_adjoint.hip, which stays as it is) -- into LDS, 11 doubles per vertex.
+//             vertex is out (the expressions of fd_operator.h's prologue, written out here: DESIGN.md 4.14) -- into LDS, 11
+//             doubles per vertex.
 //             (128, not 256, vertices: the 10 KB this saves is what lets two workgroups share a CU's LDS.)
 // and each super-tile in chunks of 32 vertices:
 //   form      thread t owns panel column t & 127 and the chunk's vertices 16 (t >> 7) .. + 16 (a broadcast read of x),
@@ -32,8 +33,7 @@
 // and a column's sums do not depend on what the other columns hold, so frame f's block has the same bits whatever the other
 // frames are and however many there are.  Everything is fp64; built with -ffp-contract=off like fd_adjoint.hip: every fused
 // multiply-add is written out.
-#include "fd_pack.h"
-#include "fd_transport.h"
+#include "fd_operator.h"
 
 namespace fd {
 
@@ -48,8 +48,6 @@ constexpr int kChunk = 32;                   // vertices staged through LDS per 
 constexpr int kPsiRow = kPanel + 16;         // doubles per staged vertex row of Psi: the two vertex rows of a 32-lane read on disjoint banks
 constexpr int kRRow = kChunk + 2;            // doubles per staged column of R
 constexpr int kVRow = 11;                    // doubles per prepared vertex: x, f, a1, a2 and one of padding (an odd stride)
-constexpr int kMaxRanges = 256;
-constexpr size_t kScratchBound = (size_t)256 << 20;      // bytes of partial blocks at most
 static_assert(kFrames == FD_MAX_BATCH, "a group is FD_MAX_BATCH frames");
 
 using packing::phi_grad64;
@@ -228,19 +226,12 @@ __device__ __forceinline__ void adjoint64_shot_body(const ShotParams &p)
     }
 }
 
-// stable names for profiles: k_adjoint64_shot_<kind>
-#define FD_ADJ_SHOT_KERNEL(NAME, KIND) \
-    __global__ __launch_bounds__(kBlock, 2) void k_adjoint64_shot_##NAME(const ShotParams p) { adjoint64_shot_body<KIND>(p); }
-FD_ADJ_SHOT_KERNEL(gaussian, FD_KERNEL_GAUSSIAN)
-FD_ADJ_SHOT_KERNEL(thin_plate, FD_KERNEL_THIN_PLATE)
-FD_ADJ_SHOT_KERNEL(biharmonic, FD_KERNEL_BIHARMONIC)
-FD_ADJ_SHOT_KERNEL(cubic, FD_KERNEL_CUBIC)
-#undef FD_ADJ_SHOT_KERNEL
+// k_adjoint64_shot_<kind> and k_adjoint64_shot_launch
+FD_OP_KERNELS(k_adjoint64_shot_, , (kBlock, 2), ShotParams, adjoint64_shot_body<KIND>(p))
 
 // The ranges' blocks added in their order, the same for every call with this N and C: one thread per entry (row, column) of the
-// group, consecutive threads on consecutive columns.  Record position `row` of a multilayer model (centre-major, fd_pack.h)
-// goes back to its row of W (layer-major); `wscale` is the factor between W and the records' weights; + 0.0 keeps an empty sum
-// at +0 under a negative factor.  grad_W is the group's first frame: nF blocks of (C + 4) x 3.
+// group, consecutive threads on consecutive columns, stored by fd_operator.h's row rule.  grad_W is the group's first frame:
+// nF blocks of (C + 4) x 3.
 __global__ __launch_bounds__(kBlock) void k_adjoint64_shot_reduce(const double *partial, int nranges, int nt, int nF, int C,
                                                                   int layers, int T, double wscale, double *grad_W)
 {
@@ -255,36 +246,18 @@ __global__ __launch_bounds__(kBlock) void k_adjoint64_shot_reduce(const double *
     for (int r = 0; r < nranges; ++r) sum += src[(size_t)r * stride];
     const int f = col / 3, a = col % 3;
     double *out = grad_W + (size_t)f * n * 3;
-    if (row < C) {
-        int j = row;
-        if (layers > 1) { const int Mc = C / layers; j = (row % layers) * Mc + row / layers; }
-        out[3 * j + a] = wscale * sum + 0.0;
-    } else {
-        out[3 * row + a] = row - C < T ? sum : 0.0;
-    }
+    op::store_row(out, row, a, C, layers, T, wscale, sum);
 }
 
-int64_t shot_per(int64_t N, int C)
-{
-    const size_t block = (size_t)(C + 4 + 15) / 16 * 16 * kCols * sizeof(double);
-    int64_t maxr = (int64_t)(kScratchBound / block);
-    maxr = maxr < 1 ? 1 : (maxr > kMaxRanges ? kMaxRanges : maxr);
-    const int64_t supers = (N + kSuper - 1) / kSuper;
-    return (supers + maxr - 1) / maxr * kSuper;
-}
+int64_t shot_per(int64_t N, int C) { return op::range_per(N, op::padded_rows(C) * kCols * sizeof(double), kSuper); }
 
 }  // namespace
 
-int adjoint_shot_ranges(int64_t N, int C)
-{
-    if (N <= 0) return 0;
-    const int64_t per = shot_per(N, C);
-    return (int)((N + per - 1) / per);
-}
+int adjoint_shot_ranges(int64_t N, int C) { return op::range_count(N, shot_per(N, C)); }
 
 size_t adjoint_shot_partial_doubles(int64_t N, int C)
 {
-    return (size_t)adjoint_shot_ranges(N, C) * ((size_t)(C + 4 + 15) / 16 * 16) * kCols;
+    return (size_t)adjoint_shot_ranges(N, C) * op::padded_rows(C) * kCols;
 }
 
 hipError_t launch_adjoint_shot(const DeformArgs &a, const AdjointShotArgs &g, hipStream_t stream)
@@ -296,24 +269,14 @@ hipError_t launch_adjoint_shot(const DeformArgs &a, const AdjointShotArgs &g, hi
         const int nF = g.F - f0 < kFrames ? g.F - f0 : kFrames;
         if (ranges > 0) {
             ShotParams p;
-            p.N = a.N;
-            p.P = a.P_in; p.G = g.G + (size_t)f0 * (size_t)a.N * 3; p.dist2 = a.dist2;
-            p.tu = a.tu; p.tv = a.tv; p.nrm = a.nrm;
-            p.radius2 = a.radius2; p.falloffrate = a.falloffrate;
+            op::fill_mesh(p, a);
+            p.P = a.P_in; p.G = g.G + (size_t)f0 * (size_t)a.N * 3;
             p.C = a.M; p.nt = nt; p.nF = nF;
             p.per = shot_per(a.N, a.M);
             p.rec64 = a.rec64; p.model = a.model;
             p.partial = g.partial;
             const dim3 grid((unsigned)ranges, (unsigned)((nt + 7) / 8));
-            switch (a.kind) {
-            case FD_KERNEL_GAUSSIAN:
-            case FD_KERNEL_GAUSSIAN_QNN: hipLaunchKernelGGL(k_adjoint64_shot_gaussian, grid, dim3(kBlock), 0, stream, p); break;
-            case FD_KERNEL_THIN_PLATE: hipLaunchKernelGGL(k_adjoint64_shot_thin_plate, grid, dim3(kBlock), 0, stream, p); break;
-            case FD_KERNEL_BIHARMONIC: hipLaunchKernelGGL(k_adjoint64_shot_biharmonic, grid, dim3(kBlock), 0, stream, p); break;
-            case FD_KERNEL_CUBIC: hipLaunchKernelGGL(k_adjoint64_shot_cubic, grid, dim3(kBlock), 0, stream, p); break;
-            default: return hipErrorInvalidValue;
-            }
-            const hipError_t e = hipGetLastError();
+            const hipError_t e = k_adjoint64_shot_launch(a.kind, grid, stream, p);
             if (e != hipSuccess) return e;
         }
         const int entries = n * 3 * nF;

@@ -21,8 +21,7 @@
 // columns of polynomial terms the model lacks and mirrors the upper triangle into the lower.  No atomics: the ranges are a
 // function of N and C alone (gram_ranges), so the same inputs give the same bits.  Everything is fp64; built with
 // -ffp-contract=off like fd_adjoint.hip: every fused multiply-add is written out.
-#include "fd_pack.h"
-#include "fd_transport.h"
+#include "fd_operator.h"
 
 namespace fd {
 
@@ -33,8 +32,6 @@ constexpr int kPanel = 128;                  // columns of a panel: 8 tiles, two
 constexpr int kSuper = 256;                  // vertices whose x and q are formed at a time
 constexpr int kChunk = 32;                   // vertices staged through LDS per contraction (8 MFMA depths)
 constexpr int kRow = 2 * kPanel + 16;        // doubles per staged vertex row
-constexpr int kMaxRanges = 256;
-constexpr size_t kScratchBound = (size_t)256 << 20;      // bytes of partial blocks at most (with all six components)
 
 using packing::phi_grad64;
 typedef double double4_t __attribute__((ext_vector_type(4)));
@@ -188,14 +185,8 @@ __device__ __forceinline__ void gram64_body(const GramParams &p)
     }
 }
 
-// stable names for profiles: k_gram64_<kind>
-#define FD_GRAM_KERNEL(NAME, KIND) \
-    __global__ __launch_bounds__(kBlock) void k_gram64_##NAME(const GramParams p) { gram64_body<KIND>(p); }
-FD_GRAM_KERNEL(gaussian, FD_KERNEL_GAUSSIAN)
-FD_GRAM_KERNEL(thin_plate, FD_KERNEL_THIN_PLATE)
-FD_GRAM_KERNEL(biharmonic, FD_KERNEL_BIHARMONIC)
-FD_GRAM_KERNEL(cubic, FD_KERNEL_CUBIC)
-#undef FD_GRAM_KERNEL
+// k_gram64_<kind> and k_gram64_launch
+FD_OP_KERNELS(k_gram64_, , (kBlock), GramParams, gram64_body<KIND>(p))
 
 // The ranges' blocks added in their order, the same for every call with this N and C: one thread per entry j <= k of one
 // component.  Record position `j` of a multilayer model (centre-major, fd_pack.h) goes back to its row of W (layer-major);
@@ -230,28 +221,20 @@ __global__ __launch_bounds__(kBlock) void k_gram64_reduce(const double *partial,
     Hq[(size_t)ko * n + jo] = val;
 }
 
+// (a range's block: all six components)
 int64_t gram_per(int64_t N, int C)
 {
-    const size_t ld = (size_t)(C + 4 + 15) / 16 * 16;
-    const size_t block = 6 * ld * ld * sizeof(double);
-    int64_t maxr = (int64_t)(kScratchBound / block);
-    maxr = maxr < 1 ? 1 : (maxr > kMaxRanges ? kMaxRanges : maxr);
-    const int64_t supers = (N + kSuper - 1) / kSuper;
-    return (supers + maxr - 1) / maxr * kSuper;
+    const size_t ld = op::padded_rows(C);
+    return op::range_per(N, 6 * ld * ld * sizeof(double), kSuper);
 }
 
 }  // namespace
 
-int gram_ranges(int64_t N, int C)
-{
-    if (N <= 0) return 0;
-    const int64_t per = gram_per(N, C);
-    return (int)((N + per - 1) / per);
-}
+int gram_ranges(int64_t N, int C) { return op::range_count(N, gram_per(N, C)); }
 
 size_t gram_partial_doubles(int64_t N, int C, int nq)
 {
-    const size_t ld = (size_t)(C + 4 + 15) / 16 * 16;
+    const size_t ld = op::padded_rows(C);
     return (size_t)gram_ranges(N, C) * (size_t)nq * ld * ld;
 }
 
@@ -262,25 +245,15 @@ hipError_t launch_gram(const DeformArgs &a, const GramArgs &g, hipStream_t strea
     const int nt = (a.M + 4 + 15) / 16;
     if (ranges > 0) {
         GramParams p;
-        p.N = a.N;
-        p.P = a.P_in; p.omega = g.omega; p.dist2 = a.dist2;
-        p.tu = a.tu; p.tv = a.tv; p.nrm = a.nrm;
-        p.radius2 = a.radius2; p.falloffrate = a.falloffrate;
+        op::fill_mesh(p, a);
+        p.P = a.P_in; p.omega = g.omega;
         p.C = a.M; p.nt = nt; p.nq = nq;
         p.per = gram_per(a.N, a.M);
         p.rec64 = a.rec64; p.model = a.model;
         p.partial = g.partial;
         const int np = (nt + 7) / 8;
         const dim3 grid((unsigned)ranges, (unsigned)(np * (np + 1) / 2), (unsigned)nq);
-        switch (a.kind) {
-        case FD_KERNEL_GAUSSIAN:
-        case FD_KERNEL_GAUSSIAN_QNN: hipLaunchKernelGGL(k_gram64_gaussian, grid, dim3(kBlock), 0, stream, p); break;
-        case FD_KERNEL_THIN_PLATE: hipLaunchKernelGGL(k_gram64_thin_plate, grid, dim3(kBlock), 0, stream, p); break;
-        case FD_KERNEL_BIHARMONIC: hipLaunchKernelGGL(k_gram64_biharmonic, grid, dim3(kBlock), 0, stream, p); break;
-        case FD_KERNEL_CUBIC: hipLaunchKernelGGL(k_gram64_cubic, grid, dim3(kBlock), 0, stream, p); break;
-        default: return hipErrorInvalidValue;
-        }
-        const hipError_t e = hipGetLastError();
+        const hipError_t e = k_gram64_launch(a.kind, grid, stream, p);
         if (e != hipSuccess) return e;
     }
     const int64_t entries = (int64_t)nq * (a.M + 4) * (a.M + 4);

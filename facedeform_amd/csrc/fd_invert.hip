@@ -9,8 +9,7 @@
 // g of a record from ONE transcendental.  The step loop's exit is wave-uniform; a lane that has converged, is gated or lies past
 // N keeps its x under a mask (its arithmetic runs on and is dropped) and no lane returns early.  max_iter bounds the loop.
 // No LDS, no atomics.  Built with -ffp-contract=off like fd_vectors.hip: every fused multiply-add is written out.
-#include "fd_pack.h"
-#include "fd_transport.h"
+#include "fd_operator.h"
 
 namespace fd {
 
@@ -24,18 +23,14 @@ using packing::phi_grad64;       // phi and g of grad phi = grad_scale64 g (x - 
 
 typedef const __attribute__((address_space(4))) Rec64 *ConstRec64;
 
-struct InvParams {
-    int64_t N;
-    const float *Y, *dist2;
-    const float *tu, *tv, *nrm;          // projection frames (all or none)
-    float *X;                            // may alias Y
-    float *residual;                     // N or null
-    int *iters;                          // N or null
-    float radius2, falloffrate;
-    int Mpad, max_iter;
+struct InvParams : op::Mesh {            // P: the deformed points y
+    int Mpad, max_iter;                  // the inputs first, in the order that adds no SGPR spill
     double tol;                          // > 0: every vertex's; otherwise 2^-25 max(|y|_inf, s) per vertex
     const Rec64 *rec64;
     const DevModel *model;
+    float *X;                            // may alias P
+    float *residual;                     // N or null
+    int *iters;                          // N or null
 };
 
 __device__ __forceinline__ bool finite3(const double v[3]) { return isfinite(v[0]) && isfinite(v[1]) && isfinite(v[2]); }
@@ -58,17 +53,14 @@ __device__ __forceinline__ void invert64_body(const InvParams &p)
     for (int v = 0; v < kV; ++v) {
         const int64_t i = base + v * kBlock + tid;
         const int64_t ic = i < p.N ? i : p.N - 1;
+        solve[v] = op::vertex(p, i, ic, p.N, built, x[v], f[v]);
+        active[v] = solve[v];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            yf[v][c] = p.Y[3 * ic + c];
-            x[v][c] = (double)yf[v][c];
+            yf[v][c] = p.P[3 * ic + c];       // x0 = y; the fp32 value is what a vertex outside the solve is given back
             best[v][c] = x[v][c];
             a1[v][c] = 0.0; a2[v][c] = 0.0;
         }
-        const float d2 = p.dist2 ? p.dist2[ic] : 0.f;
-        solve[v] = (i < p.N) && !(d2 > p.radius2) && built;
-        active[v] = solve[v];
-        f[v] = (double)transport::falloff(p.dist2 != nullptr, p.radius2, p.falloffrate, d2);
         if (proj) transport::axes<double>(p.tu, p.tv, p.nrm, ic, a1[v], a2[v]);
         const double ymax = fmax(fabs(x[v][0]), fmax(fabs(x[v][1]), fabs(x[v][2])));
         tol[v] = p.tol > 0.0 ? p.tol : 2.98023223876953125e-08 * fmax(ymax, scale);      // 2^-25
@@ -129,10 +121,7 @@ __device__ __forceinline__ void invert64_body(const InvParams &p)
 #pragma unroll
             for (int q = 0; q < 9; ++q) R[q] = fma(gs, S[v][q], af[4 * (q / 3) + 1 + q % 3]);
             if (proj) {
-                const double p1 = a1[v][0] * d[0] + a1[v][1] * d[1] + a1[v][2] * d[2];
-                const double p2 = a2[v][0] * d[0] + a2[v][1] * d[1] + a2[v][2] * d[2];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) d[c] = a1[v][c] * p1 + a2[v][c] * p2;
+                op::project(a1[v], a2[v], d);
                 transport::project(R, a1[v], a2[v]);
             }
             double F[3], A[9];
@@ -186,41 +175,24 @@ __device__ __forceinline__ void invert64_body(const InvParams &p)
     }
 }
 
-// stable names for profiles: k_invert64_<kind>
-#define FD_INV_KERNEL(NAME, KIND) \
-    __global__ __launch_bounds__(kBlock) void k_invert64_##NAME(const InvParams p) { invert64_body<KIND>(p); }
-FD_INV_KERNEL(gaussian, FD_KERNEL_GAUSSIAN)
-FD_INV_KERNEL(thin_plate, FD_KERNEL_THIN_PLATE)
-FD_INV_KERNEL(biharmonic, FD_KERNEL_BIHARMONIC)
-FD_INV_KERNEL(cubic, FD_KERNEL_CUBIC)
-#undef FD_INV_KERNEL
+// k_invert64_<kind> and k_invert64_launch
+FD_OP_KERNELS(k_invert64_, , (kBlock), InvParams, invert64_body<KIND>(p))
 
 }  // namespace
 
 hipError_t launch_invert(const DeformArgs &a, const InvertArgs &v, hipStream_t stream)
 {
     if (a.N <= 0) return hipSuccess;
-    InvParams p;
-    p.N = a.N;
-    p.Y = a.P_in; p.X = a.P_out; p.dist2 = a.dist2;
-    p.tu = a.tu; p.tv = a.tv; p.nrm = a.nrm;
+    InvParams p = op::params_of<InvParams>(a);
+    p.X = a.P_out;
     p.residual = v.residual_out; p.iters = v.iters_out;
-    p.radius2 = a.radius2; p.falloffrate = a.falloffrate;
     p.Mpad = a.Mpad;
     p.max_iter = v.max_iter <= 0 ? kInvertDefaultIter : (v.max_iter > kInvertMaxIter ? kInvertMaxIter : v.max_iter);
     p.tol = v.tol > 0.0 ? v.tol : 0.0;
     p.rec64 = a.rec64; p.model = a.model;
     const int64_t per = (int64_t)kBlock * kV;
     const dim3 grid((unsigned)((a.N + per - 1) / per));
-    switch (a.kind) {
-    case FD_KERNEL_GAUSSIAN:
-    case FD_KERNEL_GAUSSIAN_QNN: hipLaunchKernelGGL(k_invert64_gaussian, grid, dim3(kBlock), 0, stream, p); break;
-    case FD_KERNEL_THIN_PLATE: hipLaunchKernelGGL(k_invert64_thin_plate, grid, dim3(kBlock), 0, stream, p); break;
-    case FD_KERNEL_BIHARMONIC: hipLaunchKernelGGL(k_invert64_biharmonic, grid, dim3(kBlock), 0, stream, p); break;
-    case FD_KERNEL_CUBIC: hipLaunchKernelGGL(k_invert64_cubic, grid, dim3(kBlock), 0, stream, p); break;
-    default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return k_invert64_launch(a.kind, grid, stream, p);
 }
 
 }  // namespace fd

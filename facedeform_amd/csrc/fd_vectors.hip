@@ -10,8 +10,7 @@
 // Per (vertex, centre) pair: 3 sub, 3 fma (d2), one transcendental, 1-2 for g, 3 mul (w g), 9 fma.
 // Built with -ffp-contract=off like fd_eval.hip: every fused multiply-add is written out.
 #include "fd_eval_common.h"
-#include "fd_pack.h"
-#include "fd_transport.h"
+#include "fd_operator.h"
 
 namespace fd {
 
@@ -80,7 +79,8 @@ __device__ __forceinline__ void pass_through(const VecParams &p, int64_t i)
         for (int q = 0; q < 9; ++q) p.jac[9 * i + q] = (q % 4 == 0) ? 1.f : 0.f;
 }
 
-// fd_eval.hip's fall-off (:423-424), the same operations: the f the deformation multiplied by
+// transport::falloff's operations (fd_transport.h), kept here as text: called through that function k_vectors64_thin_plate
+// measured above the range of the form with this text
 __device__ __forceinline__ float falloff_of(const VecParams &p, float dist2)
 {
     float falloff = 1.f;
@@ -226,15 +226,9 @@ __device__ __forceinline__ void vectors64_body(const VecParams &p)
     }
 }
 
-// stable names for profiles: k_vectors32_<kind> / k_vectors64_<kind>
-#define FD_VEC_KERNELS(NAME, KIND)                                                                   \
-    __global__ __launch_bounds__(kBlock) void k_vectors32_##NAME(const VecParams p) { vectors32_body<KIND>(p); } \
-    __global__ __launch_bounds__(kBlock) void k_vectors64_##NAME(const VecParams p) { vectors64_body<KIND>(p); }
-FD_VEC_KERNELS(gaussian, FD_KERNEL_GAUSSIAN)
-FD_VEC_KERNELS(thin_plate, FD_KERNEL_THIN_PLATE)
-FD_VEC_KERNELS(biharmonic, FD_KERNEL_BIHARMONIC)
-FD_VEC_KERNELS(cubic, FD_KERNEL_CUBIC)
-#undef FD_VEC_KERNELS
+// k_vectors32_<kind> / k_vectors64_<kind> and their k_vectors32_launch / k_vectors64_launch
+FD_OP_KERNELS(k_vectors32_, , (kBlock), VecParams, vectors32_body<KIND>(p))
+FD_OP_KERNELS(k_vectors64_, , (kBlock), VecParams, vectors64_body<KIND>(p))
 
 }  // namespace
 
@@ -242,31 +236,15 @@ hipError_t launch_vectors(const DeformArgs &a, const VectorArgs &v, hipStream_t 
 {
     if (a.N <= 0) return hipSuccess;
     VecParams p;
-    p.N = a.N;
-    p.P_in = a.P_in; p.dist2 = a.dist2;
-    p.tu = a.tu; p.tv = a.tv; p.nrm = a.nrm;
+    op::fill_mesh(p, a);
+    p.P_in = a.P_in;
     p.vN = v.N; p.vtu = v.tu; p.vtv = v.tv;
     p.oN = v.N_out; p.otu = v.tu_out; p.otv = v.tv_out; p.jac = v.jacobian;
-    p.radius2 = a.radius2; p.falloffrate = a.falloffrate;
     p.Mpad = a.Mpad;
     p.rec32 = a.rec32; p.rec64 = a.rec64; p.model = a.model;
     const int64_t per = (int64_t)kBlock * 2;
     const dim3 grid((unsigned)((a.N + per - 1) / per));
-    const bool f64 = a.precision == FD_EVAL_FP64;
-#define FD_VEC_LAUNCH(NAME)                                                                   \
-    if (f64) hipLaunchKernelGGL(k_vectors64_##NAME, grid, dim3(kBlock), 0, stream, p);        \
-    else hipLaunchKernelGGL(k_vectors32_##NAME, grid, dim3(kBlock), 0, stream, p);            \
-    break;
-    switch (a.kind) {
-    case FD_KERNEL_GAUSSIAN:
-    case FD_KERNEL_GAUSSIAN_QNN: FD_VEC_LAUNCH(gaussian)
-    case FD_KERNEL_THIN_PLATE: FD_VEC_LAUNCH(thin_plate)
-    case FD_KERNEL_BIHARMONIC: FD_VEC_LAUNCH(biharmonic)
-    case FD_KERNEL_CUBIC: FD_VEC_LAUNCH(cubic)
-    default: return hipErrorInvalidValue;
-    }
-#undef FD_VEC_LAUNCH
-    return hipGetLastError();
+    return a.precision == FD_EVAL_FP64 ? k_vectors64_launch(a.kind, grid, stream, p) : k_vectors32_launch(a.kind, grid, stream, p);
 }
 
 }  // namespace fd

@@ -3,14 +3,17 @@
     python tests/tools/operators_digest.py > listing.txt          # in each of the two trees; the listings must be equal
 
 Fixed seed.  Models: thin-plate, QNN and a three-layer multilayer model, linear term, M in {5, 60, 253} control points (253:
-C + 4 = 257, a third Gram panel and a 17th tile).  Meshes: the first N in {0, 1, 255, 257, 1000} vertices of a head mesh -- an
+C + 4 = 257, a third Gram panel and a 17th tile), and Gaussian, biharmonic and cubic at M = 60 -- with them every kernel
+instantiation of the operators' files runs.  Meshes: the first N in {0, 1, 255, 257, 1000} vertices of a head mesh -- an
 empty call, a lone vertex, both sides of a 256-vertex tile -- without and with dist2 (uniform on [0, radius2 / 0.9): about a
 tenth of the vertices gated) and without and with projection frames.  Per mesh and model, one line for each of
   deform        fd_deform and fd_deform_dev: P_out, fd_falloff
   vectors       fd_deform_vectors and fd_deform_vectors_dev, all outputs and the Jacobian; with projection frames the device
                 call once more with P_out = P_in and N_out = nrm in place, which sets P_in aside
+  vectors64     fd_deform_vectors_dev with the context at FD_EVAL_FP64, all outputs and the Jacobian
   invert        fd_invert and fd_invert_dev on the deformed points: X, residual, iters
   adjoint       fd_deform_adjoint and fd_deform_adjoint_dev
+  adjoint_points  fd_deform_adjoint_points and fd_deform_adjoint_points_dev, without and with grad_f
   gram          fd_deform_gram and fd_deform_gram_dev, omega given and not
   adjoint_shot  fd_deform_adjoint_shot and fd_deform_adjoint_shot_dev at F in {1, 3, 33} (33: across the 32-frame group)
   fit           fd_fit_deltas, omega given and not, S given and not: the deltas, and the report's order, E0, E_fit and pivots
@@ -34,6 +37,8 @@ FIT_CENTRES = (5, 60)
 FRAMES = (1, 3, 33)
 MODELS = [("thin_plate", capi.KERNEL_THIN_PLATE, []), ("qnn", capi.KERNEL_GAUSSIAN_QNN, [1.0, 5.0]),
           ("multilayer3", capi.KERNEL_GAUSSIAN_ML, [0.7, 3, 0.1])]
+KIND_MODELS = [("gaussian", capi.KERNEL_GAUSSIAN, [0.35]), ("biharmonic", capi.KERNEL_BIHARMONIC, []),
+               ("cubic", capi.KERNEL_CUBIC, [])]        # at M = 60 alone, without the two fits
 DEV = None
 
 
@@ -128,6 +133,12 @@ def run_case(e, c, n, with_fits, S):
         e.deform_vectors_dev(N, ptr(c_P), ptr(c_P), d_falloff=ptr(o_f), d_N=ptr(c_nr), d_N_out=ptr(c_nr), **ckw); sync()
         res += [c_P, c_nr, o_f]
     out.append(("vectors", digest(res)))
+    e.set_eval_precision(capi.EVAL_FP64)
+    o_P, o_f, o_V, o_J = fresh((N, 3)), fresh((N,)), [fresh((N, 3)) for _ in range(3)], fresh((N, 9))
+    e.deform_vectors_dev(N, ptr(d_P), ptr(o_P), d_falloff=ptr(o_f), d_N=ptr(d_V[0]), d_N_out=ptr(o_V[0]), d_vtu=ptr(d_V[1]),
+                         d_vtu_out=ptr(o_V[1]), d_vtv=ptr(d_V[2]), d_vtv_out=ptr(o_V[2]), d_jacobian=ptr(o_J), **dkw); sync()
+    e.set_eval_precision(capi.EVAL_FP32)
+    out.append(("vectors64", digest([o_P, o_f, o_J] + o_V)))
 
     # invert, on the deformed points
     res = list(e.invert(Y, **hkw))
@@ -140,6 +151,14 @@ def run_case(e, c, n, with_fits, S):
     d_G, o_W = up(G), fresh((n, 3), torch.float64)
     e.deform_adjoint_dev(N, ptr(d_P), ptr(d_G), ptr(o_W), **dkw); sync()
     out.append(("adjoint", digest(res + [o_W])))
+
+    # adjoint_points
+    res = [e.deform_adjoint_points(P, G[0], **hkw)] + list(e.deform_adjoint_points(P, G[0], want_grad_f=True, **hkw))
+    for want_f in (False, True):
+        o_gP, o_gf = fresh((N, 3), torch.float64), fresh((N,), torch.float64)
+        e.deform_adjoint_points_dev(N, ptr(d_P), ptr(d_G), ptr(o_gP), d_grad_f=ptr(o_gf) if want_f else 0, **dkw); sync()
+        res += [o_gP, o_gf]
+    out.append(("adjoint_points", digest(res)))
 
     # gram
     res = []
@@ -185,16 +204,15 @@ def main():
         sys.exit("no GPU")
     DEV = torch.device("cuda", 0)
     cases = list(mesh_cases())
-    for name, kind, params in MODELS:
-        for M in CENTRES:
-            e = engine(kind, params, M)
-            n = int(e.L.fd_model_centres(e.ctx)) + 4
-            with_fits = M in FIT_CENTRES
-            S = e.solve_operator() if with_fits else None
-            for c in cases:
-                for op, h in run_case(e, c, n, with_fits, S):
-                    print("%-11s M=%-3d %s %-12s %s" % (name, M, c["label"], op, h), flush=True)
-            e.close()
+    for (name, kind, params), M in [(m, M) for m in MODELS for M in CENTRES] + [(m, 60) for m in KIND_MODELS]:
+        e = engine(kind, params, M)
+        n = int(e.L.fd_model_centres(e.ctx)) + 4
+        with_fits = M in FIT_CENTRES and (name, kind, params) in MODELS
+        S = e.solve_operator() if with_fits else None
+        for c in cases:
+            for op, h in run_case(e, c, n, with_fits, S):
+                print("%-11s M=%-3d %s %-14s %s" % (name, M, c["label"], op, h), flush=True)
+        e.close()
     # the adjoint over a second 512-centre span
     e = engine(capi.KERNEL_THIN_PLATE, [], 520)
     c = [c for c in cases if c["N"] == 1000][-1]
@@ -204,7 +222,7 @@ def main():
     e.deform_adjoint_dev(1000, ptr(d_P), ptr(d_G), ptr(o_W), d_dist2=ptr(d_d2), d_tu=ptr(d_fr[0]), d_tv=ptr(d_fr[1]), d_nrm=ptr(d_fr[2]),
                          radius2=RADIUS2, falloffrate=RATE)
     torch.cuda.synchronize()
-    print("%-11s M=%-3d %s %-12s %s" % ("thin_plate", 520, c["label"], "adjoint", digest([host, o_W])), flush=True)
+    print("%-11s M=%-3d %s %-14s %s" % ("thin_plate", 520, c["label"], "adjoint", digest([host, o_W])), flush=True)
     e.close()
 
 
