@@ -112,6 +112,7 @@ EXPORTS = [
     "fd_batch_deform_shared_ml_dev", "fd_shared_ml_kernel_name",
     "fd_batch_deform_shared_ml_fp64_dev", "fd_shared_ml_fp64_kernel_name",
     "fd_batch_deform_vectors_shared_fp64_dev", "fd_shared_vectors_fp64_kernel_name",
+    "fd_batch_deform_adjoint_points_shared_dev", "fd_shared_adjoint_points_kernel_name",
     "fd_batch_deform_vectors_shared_ml_fp64_dev", "fd_shared_vectors_ml_fp64_kernel_name",
     "fd_batch_deform_vectors_shared_ml_dev", "fd_shared_vectors_ml_kernel_name",
     "fdsop_create", "fdsop_destroy", "fdsop_set_float", "fdsop_set_int", "fdsop_set_string",
@@ -267,6 +268,9 @@ def load() -> C.CDLL:
     L.fd_batch_deform_vectors_shared_fp64_dev.argtypes = [vp, vp, i64, vp, pv, vp, pv, vp, vp, vp, C.c_float, C.c_float, C.POINTER(FdBatchVectors)]
     L.fd_batch_deform_vectors_shared_fp64_dev.restype = i32
     L.fd_shared_vectors_fp64_kernel_name.argtypes = [i32, i32, i32]; L.fd_shared_vectors_fp64_kernel_name.restype = C.c_char_p
+    L.fd_batch_deform_adjoint_points_shared_dev.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, vp]
+    L.fd_batch_deform_adjoint_points_shared_dev.restype = i32
+    L.fd_shared_adjoint_points_kernel_name.argtypes = [i32, i32, i32]; L.fd_shared_adjoint_points_kernel_name.restype = C.c_char_p
     L.fd_batch_deform_vectors_shared_ml_fp64_dev.argtypes = [vp, vp, i64, vp, pv, vp, pv, vp, vp, vp, C.c_float, C.c_float, C.POINTER(FdBatchVectors)]
     L.fd_batch_deform_vectors_shared_ml_fp64_dev.restype = i32
     L.fd_shared_vectors_ml_fp64_kernel_name.argtypes = [i32, i32, i32]; L.fd_shared_vectors_ml_fp64_kernel_name.restype = C.c_char_p
@@ -890,6 +894,17 @@ class Batch:
         for the vectors."""
         self.deform_vectors_shared_dev(N, d_P_in, d_P_out, _call="fd_batch_deform_vectors_shared_fp64_dev", **kw)
 
+    def deform_adjoint_points_shared_dev(self, N: int, d_P_in: int, d_G: int, d_grad_P: int, d_dist2: int = 0, d_tangents=None,
+                                         radius2=1.0, falloffrate=1.0, stream_ptr: int | None = None):
+        """fd_batch_deform_adjoint_points_shared_dev: grad_P = sum_f A_f^T g_f over the batch's frames of one mesh and one
+        rest rig.  Device pointers (ints): d_G is n x N x 3 float32, frame-major; d_grad_P N x 3 float64; d_tangents =
+        (tu, tv, nrm) or None.  Asynchronous on stream_ptr (None: context 0's)."""
+        vp = C.c_void_p
+        tu, tv, nr = d_tangents if d_tangents is not None else (0, 0, 0)
+        self._check(self.L.fd_batch_deform_adjoint_points_shared_dev(self.h, vp(stream_ptr or 0), N, vp(d_P_in or None), vp(d_G or None),
+                                                                     vp(d_dist2 or None), vp(tu or None), vp(tv or None), vp(nr or None),
+                                                                     float(radius2), float(falloffrate), vp(d_grad_P or None)))
+
     def deform_vectors_shared_ml_fp64_dev(self, N: int, d_P_in: int, d_P_out, **kw):
         """fd_batch_deform_vectors_shared_ml_fp64_dev: deform_vectors_shared_fp64_dev's arguments (same keywords); a shot of
         multilayer models gets its positions and its vectors in fp64 by one launch each, anything else exactly what
@@ -1086,6 +1101,11 @@ class Morph:
 def fd_shared_vectors_kernel_name(M: int, frames: int, kind: int) -> str:
     """The kernel fd_batch_deform_vectors_shared_dev's vector launch takes ("" where it runs the per-context launches)."""
     return load().fd_shared_vectors_kernel_name(int(M), int(frames), int(kind)).decode()
+
+
+def fd_shared_adjoint_points_kernel_name(M: int, frames: int, kind: int) -> str:
+    """The kernel fd_batch_deform_adjoint_points_shared_dev's one launch takes ("" where it runs the per-context launches)."""
+    return load().fd_shared_adjoint_points_kernel_name(int(M), int(frames), int(kind)).decode()
 
 
 def fd_shared_vectors_fp64_kernel_name(M: int, frames: int, kind: int) -> str:

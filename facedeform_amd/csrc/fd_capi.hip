@@ -207,6 +207,7 @@ struct fd_batch {
     ShotScratch s64;                     // fd_batch_deform_shared_fp64_dev
     ShotScratch sml;                     // fd_batch_deform_shared_ml_dev, for the multilayer shot launch
     ShotScratch sml64;                   // fd_batch_deform_shared_ml_fp64_dev, for the fp64 multilayer shot launch
+    ShotScratch sadjp;                   // fd_batch_deform_adjoint_points_shared_dev: its pack kernel's copy, or the per-context route's one-frame result
     Event group_ev;                      // fd_batch_cook_group: behind the group's builds, for the evaluation stream
     // fd_batch_cook_group with the evaluation on the build stream itself (one unpipelined group): stream order does what the
     // events between build, packing and evaluation do across streams, and every event record is a barrier packet that keeps the
@@ -1549,7 +1550,7 @@ static void fill_eval_common(SharedEvalCommon &a, const fd_batch *b, const ShotS
 {
     fill_mesh(a, N, d_P_in, d_dist2, d_tu, d_tv, d_nrm, radius2, falloffrate);
     a.nF = b->n;
-    for (int i = 0; i < b->n; ++i) { a.model[i] = b->ctxs[i]->d_model; a.P_out[i] = d_P_out[i]; }
+    for (int i = 0; i < b->n; ++i) { a.model[i] = b->ctxs[i]->d_model; a.P_out[i] = d_P_out ? d_P_out[i] : nullptr; }      // (no table: a call without position outputs)
     a.falloff_out = d_falloff_out;
     a.delta_out = b->ctxs[0]->output == FD_OUTPUT_DISPLACEMENT;
     a.max_wgs = b->eval_cus;
@@ -2871,6 +2872,24 @@ static bool shared64_fast(const fd_batch *b)
     return fast;
 }
 
+// every context holds a model (built or being built) of ONE rest rig: each read its rest points in place from the SAME device
+// array (as fd_batch_deform_shared_dev), with one kernel and term; `outputs`: and one fd_set_output setting
+static int shot_check_rig(fd_batch *b, const char *who, bool outputs)
+{
+    const fd_ctx *c0 = b->ctxs[0];
+    for (int i = 0; i < b->n; ++i) {
+        const fd_ctx *c = b->ctxs[i];
+        if (!c->built && !c->build_pending) { batch_err(b, "%s: context %d has no built model", who, i); return FD_E_NOT_BUILT; }
+        if (!c->rest_src || c->rest_src != c0->rest_src || !same_model(c, c0)) {
+            batch_err(b, "%s: the contexts must share one rest rig (fd_batch_set_points_dev with the "
+                         "same rest array for all), kernel and term; context %d does not", who, i);
+            return FD_E_INVALID;
+        }
+        if (outputs && c->output != c0->output) { batch_err(b, "%s: context %d has another fd_set_output setting than context 0", who, i); return FD_E_INVALID; }
+    }
+    return FD_OK;
+}
+
 int fd_batch_deform_shared_fp64_dev(fd_batch *b, void *hip_stream, int64_t N, const float *d_P_in, float *const *d_P_out,
                                     const float *d_dist2, float *const *d_falloff_out, const float *d_tu, const float *d_tv,
                                     const float *d_nrm, float radius2, float falloffrate)
@@ -2886,17 +2905,7 @@ int fd_batch_deform_shared_fp64_dev(fd_batch *b, void *hip_stream, int64_t N, co
     if (rc) { batch_err(b, "%s", c0->err); return rc; }
     hipStream_t stream = hip_stream ? (hipStream_t)hip_stream : cur_stream(c0);
     const bool fast = shared64_fast(b);
-    for (int i = 0; i < b->n; ++i) {
-        fd_ctx *c = b->ctxs[i];
-        if (!c->built && !c->build_pending) { batch_err(b, "%s: context %d has no built model", who, i); return FD_E_NOT_BUILT; }
-        // one rest rig: every context read its rest points in place from the SAME device array (as fd_batch_deform_shared_dev)
-        if (!c->rest_src || c->rest_src != c0->rest_src || !same_model(c, c0)) {
-            batch_err(b, "%s: the contexts must share one rest rig (fd_batch_set_points_dev with the "
-                         "same rest array for all), kernel and term; context %d does not", who, i);
-            return FD_E_INVALID;
-        }
-        if (c->output != c0->output) { batch_err(b, "%s: context %d has another fd_set_output setting than context 0", who, i); return FD_E_INVALID; }
-    }
+    if ((rc = shot_check_rig(b, who, true))) return rc;
     ShotScratch &sc = b->s64;
     if ((rc = shot_begin(b, who, sc, stream))) return rc;
     if (!fast) {
@@ -2977,6 +2986,68 @@ const char *fd_shared_vectors_fp64_kernel_name(int M, int frames, int kind)
 {
     if (M <= 0 || !shared64_kind(kind)) return "";
     return shared_vectors64_kernel_name(round_up(M, kRecPad), frames, kind);
+}
+
+// ---- the adjoint in the vertex positions summed over the frames of a shot (fd_adjoint_points_shot.hip) ----
+// grad_P = sum_f A_f^T g_f by one matrix-pipe launch on a scratch of its own; where that launch does not apply (the multilayer
+// model, an eval_variant override, fewer frames than shared_adjoint_points_min_frames), launch_adjoint_points per context and
+// the additions in frame order
+int fd_batch_deform_adjoint_points_shared_dev(fd_batch *b, void *hip_stream, int64_t N, const float *d_P_in, const float *d_G,
+                                              const float *d_dist2, const float *d_tu, const float *d_tv, const float *d_nrm,
+                                              float radius2, float falloffrate, double *d_grad_P)
+{
+    if (!b) return FD_E_INVALID;
+    const char *who = "fd_batch_deform_adjoint_points_shared_dev";
+    if (!d_G || !d_grad_P) { batch_err(b, "%s: bad G / grad_P pointers", who); return FD_E_INVALID; }
+    int rc = shot_check_mesh(b, who, N, d_P_in, d_tu, d_tv, d_nrm);
+    if (rc) return rc;
+    for (const void *in : {(const void *)d_P_in, (const void *)d_G, (const void *)d_dist2, (const void *)d_tu, (const void *)d_tv, (const void *)d_nrm})
+        if (in && in == (const void *)d_grad_P) { batch_err(b, "%s: grad_P is an input array", who); return FD_E_INVALID; }
+    if ((rc = shot_check_rig(b, who, false))) return rc;
+    if (N == 0) return FD_OK;
+    fd_ctx *c0 = b->ctxs[0];
+    rc = use_device(c0);
+    if (rc) { batch_err(b, "%s", c0->err); return rc; }
+    hipStream_t stream = hip_stream ? (hipStream_t)hip_stream : cur_stream(c0);
+    ShotScratch &sc = b->sadjp;
+    if ((rc = shot_begin(b, who, sc, stream))) return rc;
+    if (!shared64_fast(b) || b->n < shared_adjoint_points_min_frames(eval_kind(c0))) {
+        // frame 0 into grad_P, every later frame into the scratch and added: the frame-ordered sum of the one-frame results
+        if (b->n > 1 && (rc = shot_reserve(b, who, sc, sizeof(double) * 3 * (size_t)N, stream))) return rc;
+        for (int i = 0; i < b->n; ++i) {
+            const DeformArgs a = deform_args(b->ctxs[i], Mesh{N, d_P_in, d_dist2, d_tu, d_tv, d_nrm, radius2, falloffrate}, nullptr, nullptr);
+            double *dst = i == 0 ? d_grad_P : (double *)(void *)sc.d;
+            hipError_t e = launch_adjoint_points(a, AdjointPointsArgs{d_G + (size_t)i * (size_t)N * 3, dst, nullptr}, stream);
+            if (e == hipSuccess && i > 0) e = launch_adjoint_points_add(d_grad_P, dst, 3 * N, stream);
+            if (e != hipSuccess) { batch_err(b, "launch_adjoint_points failed: %s", hipGetErrorString(e)); return FD_E_DEVICE; }
+        }
+        // these launches read the models to their end
+        if (hipEventRecord(sc.consumed_ev, stream) != hipSuccess) { (void)hipGetLastError(); return FD_E_DEVICE; }
+        sc.consumed = true;
+        if (b->n > 1) sc.eval_pending = record_eval(sc.eval_ev, stream);
+        return FD_OK;
+    }
+    SharedAdjointPointsArgs a{};
+    a.M = c0->M; a.Mpad = round_up(c0->M, kRecPad); a.kind = eval_kind(c0);
+    const bool same_rig = one_build(b);
+    for (int i = 0; i < b->n; ++i) {
+        fd_ctx *c = b->ctxs[i];
+        a.rec64[i] = c->d_rec64;
+        a.centres[i] = same_rig ? c0->d_centres : c->d_centres;       // (one batched build read one array: equal by construction)
+    }
+    if ((rc = shot_reserve(b, who, sc, shared_adjoint_points_scratch_bytes(a.Mpad, b->n), stream))) return rc;
+    fill_eval_common(a, b, sc, N, d_P_in, nullptr, d_dist2, nullptr, d_tu, d_tv, d_nrm, radius2, falloffrate);
+    a.G = d_G; a.grad_P = d_grad_P;
+    hipError_t e = launch_adjoint_points_shared(a, stream);
+    if (e != hipSuccess) { batch_err(b, "launch_adjoint_points_shared failed: %s", hipGetErrorString(e)); return FD_E_DEVICE; }
+    shot_evaluated(sc, stream);
+    return FD_OK;
+}
+
+const char *fd_shared_adjoint_points_kernel_name(int M, int frames, int kind)
+{
+    if (M <= 0 || !shared64_kind(kind)) return "";
+    return shared_adjoint_points_kernel_name(round_up(M, kRecPad), frames, kind);
 }
 
 // ---- every frame of a shot of multilayer models by one matrix-pipe launch (fd_eval_shared_ml.hip) ----
@@ -3184,9 +3255,9 @@ int fd_batch_wait_consumed(fd_batch *b, void *hip_stream)
     if (!b) return FD_E_INVALID;
     hipEvent_t ev = b->consumed_override ? b->consumed_override : (b->packed_valid ? b->sets[b->cur_set].packed_ev : b->fallback_ev);
     // ... and the reads of the calls that keep a scratch of their own as well
-    hipEvent_t evs[4] = {ev, nullptr, nullptr, nullptr};
+    hipEvent_t evs[5] = {ev, nullptr, nullptr, nullptr, nullptr};
     int n_ev = ev ? 1 : 0;
-    for (const ShotScratch *sc : {&b->s64, &b->sml, &b->sml64})
+    for (const ShotScratch *sc : {&b->s64, &b->sml, &b->sml64, &b->sadjp})
         if (sc->consumed) evs[n_ev++] = sc->consumed_ev;
     if (n_ev == 0) return FD_OK;                 // no shared-rig evaluation enqueued: nothing reads the models beyond stream order
     fd_ctx *c0 = b->ctxs[0];

@@ -424,6 +424,23 @@ struct SharedVector64Args : SharedVectorCommon {
 hipError_t launch_vectors_shared64(const SharedVector64Args &a, hipStream_t stream);
 const char *shared_vectors64_kernel_name(int Mpad, int nF, int kind);      // "" below shared_vectors64_min_frames too
 int shared_vectors64_min_frames(int kind);                                  // fewer frames: the per-context launches are faster
+// The adjoint in the vertex positions summed over the frames of that batch, grad_P = sum_f A_f^T g_f, in fp64 by one
+// matrix-pipe launch (fd_adjoint_points_shot.hip, fd_batch_deform_adjoint_points_shared_dev): a pack kernel copies what the
+// launch needs of the models into `scratch` (shared_adjoint_points_scratch_bytes, a scratch of this call's own; packed_ev is
+// recorded behind it), the main launch reads only that copy.  P_out, falloff_out and delta_out are not looked at.
+struct SharedAdjointPointsArgs : SharedEvalCommon {
+    int M, Mpad, kind;                    // kind: any but the multilayer model's
+    const Rec64 *rec64[kMaxBatch];
+    const double *centres[kMaxBatch];     // as Shared64Args::centres; a frame that differs contributes g_f alone
+    const float *G;                       // nF x N x 3, frame-major
+    double *grad_P;                       // N x 3
+};
+hipError_t launch_adjoint_points_shared(const SharedAdjointPointsArgs &a, hipStream_t stream);
+size_t shared_adjoint_points_scratch_bytes(int Mpad, int nF);
+const char *shared_adjoint_points_kernel_name(int Mpad, int nF, int kind);  // "" below shared_adjoint_points_min_frames too
+int shared_adjoint_points_min_frames(int kind);                             // fewer frames: the per-context launches are faster
+// sum[i] += term[i], i < n: the per-context route of that call adds the one-frame results in frame order with it
+hipError_t launch_adjoint_points_add(double *sum, const double *term, int64_t n, hipStream_t stream);
 // Every frame of a shared-rig batch of MULTILAYER models by one matrix-pipe launch (fd_eval_shared_ml.hip,
 // fd_batch_deform_shared_ml_dev): a pack kernel copies what the launch needs of the models into `scratch`
 // (shared_ml_scratch_bytes; packed_ev is recorded behind it, may be null), the evaluation reads only that copy.

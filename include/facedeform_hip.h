@@ -1069,6 +1069,62 @@ int fd_batch_deform_vectors_shared_ml_fp64_dev(fd_batch *batch, void *hip_stream
  * the threshold above).  It sees no context: another kind, an imported model or an eval_variant override delegate
  * whatever this returns.  For tests and profiles. */
 const char *fd_shared_vectors_ml_fp64_kernel_name(int M, int layers, int frames);
+/* The adjoint of the deformation in the vertex positions, summed over the frames of a shot:
+ *     grad_P[v] = sum_f A_{f,v}^T g_{f,v},      A_f = I + f Pi J_f(x) the Jacobian of frame f's map (fd_deform_vectors),
+ * for the batch's n contexts, which hold n models of ONE rest rig (the condition of fd_batch_deform_shared_fp64_dev: the same
+ * in-place rest array, kernel and term; FD_E_INVALID otherwise), on one mesh with one dist2, one set of projection frames,
+ * one radius2 and one falloffrate.  It is the gradient that moves the rest mesh or the evaluation points against n scans
+ * at once, and what autograd returns for P when P feeds n frames.  With r_{f,v} = f_v Pi_v g_{f,v}:
+ *     grad_P[v] = sum_f g_{f,v}  +  sum_{f built} J_f(x_v)^T r_{f,v}.
+ *   d_G: n x N x 3 fp32, frame-major (frame f's cotangents at d_G + 3 N f, context f's), as fd_deform_adjoint_shot takes
+ *     them.  d_grad_P: N x 3 fp64.  d_P_in, d_dist2, d_tu, d_tv, d_nrm, radius2, falloffrate: as for fd_deform_dev.
+ *   Arithmetic: everything is fp64; positions and G are widened; x - c_j in raw coordinates on the fp64 records; phi' of
+ *     the kind from its one transcendental, as fd_deform_adjoint_points forms it; gate, fall-off and projection axes are
+ *     the forward path's own code.
+ *   One launch: for thin-plate, Gaussian, QNN, biharmonic and cubic models (any term, any M, no eval_variant override)
+ *     from 2 frames upwards (the threshold of every kind.  Measured at 1M vertices and 256 centres with dist2 and frames, device
+ *     events, medians of 25, the launch against n one-frame launches plus the additions: thin-plate 1.01 / 0.82 ms at 1
+ *     frame (0.81x), 1.01 / 1.60 ms at 2 (1.59x), 2.08 / 24.1 ms at 32 (11.6x); QNN 0.51 / 0.34 ms at 1 (0.66x),
+ *     0.51 / 0.67 ms at 2 (1.33x), 1.55 / 9.88 ms at 32 (6.4x); biharmonic 0.71x at 1, 1.42x at 2; cubic 0.63x at 1,
+ *     1.27x at 2), a pack kernel copies the
+ *     frames' fp64 weights, the centre records, the affine parts and the frames' status into scratch of the batch that
+ *     only this call uses, and one persistent launch reads that copy alone.  The sum over the frames is taken inside the
+ *     sum over the centres:
+ *         sum_f J_f^T r_f = gs sum_j g_j(x) (x - c_j) s_j + sum_f L_f^T r_f,     s_j = sum_{f,b} w_{f,j,b} r_{f,b},
+ *     s and sum_f L_f^T r_f on v_mfma_f64_16x16x4_f64 (depth 3 n), the basis g_j(x) (x - c_j) once per (vertex, centre)
+ *     whatever n is.  The result differs from the sum of n fd_deform_adjoint_points_dev results only by the order and
+ *     association of the fp64 additions; it is not bit-equal to it.
+ *   Everywhere else -- the multilayer model, an eval_variant override, fewer frames -- the call runs
+ *     fd_deform_adjoint_points_dev's launch per context and adds the n results in frame order, ((p_0 + p_1) + p_2) + ...:
+ *     bit for bit that sum.  (With one frame: bit for bit fd_deform_adjoint_points_dev.)
+ *   Vertices where every A_f = I -- gated vertices, vertices with f = 0, all vertices when no frame is built: grad_P[v] is
+ *     the fp64 sum of the widened g_{f,v} in frame order, (g_0 + g_1) + g_2 ..., and nothing else.  A select, not a
+ *     product: NaN or infinity in the weights or the basis cannot reach it, nor can the G of such a vertex reach another.
+ *     With one frame this is g widened, bit for bit.  A frame whose model is not built (terminationtype != 1, or centres
+ *     that differ from context 0's) contributes g_{f,v} only, with FD_OK; the status arrives with the next call, as for
+ *     fd_batch_deform_shared_fp64_dev.
+ *   Bits: no atomics.  A vertex's result depends on its own inputs, n and the models only: the same bits for any N, in one
+ *     range or in two, at any place in the launch, on every call, with any fd_batch_set_eval_cus.
+ *   Checks, errors, the status poll and repair and the ordering of hip_stream behind the batch's builds are those of
+ *     fd_batch_deform_shared_fp64_dev.  FD_E_INVALID before any device work: a NULL batch, a NULL d_G or d_grad_P, N < 0,
+ *     a NULL d_P_in with N > 0, some but not all of d_tu / d_tv / d_nrm, d_grad_P equal to an input array (no aliasing is
+ *     allowed), contexts of different rest arrays, kernels or terms.  N = 0 writes nothing.  fd_set_output has no effect.
+ *   Reads of the models: the one launch reads only its scratch, the mesh and G; fd_batch_wait_consumed covers this call as
+ *     it covers fd_batch_deform_shared_fp64_dev (on the per-context route its event lies behind the last launch), and
+ *     the next call's pack kernel waits for this call's own event before it rewrites the scratch.
+ *   Out of scope: per-frame outputs A_f^T g_f (n calls of fd_deform_adjoint_points_dev, or the Jacobian of
+ *     fd_batch_deform_vectors_shared_fp64_dev); grad_f per frame; a one-launch multilayer form; fp32 accumulation;
+ *     host-array forms; fdsop_* and the HDK wrapper.
+ * Asynchronous on hip_stream (NULL: context 0's). */
+int fd_batch_deform_adjoint_points_shared_dev(fd_batch *batch, void *hip_stream, int64_t N, const float *d_P_in,
+                                              const float *d_G, const float *d_dist2,
+                                              const float *d_tu, const float *d_tv, const float *d_nrm,
+                                              float radius2, float falloffrate, double *d_grad_P);
+/* The kernel the one launch of fd_batch_deform_adjoint_points_shared_dev takes for M centres, `frames` contexts and `kind`
+ * ("k_adjoint_points64_shot"), or "" where the per-context launches run (M <= 0, frames outside 1..FD_MAX_BATCH or below the
+ * threshold above, the multilayer kind).  It sees no context: an eval_variant override takes the per-context route
+ * whatever this returns.  For tests and profiles. */
+const char *fd_shared_adjoint_points_kernel_name(int M, int frames, int kind);
 /* Makes hip_stream (NULL: context 0's) wait until the batch's last fd_batch_deform_shared_dev no longer reads the
  * contexts' models: that launch copies what it needs of them (weights as fp16 tiles, the rest rig's centre tiles)
  * into the batch's own scratch with a first small kernel, and the evaluation proper reads only that copy.  A pipeline
