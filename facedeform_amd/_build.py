@@ -10,7 +10,7 @@ _ROOT = os.path.dirname(_PKG)
 CSRC = os.path.join(_PKG, "csrc")
 LIB_DIR = os.path.join(_PKG, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libfacedeform_hip.so")
-SOURCES = ["fd_eval.hip", "fd_eval_shared.hip", "fd_build.hip", "fd_nullspace.hip", "fd_build_reg.hip", "fd_build_ml_shared.hip", "fd_build_qnn_shared.hip", "fd_capi.hip", "fd_morph.hip", "fd_capture.hip", "fd_vectors.hip", "fd_invert.hip", "fd_adjoint.hip", "fd_adjoint_points.hip", "fd_adjoint_shot.hip", "fd_adjoint_points_shot.hip", "fd_gram.hip", "fd_vectors_shared.hip", "fd_eval_shared64.hip", "fd_vectors_shared64.hip", "fd_eval_shared_ml.hip", "fd_vectors_shared_ml.hip", "fd_eval_shared_ml64.hip", "fd_vectors_shared_ml64.hip", "fd_sop_host.cpp"]
+SOURCES = ["fd_eval.hip", "fd_eval_shared.hip", "fd_build.hip", "fd_nullspace.hip", "fd_build_reg.hip", "fd_build_ml_shared.hip", "fd_build_qnn_shared.hip", "fd_capi.hip", "fd_morph.hip", "fd_capture.hip", "fd_vectors.hip", "fd_invert.hip", "fd_adjoint.hip", "fd_adjoint_points.hip", "fd_adjoint_shot.hip", "fd_adjoint_points_shot.hip", "fd_gram.hip", "fd_bake.hip", "fd_vectors_shared.hip", "fd_eval_shared64.hip", "fd_vectors_shared64.hip", "fd_eval_shared_ml.hip", "fd_vectors_shared_ml.hip", "fd_eval_shared_ml64.hip", "fd_vectors_shared_ml64.hip", "fd_sop_host.cpp"]
 # per-file extras: keep the bf16 MFMA results of the evaluation kernel in VGPRs (the default puts
 # them in AGPRs and pays one v_accvgpr_read per value)
 EXTRA_FLAGS = {"fd_eval.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
@@ -32,7 +32,7 @@ EXTRA_FLAGS = {"fd_eval.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
                "fd_adjoint_points.hip": ["-mllvm", "-disable-machine-licm"],
                # the same constants under the 3 NQ operand registers of the shot form
                "fd_adjoint_points_shot.hip": ["-mllvm", "-disable-machine-licm"]}
-HEADERS = [os.path.join(CSRC, "fd_internal.h"), os.path.join(CSRC, "fd_tuning.h"), os.path.join(CSRC, "fd_pack.h"), os.path.join(CSRC, "fd_eval_common.h"), os.path.join(CSRC, "fd_transport.h"), os.path.join(CSRC, "fd_eval_point.h"), os.path.join(CSRC, "fd_shot_launch.h"), os.path.join(CSRC, "fd_vectors_shot.h"), os.path.join(CSRC, "fd_shared64.h"), os.path.join(CSRC, "fd_shared_ml64.h"), os.path.join(CSRC, "fd_shared_ml.h"), os.path.join(CSRC, "fd_shared_common.h"), os.path.join(CSRC, "fd_shared_plan.h"), os.path.join(CSRC, "fd_shared_solve.h"), os.path.join(CSRC, "fd_shot_dev.h"), os.path.join(CSRC, "fd_fit_host.h"), os.path.join(CSRC, "fd_owned.h"), os.path.join(CSRC, "fd_operator.h"), os.path.join(CSRC, "fd_adjoint_points_shot.h"), os.path.join(_ROOT, "include", "facedeform_hip.h")]
+HEADERS = [os.path.join(CSRC, "fd_internal.h"), os.path.join(CSRC, "fd_tuning.h"), os.path.join(CSRC, "fd_pack.h"), os.path.join(CSRC, "fd_eval_common.h"), os.path.join(CSRC, "fd_transport.h"), os.path.join(CSRC, "fd_eval_point.h"), os.path.join(CSRC, "fd_shot_launch.h"), os.path.join(CSRC, "fd_vectors_shot.h"), os.path.join(CSRC, "fd_shared64.h"), os.path.join(CSRC, "fd_shared_ml64.h"), os.path.join(CSRC, "fd_shared_ml.h"), os.path.join(CSRC, "fd_shared_common.h"), os.path.join(CSRC, "fd_shared_plan.h"), os.path.join(CSRC, "fd_shared_solve.h"), os.path.join(CSRC, "fd_shot_dev.h"), os.path.join(CSRC, "fd_fit_host.h"), os.path.join(CSRC, "fd_owned.h"), os.path.join(CSRC, "fd_operator.h"), os.path.join(CSRC, "fd_adjoint_points_shot.h"), os.path.join(CSRC, "fd_bake_plan.h"), os.path.join(_ROOT, "include", "facedeform_hip.h")]
 
 
 def hipcc_path() -> str:

@@ -120,6 +120,9 @@ struct fd_ctx {
     // fd_deform_gram*: the workgroups' partial blocks and, behind them, the host call's staging of H (gram_scratch); the host
     // call's omega goes through d_fall
     DevBuf<double> d_gram;
+    // fd_deform_bake*: the pack kernel's scratch (bake_scratch_doubles) and, behind it, the host call's copy of S; the host
+    // call's vertex chunk of B and, behind it, of B32 comes back through d_bakeout
+    DevBuf<double> d_bake, d_bakeout;
     // fd_deform_adjoint_shot*: the ranges' partial blocks of one group of frames and, behind them, the host call's staging of
     // grad_W (adjoint_shot_scratch); the host call's G goes group by group through d_gshot
     DevBuf<double> d_adjs;
@@ -1000,6 +1003,18 @@ static bool adjoint_points_opts_ok(fd_ctx *ctx, const fd_adjoint_points_opts *op
     return true;
 }
 
+// fd_deform_bake*: NULL opts (B alone), or a struct of at least this ABI's size; B or B32, one at least
+static bool bake_outputs_ok(fd_ctx *ctx, const double *B, const fd_bake_opts *opts)
+{
+    if (opts && opts->struct_size < (int)sizeof(fd_bake_opts)) {
+        set_err(ctx, "fd_deform_bake: opts->struct_size is %d, must be sizeof(fd_bake_opts) = %d", opts->struct_size,
+                (int)sizeof(fd_bake_opts));
+        return false;
+    }
+    if (!B && !(opts && opts->B32)) { set_err(ctx, "fd_deform_bake: B and opts->B32 are both NULL"); return false; }
+    return true;
+}
+
 // The scratch of the adjoint, the Gram operator and the shot adjoint for N vertices and C records: the workgroups' partial blocks
 // and, behind them, room for the result, where the host call stages it (*_staging).  Grown on demand (DevBuf::grow).
 // fd_deform_adjoint*: adjoint_groups(N) partial blocks of (C + 4) x 3 doubles and one more for grad_W
@@ -1119,6 +1134,20 @@ static int gram_dev(fd_ctx *ctx, const char *who, const Mesh &m, const float *d_
     if ((rc = dev_alloc(ctx, ctx->d_gram, gram_scratch(m.N, a.M, m.tu ? 6 : 1), kGrow))) return rc;
     const GramArgs g{d_omega, d_H, ctx->d_gram, term_cols(ctx->term)};
     FD_HIP(ctx, launch_gram(a, g, s));
+    return FD_OK;
+}
+
+// fd_deform_bake_dev: the pack kernel and the one launch; nothing is written for an empty mesh
+static int bake_dev(fd_ctx *ctx, const char *who, const Mesh &m, const double *d_S, double *d_B, float *d_B32)
+{
+    DeformArgs a;
+    hipStream_t s;
+    int rc = deform_begin(ctx, who, nullptr, m, nullptr, nullptr, true, &a, &s);
+    if (rc || m.N == 0) return rc;
+    if ((rc = dev_alloc(ctx, ctx->d_bake, bake_scratch_doubles(a.M, ctx->M), kGrow))) return rc;
+    const BakeArgs g{d_S, ctx->M, term_cols(ctx->term), ctx->d_bake, d_B, d_B32};
+    FD_HIP(ctx, launch_bake_pack(a, g, s));
+    FD_HIP(ctx, launch_bake(a, g, s));
     return FD_OK;
 }
 
@@ -1344,6 +1373,55 @@ static int gram_host(fd_ctx *ctx, const char *who, const Mesh &m, const float *o
     return gram_staged(ctx, who, d, omega ? ctx->d_fall : nullptr, H);
 }
 
+// fd_deform_bake on host arrays: S (computed here where the caller has none) goes up behind the pack kernel's scratch, is packed
+// once, and B and B32 come back in chunks of vertices through d_bakeout (bake_chunk_vertices: the block stays within the
+// operators' scratch bound).  A vertex's row depends on nothing else in the launch, so the chunks are the bits of one launch.
+static int bake_host(fd_ctx *ctx, const char *who, const Mesh &m, const double *S, double *B, float *B32)
+{
+    int rc = mesh_checks(ctx, who, m, true);
+    if (rc || m.N == 0) return rc;
+    const int C = model_centres(ctx), M = ctx->M;
+    const size_t s_doubles = (size_t)(C + 4) * (size_t)M;
+    std::vector<double> S_own;
+    if (!S) {
+        S_own.resize(s_doubles);
+        if ((rc = fd_solve_operator(ctx, S_own.data()))) return rc;
+        S = S_own.data();
+    }
+    if ((rc = use_device(ctx))) return rc;
+    hipStream_t s = cur_stream(ctx);
+    Mesh d;
+    if ((rc = stage_mesh(ctx, m, s, &d))) return rc;
+    DeformArgs a;
+    hipStream_t launch_stream;
+    if ((rc = deform_begin(ctx, who, nullptr, d, nullptr, nullptr, true, &a, &launch_stream))) return rc;
+    const size_t scratch = bake_scratch_doubles(C, M);
+    if ((rc = dev_alloc(ctx, ctx->d_bake, scratch + s_doubles, kGrow))) return rc;
+    const int64_t per = bake_chunk_vertices(M, B != nullptr, B32 != nullptr);
+    const size_t chunk = (size_t)(m.N < per ? m.N : per) * (size_t)M;
+    if ((rc = dev_alloc(ctx, ctx->d_bakeout, (B ? chunk : 0) + (B32 ? (chunk + 1) / 2 : 0), kGrow))) return rc;
+    double *d_S = ctx->d_bake + scratch;
+    double *d_B = B ? ctx->d_bakeout.p : nullptr;
+    float *d_B32 = B32 ? reinterpret_cast<float *>(ctx->d_bakeout + (B ? chunk : 0)) : nullptr;
+    FD_HIP(ctx, hipMemcpyAsync(d_S, S, sizeof(double) * s_doubles, hipMemcpyHostToDevice, s));
+    BakeArgs g{d_S, M, term_cols(ctx->term), ctx->d_bake, d_B, d_B32};
+    FD_HIP(ctx, launch_bake_pack(a, g, s));
+    for (int64_t v0 = 0; v0 < m.N; v0 += per) {
+        const int64_t n = m.N - v0 < per ? m.N - v0 : per;
+        DeformArgs ac = a;
+        ac.N = n;
+        ac.P_in = d.P + 3 * v0;
+        ac.dist2 = d.dist2 ? d.dist2 + v0 : nullptr;
+        if (d.tu) { ac.tu = d.tu + 3 * v0; ac.tv = d.tv + 3 * v0; ac.nrm = d.nrm + 3 * v0; }
+        FD_HIP(ctx, launch_bake(ac, g, s));
+        const size_t at = (size_t)v0 * (size_t)M, cnt = (size_t)n * (size_t)M;
+        if (B) FD_HIP(ctx, hipMemcpyAsync(B + at, d_B, sizeof(double) * cnt, hipMemcpyDeviceToHost, s));
+        if (B32) FD_HIP(ctx, hipMemcpyAsync(B32 + at, d_B32, sizeof(float) * cnt, hipMemcpyDeviceToHost, s));
+    }
+    FD_HIP(ctx, hipStreamSynchronize(s));
+    return FD_OK;
+}
+
 // The shot adjoint of a mesh that stage_mesh has put on the device, for F cotangents G on the host: G goes through d_gshot
 // one group of FD_MAX_BATCH frames at a time, each group's launches behind its copy on the stream; grad_W of all frames is staged
 // behind the partial blocks and comes back in one copy.  An empty mesh gives zeros and touches no device.
@@ -1506,6 +1584,36 @@ int fd_deform_gram(fd_ctx *ctx, int64_t N, const float *P_in, const float *omega
     if (!ctx) return FD_E_INVALID;
     if (!H || N < 0) { set_err(ctx, "fd_deform_gram: bad N / H pointers"); return FD_E_INVALID; }
     return gram_host(ctx, "fd_deform_gram", Mesh{N, P_in, dist2, tu, tv, nrm, radius2, falloffrate}, omega, H);
+}
+
+// fd_deform_bake*: what both forms check before any device work
+static int bake_checks(fd_ctx *ctx, int64_t N, int M, const void *tu, const void *tv, const void *nrm, const double *B,
+                       const fd_bake_opts *opts)
+{
+    if (N < 0) { set_err(ctx, "fd_deform_bake: N < 0"); return FD_E_INVALID; }
+    if (M != ctx->M) { set_err(ctx, "fd_deform_bake: M is %d, the context has %d control points", M, ctx->M); return FD_E_INVALID; }
+    if (!bake_outputs_ok(ctx, B, opts)) return FD_E_INVALID;
+    if (!frames_ok(tu, tv, nrm)) { set_err(ctx, "fd_deform_bake: tu, tv, nrm must be all set or all NULL"); return FD_E_INVALID; }
+    return FD_OK;
+}
+
+int fd_deform_bake_dev(fd_ctx *ctx, int64_t N, const float *d_P_in, const float *d_dist2, const float *d_tu, const float *d_tv,
+                       const float *d_nrm, float radius2, float falloffrate, const double *d_S, int M, double *d_B,
+                       const fd_bake_opts *opts)
+{
+    if (!ctx) return FD_E_INVALID;
+    if (!d_S) { set_err(ctx, "fd_deform_bake: S is NULL"); return FD_E_INVALID; }
+    if (int rc = bake_checks(ctx, N, M, d_tu, d_tv, d_nrm, d_B, opts)) return rc;
+    return bake_dev(ctx, "fd_deform_bake", Mesh{N, d_P_in, d_dist2, d_tu, d_tv, d_nrm, radius2, falloffrate}, d_S, d_B,
+                    opts ? opts->B32 : nullptr);
+}
+
+int fd_deform_bake(fd_ctx *ctx, int64_t N, const float *P_in, const float *dist2, const float *tu, const float *tv, const float *nrm,
+                   float radius2, float falloffrate, const double *S, int M, double *B, const fd_bake_opts *opts)
+{
+    if (!ctx) return FD_E_INVALID;
+    if (int rc = bake_checks(ctx, N, M, tu, tv, nrm, B, opts)) return rc;
+    return bake_host(ctx, "fd_deform_bake", Mesh{N, P_in, dist2, tu, tv, nrm, radius2, falloffrate}, S, B, opts ? opts->B32 : nullptr);
 }
 
 int fd_deform_adjoint_shot_dev(fd_ctx *ctx, int64_t N, int F, const float *d_P_in, const float *d_G, const float *d_dist2,

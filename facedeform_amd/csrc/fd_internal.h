@@ -337,6 +337,23 @@ struct GramArgs {
 int gram_ranges(int64_t N, int C);    // workgroups along the vertices: a function of N and C alone
 size_t gram_partial_doubles(int64_t N, int C, int nq);
 hipError_t launch_gram(const DeformArgs &a, const GramArgs &g, hipStream_t stream);
+// the deformer baked per vertex (fd_bake.hip, fd_deform_bake*): `a` as for the adjoint (a.M the records C); S the (C + 4) x M
+// solve operator on the device, M its columns (the control points), T as above, scratch bake_scratch_doubles(C, M) doubles; B
+// and B32 the N x M results, either may be null.  launch_bake_pack is the only reader of S and fills the scratch; launch_bake
+// reads the scratch and the mesh of `a` (one launch; N = 0 launches nothing), so one pack serves any number of vertex ranges.
+struct BakeArgs {
+    const double *S;
+    int M, T;
+    double *scratch;
+    double *B;
+    float *B32;
+};
+size_t bake_scratch_doubles(int C, int M);
+// vertices of a chunk of the host call: a multiple of the launch's vertex group whose block of B (b64) and B32 (b32) stays within
+// the operators' scratch bound (one group at least)
+int64_t bake_chunk_vertices(int M, bool b64, bool b32);
+hipError_t launch_bake_pack(const DeformArgs &a, const BakeArgs &g, hipStream_t stream);
+hipError_t launch_bake(const DeformArgs &a, const BakeArgs &g, hipStream_t stream);
 hipError_t launch_deform_batch(const DeformArgs *a, int n, hipStream_t stream);
 // frames that share the mesh and the rest rig (fd_eval.hip, k_deform32_tps_shared): phi once per
 // (vertex, centre), the 3 F-wide weight contraction on the matrix pipe

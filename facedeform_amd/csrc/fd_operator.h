@@ -1,10 +1,10 @@
 // fd_operator.h -- what the one-context operators beside the evaluation share: fd_vectors.hip, fd_invert.hip,
-// fd_adjoint.hip, fd_adjoint_points.hip, fd_adjoint_shot.hip and fd_gram.hip.
+// fd_adjoint.hip, fd_adjoint_points.hip, fd_adjoint_shot.hip, fd_gram.hip and fd_bake.hip.
 //
-// All six rest on one contract: the forward map's gate, fall-off and projection, the same operations.  For all six: the fill
+// All of them rest on one contract: the forward map's gate, fall-off and projection, the same operations.  For all: the fill
 // of the mesh fields from DeformArgs, the kind dispatch, and -- for the files that reduce partial blocks -- the partition of the
-// vertices into ranges and the row rule of the reduce kernels.  For fd_adjoint.hip and fd_invert.hip also the mesh head their
-// parameters begin with, the vertex prologue and Pi r; the other four keep those expressions written out with the argument
+// vertices into ranges and the row rule of the reduce kernels.  For fd_adjoint.hip, fd_invert.hip and fd_bake.hip also the mesh head
+// their parameters begin with and the vertex prologue, for the first two Pi r; the other four keep those expressions written out with the argument
 // layout they had, because with the head their kernels measured slower.  The walks, the LDS layouts, the MFMA
 // contractions and every constant stay in the files.  These files are built with -ffp-contract=off: every operation and its
 // order here is the result's, written out.

@@ -572,6 +572,57 @@ int fd_fit_deltas_shot(fd_ctx *ctx, int64_t N, int F, const float *P_in, const f
                        float radius2, float falloffrate, double mu, const float *delta0, const double *S,
                        double *delta_out, fd_fit_report *reports);
 
+/* ---- the baked deformer: every control point's influence on every vertex -----------------
+ * The deformation is linear in the rig's deltas: W = S delta (fd_solve_operator) and D_v = f_v Pi_v Psi_v W.  fd_deform_bake
+ * hands out that linear map itself, per vertex:
+ *   B[v][i] = f_v sum_j Psi_vj S_ji          (N x M)
+ * the cardinal function of control point i at vertex v with the vertex's fall-off folded in -- what a rigger paints and
+ * inspects as the influence of a control, and what an exporter needs to turn the node into a delta-blend rig for an engine
+ * that cannot run an RBF solve:  P'_v = P_v + Pi_v sum_i B[v][i] delta_i,  exact for every pose of the rig.
+ *
+ * Definition.  S is (C+4) x M fp64 row-major, in fd_get_weights' layout and convention, as fd_solve_operator returns it.  B is
+ *   N x M fp64 row-major, B[v][i] = f_v sum_j Psi_vj S_ji.  Psi_v is the Gram section's row: phi in W's convention, then 1, x,
+ *   y, z.  Columns for polynomial terms the model lacks count as 0.
+ * The contract.  For the built model and any delta' (M x 3),
+ *   Pi_v sum_i B[v][i] delta'_i = D_v(S delta'),
+ *   D what FD_OUTPUT_DISPLACEMENT defines, evaluated exactly.  Pi is a 3 x 3 and is not folded in: the frames are accepted,
+ *   checked by the all-or-none rule, and otherwise unused.
+ * Arithmetic.  The adjoint's: everything is fp64 whatever fd_set_eval_precision says, x - c_j in raw coordinates, phi of the
+ *   kind as the inverse forms it; the gate and f are the forward path's own code.  The product Psi S runs on the fp64 matrix
+ *   pipe; the product by f is one fp64 multiply after the sum.
+ * Kinds.  All of them; the multilayer model with its M L records and S in layer-major rows, as fd_deform_gram handles them.
+ * Rows that are exactly zero.  A gated vertex (dist2 > radius2), a vertex with f = 0 and every vertex of a model with
+ *   terminationtype != 1 (FD_OK) get a row of 0.0 by a select, not a product: P may hold NaN there.
+ * Determinism.  A vertex's row depends on its own inputs, the model and S only: the same bits for any N, at any place in the
+ *   launch, on every call, in the host and the device-pointer form.  No atomics and no partial blocks: the sum over C+4 lives
+ *   in one accumulator.  A caller short of memory bakes vertex ranges and gets the same bits.
+ * B or B32.  opts->B32, N x M fp32, is B rounded once: bit for bit (float)B, what an exporter stores.  Either output may be
+ *   NULL, not both; with opts == NULL, B is required.
+ * Aliasing.  None allowed.
+ * Checks and errors.  FD_E_INVALID for a NULL context, a NULL S in the _dev form, N < 0, M not equal to the context's number of
+ *   control points, both outputs NULL, an opts whose struct_size is too small or a bad frame triple comes before any device
+ *   work.  The build-status poll and repair, FD_E_NOT_BUILT and the ordering behind a batched build are fd_deform's.  N = 0
+ *   writes nothing.  fd_set_output has no effect. */
+typedef struct fd_bake_opts {
+    int struct_size;   /* = sizeof(fd_bake_opts); smaller is FD_E_INVALID */
+    int reserved;
+    float *B32;        /* N x M, or NULL: B rounded once to fp32 (what an exporter stores) */
+} fd_bake_opts;
+
+/* Device pointers (B32 in `opts` too), asynchronous on the context's stream: a pack kernel, the only reader of S, and one
+ * launch.  The packed copy of S lives in the context. */
+int fd_deform_bake_dev(fd_ctx *ctx, int64_t N, const float *d_P_in, const float *d_dist2,
+                       const float *d_tu, const float *d_tv, const float *d_nrm,
+                       float radius2, float falloffrate, const double *d_S, int M,
+                       double *d_B, const fd_bake_opts *opts);
+/* Same, host arrays (B32 in `opts` too); synchronous.  S == NULL computes it inside the call, as fd_fit_deltas does.  B comes
+ * back in chunks of vertices whose device block stays within 256 MiB, so a million vertices by 256 points need no 2 GB of
+ * scratch; a vertex's row depends on nothing else in the launch, so the chunks are bit-identical to one launch. */
+int fd_deform_bake(fd_ctx *ctx, int64_t N, const float *P_in, const float *dist2,
+                   const float *tu, const float *tv, const float *nrm,
+                   float radius2, float falloffrate, const double *S, int M,
+                   double *B, const fd_bake_opts *opts);
+
 /* ---- device-resident mesh (next row N3, engine side) --------------------------
  * In an animated shot the mesh on input 0 -- P, the capture's dist2, the tangent
  * frames -- is the same from cook to cook (Houdini tells by the attributes' data
