@@ -70,6 +70,11 @@ class FdBakeOpts(C.Structure):
     _fields_ = [("struct_size", C.c_int), ("reserved", C.c_int), ("B32", C.c_void_p)]
 
 
+class FdBakeGradOpts(C.Structure):
+    """fd_bake_grad_opts: the optional G32 output (N x 3 x M float32) of fd_deform_bake_grad*."""
+    _fields_ = [("struct_size", C.c_int), ("reserved", C.c_int), ("G32", C.c_void_p)]
+
+
 class FdBatchVectors(C.Structure):
     """fd_batch_vectors: ONE input array per vector (the shared mesh's, N x 3) with a table of one output pointer per
     context, and a table of Jacobian outputs (N x 9 each) or NULL."""
@@ -102,7 +107,7 @@ class FdsopShot(C.Structure):
 EXPORTS = [
     "fd_create", "fd_destroy", "fd_last_error", "fd_abi_version", "fd_set_stream", "fd_set_eval_precision", "fd_set_output", "fd_fp32_holds", "fd_set_points",
     "fd_set_points_dev", "fd_set_deltas", "fd_set_deltas_dev", "fd_set_kernel", "fd_set_term", "fd_build", "fd_build_async",
-    "fd_build_result", "fd_deform", "fd_deform_dev", "fd_deform_dev_stream", "fd_deform_vectors", "fd_deform_vectors_dev", "fd_invert", "fd_invert_dev", "fd_deform_adjoint", "fd_deform_adjoint_dev", "fd_deform_adjoint_points", "fd_deform_adjoint_points_dev", "fd_solve_operator", "fd_deform_gram", "fd_deform_gram_dev", "fd_deform_bake", "fd_deform_bake_dev", "fd_fit_deltas", "fd_deform_adjoint_shot", "fd_deform_adjoint_shot_dev", "fd_fit_deltas_shot", "fd_get_weights", "fd_model_centres", "fd_model_bytes",
+    "fd_build_result", "fd_deform", "fd_deform_dev", "fd_deform_dev_stream", "fd_deform_vectors", "fd_deform_vectors_dev", "fd_invert", "fd_invert_dev", "fd_deform_adjoint", "fd_deform_adjoint_dev", "fd_deform_adjoint_points", "fd_deform_adjoint_points_dev", "fd_solve_operator", "fd_deform_gram", "fd_deform_gram_dev", "fd_deform_bake", "fd_deform_bake_dev", "fd_deform_bake_grad", "fd_deform_bake_grad_dev", "fd_fit_deltas", "fd_deform_adjoint_shot", "fd_deform_adjoint_shot_dev", "fd_fit_deltas_shot", "fd_get_weights", "fd_model_centres", "fd_model_bytes",
     "fd_export_model", "fd_import_model", "fd_synchronize", "fd_host_alloc", "fd_host_free",
     "fd_mesh_set", "fd_mesh_size", "fd_deform_mesh", "fd_mesh_capture", "fd_mesh_get_dist2",
     "fd_capture_dist2", "fd_capture_dist2_dev", "fd_capture_islands", "fd_capture_islands_dev",
@@ -197,6 +202,10 @@ def load() -> C.CDLL:
     L.fd_deform_bake.restype = i32
     L.fd_deform_bake_dev.argtypes = [vp, i64, vp, vp, vp, vp, vp, C.c_float, C.c_float, vp, i32, vp, C.POINTER(FdBakeOpts)]
     L.fd_deform_bake_dev.restype = i32
+    L.fd_deform_bake_grad.argtypes = [vp, i64, vp, vp, vp, vp, vp, C.c_float, C.c_float, vp, i32, vp, C.POINTER(FdBakeGradOpts)]
+    L.fd_deform_bake_grad.restype = i32
+    L.fd_deform_bake_grad_dev.argtypes = [vp, i64, vp, vp, vp, vp, vp, C.c_float, C.c_float, vp, i32, vp, C.POINTER(FdBakeGradOpts)]
+    L.fd_deform_bake_grad_dev.restype = i32
     L.fd_fit_deltas.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, C.c_double, vp, vp, vp, vp]
     L.fd_fit_deltas.restype = i32
     L.fd_deform_adjoint_shot.argtypes = [vp, i64, C.c_int, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, vp]
@@ -667,6 +676,31 @@ class Engine:
         self._check(self.L.fd_deform_bake_dev(self.ctx, N, vp(d_P_in or None), vp(d_dist2 or None), vp(d_tu or None),
                                               vp(d_tv or None), vp(d_nrm or None), float(radius2), float(falloffrate),
                                               vp(d_S or None), self.M, vp(d_B or None), C.byref(opts)))
+
+    def deform_bake_grad(self, P, dist2=None, tangents=None, radius2=1.0, falloffrate=1.0, S=None, want_fp32=False):
+        """fd_deform_bake_grad: G, (N, 3, M) float64 with G[v, a, i] = f_v (dPsi_v/dx_a @ S[:, i]), deform_bake's map
+        differentiated once in x: A_v = I + Pi_v sum_i outer(delta_i, G[v, :, i]) is deform_vectors' Jacobian for every pose of
+        the rig.  S: solve_operator()'s result, or None to have it computed inside.  want_fp32: returns (G, G32), G32 = G
+        rounded once to float32."""
+        P, d2, tu, tv, nr = _mesh_arrays(P, dist2, tangents)
+        Sm = self._solve_operator_arg(S)
+        out = np.empty((P.shape[0], 3, self.M), np.float64)
+        out32 = np.empty((P.shape[0], 3, self.M), np.float32) if want_fp32 else None
+        opts = FdBakeGradOpts(C.sizeof(FdBakeGradOpts), 0, _np_ptr(out32))
+        self._check(self.L.fd_deform_bake_grad(self.ctx, P.shape[0], _np_ptr(P), _np_ptr(d2), _np_ptr(tu), _np_ptr(tv), _np_ptr(nr),
+                                               float(radius2), float(falloffrate), _np_ptr(Sm), self.M, _np_ptr(out),
+                                               C.byref(opts)))
+        return (out, out32) if want_fp32 else out
+
+    def deform_bake_grad_dev(self, N: int, d_P_in: int, d_S: int, d_G: int, d_G32: int = 0, d_dist2: int = 0, d_tu: int = 0,
+                             d_tv: int = 0, d_nrm: int = 0, radius2=1.0, falloffrate=1.0):
+        """fd_deform_bake_grad_dev: device pointers (ints), asynchronous on the context's stream; d_S is (C + 4) x M float64,
+        d_G N x 3 x M float64 or 0, d_G32 N x 3 x M float32 or 0 (one of the two at least)."""
+        vp = C.c_void_p
+        opts = FdBakeGradOpts(C.sizeof(FdBakeGradOpts), 0, vp(d_G32 or None))
+        self._check(self.L.fd_deform_bake_grad_dev(self.ctx, N, vp(d_P_in or None), vp(d_dist2 or None), vp(d_tu or None),
+                                                   vp(d_tv or None), vp(d_nrm or None), float(radius2), float(falloffrate),
+                                                   vp(d_S or None), self.M, vp(d_G or None), C.byref(opts)))
 
     def fit_deltas(self, P, T, omega=None, dist2=None, tangents=None, radius2=1.0, falloffrate=1.0, mu=0.0, delta0=None, S=None):
         """fd_fit_deltas: (delta, report) -- the (M, 3) float64 deltas that minimise sum_v omega_v |D_v(S delta) - (T_v - P_v)|^2

@@ -5,6 +5,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -120,8 +121,8 @@ struct fd_ctx {
     // fd_deform_gram*: the workgroups' partial blocks and, behind them, the host call's staging of H (gram_scratch); the host
     // call's omega goes through d_fall
     DevBuf<double> d_gram;
-    // fd_deform_bake*: the pack kernel's scratch (bake_scratch_doubles) and, behind it, the host call's copy of S; the host
-    // call's vertex chunk of B and, behind it, of B32 comes back through d_bakeout
+    // fd_deform_bake* and fd_deform_bake_grad*: the pack kernel's scratch (bake_scratch_doubles) and, behind it, the host call's
+    // copy of S; the host call's vertex chunk of B (G) and, behind it, of B32 (G32) comes back through d_bakeout
     DevBuf<double> d_bake, d_bakeout;
     // fd_deform_adjoint_shot*: the ranges' partial blocks of one group of frames and, behind them, the host call's staging of
     // grad_W (adjoint_shot_scratch); the host call's G goes group by group through d_gshot
@@ -1003,15 +1004,29 @@ static bool adjoint_points_opts_ok(fd_ctx *ctx, const fd_adjoint_points_opts *op
     return true;
 }
 
-// fd_deform_bake*: NULL opts (B alone), or a struct of at least this ABI's size; B or B32, one at least
-static bool bake_outputs_ok(fd_ctx *ctx, const double *B, const fd_bake_opts *opts)
+// fd_deform_bake* and fd_deform_bake_grad*: which of the two a call is (comps: fd_internal.h BakeArgs), with the names its
+// messages use
+struct BakeCall {
+    const char *who, *opts_name, *out, *out32;
+    int comps;
+};
+static const BakeCall kBake{"fd_deform_bake", "fd_bake_opts", "B", "B32", 1};
+static const BakeCall kBakeGrad{"fd_deform_bake_grad", "fd_bake_grad_opts", "G", "G32", 3};
+// The two opts structs are one layout under two names: the host layer reads both as fd_bake_opts (G32 as B32), and
+// sizeof(fd_bake_opts) in a message is the size of either.
+static_assert(sizeof(fd_bake_grad_opts) == sizeof(fd_bake_opts) && offsetof(fd_bake_grad_opts, struct_size) == offsetof(fd_bake_opts, struct_size) &&
+              offsetof(fd_bake_grad_opts, G32) == offsetof(fd_bake_opts, B32), "fd_bake_grad_opts is fd_bake_opts' layout");
+static const fd_bake_opts *bake_opts_view(const fd_bake_grad_opts *opts) { return reinterpret_cast<const fd_bake_opts *>(opts); }
+
+// NULL opts (B alone), or a struct of at least this ABI's size; B or B32, one at least
+static bool bake_outputs_ok(fd_ctx *ctx, const BakeCall &k, const double *B, const fd_bake_opts *opts)
 {
     if (opts && opts->struct_size < (int)sizeof(fd_bake_opts)) {
-        set_err(ctx, "fd_deform_bake: opts->struct_size is %d, must be sizeof(fd_bake_opts) = %d", opts->struct_size,
+        set_err(ctx, "%s: opts->struct_size is %d, must be sizeof(%s) = %d", k.who, opts->struct_size, k.opts_name,
                 (int)sizeof(fd_bake_opts));
         return false;
     }
-    if (!B && !(opts && opts->B32)) { set_err(ctx, "fd_deform_bake: B and opts->B32 are both NULL"); return false; }
+    if (!B && !(opts && opts->B32)) { set_err(ctx, "%s: %s and opts->%s are both NULL", k.who, k.out, k.out32); return false; }
     return true;
 }
 
@@ -1137,15 +1152,15 @@ static int gram_dev(fd_ctx *ctx, const char *who, const Mesh &m, const float *d_
     return FD_OK;
 }
 
-// fd_deform_bake_dev: the pack kernel and the one launch; nothing is written for an empty mesh
-static int bake_dev(fd_ctx *ctx, const char *who, const Mesh &m, const double *d_S, double *d_B, float *d_B32)
+// fd_deform_bake_dev and fd_deform_bake_grad_dev: the pack kernel and the one launch; nothing is written for an empty mesh
+static int bake_dev(fd_ctx *ctx, const BakeCall &k, const Mesh &m, const double *d_S, double *d_B, float *d_B32)
 {
     DeformArgs a;
     hipStream_t s;
-    int rc = deform_begin(ctx, who, nullptr, m, nullptr, nullptr, true, &a, &s);
+    int rc = deform_begin(ctx, k.who, nullptr, m, nullptr, nullptr, true, &a, &s);
     if (rc || m.N == 0) return rc;
-    if ((rc = dev_alloc(ctx, ctx->d_bake, bake_scratch_doubles(a.M, ctx->M), kGrow))) return rc;
-    const BakeArgs g{d_S, ctx->M, term_cols(ctx->term), ctx->d_bake, d_B, d_B32};
+    if ((rc = dev_alloc(ctx, ctx->d_bake, bake_scratch_doubles(a.M, ctx->M, k.comps), kGrow))) return rc;
+    const BakeArgs g{d_S, ctx->M, term_cols(ctx->term), ctx->d_bake, d_B, d_B32, k.comps};
     FD_HIP(ctx, launch_bake_pack(a, g, s));
     FD_HIP(ctx, launch_bake(a, g, s));
     return FD_OK;
@@ -1373,11 +1388,13 @@ static int gram_host(fd_ctx *ctx, const char *who, const Mesh &m, const float *o
     return gram_staged(ctx, who, d, omega ? ctx->d_fall : nullptr, H);
 }
 
-// fd_deform_bake on host arrays: S (computed here where the caller has none) goes up behind the pack kernel's scratch, is packed
-// once, and B and B32 come back in chunks of vertices through d_bakeout (bake_chunk_vertices: the block stays within the
-// operators' scratch bound).  A vertex's row depends on nothing else in the launch, so the chunks are the bits of one launch.
-static int bake_host(fd_ctx *ctx, const char *who, const Mesh &m, const double *S, double *B, float *B32)
+// fd_deform_bake and fd_deform_bake_grad on host arrays: S (computed here where the caller has none) goes up behind the pack
+// kernel's scratch, is packed once, and B and B32 (G and G32: k.comps rows of M per vertex) come back in chunks of vertices
+// through d_bakeout (bake_chunk_vertices: the block stays within the operators' scratch bound).  A vertex's rows depend on
+// nothing else in the launch, so the chunks are the bits of one launch.
+static int bake_host(fd_ctx *ctx, const BakeCall &k, const Mesh &m, const double *S, double *B, float *B32)
 {
+    const char *who = k.who;
     int rc = mesh_checks(ctx, who, m, true);
     if (rc || m.N == 0) return rc;
     const int C = model_centres(ctx), M = ctx->M;
@@ -1395,16 +1412,17 @@ static int bake_host(fd_ctx *ctx, const char *who, const Mesh &m, const double *
     DeformArgs a;
     hipStream_t launch_stream;
     if ((rc = deform_begin(ctx, who, nullptr, d, nullptr, nullptr, true, &a, &launch_stream))) return rc;
-    const size_t scratch = bake_scratch_doubles(C, M);
+    const size_t scratch = bake_scratch_doubles(C, M, k.comps);
     if ((rc = dev_alloc(ctx, ctx->d_bake, scratch + s_doubles, kGrow))) return rc;
-    const int64_t per = bake_chunk_vertices(M, B != nullptr, B32 != nullptr);
-    const size_t chunk = (size_t)(m.N < per ? m.N : per) * (size_t)M;
+    const int64_t per = bake_chunk_vertices(M, k.comps, B != nullptr, B32 != nullptr);
+    const size_t vrow = (size_t)k.comps * (size_t)M;                    // entries per vertex
+    const size_t chunk = (size_t)(m.N < per ? m.N : per) * vrow;
     if ((rc = dev_alloc(ctx, ctx->d_bakeout, (B ? chunk : 0) + (B32 ? (chunk + 1) / 2 : 0), kGrow))) return rc;
     double *d_S = ctx->d_bake + scratch;
     double *d_B = B ? ctx->d_bakeout.p : nullptr;
     float *d_B32 = B32 ? reinterpret_cast<float *>(ctx->d_bakeout + (B ? chunk : 0)) : nullptr;
     FD_HIP(ctx, hipMemcpyAsync(d_S, S, sizeof(double) * s_doubles, hipMemcpyHostToDevice, s));
-    BakeArgs g{d_S, M, term_cols(ctx->term), ctx->d_bake, d_B, d_B32};
+    BakeArgs g{d_S, M, term_cols(ctx->term), ctx->d_bake, d_B, d_B32, k.comps};
     FD_HIP(ctx, launch_bake_pack(a, g, s));
     for (int64_t v0 = 0; v0 < m.N; v0 += per) {
         const int64_t n = m.N - v0 < per ? m.N - v0 : per;
@@ -1414,7 +1432,7 @@ static int bake_host(fd_ctx *ctx, const char *who, const Mesh &m, const double *
         ac.dist2 = d.dist2 ? d.dist2 + v0 : nullptr;
         if (d.tu) { ac.tu = d.tu + 3 * v0; ac.tv = d.tv + 3 * v0; ac.nrm = d.nrm + 3 * v0; }
         FD_HIP(ctx, launch_bake(ac, g, s));
-        const size_t at = (size_t)v0 * (size_t)M, cnt = (size_t)n * (size_t)M;
+        const size_t at = (size_t)v0 * vrow, cnt = (size_t)n * vrow;
         if (B) FD_HIP(ctx, hipMemcpyAsync(B + at, d_B, sizeof(double) * cnt, hipMemcpyDeviceToHost, s));
         if (B32) FD_HIP(ctx, hipMemcpyAsync(B32 + at, d_B32, sizeof(float) * cnt, hipMemcpyDeviceToHost, s));
     }
@@ -1586,14 +1604,14 @@ int fd_deform_gram(fd_ctx *ctx, int64_t N, const float *P_in, const float *omega
     return gram_host(ctx, "fd_deform_gram", Mesh{N, P_in, dist2, tu, tv, nrm, radius2, falloffrate}, omega, H);
 }
 
-// fd_deform_bake*: what both forms check before any device work
-static int bake_checks(fd_ctx *ctx, int64_t N, int M, const void *tu, const void *tv, const void *nrm, const double *B,
-                       const fd_bake_opts *opts)
+// fd_deform_bake* and fd_deform_bake_grad*: what both forms check before any device work
+static int bake_checks(fd_ctx *ctx, const BakeCall &k, int64_t N, int M, const void *tu, const void *tv, const void *nrm,
+                       const double *B, const fd_bake_opts *opts)
 {
-    if (N < 0) { set_err(ctx, "fd_deform_bake: N < 0"); return FD_E_INVALID; }
-    if (M != ctx->M) { set_err(ctx, "fd_deform_bake: M is %d, the context has %d control points", M, ctx->M); return FD_E_INVALID; }
-    if (!bake_outputs_ok(ctx, B, opts)) return FD_E_INVALID;
-    if (!frames_ok(tu, tv, nrm)) { set_err(ctx, "fd_deform_bake: tu, tv, nrm must be all set or all NULL"); return FD_E_INVALID; }
+    if (N < 0) { set_err(ctx, "%s: N < 0", k.who); return FD_E_INVALID; }
+    if (M != ctx->M) { set_err(ctx, "%s: M is %d, the context has %d control points", k.who, M, ctx->M); return FD_E_INVALID; }
+    if (!bake_outputs_ok(ctx, k, B, opts)) return FD_E_INVALID;
+    if (!frames_ok(tu, tv, nrm)) { set_err(ctx, "%s: tu, tv, nrm must be all set or all NULL", k.who); return FD_E_INVALID; }
     return FD_OK;
 }
 
@@ -1603,17 +1621,36 @@ int fd_deform_bake_dev(fd_ctx *ctx, int64_t N, const float *d_P_in, const float 
 {
     if (!ctx) return FD_E_INVALID;
     if (!d_S) { set_err(ctx, "fd_deform_bake: S is NULL"); return FD_E_INVALID; }
-    if (int rc = bake_checks(ctx, N, M, d_tu, d_tv, d_nrm, d_B, opts)) return rc;
-    return bake_dev(ctx, "fd_deform_bake", Mesh{N, d_P_in, d_dist2, d_tu, d_tv, d_nrm, radius2, falloffrate}, d_S, d_B,
-                    opts ? opts->B32 : nullptr);
+    if (int rc = bake_checks(ctx, kBake, N, M, d_tu, d_tv, d_nrm, d_B, opts)) return rc;
+    return bake_dev(ctx, kBake, Mesh{N, d_P_in, d_dist2, d_tu, d_tv, d_nrm, radius2, falloffrate}, d_S, d_B, opts ? opts->B32 : nullptr);
 }
 
 int fd_deform_bake(fd_ctx *ctx, int64_t N, const float *P_in, const float *dist2, const float *tu, const float *tv, const float *nrm,
                    float radius2, float falloffrate, const double *S, int M, double *B, const fd_bake_opts *opts)
 {
     if (!ctx) return FD_E_INVALID;
-    if (int rc = bake_checks(ctx, N, M, tu, tv, nrm, B, opts)) return rc;
-    return bake_host(ctx, "fd_deform_bake", Mesh{N, P_in, dist2, tu, tv, nrm, radius2, falloffrate}, S, B, opts ? opts->B32 : nullptr);
+    if (int rc = bake_checks(ctx, kBake, N, M, tu, tv, nrm, B, opts)) return rc;
+    return bake_host(ctx, kBake, Mesh{N, P_in, dist2, tu, tv, nrm, radius2, falloffrate}, S, B, opts ? opts->B32 : nullptr);
+}
+
+int fd_deform_bake_grad_dev(fd_ctx *ctx, int64_t N, const float *d_P_in, const float *d_dist2, const float *d_tu, const float *d_tv,
+                            const float *d_nrm, float radius2, float falloffrate, const double *d_S, int M, double *d_G,
+                            const fd_bake_grad_opts *opts)
+{
+    if (!ctx) return FD_E_INVALID;
+    if (!d_S) { set_err(ctx, "fd_deform_bake_grad: S is NULL"); return FD_E_INVALID; }
+    if (int rc = bake_checks(ctx, kBakeGrad, N, M, d_tu, d_tv, d_nrm, d_G, bake_opts_view(opts))) return rc;
+    return bake_dev(ctx, kBakeGrad, Mesh{N, d_P_in, d_dist2, d_tu, d_tv, d_nrm, radius2, falloffrate}, d_S, d_G,
+                    opts ? opts->G32 : nullptr);
+}
+
+int fd_deform_bake_grad(fd_ctx *ctx, int64_t N, const float *P_in, const float *dist2, const float *tu, const float *tv,
+                        const float *nrm, float radius2, float falloffrate, const double *S, int M, double *G,
+                        const fd_bake_grad_opts *opts)
+{
+    if (!ctx) return FD_E_INVALID;
+    if (int rc = bake_checks(ctx, kBakeGrad, N, M, tu, tv, nrm, G, bake_opts_view(opts))) return rc;
+    return bake_host(ctx, kBakeGrad, Mesh{N, P_in, dist2, tu, tv, nrm, radius2, falloffrate}, S, G, opts ? opts->G32 : nullptr);
 }
 
 int fd_deform_adjoint_shot_dev(fd_ctx *ctx, int64_t N, int F, const float *d_P_in, const float *d_G, const float *d_dist2,

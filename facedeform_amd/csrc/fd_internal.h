@@ -337,21 +337,24 @@ struct GramArgs {
 int gram_ranges(int64_t N, int C);    // workgroups along the vertices: a function of N and C alone
 size_t gram_partial_doubles(int64_t N, int C, int nq);
 hipError_t launch_gram(const DeformArgs &a, const GramArgs &g, hipStream_t stream);
-// the deformer baked per vertex (fd_bake.hip, fd_deform_bake*): `a` as for the adjoint (a.M the records C); S the (C + 4) x M
+// the deformer baked per vertex (fd_bake.hip, fd_deform_bake* and fd_deform_bake_grad*): `a` as for the adjoint (a.M the records C); S the (C + 4) x M
 // solve operator on the device, M its columns (the control points), T as above, scratch bake_scratch_doubles(C, M) doubles; B
 // and B32 the N x M results, either may be null.  launch_bake_pack is the only reader of S and fills the scratch; launch_bake
 // reads the scratch and the mesh of `a` (one launch; N = 0 launches nothing), so one pack serves any number of vertex ranges.
+// comps = 3 is the gradient (fd_deform_bake_grad*): B and B32 are then G and G32, N x 3 x M, the scratch is laid out for the
+// gradient launch's narrower panels, and launch_bake launches that kernel.  comps is 1 or 3.
 struct BakeArgs {
     const double *S;
     int M, T;
     double *scratch;
     double *B;
     float *B32;
+    int comps;
 };
-size_t bake_scratch_doubles(int C, int M);
-// vertices of a chunk of the host call: a multiple of the launch's vertex group whose block of B (b64) and B32 (b32) stays within
-// the operators' scratch bound (one group at least)
-int64_t bake_chunk_vertices(int M, bool b64, bool b32);
+size_t bake_scratch_doubles(int C, int M, int comps);
+// vertices of a chunk of the host call: a multiple of the launch's vertex group whose block of comps x M doubles (b64) and
+// floats (b32) per vertex stays within the operators' scratch bound (one group at least)
+int64_t bake_chunk_vertices(int M, int comps, bool b64, bool b32);
 hipError_t launch_bake_pack(const DeformArgs &a, const BakeArgs &g, hipStream_t stream);
 hipError_t launch_bake(const DeformArgs &a, const BakeArgs &g, hipStream_t stream);
 hipError_t launch_deform_batch(const DeformArgs *a, int n, hipStream_t stream);

@@ -623,6 +623,61 @@ int fd_deform_bake(fd_ctx *ctx, int64_t N, const float *P_in, const float *dist2
                    float radius2, float falloffrate, const double *S, int M,
                    double *B, const fd_bake_opts *opts);
 
+/* ---- the baked deformer's gradient: what a baked rig needs to carry normals and tangents -----------------
+ * fd_deform_vectors transports vectors with the Jacobian A = I + f Pi J(x), and J is linear in the weights as the displacement
+ * is.  fd_deform_bake_grad hands out B's linear map differentiated once in x:
+ *   G[v][a][i] = f_v sum_j dPsi_vj/dx_a S_ji          (N x 3 x M)
+ *   A_v = I + Pi_v sum_i delta_i (x) G[v][.][i],   i.e.  (A_v - I)[b][a] = sum_c Pi_v[b][c] sum_i delta_i[c] G[v][a][i]
+ * exact for every pose of the rig.  With B and G an engine that cannot run an RBF solve reproduces all of fd_deform_vectors:
+ * positions, t' = A t, n' = cof(A) n.
+ *
+ * Layout.  G is N x 3 x M fp64 row-major: vertex, component a of x, control point.  For each a, G[:, a, :] is an N x M matrix
+ *   with row stride 3 M.  S is fd_deform_bake's.
+ * dPsi.  For a record, d phi_j / d x_a in W's convention:
+ *     thin-plate                 (x - c)(2 ln r + 1), 0 at r = 0
+ *     Gaussian, QNN, multilayer  -2 (x - c) / R_j^2 . phi, one record per layer
+ *     cubic                      3 r (x - c)
+ *     biharmonic                 -(x - c) / r, 0 at r = 0
+ *   for the polynomial columns 1, x, y, z: 0, delta_a0, delta_a1, delta_a2.  Columns the term lacks count as 0.
+ * The contract.  For the built model and any delta' (M x 3),
+ *   I + Pi_v sum_i delta'_i (x) G[v][.][i] = the A of fd_deform_vectors for the model built on delta',
+ *   evaluated exactly.  Pi stays out, as in the bake: the frames are accepted, checked by the all-or-none rule, and otherwise
+ *   unused.
+ * Arithmetic.  Everything is fp64 whatever fd_set_eval_precision says, x - c_j in raw coordinates, the derivative of the kind
+ *   as the inverse forms it; the gate and f are the forward path's own code.  The product runs on the fp64 matrix pipe; the
+ *   product by f is one fp64 multiply after the sum.
+ * Rows that are exactly zero (so A = I exactly, as fd_deform_vectors says).  A gated vertex (dist2 > radius2), a vertex with
+ *   f = 0 and every vertex of a model with terminationtype != 1 (FD_OK) get a 3 x M block of 0.0 by a select, not a product: P
+ *   may hold NaN there.
+ * Determinism.  A vertex's 3 x M block depends on its own inputs, the model and S only: the same bits for any N, at any place
+ *   in the launch, on every call, in the host and the device-pointer form.  No atomics and no partial blocks.
+ * G or G32.  opts->G32, N x 3 x M fp32, is G rounded once: bit for bit (float)G.  Either output may be NULL, not both; with
+ *   opts == NULL, G is required.
+ * Aliasing.  None allowed.
+ * Checks and errors.  FD_E_INVALID for a NULL context, a NULL S in the _dev form, N < 0, M not equal to the context's number of
+ *   control points, both outputs NULL, an opts whose struct_size is too small or a bad frame triple comes before any device
+ *   work.  The build-status poll and repair, FD_E_NOT_BUILT and the ordering behind a batched build are fd_deform's.  N = 0
+ *   writes nothing.  fd_set_output has no effect. */
+typedef struct fd_bake_grad_opts {
+    int struct_size;   /* = sizeof(fd_bake_grad_opts); smaller is FD_E_INVALID */
+    int reserved;
+    float *G32;        /* N x 3 x M, or NULL: G rounded once to fp32 */
+} fd_bake_grad_opts;
+
+/* Device pointers (G32 in `opts` too), asynchronous on the context's stream: the bake's pack kernel, the only reader of S, and
+ * one launch.  The packed copy of S lives in the context, in the place of the bake's. */
+int fd_deform_bake_grad_dev(fd_ctx *ctx, int64_t N, const float *d_P_in, const float *d_dist2,
+                            const float *d_tu, const float *d_tv, const float *d_nrm,
+                            float radius2, float falloffrate, const double *d_S, int M,
+                            double *d_G, const fd_bake_grad_opts *opts);
+/* Same, host arrays (G32 in `opts` too); synchronous.  S == NULL computes it inside the call.  G comes back in chunks of
+ * vertices whose device block (3 M doubles and / or floats per vertex) stays within 256 MiB; the chunks are bit-identical to
+ * one launch. */
+int fd_deform_bake_grad(fd_ctx *ctx, int64_t N, const float *P_in, const float *dist2,
+                        const float *tu, const float *tv, const float *nrm,
+                        float radius2, float falloffrate, const double *S, int M,
+                        double *G, const fd_bake_grad_opts *opts);
+
 /* ---- device-resident mesh (next row N3, engine side) --------------------------
  * In an animated shot the mesh on input 0 -- P, the capture's dist2, the tangent
  * frames -- is the same from cook to cook (Houdini tells by the attributes' data
